@@ -17,6 +17,15 @@ own batch, context tables and keys (batch sharding, no data-path collective: SUR
   --workload rotate_c5              BASELINE configs[4]: CKKS N=65536 L=16 rotate_vector with the key-switch decomposition
                                     digits spread over the ranks (one exchange per key switch) + rescale ("strong")
 
+  --dump-outputs DIR                after the timed steps, a fixed sample of what the last step computed goes to DIR/*.npy
+                                    (float64; rank 0's share; see dump_outputs)
+  --full                            everything below that checks or measures more than the headline figure: verified_items,
+                                    roofline, roofline_configs1, the counter part of roofline_step, workloads, config.batch_sweep
+                                    and cpu_baseline (null without it; the --no-* options leave single parts out)
+
+A plain run (no --full) sets up, warms up, times --steps steps and prints the line; the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step) mean the same with or without --full.
+
 One JSON line is printed by rank 0 with, besides the contract fields:
   verified_items  ciphertexts of the timed batch (16 spread evenly over every rank's share) compared word for word, outside the timed
                region, with the reference Evaluator (oracle/_ref) run on the same input and key words
@@ -61,6 +70,9 @@ def main():
         args.no_cpu_baseline = args.no_pmc = args.no_verify = args.no_children = True
     if args.sweep_child:
         return sweep_child(args)
+    if not args.full:
+        # a plain run does what the headline figure needs and nothing else: everything that checks or measures more is --full's
+        args.no_cpu_baseline = args.no_pmc = args.no_verify = args.no_children = args.no_sweep = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launcher.launch_ranks(args, os.path.abspath(__file__)))
     r = launcher.init_ranks(args)
@@ -87,6 +99,8 @@ def main():
         rate = shard.whole_job_rate(per_step, args.steps, elapsed, group, torch, cdev)
         result = dict(value=rate, ms_per_step=1e3 * elapsed / args.steps)
         per_rank = launcher.gather_per_rank(r, per_step * args.steps / local["elapsed"], 1e3 * local["elapsed"] / args.steps)
+        if args.dump_outputs and rank == 0 and B > 0:
+            dump_outputs(args.dump_outputs, work, B)
         if group is not None and w.want_verify is False and not args.no_verify and workloads.reference_available():
             verified = 0   # a rank with an empty shard has nothing to compare but joins the sum below
         if w.want_verify and B > 0:
@@ -100,11 +114,11 @@ def main():
 
     # ---- roofline leg: the batched forward NTT over the resident batch (2*B polys x K comps)
     roofline = None
-    if rank == 0 and not EMU and not args.step_child:
+    if rank == 0 and not EMU and not args.step_child and (args.full or args.ntt_only):
         roofline = counters.ntt_leg(S, w.ctx, w.xs, B, K, n)
 
     ntt_c1 = None
-    if rank == 0 and world == 1 and args.workload == "headline" and not EMU and not args.step_child:
+    if rank == 0 and world == 1 and args.workload == "headline" and not EMU and not args.step_child and (args.full or args.ntt_only):
         ntt_c1 = counters.ntt_configs1(S, torch, device)
 
     # what the step held in HBM: the pool's blocks and the largest key-switch intermediate of the timed steps
@@ -216,6 +230,29 @@ def main():
         print(json.dumps(line), flush=True)
 
 
+DUMP_ITEMS, DUMP_COEFFS = 16, 4096
+
+
+def dump_outputs(out_dir, work, B):
+    """`--dump-outputs DIR`: what the last timed step left in the output batch, as float64 .npy files - 16 items spread evenly over
+    this rank's batch (first and last included), both polynomials, every RNS component, and 4096 coefficient positions drawn once
+    with a fixed seed (all of them when N is smaller).  The inputs are seeded, so the same arguments give the same files.
+      ciphertext.npy       [item][poly][component][coefficient]: the residue words as float64 (exact below 2^53)
+      ciphertext_lo32.npy  the same words modulo 2^32 (exact): with ciphertext.npy every bit of a 60-bit residue is compared
+      scale.npy            [1]: the output's scale (CKKS; 1.0 otherwise)
+    At the headline shape that is 2 x 14.7 MB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    take = min(DUMP_ITEMS, B)
+    items = sorted({int(round(i * (B - 1) / max(1, take - 1))) for i in range(take)})
+    n = work.item_to_numpy(items[0]).shape[-1]
+    cols = np.arange(n) if n <= DUMP_COEFFS else np.sort(np.random.default_rng(0x5EA1).choice(n, DUMP_COEFFS, replace=False))
+    words = np.stack([work.item_to_numpy(b)[:, :, cols] for b in items])
+    np.save(os.path.join(out_dir, "ciphertext.npy"), words.astype(np.float64))
+    np.save(os.path.join(out_dir, "ciphertext_lo32.npy"), (words & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(out_dir, "scale.npy"), np.array([work.scale()], dtype=np.float64))
+
+
 def sweep_child(args):
     """`--sweep-child`: the headline step at the batch sizes of --sweep, one after the other in this process (a context, a key and
     a pair of resident input batches per size, freed before the next); batch 1 eager and as a hipGraph replay.  Prints one JSON
@@ -271,7 +308,7 @@ def child_workload(name, args):
     """one of the other BASELINE workloads as a child run of this script (its own process: the parent's 55 GB are released
     first); the child's line reduced to what identifies and qualifies the number.  Never takes the headline down."""
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(args.child_steps), "--warmup", "1",
-           "--no-cpu-baseline", "--no-pmc", "--no-children"]
+           "--full", "--no-cpu-baseline", "--no-pmc", "--no-children"]
     if args.no_verify:
         cmd.append("--no-verify")
     try:

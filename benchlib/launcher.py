@@ -44,6 +44,11 @@ def parse(argv=None):
                     "communicator, so that the digit-parallel exchange of one overlaps the key-switch kernels of the next")
     ap.add_argument("--graph", action="store_true", help="replay the step as one captured hipGraph (Evaluator_BeginCapture/EndCapture): "
                     "for launch-bound small batches; the default (eager) path is what the headline number uses")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: the reference check of sampled items, the roofline "
+                    "legs, the rocprofv3 PMC passes, the appended workloads, the batch sweep and the CPU baseline (the --no-* options "
+                    "leave parts of it out); without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write a fixed sample of what the last "
+                    "step computed as DIR/<name>.npy (float64)")
     return ap.parse_args(argv)
 
 

@@ -53,7 +53,7 @@ def test_world_size_2_gloo(emu):
 
 @pytest.mark.parametrize("workload", ["headline", "bfv_c4", "rotate_c5"])
 def test_bench_gpus_2_starts_two_ranks(emu, workload):
-    """`python bench.py --gpus 2` with no torchrun environment starts the two ranks itself; here on the
+    """`python bench.py --gpus 2 --full` with no torchrun environment starts the two ranks itself; here on the
     emulated kernels with gloo (SEALHIP_BENCH_EMU=1).  The line must say n_gpus 2, both ranks' sampled items must have
     been checked against the reference, and a WORLD_SIZE that disagrees with --gpus is refused."""
     import json
@@ -61,7 +61,7 @@ def test_bench_gpus_2_starts_two_ranks(emu, workload):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SEALHIP_BENCH_EMU"] = "1"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--workload", workload], env=env, capture_output=True, text=True, timeout=600)
+                          "--workload", workload, "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -83,7 +83,7 @@ def test_bench_gpus_2_starts_two_ranks(emu, workload):
 
 @pytest.mark.parametrize("workload", ["headline", "bfv_c4", "rotate_c5"])
 def test_bench_gpus_8_emulated(emu, workload):
-    """`python bench.py --gpus 8` - the shape the driver's scaling run has - as eight real processes over gloo on the emulated kernels
+    """`python bench.py --gpus 8 --full` - the shape the driver's scaling run has - as eight real processes over gloo on the emulated kernels
     (VERDICT r5 #4): the probe collective reaches all eight, every rank reports its own rate, the sampled items of every rank that
     owns any equal the reference's.  bfv_c4 shards a total batch of 4 over 8 ranks (four ranks own NOTHING and still pass every
     barrier), rotate_c5 spreads K = 3 key-switch digits over 8 ranks (five ranks own no digit and contribute zero sums)."""
@@ -92,7 +92,7 @@ def test_bench_gpus_8_emulated(emu, workload):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SEALHIP_BENCH_EMU"] = "1"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1",
-                          "--workload", workload], env=env, capture_output=True, text=True, timeout=900)
+                          "--workload", workload, "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -115,14 +115,14 @@ def test_bench_gpus_8_emulated(emu, workload):
 
 @pytest.mark.parametrize("workload", ["headline", "bfv_c4"])
 def test_bench_streams_divides_the_batch(emu, workload):
-    """`bench.py --streams 2`: two evaluators on two streams, each with half of the rank's batch; the sampled items of the
+    """`bench.py --streams 2 --full`: two evaluators on two streams, each with half of the rank's batch; the sampled items of the
     joined output are still the reference's (emulated kernels)."""
     import json
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SEALHIP_BENCH_EMU"] = "1"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--streams", "2", "--steps", "1", "--warmup", "1", "--batch", "5",
-                          "--workload", workload, "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                          "--workload", workload, "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert "2 evaluators" in line["config"]["launch"] and line["value"] > 0
@@ -132,14 +132,14 @@ def test_bench_streams_divides_the_batch(emu, workload):
 
 
 def test_bench_rotate_c5_pipelined_exchange(emu):
-    """`bench.py --workload rotate_c5 --gpus 2 --streams 2`: two sub-batches per rank, each with its own evaluator / stream, sharing
+    """`bench.py --workload rotate_c5 --gpus 2 --streams 2 --full`: two sub-batches per rank, each with its own evaluator / stream, sharing
     the exchange; every rank's sampled items equal the reference's rotate + rescale (VERDICT r2 #7: the pipelined form)"""
     import json
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SEALHIP_BENCH_EMU"] = "1"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "rotate_c5",
-                          "--streams", "2", "--batch", "4"], env=env, capture_output=True, text=True, timeout=600)
+                          "--streams", "2", "--batch", "4", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
     assert line["n_gpus"] == 2 and line["value"] > 0
@@ -150,13 +150,13 @@ def test_bench_rotate_c5_pipelined_exchange(emu):
 
 
 def test_bench_default_line_carries_configs3_and_configs4(emu):
-    """`python bench.py` (one GPU, headline): BASELINE configs[3] and configs[4] are timed by child runs and attached to the same
+    """`python bench.py --full` (one GPU, headline): BASELINE configs[3] and configs[4] are timed by child runs and attached to the same
     line with their own value / verified_items (VERDICT r3 #2); --no-children leaves them out"""
     import json
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SEALHIP_BENCH_EMU"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--child-steps", "2"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--child-steps", "2", "--full"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -171,9 +171,42 @@ def test_bench_default_line_carries_configs3_and_configs4(emu):
         assert ("configs[3]" if name == "bfv_c4" else "configs[4]") in wl["config"]["workload"]
         if sealref.available():
             assert wl["verified_items"] >= 2, (name, wl)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--no-children"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--full", "--no-children"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])["workloads"] is None
+
+
+def test_bench_plain_run_and_dump_outputs(emu, tmp_path):
+    """`python bench.py --steps 3 --warmup 1 --dump-outputs DIR` (no --full): the line carries the contract fields and --steps, and
+    nothing that --full adds; DIR holds float64 arrays of the last step's output, the same from run to run (seeded inputs)"""
+    import json
+    import numpy as np
+    root = os.path.dirname(HERE)
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["SEALHIP_BENCH_EMU"] = "1"
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "ciphertexts/s" and line["higher_is_better"] is True and line["dtype"] == "u64" and line["metric"]
+        for k in ("verified_items", "roofline", "roofline_configs1", "workloads", "cpu_baseline"):
+            assert line[k] is None, (k, line[k])
+        assert line["config"]["batch_sweep"] is None
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ["ciphertext.npy", "ciphertext_lo32.npy", "scale.npy"], files
+        arrays = {f: np.load(tmp_path / run / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 << 20
+        assert arrays["ciphertext.npy"].shape == (2, 2, 2, 1024)   # emulated headline: batch 2, size 2, K - 1 = 2, N = 1024
+        assert arrays["ciphertext.npy"].any()
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def test_device_memory_estimate_tracks_the_workloads():

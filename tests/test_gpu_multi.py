@@ -45,7 +45,7 @@ def test_digit_parallel_over_real_ranks(gpu, exchange):
 @pytest.mark.parametrize("workload,extra", [("headline", ["--batch", "8"]), ("bfv_c4", ["--total-batch", "16"]),
                                             ("rotate_c5", ["--batch", "2", "--exchange", "reduce_scatter"])])
 def test_bench_over_real_ranks(gpu, workload, extra):
-    """`python bench.py --gpus 2` on real GPUs: the launcher starts one rank per GPU, the probe all-reduce reaches both
+    """`python bench.py --gpus 2 --full` on real GPUs: the launcher starts one rank per GPU, the probe all-reduce reaches both
     over RCCL (rccl_ranks in the line), every rank's sampled items equal the reference's, every rank reports its own rate.  Batch
     sharding for the headline and configs[3], the digit-parallel exchange inside the library for configs[4]."""
     import json
@@ -56,7 +56,7 @@ def test_bench_over_real_ranks(gpu, workload, extra):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", workload,
-                          "--no-cpu-baseline", "--no-pmc"] + extra, env=env, capture_output=True, text=True, timeout=1500)
+                          "--full", "--no-cpu-baseline", "--no-pmc"] + extra, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and line["collective_backend"] == "nccl", line
@@ -69,7 +69,7 @@ def test_bench_over_real_ranks(gpu, workload, extra):
 @pytest.mark.gpu
 @pytest.mark.parametrize("workload,extra", [("rotate_c5", ["--batch", "2"]), ("bfv_c4", ["--total-batch", "6"]), ("headline", ["--batch", "3"])])
 def test_two_processes_share_the_one_gpu(gpu, workload, extra):
-    """The only N > 1 evidence a one-GPU box can give (VERDICT r4 next #7b): `python bench.py --gpus 2` with both ranks on device 0
+    """The only N > 1 evidence a one-GPU box can give (VERDICT r4 next #7b): `python bench.py --gpus 2 --full` with both ranks on device 0
     (SEALHIP_BENCH_SHARE_GPU=1: process group gloo, RCCL refuses two ranks on one device) and the REAL kernels - batch sharding for
     the headline and configs[3] (uneven shards: 3 + 3 of 6, 3 each), and for configs[4] the digit-parallel key switch across a real
     process boundary: each rank runs switch_key_partial on its digits, the partial sums are added by torch.distributed, each
@@ -79,7 +79,7 @@ def test_two_processes_share_the_one_gpu(gpu, workload, extra):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", SEALHIP_BENCH_SHARE_GPU="1")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", workload,
-                          "--no-cpu-baseline", "--no-pmc", "--no-children"] + extra, env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-pmc", "--no-children"] + extra, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and line["collective_backend"] == "gloo", line
@@ -94,7 +94,7 @@ def test_two_processes_share_the_one_gpu(gpu, workload, extra):
 @pytest.mark.gpu
 @pytest.mark.parametrize("workload,extra", [("headline", ["--batch", "1"]), ("bfv_c4", ["--total-batch", "9"]), ("rotate_c5", ["--batch", "2"])])
 def test_eight_processes_share_the_one_gpu(gpu, workload, extra):
-    """Eight-rank first contact as far as a one-GPU box allows: `python bench.py --gpus 8`, the eight ranks real
+    """Eight-rank first contact as far as a one-GPU box allows: `python bench.py --gpus 8 --full`, the eight ranks real
     processes with the REAL kernels on device 0 (SEALHIP_BENCH_SHARE_GPU=1, gloo).  One item per rank for the headline; 9 items over 8
     ranks for configs[3] (shards 2, 1, 1, ...); configs[4] with 15 digits over 8 ranks (2, 2, ..., 1).  Every rank pinned to its own
     CPUs, every rank's items equal the reference's.  (The ring kernel is opt-in and stays off: processes that share a GPU must not
@@ -104,7 +104,7 @@ def test_eight_processes_share_the_one_gpu(gpu, workload, extra):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SEALHIP_NTT_RING")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", SEALHIP_BENCH_SHARE_GPU="1")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--workload", workload,
-                          "--no-cpu-baseline", "--no-pmc", "--no-children"] + extra, env=env, capture_output=True, text=True, timeout=1500)
+                          "--full", "--no-cpu-baseline", "--no-pmc", "--no-children"] + extra, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 8 and line["rccl_ranks"] == 8 and line["collective_backend"] == "gloo", line

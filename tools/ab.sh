@@ -30,7 +30,7 @@ mkdir -p $OUT
 cp seal_amd/lib/libsealhip.so /tmp/libsealhip_default.so
 trap 'cp /tmp/libsealhip_default.so $REPO/seal_amd/lib/libsealhip.so' EXIT
 use_lib() { if [ "$1" = "default" ]; then cp /tmp/libsealhip_default.so seal_amd/lib/libsealhip.so; else cp seal_amd/lib/variants/$1.so seal_amd/lib/libsealhip.so; fi; }
-common="--no-cpu-baseline --no-pmc --no-verify --no-children"
+common="--full --no-cpu-baseline --no-pmc --no-verify --no-children"
 one() {  # label lib envs round
   local label=$1 libn=$2 envs=$3 r=$4 envargs
   envargs=$(echo "${envs:-SEALHIP_AB_NONE=1}" | tr ',' ' ')

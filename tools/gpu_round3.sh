@@ -2,7 +2,7 @@
 # Regenerates the measurements behind profiles/r03_* on one MI355X (run from the repo root on the GPU box:
 # `gpurun -- tools/gpu_round3.sh all`).  Output goes to gpurun_out/r03/; copy what you want judged into profiles/.
 #   tests     pytest -m gpu + smoke                                   -> pytest.txt, smoke.txt
-#   bench     python bench.py for the three workloads (CPU baseline + live PMC)  -> bench_*.json
+#   bench     python bench.py --full for the three workloads (CPU baseline + live PMC)  -> bench_*.json
 #   trace     rocprofv3 --kernel-trace --stats of a short bench        -> rocprof_bench_kernel_stats.txt, step_timeline.txt
 #   counters  PMC tables: the 2^16 NTT launch, the key-switch kernels, the single-launch integer transforms
 #   configs1  dispatch time line of the configs[1] chain {60,40,40,60}
@@ -17,8 +17,8 @@ for what in "$@"; do
     (timeout 1500 python -m pytest tests -m gpu -q -rs > $O/pytest.txt 2>&1; echo "rc=$?" >> $O/pytest.txt); tail -3 $O/pytest.txt
     (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?" >> $O/smoke.txt); tail -1 $O/smoke.txt ;;&
   bench|all)
-    timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-200 $O/bench.json
-    for w in bfv_c4 rotate_c5; do timeout 900 python bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.err; echo "bench $w rc=$?"; cut -c1-200 $O/bench_$w.json; done ;;&
+    timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-200 $O/bench.json
+    for w in bfv_c4 rotate_c5; do timeout 900 python bench.py --workload $w --full > $O/bench_$w.json 2> $O/bench_$w.err; echo "bench $w rc=$?"; cut -c1-200 $O/bench_$w.json; done ;;&
   trace|all)
     (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pmc --no-verify > $O/prof.log 2>&1)
     DB=$(find $O/prof -name "*.db" | head -1)

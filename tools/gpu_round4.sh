@@ -4,7 +4,7 @@
 #   order     tools/microbench/d2d_order: does the runtime order copy -> memset -> in-place kernel -> download on one stream?
 #   soak      tests/soak_cases.py for SOAK_SECONDS (default 150) in every host-copy mode
 #   tests     pytest -m gpu + smoke
-#   bench     python bench.py (default line: headline + the configs[3] / configs[4] children)
+#   bench     python bench.py --full (default line: headline + the configs[3] / configs[4] children)
 #   trace     rocprofv3 --kernel-trace --stats of a short bench + the step's time line
 set -u
 export TMPDIR=/tmp
@@ -35,7 +35,7 @@ PY
     (timeout 1500 python -m pytest tests -m gpu -q -rs > $O/pytest.txt 2>&1; echo "rc=$?" >> $O/pytest.txt); tail -4 $O/pytest.txt
     (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?" >> $O/smoke.txt); tail -1 $O/smoke.txt ;;
   bench)
-    timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-300 $O/bench.json ;;
+    timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-300 $O/bench.json ;;
   trace)
     (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pmc --no-verify --no-children > $O/prof.log 2>&1)
     DB=$(find $O/prof -name "*.db" | head -1)

@@ -10,7 +10,7 @@
 #   chunk2 chunktrace pipe mall nttvar wg8k pack packtrace p1bound lean1 pbbound fchunks invwant t2wg bfvtrace2 multi fuzzchunk
 #             the other A/Bs and traces of the round, each behind the profiles/r05_* file that quotes it
 #   tests     pytest -m gpu + smoke
-#   bench     python bench.py (default line)
+#   bench     python bench.py --full (default line)
 #   trace     rocprofv3 --kernel-trace --stats of a short bench + the step's time line
 # Library variants the A/B sections name (seal_amd/lib/variants/NAME.so; build first with tools/quick/build_variant.sh NAME "FLAGS"):
 #   prio1 / prio2   -DSEALHIP_PRIO=1 / =2            nt0      -DSEALHIP_KS_NT=0           p2w2 / p1w2  -DSEALHIP_FP_WAVES_P2=2 / _P1=2
@@ -119,7 +119,7 @@ for what in "$@"; do
     (timeout 1800 python -m pytest tests -m gpu -q -rs > $O/pytest.txt 2>&1; echo "rc=$?" >> $O/pytest.txt); tail -6 $O/pytest.txt
     (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?" >> $O/smoke.txt); tail -1 $O/smoke.txt ;;
   bench)
-    timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json ;;
+    timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json ;;
   trace)
     (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $REPO/bench.py --steps 3 --warmup 1 $common > $O/prof.log 2>&1)
     DB=$(find $O/prof -name "*.db" | head -1)

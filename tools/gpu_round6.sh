@@ -11,7 +11,7 @@
 #   fuzz      tools/quick/fuzz_deferred.py, FUZZ_SECONDS (default 300): random sequences with deferred tails and pending products
 #   multi     the two- and eight-process tests that share the one GPU (r06_pytest_multi.txt)
 #   tests     pytest -m gpu + smoke
-#   bench     python bench.py (default line)
+#   bench     python bench.py --full (default line)
 #   trace     rocprofv3 --kernel-trace --stats of a short bench + the step's time line
 # Microbenchmarks are built on the box: hipcc -O3 --offload-arch=gfx950 tools/microbench/X.hip -o tools/microbench/X
 set -u
@@ -52,7 +52,7 @@ import json,sys; j=json.loads(sys.stdin.read()); print('batch $b %-8s %.4f ms/st
     (timeout 1800 python -m pytest tests -m gpu -q -rs --durations=8 > $O/pytest.txt 2>&1; echo "rc=$?" >> $O/pytest.txt); tail -6 $O/pytest.txt
     (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?" >> $O/smoke.txt); tail -1 $O/smoke.txt ;;
   bench)
-    timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json ;;
+    timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json ;;
   trace)
     (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python $REPO/bench.py --steps 3 --warmup 1 $common > $O/prof.log 2>&1)
     DB=$(find $O/prof -name "*.db" | head -1)
