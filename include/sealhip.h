@@ -174,6 +174,25 @@ SHL_FUNC CKKSEncoder_Encode4(void *thisptr, double value_re, double value_im, ui
 SHL_FUNC CKKSEncoder_Encode5(void *thisptr, int64_t value, uint64_t *parms_id, void *destination);
 SHL_FUNC CKKSEncoder_Decode1(void *thisptr, void *plain, uint64_t *value_count, double *values, void *pool);
 SHL_FUNC CKKSEncoder_Decode2(void *thisptr, void *plain, uint64_t *value_count, double *values, void *pool);
+/* Whole batches in device memory (library extensions, like BatchEncoder_*Device).
+ * EncodeDevice: device_values = `batch` vectors of value_count <= N/2 doubles ([batch][value_count]) or, is_complex, of
+ *   value_count complex numbers ([batch][value_count][2], re and im interleaved as Encode2 takes them); shorter vectors are
+ *   zero-padded.  device_words = [batch][K][N] words, K = the number of primes at parms_id: item b equals, word for word, the
+ *   reference's encode(values_b, parms_id, scale).data() - the layout Decryptor_DecryptBatch writes for CKKS and
+ *   Plaintext_SetFromDevice takes.
+ * DecodeDevice: device_words = [batch][K][N] NTT-form words at parms_id (a data level) with `scale`, e.g. Decryptor_DecryptBatch's
+ *   output; it is not modified.  device_values = [batch][N/2] doubles (real parts) or, want_complex, [batch][N/2][2]: item b
+ *   equals the reference's decode of a plaintext with those words, parms_id and scale, bit for bit.
+ * Both run on the NULL stream and return after the work is done (encode synchronises once, at the end); batch == 0 does nothing.
+ * Arguments are checked as Encode / Decode and the reference check them (ckks.h:463-509, 686-716) - parms_id, scale,
+ * value_count, NULL pointers - and input and output must not overlap: SHL_E_INVALIDARG.  Encode's data-dependent checks (a value
+ * that is not finite; a coefficient that is NaN, infinite or too large for the level's modulus, ckks.h:525-548) are made per
+ * item on the device: SHL_E_INVALIDARG naming the first failing item, and the output words are then unspecified.  The batch is
+ * worked through in chunks whose scratch stays within 256 MiB (one item where an item needs more), returned to the pool. */
+SHL_FUNC CKKSEncoder_EncodeDevice(void *thisptr, const double *device_values, uint64_t value_count, uint64_t batch, bool is_complex,
+                                  uint64_t *parms_id, double scale, uint64_t *device_words);
+SHL_FUNC CKKSEncoder_DecodeDevice(void *thisptr, const uint64_t *device_words, uint64_t batch, uint64_t *parms_id, double scale,
+                                  bool want_complex, double *device_values);
 
 /* BatchEncoder (native/src/seal/c/batchencoder.h:16-30; seal::BatchEncoder::encode / decode, native/src/seal/batchencoder.cpp:97-447):
  * N integers modulo t <-> one plaintext polynomial through the NTT modulo t and the matrix index map.  Encode1 / Decode1 take

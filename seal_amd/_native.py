@@ -69,6 +69,7 @@ KeyGenerator_CreateRelinKeys KeyGenerator_CreateGaloisKeysFromSteps KeyGenerator
 SecretKey_Create SecretKey_Destroy SecretKey_Set SecretKey_UnsafeLoad SecretKey_Load Decryptor_Create Decryptor_Destroy
 Decryptor_Decrypt Decryptor_InvariantNoiseBudget Decryptor_DecryptBatchWords Decryptor_DecryptBatch
 CKKSEncoder_Create CKKSEncoder_Destroy CKKSEncoder_SlotCount CKKSEncoder_Encode1 CKKSEncoder_Encode2 CKKSEncoder_Encode3 CKKSEncoder_Encode4 CKKSEncoder_Encode5 CKKSEncoder_Decode1 CKKSEncoder_Decode2
+CKKSEncoder_EncodeDevice CKKSEncoder_DecodeDevice
 BatchEncoder_Create BatchEncoder_Destroy BatchEncoder_GetSlotCount BatchEncoder_Encode1 BatchEncoder_Encode2 BatchEncoder_Decode1
 BatchEncoder_Decode2 BatchEncoder_EncodeDevice BatchEncoder_DecodeDevice
 PublicKey_Create PublicKey_Destroy PublicKey_Set PublicKey_UnsafeLoad PublicKey_Load Encryptor_Encrypt Encryptor_EncryptZero1 Encryptor_EncryptZero2 Encryptor_EncryptZeroSymmetric2

@@ -551,6 +551,18 @@ class Plaintext:
         p.set_scale(scale)
         return p
 
+    def set_from_device(self, buf, count, offset=0, parms_id=None, scale=None):
+        """Plaintext_SetFromDevice: `count` words of a DeviceBuffer from word `offset` on (e.g. item b of encode_device's output:
+        offset b*K*N, count K*N); with parms_id the words are the NTT form at that level"""
+        if offset < 0 or offset + count > buf.words:
+            raise ValueError("words [%d, %d) are outside the buffer of %d words" % (offset, offset + count, buf.words))
+        N.check(N.lib().Plaintext_SetFromDevice(self._h, C.c_uint64(count), C.c_void_p(buf.ptr + 8 * offset)))
+        if parms_id is not None:
+            self.set_parms_id(parms_id)
+        if scale is not None:
+            self.set_scale(scale)
+        return self
+
     def coeff_count(self):
         v = C.c_uint64()
         N.check(N.lib().Plaintext_CoeffCount(self._h, C.byref(v)))
@@ -860,6 +872,31 @@ class CKKSEncoder:
         out = np.zeros(self.slot_count(), dtype=np.complex128 if complex_values else np.float64)
         fn = N.lib().CKKSEncoder_Decode2 if complex_values else N.lib().CKKSEncoder_Decode1
         N.check(fn(self._h, plain._h, C.byref(n), _p(out), None))
+        return out
+
+    def encode_device(self, values, batch, parms_id, scale, complex_values=False, count=None, out=None):
+        """values: DeviceBuffer of `batch` vectors of `count` doubles ([batch][count]) or complex numbers ([batch][count][2]);
+        count defaults to what the buffer holds.  -> DeviceBuffer of [batch][K][N] NTT-form plaintext words (`out` reuses one)"""
+        per = 2 if complex_values else 1
+        if count is None:
+            count = values.words // (batch * per) if batch else 0
+        try:
+            K = len(self.context.coeff_modulus_at(self.context.chain_index(parms_id)))
+        except N.SealHipError:
+            K = 1   # an unknown parms_id: the call below rejects it
+        out = out if out is not None else DeviceBuffer(max(batch * K * 2 * self.slot_count(), 1))
+        pid = (C.c_uint64 * 4)(*parms_id)
+        N.check(N.lib().CKKSEncoder_EncodeDevice(self._h, C.c_void_p(values.ptr), C.c_uint64(count), C.c_uint64(batch), C.c_bool(complex_values),
+                                                 pid, C.c_double(scale), C.c_void_p(out.ptr)))
+        return out
+
+    def decode_device(self, words, batch, parms_id, scale, complex_values=False, out=None):
+        """words: DeviceBuffer of [batch][K][N] NTT-form words (e.g. Decryptor.decrypt_batch's) -> DeviceBuffer of [batch][N/2]
+        doubles, or [batch][N/2][2] (re, im) with complex_values; read it with DeviceBuffer.to_array"""
+        out = out if out is not None else DeviceBuffer(max(batch * self.slot_count() * (2 if complex_values else 1), 1))
+        pid = (C.c_uint64 * 4)(*parms_id)
+        N.check(N.lib().CKKSEncoder_DecodeDevice(self._h, C.c_void_p(words.ptr), C.c_uint64(batch), pid, C.c_double(scale),
+                                                 C.c_bool(complex_values), C.c_void_p(out.ptr)))
         return out
 
 
@@ -1467,6 +1504,22 @@ class DeviceBuffer:
     def to_numpy(self, shape):
         out = np.zeros(shape, dtype=np.uint64)
         N.check(N.lib().shl_memcpy_d2h(_p(out), self._ptr, C.c_uint64(out.size * 8)))
+        return out
+
+    @staticmethod
+    def from_array(a):
+        """the bytes of a float64, complex128 or (u)int64 array, unchanged (from_numpy converts to uint64)"""
+        a = np.ascontiguousarray(a)
+        if a.dtype.itemsize not in (8, 16):
+            raise TypeError("from_array takes 8-byte or complex128 elements, not %s" % a.dtype)
+        b = DeviceBuffer(max(a.nbytes // 8, 1))
+        N.check(N.lib().shl_memcpy_h2d(b._ptr, _p(a), C.c_uint64(a.nbytes)))
+        return b
+
+    def to_array(self, shape, dtype=np.float64):
+        """the buffer's leading bytes as an array of `dtype` (float64 for decode_device's output; complex128 for its complex form)"""
+        out = np.zeros(shape, dtype=dtype)
+        N.check(N.lib().shl_memcpy_d2h(_p(out), self._ptr, C.c_uint64(out.nbytes)))
         return out
 
 

@@ -350,6 +350,23 @@ extern "C"
         SHL_CATCH
     }
 
+    SHL_FUNC CKKSEncoder_EncodeDevice(void *thisptr, const double *device_values, uint64_t value_count, uint64_t batch, bool is_complex,
+                                      uint64_t *parms_id, double scale, uint64_t *device_words)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        SHL_TRY
+        as<CKKSEncoder>(thisptr)->encode_device(device_values, (size_t)value_count, (size_t)batch, is_complex, parms_id, scale, device_words);
+        SHL_CATCH
+    }
+    SHL_FUNC CKKSEncoder_DecodeDevice(void *thisptr, const uint64_t *device_words, uint64_t batch, uint64_t *parms_id, double scale,
+                                      bool want_complex, double *device_values)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        SHL_TRY
+        as<CKKSEncoder>(thisptr)->decode_device(device_words, (size_t)batch, parms_id, scale, want_complex, device_values);
+        SHL_CATCH
+    }
+
     // ------------------------------------------------------------------ BatchEncoder (native/src/seal/c/batchencoder.h)
     SHL_FUNC BatchEncoder_Create(void *context, void **batch_encoder)
     {

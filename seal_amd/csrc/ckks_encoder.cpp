@@ -4,7 +4,9 @@
 #include <algorithm>
 #include <cmath>
 #include <complex>
+#include <cstdlib>
 #include <cstring>
+#include <string>
 
 namespace sealhip
 {
@@ -49,6 +51,30 @@ namespace sealhip
                 return std::conj(get_root(degree - index));
             }
         };
+        // encode_internal rejects a vector whose largest |coefficient| c has safe_ceil_log2_int(max(c, 1.0)) + 1 >=
+        // total_coeff_modulus_bit_count (ckks.h:525-548).  The largest c that passes, found once per level with the same libm
+        // log2 the reference calls (monotonic), lets the kernels decide per coefficient with one comparison: fail iff
+        // !(|c| <= limit), which also catches NaN and infinity.
+        double coeff_limit(int total_bits)
+        {
+            if (total_bits < 2)
+                return -1.0;
+            auto passes = [total_bits](double x) { return static_cast<int>(std::ceil(std::log2(x))) + 1 < total_bits; };
+            uint64_t lo, hi;
+            const double dlo = std::ldexp(1.0, total_bits - 2), dhi = std::ldexp(1.0, total_bits - 1);
+            std::memcpy(&lo, &dlo, 8);
+            std::memcpy(&hi, &dhi, 8);
+            while (hi - lo > 1) // passes(lo), !passes(hi); positive doubles order like their bit patterns
+            {
+                const uint64_t mid = lo + (hi - lo) / 2;
+                double x;
+                std::memcpy(&x, &mid, 8);
+                (passes(x) ? lo : hi) = mid;
+            }
+            double limit;
+            std::memcpy(&limit, &lo, 8);
+            return limit;
+        }
         uint32_t reverse_bits(uint64_t v, int bits)
         {
             uint64_t r = 0;
@@ -64,6 +90,8 @@ namespace sealhip
             throw std::invalid_argument("unsupported scheme");
         const size_t n = context.n();
         const int logn = context.log_n();
+        if (logn < 1 || logn > (int)(kFftLdsLog + kFftMaxColumnLog))
+            throw std::invalid_argument("poly_modulus_degree is not supported by the CKKS encoder");
         slots_ = n >> 1;
         std::vector<uint32_t> map(n);
         const uint64_t m = (uint64_t)n << 1;
@@ -89,16 +117,20 @@ namespace sealhip
             rp[1] = { 0, 1 };
             irp[1] = { 0, -1 };
         }
-        ck(hipMalloc(reinterpret_cast<void **>(&map_), n * 4), "hipMalloc ckks map");
+        // the kernels walk coefficient positions: position -> slot (< N/2) or conjugate slot (>= N/2)
+        std::vector<uint32_t> inv(n);
+        for (size_t i = 0; i < n; i++)
+            inv[map[i]] = (uint32_t)i;
+        ck(hipMalloc(reinterpret_cast<void **>(&inv_map_), n * 4), "hipMalloc ckks map");
         ck(hipMalloc(reinterpret_cast<void **>(&roots_), n * 16), "hipMalloc ckks roots");
         ck(hipMalloc(reinterpret_cast<void **>(&inv_roots_), n * 16), "hipMalloc ckks roots");
-        ck(hipMemcpy(map_, map.data(), n * 4, hipMemcpyHostToDevice), "upload ckks map");
+        ck(hipMemcpy(inv_map_, inv.data(), n * 4, hipMemcpyHostToDevice), "upload ckks map");
         ck(hipMemcpy(roots_, rp.data(), n * 16, hipMemcpyHostToDevice), "upload ckks roots");
         ck(hipMemcpy(inv_roots_, irp.data(), n * 16, hipMemcpyHostToDevice), "upload ckks roots");
     }
     CKKSEncoder::~CKKSEncoder()
     {
-        (void)hipFree(map_);
+        (void)hipFree(inv_map_);
         (void)hipFree(roots_);
         (void)hipFree(inv_roots_);
         for (auto &kv : consts_)
@@ -158,72 +190,124 @@ namespace sealhip
             return it->second;
         LevelConst lc;
         lc.dev = build_crt_constants(context_, lvl);
+        lc.coeff_limit = coeff_limit(lvl.total_coeff_modulus_bit_count);
         return consts_.emplace(lvl.chain_index, lc).first->second;
+    }
+
+    unsigned CKKSEncoder::block_log() const
+    {
+        const unsigned n_log = (unsigned)context_.log_n();
+        unsigned b = std::min(n_log, kFftLdsLog);
+        // development builds only (SEALHIP_AB_SWITCHES): a smaller LDS block, so that the emulated tests reach the two-pass split
+        // and every column-stage count at small N
+        if (const char *e = shl_ab_getenv("SEALHIP_CKKS_FFT_BLOCK_LOG"))
+            b = std::max<unsigned>(std::min<unsigned>((unsigned)std::atoi(e), b), std::max(1u, n_log > kFftMaxColumnLog ? n_log - kFftMaxColumnLog : 1u));
+        return b;
+    }
+    size_t CKKSEncoder::chunk_items(size_t item_words) const
+    {
+        size_t budget = kCkksBatchScratchBytes;
+        if (const char *e = shl_ab_getenv("SEALHIP_CKKS_SCRATCH_BYTES")) // development builds only: chunk edges at small N
+            budget = (size_t)std::strtoull(e, nullptr, 10);
+        const size_t items = item_words ? budget / (item_words * 8) : budget;
+        return std::max<size_t>(1, std::min<size_t>(items, 65535)); // items are the grid's y dimension
+    }
+    static bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+    {
+        const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+        return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+    }
+
+    // encode_internal's argument checks, in its order (ckks.h:463-509)
+    const Level &CKKSEncoder::encode_level(const uint64_t *parms_id, double scale, size_t value_count, bool have_values) const
+    {
+        const Level *lvl = parms_id ? context_.level_by_parms_id(parms_id) : nullptr;
+        if (!lvl)
+            throw std::invalid_argument("parms_id is not valid for encryption parameters");
+        if (!have_values && value_count > 0)
+            throw std::invalid_argument("values cannot be null");
+        if (value_count > slots_)
+            throw std::invalid_argument("values_size is too large");
+        if (!std::isnormal(scale) || scale <= 0 || (static_cast<int>(std::log2(scale)) + 1 >= lvl->total_coeff_modulus_bit_count))
+            throw std::invalid_argument("scale out of bounds");
+        return *lvl;
+    }
+    // decode_internal's (ckks.h:686-716): a plaintext at a data level with a sane scale
+    const Level &CKKSEncoder::decode_level(const uint64_t *parms_id, double scale) const
+    {
+        const Level *lvl = parms_id ? context_.level_by_parms_id(parms_id) : nullptr;
+        if (!lvl || lvl->chain_index > context_.first_level().chain_index)
+            throw std::invalid_argument("plain is not valid for encryption parameters");
+        if (!std::isnormal(scale) || scale <= 0 || (static_cast<int>(std::log2(scale)) >= lvl->total_coeff_modulus_bit_count))
+            throw std::invalid_argument("scale out of bounds");
+        return *lvl;
+    }
+
+    void CKKSEncoder::encode_batch(const double *values, size_t value_count, size_t batch, bool is_complex, const Level &lvl, double scale,
+                                   uint64_t *words) const
+    {
+        // ckks.h:510-680 for every item: placement + transform_from_rev + check + rounding / decomposition (k_ckks_encode), then
+        // the forward NTT of every item's K residue polynomials
+        const size_t n = context_.n(), K = lvl.K;
+        const unsigned n_log = (unsigned)context_.log_n(), b = block_log();
+        const LevelConst &lc = level_const(lvl);
+        const bool two_pass = b < n_log;
+        const size_t chunk = two_pass ? chunk_items(2 * n) : std::min<size_t>(batch, 65535);
+        const size_t vstride = value_count * (is_complex ? 2 : 1);
+        Scratch fail(1), mid(two_pass ? std::min(chunk, batch) * 2 * n : 1);
+        ck(hipMemsetAsync(fail.p, 0, 8, nullptr), "zero failure word");
+        for (size_t c0 = 0; c0 < batch; c0 += chunk)
+        {
+            const size_t items = std::min(chunk, batch - c0);
+            CkksEncodeArgs a{};
+            a.values = value_count ? values + c0 * vstride : nullptr;
+            a.value_count = value_count;
+            a.is_complex = is_complex;
+            a.inv_map = inv_map_;
+            a.inv_roots = inv_roots_;
+            a.mods = context_.dev_mods();
+            a.K = (unsigned)K;
+            a.fix = scale / static_cast<double>(n);
+            a.coeff_limit = lc.coeff_limit;
+            a.words = words + c0 * K * n;
+            a.mid = reinterpret_cast<double2 *>(mid.p);
+            a.fail = reinterpret_cast<unsigned *>(fail.p);
+            a.item0 = (unsigned)c0;
+            a.n_log = n_log;
+            a.block_log = b;
+            ck(k_ckks_encode(a, (unsigned)items, nullptr), "ckks encode");
+            NttBatch nb{};
+            nb.data = a.words;
+            nb.outer_stride = K * n;
+            nb.ncomp = (unsigned)K;
+            nb.nouter = (unsigned)items;
+            nb.prime_first = 0;
+            ck(ntt_forward(context_.ntt_tables(), nb, 0, nullptr), "ntt plaintexts");
+        }
+        unsigned f = 0;
+        ck(hipMemcpy(&f, fail.p, 4, hipMemcpyDeviceToHost), "encode sync");
+        if (f)
+        {
+            const unsigned code = ~f;
+            throw std::invalid_argument(std::string(code & 1 ? "encoded values are too large" : "values must be finite") + " (item " +
+                                        std::to_string(code >> 1) + ")");
+        }
     }
 
     void CKKSEncoder::encode(const double *values, size_t count, bool is_complex, const uint64_t *parms_id, double scale, Plaintext &dest) const
     {
-        // ckks.h:458-680
-        const Level *lvl = parms_id ? context_.level_by_parms_id(parms_id) : nullptr;
-        if (!lvl)
-            throw std::invalid_argument("parms_id is not valid for encryption parameters");
-        if (!values && count > 0)
-            throw std::invalid_argument("values cannot be null");
-        if (count > slots_)
-            throw std::invalid_argument("values_size is too large");
+        // ckks.h:458-680: a batch of one
         if (&dest.context() != &context_)
             throw std::invalid_argument("destination belongs to another context");
-        if (!std::isnormal(scale) || scale <= 0 || (static_cast<int>(std::log2(scale)) + 1 >= lvl->total_coeff_modulus_bit_count))
-            throw std::invalid_argument("scale out of bounds");
-        for (size_t i = 0; i < (is_complex ? 2 * count : count); i++)
-            if (!std::isfinite(values[i]))
-                throw std::invalid_argument("values must be finite");
-        const size_t n = context_.n(), K = lvl->K;
-        const unsigned n_log = (unsigned)context_.log_n();
-        std::vector<double> in(2 * count, 0.0);
-        for (size_t i = 0; i < count; i++)
-        {
-            in[2 * i] = is_complex ? values[2 * i] : values[i];
-            in[2 * i + 1] = is_complex ? values[2 * i + 1] : 0.0;
-        }
-        Scratch vin(count ? 2 * count : 1), conj(2 * n), aux(2);
-        double2 *cv = reinterpret_cast<double2 *>(conj.p);
-        ck(hipStreamSynchronize(nullptr), "encode sync");
-        ck(hipMemsetAsync(cv, 0, n * 16, nullptr), "zero values");
-        if (count)
-        {
-            ck(hipMemcpy(vin.p, in.data(), 2 * count * 8, hipMemcpyHostToDevice), "upload values");
-            ck(k_ckks_place(map_, reinterpret_cast<const double2 *>(vin.p), cv, n_log, (unsigned)count, nullptr), "place values");
-        }
-        // fft_handler_.transform_from_rev(conj_values, logn, inv_root_powers_, &fix) with fix = scale / n
-        const double fix = scale / static_cast<double>(n);
-        ck(hipMemcpy(aux.p, &fix, 8, hipMemcpyHostToDevice), "upload fix");
-        for (unsigned g = 0; g + 1 < n_log; g++)
-            ck(k_fft_gs_stage(cv, inv_roots_, n_log, g, 1, nullptr, nullptr), "fft stage");
-        ck(k_fft_gs_stage(cv, inv_roots_, n_log, n_log - 1, 1, reinterpret_cast<const double *>(aux.p), nullptr), "fft last stage");
-        // the largest coefficient decides the arithmetic width (ckks.h:525-548)
-        ck(hipMemsetAsync(aux.p + 1, 0, 8, nullptr), "zero max");
-        ck(k_max_abs_real(cv, n, reinterpret_cast<unsigned long long *>(aux.p + 1), nullptr), "max coefficient");
-        double max_coeff;
-        ck(hipMemcpy(&max_coeff, aux.p + 1, 8, hipMemcpyDeviceToHost), "download max");
-        if (std::isnan(max_coeff) || !std::isfinite(max_coeff))
-            throw std::invalid_argument("encoded values are too large");
-        const double mc = std::max<>(max_coeff, 1.0);
-        const int max_coeff_bit_count = static_cast<int>(std::ceil(std::log2(mc))) + 1; // util::safe_ceil_log2_int
-        if (max_coeff_bit_count >= lvl->total_coeff_modulus_bit_count)
-            throw std::invalid_argument("encoded values are too large");
+        const Level &lvl = encode_level(parms_id, scale, count, values != nullptr);
+        const size_t n = context_.n(), K = lvl.K, vw = count * (is_complex ? 2 : 1);
+        Scratch vin(vw ? vw : 1);
+        if (vw)
+            ck(hipMemcpy(vin.p, values, vw * 8, hipMemcpyHostToDevice), "upload values");
         uint64_t *slab = DevicePool::global().alloc_words(K * n);
         try
         {
-            ck(k_ckks_decompose(context_.dev_mods(), cv, slab, n_log, (unsigned)K, 1, max_coeff_bit_count <= 64 ? 64 : (max_coeff_bit_count <= 128 ? 128 : 0), nullptr), "decompose");
-            NttBatch b{};
-            b.data = slab;
-            b.outer_stride = K * n;
-            b.ncomp = (unsigned)K;
-            b.nouter = 1;
-            b.prime_first = 0;
-            ck(ntt_forward(context_.ntt_tables(), b, 0, nullptr), "ntt plaintext");
-            ck(hipStreamSynchronize(nullptr), "encode sync");
+            encode_batch(reinterpret_cast<const double *>(vin.p), count, 1, is_complex, lvl, scale, slab);
         }
         catch (...)
         {
@@ -231,8 +315,20 @@ namespace sealhip
             throw;
         }
         dest.adopt(slab, K * n, K * n);
-        dest.set_level(lvl);
+        dest.set_level(&lvl);
         dest.scale() = scale;
+    }
+    void CKKSEncoder::encode_device(const double *values, size_t value_count, size_t batch, bool is_complex, const uint64_t *parms_id, double scale,
+                                    uint64_t *words) const
+    {
+        const Level &lvl = encode_level(parms_id, scale, value_count, values != nullptr || !batch);
+        if (!batch)
+            return;
+        if (!words)
+            throw std::invalid_argument("destination cannot be null");
+        if (overlap(values, batch * value_count * (is_complex ? 16 : 8), words, batch * lvl.K * context_.n() * 8))
+            throw std::invalid_argument("values and destination overlap");
+        encode_batch(values, value_count, batch, is_complex, lvl, scale, words);
     }
 
     void CKKSEncoder::fill_constant(const Level &lvl, const std::vector<uint64_t> &residues, double scale, Plaintext &dest) const
@@ -327,49 +423,74 @@ namespace sealhip
         fill_constant(*lvl, residues, 1.0, dest);
     }
 
+    void CKKSEncoder::decode_batch(const uint64_t *words, size_t batch, const Level &lvl, double scale, bool want_complex, double *values) const
+    {
+        // ckks.h:717-789 for every item: the inverse NTT on a copy, then CRT composition + scaling + transform_to_rev + the slot
+        // gather (k_ckks_decode)
+        const size_t n = context_.n(), K = lvl.K;
+        const unsigned n_log = (unsigned)context_.log_n(), b = block_log();
+        const LevelConst &lc = level_const(lvl);
+        const bool two_pass = b < n_log;
+        const size_t chunk = chunk_items(K * n + (two_pass ? 2 * n : 0));
+        const size_t first = std::min(chunk, batch);
+        Scratch copy(first * K * n), mid(two_pass ? first * 2 * n : 1);
+        for (size_t c0 = 0; c0 < batch; c0 += chunk)
+        {
+            const size_t items = std::min(chunk, batch - c0);
+            ck(hipMemcpyAsync(copy.p, words + c0 * K * n, items * K * n * 8, hipMemcpyDeviceToDevice, nullptr), "copy words");
+            NttBatch nb{};
+            nb.data = copy.p;
+            nb.outer_stride = K * n;
+            nb.ncomp = (unsigned)K;
+            nb.nouter = (unsigned)items;
+            nb.prime_first = 0;
+            ck(ntt_inverse(context_.ntt_tables(), nb, 0, nullptr), "intt plaintexts");
+            CkksDecodeArgs a{};
+            a.residues = copy.p;
+            a.mods = context_.dev_mods();
+            a.punct = lc.dev;
+            a.inv_punct = reinterpret_cast<const ShoupOp *>(lc.dev + K * K + 2 * K);
+            a.q_words = lc.dev + K * K;
+            a.half_words = lc.dev + K * K + K;
+            a.inv_scale = double(1.0) / scale;
+            a.inv_map = inv_map_;
+            a.roots = roots_;
+            a.mid = reinterpret_cast<double2 *>(mid.p);
+            a.out = values + c0 * slots_ * (want_complex ? 2 : 1);
+            a.want_complex = want_complex;
+            a.K = (unsigned)K;
+            a.n_log = n_log;
+            a.block_log = b;
+            ck(k_ckks_decode(a, (unsigned)items, nullptr), "ckks decode");
+        }
+        ck(hipStreamSynchronize(nullptr), "decode sync"); // the scratch goes back to the pool
+    }
+
     void CKKSEncoder::decode(const Plaintext &plain, double *values, bool want_complex) const
     {
-        // ckks.h:683-789
+        // ckks.h:683-789: a batch of one
         if (&plain.context() != &context_ || (plain.is_ntt_form() && plain.coeff_count() != plain.level()->K * context_.n()))
             throw std::invalid_argument("plain is not valid for encryption parameters");
         if (!plain.is_ntt_form())
             throw std::invalid_argument("plain is not in NTT form");
         if (!values)
             throw std::invalid_argument("destination cannot be null");
-        const Level &lvl = *plain.level();
-        if (lvl.chain_index > context_.first_level().chain_index)
-            throw std::invalid_argument("plain is not valid for encryption parameters");
-        if (!std::isnormal(plain.scale()) || plain.scale() <= 0 ||
-            (static_cast<int>(std::log2(plain.scale())) >= lvl.total_coeff_modulus_bit_count))
-            throw std::invalid_argument("scale out of bounds");
-        const size_t n = context_.n(), K = lvl.K;
-        const unsigned n_log = (unsigned)context_.log_n();
-        const double inv_scale = double(1.0) / plain.scale();
-        const LevelConst &lc = level_const(lvl);
-        Scratch copy(K * n), res(2 * n), out(2 * slots_);
-        ck(hipStreamSynchronize(nullptr), "decode sync");
-        ck(hipMemcpyAsync(copy.p, plain.data(), K * n * 8, hipMemcpyDeviceToDevice, nullptr), "copy plain");
-        NttBatch b{};
-        b.data = copy.p;
-        b.outer_stride = K * n;
-        b.ncomp = (unsigned)K;
-        b.nouter = 1;
-        b.prime_first = 0;
-        ck(ntt_inverse(context_.ntt_tables(), b, 0, nullptr), "intt plaintext");
-        double2 *rv = reinterpret_cast<double2 *>(res.p);
-        ck(k_ckks_compose_scale(context_.dev_mods(), copy.p, lc.dev, reinterpret_cast<const ShoupOp *>(lc.dev + K * K + 2 * K), lc.dev + K * K,
-                                lc.dev + K * K + K, inv_scale, rv, n_log, (unsigned)K, 1, nullptr),
-           "crt compose");
-        // fft_handler_.transform_to_rev(res, logn, root_powers_)
-        for (int g = (int)n_log - 1; g >= 0; g--)
-            ck(k_fft_ct_stage(rv, roots_, n_log, (unsigned)g, 1, nullptr), "fft stage");
-        ck(k_ckks_gather(map_, rv, reinterpret_cast<double2 *>(out.p), n_log, nullptr), "gather slots");
-        std::vector<double> host(2 * slots_);
-        ck(hipMemcpy(host.data(), out.p, 2 * slots_ * 8, hipMemcpyDeviceToHost), "download values");
-        if (want_complex)
-            std::memcpy(values, host.data(), 2 * slots_ * 8);
-        else
-            for (size_t i = 0; i < slots_; i++)
-                values[i] = host[2 * i]; // from_complex<double>: the real part
+        const Level &lvl = decode_level(plain.level()->parms_id, plain.scale());
+        const size_t words = slots_ * (want_complex ? 2 : 1);
+        Scratch out(words);
+        decode_batch(plain.data(), 1, lvl, plain.scale(), want_complex, reinterpret_cast<double *>(out.p));
+        ck(hipMemcpy(values, out.p, words * 8, hipMemcpyDeviceToHost), "download values");
+    }
+    void CKKSEncoder::decode_device(const uint64_t *words, size_t batch, const uint64_t *parms_id, double scale, bool want_complex,
+                                    double *values) const
+    {
+        const Level &lvl = decode_level(parms_id, scale);
+        if (!batch)
+            return;
+        if (!words || !values)
+            throw std::invalid_argument(words ? "destination cannot be null" : "plain cannot be null");
+        if (overlap(words, batch * lvl.K * context_.n() * 8, values, batch * slots_ * (want_complex ? 16 : 8)))
+            throw std::invalid_argument("plain and destination overlap");
+        decode_batch(words, batch, lvl, scale, want_complex, values);
     }
 } // namespace sealhip

@@ -13,6 +13,10 @@ namespace sealhip
     // (Q / q_j)^-1 mod q_j as K Shoup pairs.  The caller owns the block (hipFree).
     uint64_t *build_crt_constants(const Context &context, const Level &lvl);
 
+    // The batched forms work through the batch in chunks whose scratch (the pass-to-pass vectors, and for decode the copy of the
+    // words the inverse NTT runs on) stays within this many bytes; an item that needs more alone is a chunk of one.
+    constexpr size_t kCkksBatchScratchBytes = size_t(256) << 20;
+
     class CKKSEncoder
     {
     public:
@@ -30,17 +34,31 @@ namespace sealhip
         void encode_integer(int64_t value, const uint64_t *parms_id, Plaintext &destination) const;
         // CKKSEncoder::decode (ckks.h:683-789): N/2 complex numbers as (re, im) pairs, or their real parts
         void decode(const Plaintext &plain, double *values, bool want_complex) const;
+        // whole batches in device memory (CKKSEncoder_EncodeDevice / _DecodeDevice, include/sealhip.h): encode writes [batch][K][N]
+        // NTT-form words, item b = encode(values_b, parms_id, scale).data(); decode reads such words and writes [batch][N/2] reals
+        // or [batch][N/2][2] (re, im).  Null stream; both return after the work is done.
+        void encode_device(const double *values, size_t value_count, size_t batch, bool is_complex, const uint64_t *parms_id, double scale,
+                           uint64_t *words) const;
+        void decode_device(const uint64_t *words, size_t batch, const uint64_t *parms_id, double scale, bool want_complex, double *values) const;
 
     private:
         void fill_constant(const Level &lvl, const std::vector<uint64_t> &residues, double scale, Plaintext &destination) const;
         struct LevelConst
         {
             uint64_t *dev = nullptr; // punct [K][K] | q_words [K] | half_words [K] | inv_punct [K] Shoup pairs
+            double coeff_limit = 0;  // the largest |coefficient| encode_internal accepts at this level (see coeff_limit())
         };
         const LevelConst &level_const(const Level &lvl) const;
+        const Level &encode_level(const uint64_t *parms_id, double scale, size_t value_count, bool have_values) const;
+        const Level &decode_level(const uint64_t *parms_id, double scale) const;
+        void encode_batch(const double *values, size_t value_count, size_t batch, bool is_complex, const Level &lvl, double scale,
+                          uint64_t *words) const;
+        void decode_batch(const uint64_t *words, size_t batch, const Level &lvl, double scale, bool want_complex, double *values) const;
+        unsigned block_log() const;
+        size_t chunk_items(size_t item_words) const;
         const Context &context_;
         size_t slots_;
-        uint32_t *map_ = nullptr;
+        uint32_t *inv_map_ = nullptr;
         double2 *roots_ = nullptr, *inv_roots_ = nullptr;
         mutable std::mutex mu_;
         mutable std::map<size_t, LevelConst> consts_;
