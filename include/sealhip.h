@@ -568,7 +568,7 @@ SHL_FUNC SealHip_PoolStats(uint64_t *bytes_held, uint64_t *cross_stream_waits);
  *     device reports a memory fault: its handler on the stack tells that case from a C++ one) and then lets the abort proceed
  *     with the default disposition.  A later call only changes the path. */
 SHL_FUNC SealHip_InstallAbortTrace(const char *path);
-/* Environment.  The product library reads nine variables, each exercised by a test; everything else that earlier
+/* Environment.  The product library reads eleven variables, each exercised by a test; everything else that earlier
  * rounds could switch at run time (superseded kernels, fork / no-fork of the side streams, ...) only exists in development
  * builds made with -DSEALHIP_AB_SWITCHES (seal_amd/csrc/modarith.h: shl_ab_getenv).
  *   SEALHIP_NO_FP=1                  every prime on the 64-bit integer back end (no exact double-precision arithmetic for
@@ -584,7 +584,11 @@ SHL_FUNC SealHip_InstallAbortTrace(const char *path);
  *   SEALHIP_KS_CHUNK=<items>         chunk size of a key switch over a large batch (below; 0 = never cut; default: the items
  *                                    that make 8192 pass-2 workgroups - 32 at N = 2^16 with 16 moduli)
  *   SEALHIP_KS_LANES=<1..4>          streams the chunks are dealt to (default 3; 1 = one after the other on the evaluator's stream)
- *   SEALHIP_KS_SCRATCH_CAP_MIB=<n>   upper bound of the key switch's intermediate (default 16384); chunk / lanes shrink to fit */
+ *   SEALHIP_KS_SCRATCH_CAP_MIB=<n>   upper bound of the key switch's intermediate (default 16384); chunk / lanes shrink to fit
+ *   SEALHIP_LAZY_PRODUCT=0           tensor products are formed when Evaluator_Multiply is called (no deferred products, below)
+ *   SEALHIP_LAZY_PRODUCT_MIN_WGS=<n> a product is deferred when its key switch would launch more than <n> second-pass workgroups
+ *                                    (default 1024: the batches whose key switch runs as one digit group); tests reach the
+ *                                    deferred form at small batches with 0, together with SEALHIP_KS_SPLIT=1 */
 /* Chunked key switching (round 5).  switch_key_inplace needs K (K + 1) half-transformed digits per ciphertext between its two
  * kernels (126 MB at N = 2^16, K = 15).  For a batch of 1.5 chunks or more (2^13 <= N <= 2^16, register-order keys, one digit group) the batch is cut
  * into chunks dealt round-robin to `lanes` streams forked from and joined to the evaluator's stream: the intermediate held

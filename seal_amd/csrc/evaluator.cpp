@@ -56,8 +56,7 @@ namespace sealhip
         }
         // the sums were produced on this evaluator's stream: the tail runs there too; a caller working on another stream
         // (another evaluator, a host copy) continues only when it is done
-        static const bool trace = shl_ab_getenv("SEALHIP_KS_TRACE") != nullptr; // tests: which tail ran
-        if (trace)
+        if (ks_switches().trace) // tests: which tail ran
             std::fprintf(stderr, t.with_addend ? "[ks] plain tail, addend in the sums\n" : "[ks] plain tail\n");
         g_tail_plain++;
         try
@@ -84,17 +83,17 @@ namespace sealhip
         formed = g_prod_formed.load();
         dropped = g_prod_dropped.load();
     }
-    // the launcher's rule: CKKS at a two-pass size, a batch whose key switch runs un-split (the fused relinearisation's configuration)
+    // CKKS at a two-pass size, a batch whose key switch runs un-split (the fused relinearisation's configuration) - asked of the shape's
+    // half of the route's rule, no key being known yet.  SEALHIP_LAZY_PRODUCT_MIN_WGS moves the threshold of that rule (1024 pass-2
+    // workgroups): tests reach the fused path at small batches with it, together with SEALHIP_KS_SPLIT=1
     bool Evaluator::may_defer_product(const Level &lvl, size_t batch) const
     {
-        const char *lazy_env = std::getenv("SEALHIP_LAZY_PRODUCT"); // (read per call: the tests switch it)
-        if (lazy_env && std::atoi(lazy_env) == 0)
+        if (!KsSwitches::lazy_product() || capturing_ || transparent_check_ || lvl.K < 2 || !ntt2_supports(context_.log_n()))
             return false;
-        // (SEALHIP_LAZY_PRODUCT_MIN_WGS: tests reach the fused path at small batches together with SEALHIP_KS_SPLIT=1)
-        const char *min_env = std::getenv("SEALHIP_LAZY_PRODUCT_MIN_WGS");
-        const size_t min_wgs = min_env ? (size_t)std::atol(min_env) : 1024;
-        return !capturing_ && !transparent_check_ && lvl.K >= 2 && ntt2_supports(context_.log_n()) &&
-               batch * (lvl.K + 1) * (context_.n() >> 12) > min_wgs;
+        size_t min_wgs;
+        if (KsSwitches::lazy_product_min_wgs(min_wgs))
+            return batch * (lvl.K + 1) * (context_.n() >> 12) > min_wgs;
+        return ks_shape_split(lvl, batch) <= 1;
     }
     void Evaluator::defer_product(Ciphertext &dest, const Ciphertext *x, const Ciphertext *y, uint64_t *own) const
     {
@@ -418,6 +417,16 @@ namespace sealhip
         return !(!std::isnormal(scale) || scale <= 0 || (static_cast<int>(std::log2(scale)) >= bound));
     }
 
+    void Evaluator::check_native_form(const Ciphertext &e) const
+    {
+        const Scheme scheme = context_.scheme();
+        if (scheme == Scheme::bfv && e.is_ntt_form())
+            throw std::invalid_argument("BFV encrypted cannot be in NTT form");
+        if (scheme == Scheme::ckks && !e.is_ntt_form())
+            throw std::invalid_argument("CKKS encrypted must be in NTT form");
+        if (scheme == Scheme::bgv && !e.is_ntt_form())
+            throw std::invalid_argument("BGV encrypted must be in NTT form");
+    }
     void Evaluator::check_valid(const Ciphertext &ct, const char *what) const
     {
         // is_metadata_valid_for + is_buffer_valid (valcheck.cpp:81-139, 221-237)
@@ -994,11 +1003,10 @@ namespace sealhip
             const bool defer = may_defer_product(lvl, e1.batch());
             // (development builds, bound only: SEALHIP_AB_SKIP_TENSOR leaves the product unwritten after two real calls - what fusing the
             // tensor product into its consumers could save at most, profiles/r06_lazy_product.txt)
-            static const bool skip_tensor = shl_ab_getenv("SEALHIP_AB_SKIP_TENSOR") != nullptr;
             static std::atomic<unsigned> tensor_calls{ 0 };
             if (defer)
                 defer_product(dest, &e1, &e2, nullptr);
-            else if (!skip_tensor || tensor_calls.fetch_add(1) < 2)
+            else if (!ks_switches().skip_tensor || tensor_calls.fetch_add(1) < 2)
                 ck(k_ckks_multiply_2x2(context_.dev_mods(), context_.ntt_tables().fpd, nullptr, xw, yw, dest.data(), g, stream_), "ckks_multiply");
             dest.is_ntt_form() = true;
             dest.correction_factor() = 1;

@@ -62,6 +62,40 @@ namespace sealhip
     // chunked key switching (evaluator_keyswitch.cpp): calls that ran in chunks, chunks issued, largest intermediate held since the previous query (words)
     void ks_chunk_stats(uint64_t *calls, uint64_t *chunks, uint64_t *scratch_words_max);
 
+    // ---- what a key switch decides before it launches (evaluator_keyswitch.cpp: Evaluator::ks_route - the one place that decides)
+    // chunks of a large batch dealt to forked lanes (evaluator_keyswitch.cpp: ks_plan)
+    struct KsPlan
+    {
+        unsigned chunk; // items per chunk
+        unsigned lanes; // streams the chunks are dealt to (1 = everything on the evaluator's stream)
+        unsigned chunks(unsigned batch) const { return (batch + chunk - 1) / chunk; }
+    };
+    struct KsRoute
+    {
+        bool fused = false; // the key is in register order (which it only is at a two-pass size): ks1t + ks2, not transform + inner product
+        unsigned split = 1; // in-launch digit groups (small batches, fused only); `split` sum buffers leave the launch
+        bool fold = false;  // CKKS, fused: the sums leave as c + S P^-1 - from ks2's epilogue (split 1) or the pass that adds the groups
+        bool defer = false; // CKKS and BFV at the two-pass sizes: the mod-down is left pending (LazyTail)
+        KsPlan plan{ 0, 1 };
+        unsigned j0 = 0, j1 = 0; // the digits this call sums (a rank's share in the digit-parallel forms, else all K)
+        // the un-split folded launch is the only one whose kernels can form or permute their operands as they load them:
+        bool takes_product() const { return fused && fold && split == 1; } // may a pending tensor product be consumed here
+        bool reads_through_map() const;                                    // may a rotation's operand be read through the index map here
+    };
+    // What rides along into the sums of an un-split folded key switch (KsFusedArgs::fold_*); anything but nothing() needs such a route.
+    struct KsAddend
+    {
+        bool folds = false;                // false: nothing rides along
+        bool c1_zero = false;              // the second polynomial is zero and has NOT been written (always so for a rotation's operand)
+        uint32_t galois_elt = 0;           // != 0: c0 and the target are the UNPERMUTED polynomials of a rotation's operand, read
+        const uint64_t *c0 = nullptr;      //       through the automorphism's index map; else the ciphertext's own planes
+        const LazyProduct *prod = nullptr; // the operands of a tensor product that was never stored, instead of planes
+        static KsAddend nothing() { return {}; }
+        static KsAddend planes(bool c1_zero_unwritten = false) { return { true, c1_zero_unwritten, 0, nullptr, nullptr }; }
+        static KsAddend galois(uint32_t elt, const uint64_t *operand_c0) { return { true, true, elt, operand_c0, nullptr }; }
+        static KsAddend product(const LazyProduct &p) { return { true, false, 0, nullptr, &p }; }
+    };
+
     class Ciphertext
     {
     public:
@@ -329,37 +363,10 @@ namespace sealhip
         static size_t galois_index(uint32_t galois_elt);   // GaloisKeys::get_index (galoiskeys.h:48)
         uint32_t galois_elt_from_step(int step) const;      // GaloisTool::get_elt_from_step (galois.cpp:53)
 
-        // switch_key_inplace (evaluator.cpp:2561): encrypted (size >= 2) += KS(target), target = one
-        // plane [batch][K][N] in the scheme's native form.
-        // c1_zero_unwritten: the caller's ciphertext is (c0, 0) and its second polynomial has NOT been written (rotations); it is zeroed here
-        // only when somebody is going to read it
-        // galois_elt / galois_c0 (round 6, rotations at the batches that fold the addend into un-split sums, ks_gathers()): `target` and
-        // galois_c0 are the UNPERMUTED c1 and c0 of the operand, read through the NTT-domain automorphism inside the key switch's
-        // kernels; encrypted's own polynomials are then never read
-        void switch_key_inplace(Ciphertext &encrypted, const uint64_t *target, const KSwitchKeys &keys, size_t key_index, bool c1_zero_unwritten = false,
-                                uint32_t galois_elt = 0, const uint64_t *galois_c0 = nullptr) const;
-        // the rules of switch_key_inplace, for callers that prepare their operands differently per path
-        unsigned ks_split(const Ciphertext &encrypted, const KSwitchKeys &keys, size_t key_index) const;
-        bool ks_folds(const KSwitchKeys &keys, size_t key_index, unsigned K) const;
         // the two halves of switch_key_inplace for digit-parallel key switching over several GPUs:
         // acc = [batch][2][K+1][N] words (switch_key_acc_words); partial fills it with the canonical partial sums of
         // the digits [j0, j1); finish reduces the sum of `parts` such buffers and applies the mod-down to encrypted.
         size_t switch_key_acc_words(const Ciphertext &encrypted) const;
-        // split > 1 (fused path only): the digit range is cut into `split` in-launch groups and acc holds `split` buffers
-        // (ntt2_kernels.h: KsFusedArgs::parts); the caller adds them with k_keyswitch_reduce(..., local_parts = split)
-        // product (round 6, CKKS, fused path, split 1, fold_addend): `encrypted` is a tensor product that was never stored - `target`
-        // is where its third polynomial is WRITTEN (by the inverse transform that forms it from the operands), the two leading
-        // polynomials are formed in the key switch's epilogue (KsFusedArgs::fold_x)
-        void switch_key_partial(const Ciphertext &encrypted, const uint64_t *target, const KSwitchKeys &keys, size_t key_index,
-                                unsigned j0, unsigned j1, uint64_t *acc, unsigned split = 1, bool fold_addend = false,
-                                const LazyProduct *product = nullptr, bool addend1_zero = false, uint32_t galois_elt = 0,
-                                const uint64_t *galois_c0 = nullptr) const;
-        // fold_addend (CKKS, fused path, the full digit range, split 1): the data-prime components of acc leave as c + S P^-1
-        // (KsFusedArgs::fold_c0); the matching finish call says so with acc_has_addend
-        // may_defer (relinearize_finish / apply_galois_finish / the in-library exchange): CKKS at the two-pass sizes copies the reduced
-        // sums - with the ciphertext's words added - into a block of its own and leaves the mod-down pending like switch_key_inplace
-        // does (LazyTail), so that a rescale that follows folds both divisions; `acc` is not referenced after the call returns
-        void switch_key_finish(Ciphertext &encrypted, uint64_t *acc, unsigned parts, bool acc_has_addend = false, bool may_defer = false) const;
         // relinearize (size 3 -> 2) and apply_galois (size 2) split the same way: *_partial leaves `encrypted` ready for
         // the finish call (for apply_galois: c0 <- pi(c0), c1 <- 0) and writes this rank's partial sums to acc
         void relinearize_partial(Ciphertext &encrypted, const KSwitchKeys &relin_keys, unsigned j0, unsigned j1, uint64_t *acc) const;
@@ -403,6 +410,7 @@ namespace sealhip
     private:
         friend class Encryptor; // public-key encryption ends with one modulus switch from the level above (encryptor.cpp:139-186)
         void check_valid(const Ciphertext &ct, const char *what) const;
+        void check_native_form(const Ciphertext &ct) const; // coefficient form for BFV, NTT form for CKKS and BGV
         bool scale_within_bounds(double scale, const Level &lvl) const;
         void bfv_multiply(Ciphertext &e1, const Ciphertext &e2) const;
         void bfv_multiply_to(const Ciphertext &e1, const Ciphertext &e2, Ciphertext &dst) const;
@@ -423,6 +431,26 @@ namespace sealhip
         void rotate_internal(const Ciphertext &encrypted, int steps, const KSwitchKeys &galois_keys, Ciphertext &destination) const;
         void conjugate_internal(Ciphertext &encrypted, const KSwitchKeys &galois_keys) const;
         void throw_if_transparent(const Ciphertext &ct) const;
+        // ---- the key switch proper (evaluator_keyswitch.cpp).  ks_route decides everything once; the callers branch on it and hand the same
+        // object down.  digit_parallel: the sums of [j0, j1) leave for the caller's exchange - one group, nothing folded, no tail here.
+        KsRoute ks_route(const Level &lvl, size_t batch) const; // the half no key changes: defer, and fold as a register-order key would
+        KsRoute ks_route(const Level &lvl, size_t batch, const KSwitchKeys &keys, size_t key_index, unsigned j0, unsigned j1,
+                         bool digit_parallel = false) const;
+        unsigned ks_shape_split(const Level &lvl, size_t batch) const; // digit groups a batch of this shape would run in (before cap and override)
+        // switch_key_inplace (evaluator.cpp:2561): encrypted (size >= 2) += KS(target), target = one plane [batch][K][N] in the scheme's
+        // native form.  `addend` says what the caller HAS (its own planes, c1 possibly zero and unwritten - zeroed here only when
+        // somebody is going to read it; or a rotation's unpermuted operand); the route says whether it is folded.
+        void switch_key_inplace(Ciphertext &encrypted, const uint64_t *target, const KSwitchKeys &keys, size_t key_index, const KsRoute &route,
+                                const KsAddend &addend = KsAddend::planes()) const;
+        // its two halves.  partial: acc = route.split buffers of [batch][2][K+1][N] words (switch_key_acc_words) <- the canonical partial
+        // sums of the digits [route.j0, route.j1), each group's in its own buffer (KsFusedArgs::parts), `addend` folded in.  With a
+        // product `target` only names the third polynomial: it is formed from the operands where it is used.
+        void switch_key_partial(const Ciphertext &encrypted, const uint64_t *target, const KSwitchKeys &keys, size_t key_index, uint64_t *acc,
+                                const KsRoute &route, const KsAddend &addend = KsAddend::nothing()) const;
+        // finish: reduces the sum of `parts` buffers and applies the mod-down to encrypted.  acc_has_addend: the sums were folded.
+        // may_defer (the digit-parallel finishes): where the route defers and folds, the pass that reduces the sums adds the ciphertext's
+        // words into a block of the pool's and the mod-down stays pending; `acc` is not referenced after the call returns
+        void switch_key_finish(Ciphertext &encrypted, uint64_t *acc, unsigned parts, bool acc_has_addend = false, bool may_defer = false) const;
         void switch_key_exchange_finish(Ciphertext &encrypted, uint64_t *acc, Comm &comm, KsExchange how) const;
         const uint32_t *ks_comp_prime(unsigned K) const;
         int ks_class_hint(unsigned K) const;

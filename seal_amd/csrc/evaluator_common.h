@@ -104,6 +104,20 @@ namespace sealhip
         }
     } // namespace
 
+    // The key switch's environment switches: read here and nowhere else (defined, with the table of names, in evaluator_keyswitch.cpp).
+    struct KsSwitches
+    {
+        bool eager_tail, no_fold, class_fork, trace, galois_kernels, skip_tensor; // read once per process: ks_switches()
+        // read at every call (tests flip these inside one process)
+        static unsigned split(unsigned chosen);  // SEALHIP_KS_SPLIT, else `chosen`
+        static unsigned chunk(unsigned chosen);  // SEALHIP_KS_CHUNK, else `chosen`
+        static unsigned lanes();                 // SEALHIP_KS_LANES, else 3
+        static unsigned scratch_cap_mib();       // SEALHIP_KS_SCRATCH_CAP_MIB, else 16384
+        static bool lazy_product();              // SEALHIP_LAZY_PRODUCT: false only when set to 0
+        static bool lazy_product_min_wgs(size_t &min_wgs); // SEALHIP_LAZY_PRODUCT_MIN_WGS: false = not set
+    };
+    const KsSwitches &ks_switches();
+
     // deferred key-switch tails: counters behind SealHip_TailStats (defined in evaluator.cpp)
     extern std::atomic<uint64_t> g_tail_folded, g_tail_plain, g_tail_dropped;
 } // namespace sealhip

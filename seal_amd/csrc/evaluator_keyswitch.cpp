@@ -17,17 +17,6 @@ namespace sealhip
         // What the lanes buy is the launch tails of the chunks (one lane: -2.1 %; three: +0.7 % +- 0.7 against one launch over the
         // batch) - NOT an overlap of the two passes: both need the vector ALU, side by side each runs slower by what the other
         // takes, staggered or in lockstep (profiles/r05_ks_chunked.txt).
-        struct KsPlan
-        {
-            unsigned chunk; // items per chunk
-            unsigned lanes; // streams the chunks are dealt to (1 = everything on the evaluator's stream)
-            unsigned chunks(unsigned batch) const { return (batch + chunk - 1) / chunk; }
-        };
-        unsigned env_unsigned(const char *name, unsigned fallback)
-        {
-            const char *v = std::getenv(name);
-            return v && *v ? (unsigned)std::strtoul(v, nullptr, 10) : fallback;
-        }
         // words_per_item = (K + 1) K N; wgs_per_item = pass-2 workgroups of one ciphertext ((K + 1) tiles)
         KsPlan ks_plan(unsigned batch, size_t words_per_item, size_t wgs_per_item, bool may_chunk, bool may_lane)
         {
@@ -37,8 +26,8 @@ namespace sealhip
             // a chunk must still fill the chip several times over (pass 2 keeps 512 workgroups resident; the kernels reach
             // their rate from 18 - 64 C5 ciphertexts on, profiles/r03_ks_batch_sweep.txt): >= 8192 pass-2 workgroups
             unsigned chunk = (unsigned)((8192 + wgs_per_item - 1) / (wgs_per_item ? wgs_per_item : 1));
-            chunk = env_unsigned("SEALHIP_KS_CHUNK", chunk < 8 ? 8 : chunk);
-            unsigned lanes = env_unsigned("SEALHIP_KS_LANES", 3);
+            chunk = KsSwitches::chunk(chunk < 8 ? 8 : chunk);
+            unsigned lanes = KsSwitches::lanes();
             if (lanes < 1 || !may_lane)
                 lanes = 1;
             if (lanes > 4)
@@ -46,7 +35,7 @@ namespace sealhip
             if (chunk == 0 || 2 * chunk > batch + chunk / 2) // fewer than ~1.5 chunks: not worth cutting
                 return p;
             // scratch cap (default 16 GiB): lanes x chunk items of the intermediate
-            const double cap = (double)env_unsigned("SEALHIP_KS_SCRATCH_CAP_MIB", 16384) * 1048576.0;
+            const double cap = (double)KsSwitches::scratch_cap_mib() * 1048576.0;
             while (chunk > 1 && (double)lanes * chunk * words_per_item * 8.0 > cap)
             {
                 if (lanes > 2)
@@ -138,6 +127,108 @@ namespace sealhip
             *scratch_words_max = g_ks_scratch_words_max.exchange(0); // ... since the previous query
     }
 
+    // ---- The key switch's environment switches.  This is the only place that reads them.
+    //   name                           build        read      set by
+    //   SEALHIP_KS_SPLIT               product      per call  tests/parity_cases.py, test_emu_parity.py, test_gpu_parity.py, test_fuzz.py
+    //   SEALHIP_KS_CHUNK               product      per call  tests/parity_cases.py, test_emu_parity.py
+    //   SEALHIP_KS_LANES               product      per call  tests/parity_cases.py, test_emu_parity.py
+    //   SEALHIP_KS_SCRATCH_CAP_MIB     product      per call  tests/parity_cases.py, test_gpu_parity.py, test_dist_gloo.py; bench.py's launcher
+    //   SEALHIP_LAZY_PRODUCT           product      per call  tests/parity_cases.py
+    //   SEALHIP_LAZY_PRODUCT_MIN_WGS   product      per call  tests/parity_cases.py, test_fuzz.py
+    //   SEALHIP_KS_EAGER_TAIL          product      once      tests/parity_cases.py, dist_worker.py (fresh processes)
+    //   SEALHIP_KS_NO_FOLD             development  once      tests/test_emu_parity.py (fresh process)
+    //   SEALHIP_KS_TRACE               development  once      tests/test_emu_parity.py
+    //   SEALHIP_KS_CLASS_FORK          development  once      - (A/B: the integer class of a chunk on the launcher's side stream)
+    //   SEALHIP_GALOIS_KERNELS         development  once      - (A/B: rotations always through the permutation kernels)
+    //   SEALHIP_AB_SKIP_TENSOR         development  once      - (bound only: the tensor product left unwritten)
+    // (development = only in builds made with -DSEALHIP_AB_SWITCHES, modarith.h: shl_ab_getenv)
+    const KsSwitches &ks_switches()
+    {
+        static const KsSwitches sw{ std::getenv("SEALHIP_KS_EAGER_TAIL") != nullptr,   shl_ab_getenv("SEALHIP_KS_NO_FOLD") != nullptr,
+                                    shl_ab_getenv("SEALHIP_KS_CLASS_FORK") != nullptr, shl_ab_getenv("SEALHIP_KS_TRACE") != nullptr,
+                                    shl_ab_getenv("SEALHIP_GALOIS_KERNELS") != nullptr, shl_ab_getenv("SEALHIP_AB_SKIP_TENSOR") != nullptr };
+        return sw;
+    }
+    static unsigned env_unsigned(const char *name, unsigned fallback)
+    {
+        const char *v = std::getenv(name);
+        return v && *v ? (unsigned)std::strtoul(v, nullptr, 10) : fallback;
+    }
+    unsigned KsSwitches::split(unsigned chosen)
+    {
+        const char *v = std::getenv("SEALHIP_KS_SPLIT");
+        return v ? (unsigned)std::atoi(v) : chosen;
+    }
+    unsigned KsSwitches::chunk(unsigned chosen) { return env_unsigned("SEALHIP_KS_CHUNK", chosen); }
+    unsigned KsSwitches::lanes() { return env_unsigned("SEALHIP_KS_LANES", 3); }
+    unsigned KsSwitches::scratch_cap_mib() { return env_unsigned("SEALHIP_KS_SCRATCH_CAP_MIB", 16384); }
+    bool KsSwitches::lazy_product()
+    {
+        const char *v = std::getenv("SEALHIP_LAZY_PRODUCT");
+        return !(v && std::atoi(v) == 0);
+    }
+    bool KsSwitches::lazy_product_min_wgs(size_t &min_wgs)
+    {
+        const char *v = std::getenv("SEALHIP_LAZY_PRODUCT_MIN_WGS");
+        if (v)
+            min_wgs = (size_t)std::atol(v);
+        return v != nullptr;
+    }
+
+    // ---- The route: which of the key switch's forms a call takes.  Decided here, once; everybody else asks the object.
+    // Small batches do not fill the chip: one workgroup per (target modulus, tile, batch item) is 16 (K+1) workgroups per
+    // ciphertext at N = 2^16, each looping over all K digits, and only 2 x 16 of them for the two 60-bit moduli.  Cut the
+    // digit loop into `split` in-launch groups (their partial sums are added by a reduce pass): single-ciphertext
+    // latency of multiply+relinearize+rescale at C5 0.63 -> 0.40 ms (profiles/HISTORY.md section 5, "Small batches / latency").
+    // This is the shape's half of the rule - also asked at multiply time, before any key is known (may_defer_product).
+    unsigned Evaluator::ks_shape_split(const Level &lvl, size_t batch) const
+    {
+        const size_t wgs = batch * (size_t)(lvl.K + 1) * (context_.n() >> 12);
+        return (unsigned)(2048 / (wgs ? wgs : 1)); // measured at C5: best split 4 / 4 / 2 / 1 at batch 1 / 2 / 4 / >= 8
+    }
+    // CKKS at the two-pass sizes: leave the mod-down to whoever touches the ciphertext next (LazyTail) - a rescale on this
+    // evaluator then does both rounding divisions with one transform per component.  SEALHIP_KS_EAGER_TAIL=1: always now.
+    // BFV at the same sizes (round 4): a mod_switch_to_next on this evaluator folds the mod-down into its own division (one
+    // element-wise pass after the inverse transforms, switch_key_finish_modswitch_bfv); anything else completes it first.
+    // CKKS on the fused path: the sums leave the key switch with the ciphertext's words already added (c + S P^-1), so that the
+    // tail reads one operand per component instead of two.  SEALHIP_KS_NO_FOLD=1 (development builds): the round-3 form
+    KsRoute Evaluator::ks_route(const Level &lvl, size_t batch) const
+    {
+        const KsSwitches &sw = ks_switches();
+        const Scheme sch = context_.scheme();
+        KsRoute r;
+        r.defer = !sw.eager_tail && (sch == Scheme::ckks || sch == Scheme::bfv) && ntt2_supports(context_.log_n()) && lvl.K >= 2;
+        r.fold = r.defer && !sw.no_fold && sch == Scheme::ckks;
+        r.plan = KsPlan{ (unsigned)batch, 1 };
+        return r;
+    }
+    // (a key that is absent or foreign gives the unfused route: switch_key_partial then raises what the reference raises)
+    KsRoute Evaluator::ks_route(const Level &lvl, size_t batch, const KSwitchKeys &keys, size_t key_index, unsigned j0, unsigned j1,
+                                bool digit_parallel) const
+    {
+        const unsigned K = lvl.K;
+        KsRoute r = ks_route(lvl, batch);
+        r.j0 = j0;
+        r.j1 = j1;
+        r.fused = keys.context() == &context_ && key_index < keys.slots() && keys.has_key(key_index) && keys.key(key_index).register_order;
+        r.fold = r.fold && r.fused && !digit_parallel;
+        if (!r.fused)
+            return r;
+        if (!digit_parallel)
+        {
+            // (round 6, batch 1: split 8 / 6 / 5 / 4 / 3 / 2 = 0.338 / 0.334 / 0.330 / 0.328 / 0.337 / 0.360 ms eager, 0.315 / 0.312 / 0.300 /
+            // 0.296 / 0.307 / 0.316 ms as a graph replay: the pass that adds the groups reads `split` buffers of 16 MiB)
+            const unsigned shape = ks_shape_split(lvl, batch);
+            r.split = KsSwitches::split(shape > 4 ? 4 : shape); // SEALHIP_KS_SPLIT overrides (tests, A/B)
+            // at most 8 (eight canonical residues below 2^61 still fit a 64-bit word) and K, at least 1
+            r.split = std::max(1u, std::min({ r.split, 8u, K }));
+        }
+        // large batches: chunks dealt to lanes (above); only the un-split launch is cut
+        r.plan = ks_plan((unsigned)batch, (size_t)(K + 1) * K * context_.n(), (size_t)(K + 1) * (context_.n() >> 12), r.split == 1, !capturing_);
+        return r;
+    }
+    bool KsRoute::reads_through_map() const { return takes_product() && !ks_switches().galois_kernels; }
+
     // ---- relinearize (evaluator.cpp:1144-1199)
     void Evaluator::relinearize_inplace(Ciphertext &e, const KSwitchKeys &relin_keys) const
     {
@@ -159,7 +250,10 @@ namespace sealhip
         size_t relins_needed = size - destination_size;
         // the reference passes the LAST polynomial as the target of every step (evaluator.cpp:1180-1188)
         for (size_t I = 0; I < relins_needed; I++)
-            switch_key_inplace(e, e.plane(size - 1), relin_keys, relin_index(size - 1 - I));
+        {
+            const size_t key_index = relin_index(size - 1 - I);
+            switch_key_inplace(e, e.plane(size - 1), relin_keys, key_index, ks_route(*e.level(), e.batch(), relin_keys, key_index, 0, e.level()->K));
+        }
         e.resize(e.level(), destination_size, stream_);
         throw_if_transparent(e);
     }
@@ -170,24 +264,13 @@ namespace sealhip
     void lazy_product_count_fused();
     bool Evaluator::relinearize_from_product(Ciphertext &e, const KSwitchKeys &relin_keys) const
     {
-        static const bool lazy_ok = !std::getenv("SEALHIP_KS_EAGER_TAIL"), fold_ok = !shl_ab_getenv("SEALHIP_KS_NO_FOLD");
         const size_t key_index = relin_index(2);
         const LazyProduct *pending = e.lazy_prod_;
-        if (!pending || pending->owner != this || capturing_ || !lazy_ok || !fold_ok || context_.scheme() != Scheme::ckks || !e.is_ntt_form() ||
-            !ntt2_supports(context_.log_n()) || !context_.using_keyswitching())
-            return false;
         const unsigned K = e.level()->K;
-        if (K < 2 || key_index >= relin_keys.slots() || !relin_keys.has_key(key_index) || !relin_keys.key(key_index).register_order)
+        // (a digit loop cut into groups has a reduce pass that wants the product's words; an unfolded or unfused one reads them itself)
+        const KsRoute route = ks_route(*e.level(), e.batch(), relin_keys, key_index, 0, K);
+        if (!pending || pending->owner != this || capturing_ || !e.is_ntt_form() || !context_.using_keyswitching() || !route.takes_product())
             return false;
-        {
-            // the rule of switch_key_inplace: the digit loop cut into groups (small batches) has a reduce pass that wants the product's words
-            const size_t wgs = e.batch() * (size_t)(K + 1) * (context_.n() >> 12);
-            unsigned split = (unsigned)(2048 / (wgs ? wgs : 1));
-            if (const char *f = std::getenv("SEALHIP_KS_SPLIT"))
-                split = (unsigned)std::atoi(f);
-            if (split > 1)
-                return false;
-        }
         const KSwitchKeys::Key &key = relin_keys.key(key_index);
         if (key.digit0 != 0 || key.digits < K)
             return false;
@@ -198,7 +281,7 @@ namespace sealhip
         try
         {
             Scratch acc(switch_key_acc_words(e));
-            switch_key_partial(e, target, relin_keys, key_index, 0, K, acc.p, 1, true, &p);
+            switch_key_partial(e, target, relin_keys, key_index, acc.p, route, KsAddend::product(p));
             defer_tail(e, acc.release(), true);
         }
         catch (...)
@@ -232,7 +315,7 @@ namespace sealhip
             throw std::invalid_argument("relin_keys is not valid for encryption parameters");
         if (e.size() != 3)
             throw std::invalid_argument("digit-parallel relinearization takes a size-3 ciphertext");
-        switch_key_partial(e, e.plane(2), relin_keys, relin_index(2), j0, j1, acc);
+        switch_key_partial(e, e.plane(2), relin_keys, relin_index(2), acc, ks_route(*e.level(), e.batch(), relin_keys, relin_index(2), j0, j1, true));
     }
     void Evaluator::relinearize_finish(Ciphertext &e, uint64_t *acc, unsigned parts) const
     {
@@ -260,13 +343,13 @@ namespace sealhip
         const Scheme scheme = context_.scheme();
         PlaneGeom g{ (unsigned)context_.log_n(), e.level()->K, (unsigned)e.batch() };
         const int ntt_form = scheme == Scheme::bfv ? 0 : 1;
-        if ((ntt_form != 0) != e.is_ntt_form())
-            throw std::invalid_argument(ntt_form ? "encrypted must be in NTT form" : "BFV encrypted cannot be in NTT form");
+        check_native_form(e);
         Scratch perm(2 * g.words()); // [pi(c0), pi(c1)]
         ck(k_apply_galois(context_.dev_mods(), e.data(), perm.p, galois_elt, ntt_form, g, 2, stream_), "apply_galois");
         ck(hipMemcpyAsync(e.plane(0), perm.p, g.words() * 8, hipMemcpyDeviceToDevice, stream_), "galois copy c0");
         ck(hipMemsetAsync(e.plane(1), 0, g.words() * 8, stream_), "galois zero c1");
-        switch_key_partial(e, perm.p + g.words(), galois_keys, galois_index(galois_elt), j0, j1, acc);
+        switch_key_partial(e, perm.p + g.words(), galois_keys, galois_index(galois_elt), acc,
+                           ks_route(*e.level(), e.batch(), galois_keys, galois_index(galois_elt), j0, j1, true));
     }
     void Evaluator::apply_galois_finish(Ciphertext &e, uint64_t *acc, unsigned parts) const
     {
@@ -288,10 +371,8 @@ namespace sealhip
         return (size_t)e.batch() * 2 * (e.level()->K + 1) * context_.n();
     }
 
-    void Evaluator::switch_key_partial(
-        const Ciphertext &e, const uint64_t *target, const KSwitchKeys &keys, size_t key_index, unsigned j0, unsigned j1,
-        uint64_t *acc_out, unsigned split, bool fold_addend, const LazyProduct *product, bool addend1_zero, uint32_t galois_elt,
-        const uint64_t *galois_c0) const
+    void Evaluator::switch_key_partial(const Ciphertext &e, const uint64_t *target, const KSwitchKeys &keys, size_t key_index, uint64_t *acc_out,
+                                       const KsRoute &route, const KsAddend &addend) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         check_valid(e, "encrypted");
@@ -301,23 +382,19 @@ namespace sealhip
             throw std::invalid_argument("acc");
         if (!context_.using_keyswitching())
             throw std::logic_error("keyswitching is not supported by the context");
+        const unsigned j0 = route.j0, j1 = route.j1, split = route.split;
         if (keys.context() != &context_ && !(j0 == j1 && !keys.context()))
             throw std::invalid_argument("parameter mismatch");
         if (j0 == j1 && j0 <= e.level()->K)
         {
             // a rank without digits (more ranks than digits) needs no key: its partial sums are zero
-            ck(hipMemsetAsync(acc_out, 0, switch_key_acc_words(e) * 8 * (split ? split : 1), stream_), "ks zero partial sums");
+            ck(hipMemsetAsync(acc_out, 0, switch_key_acc_words(e) * 8 * split, stream_), "ks zero partial sums");
             return;
         }
         if (key_index >= keys.slots())
             throw std::out_of_range("kswitch_keys_index");
         const Scheme scheme = context_.scheme();
-        if (scheme == Scheme::bfv && e.is_ntt_form())
-            throw std::invalid_argument("BFV encrypted cannot be in NTT form");
-        if (scheme == Scheme::ckks && !e.is_ntt_form())
-            throw std::invalid_argument("CKKS encrypted must be in NTT form");
-        if (scheme == Scheme::bgv && !e.is_ntt_form())
-            throw std::invalid_argument("BGV encrypted must be in NTT form");
+        check_native_form(e);
         if (!keys.has_key(key_index))
             throw std::invalid_argument("kswitch_keys is not valid for encryption parameters");
         const KSwitchKeys::Key &key = keys.key(key_index);
@@ -326,18 +403,18 @@ namespace sealhip
         const unsigned K = lvl.K, L = klvl.K;
         if (j1 > K || j0 > j1)
             throw std::invalid_argument("digit range");
-        if (fold_addend && !(scheme == Scheme::ckks && key.register_order && j0 == 0 && j1 == K && split <= 1))
-            throw std::invalid_argument("fold_addend"); // the addend may only join the complete sum, on the fused path
+        const bool folds = addend.folds;
+        if (folds && !(route.takes_product() && j0 == 0 && j1 == K))
+            throw std::invalid_argument("fold_addend"); // an addend may only join the complete sum of the un-split folded launch
         if (j0 < j1 && (key.digit0 > j0 || key.digit0 + key.digits < j1))
             throw std::invalid_argument("kswitch_keys inner dimension is too small");
         if (e.size() < 2)
             throw std::invalid_argument("encrypted size must be at least 2");
-        if (product && !(fold_addend && ntt2_supports(context_.log_n()) && (!product->x || (product->x->level() == e.level() && product->x->batch() == e.batch())) &&
+        const LazyProduct *product = addend.prod;
+        if (product && !((!product->x || (product->x->level() == e.level() && product->x->batch() == e.batch())) &&
                          (!product->y || (product->y->level() == e.level() && product->y->batch() == e.batch())) &&
                          (product->own || (product->x && product->y))))
             throw std::invalid_argument("product");
-        if (galois_elt && !(fold_addend && addend1_zero && !product && galois_c0 && scheme == Scheme::ckks && ntt2_supports(context_.log_n())))
-            throw std::invalid_argument("galois_elt"); // the gather lives in the two-pass inverse transform and in ks2's folded epilogue
         // (the operands' words: read once - a live operand's data() completes whatever is pending on it)
         const uint64_t *prod_xw = product ? product->xw() : nullptr, *prod_yw = product ? product->yw() : nullptr;
 
@@ -347,178 +424,144 @@ namespace sealhip
         const NttTables &tb = context_.ntt_tables();
         const ModDesc *mods = context_.dev_mods();
         const uint32_t *map = ks_comp_prime(K);
+        const size_t poly_words = (size_t)K * N; // one polynomial of one item in the [batch][K][N] planes
         // t_target: coefficient form of every decomposition digit (evaluator.cpp:2651-2658)
         const bool ntt_target = scheme == Scheme::ckks || scheme == Scheme::bgv; // the target is in NTT form
         // BFV on the fused path: the target is in coefficient form already and the kernels only read it - no copy
-        const bool read_in_place = !ntt_target && key.register_order;
-        Scratch t(read_in_place ? 1 : (size_t)B * K * N);
+        const bool read_in_place = !ntt_target && route.fused;
+        Scratch t(read_in_place ? 1 : (size_t)B * poly_words);
         const uint64_t *digits = read_in_place ? target : t.p;
-        // fused path, large batches: chunks dealt to lanes (above); the inverse transform of the target then runs per chunk
-        // inside its lane
-        const size_t ks_item_words = (size_t)(K + 1) * K * N;
-        const KsPlan plan = key.register_order
-                                ? ks_plan(B, ks_item_words, (size_t)(K + 1) * (N >> 12), split <= 1 && ntt2_supports(context_.log_n()), !capturing_)
-                                : KsPlan{ B, 1 };
+        // large batches: chunks dealt to lanes (above); the inverse transform of the target then runs per chunk inside its lane
+        const KsPlan &plan = route.plan;
         const bool chunked = plan.chunk < B;
         const bool inverse_in_lane = chunked && !read_in_place && ntt_target;
-        if (read_in_place || inverse_in_lane)
-            ;
-        else if (ntt_target && ntt2_supports(context_.log_n()))
-        {
-            // out-of-place: the two-pass engine reads the target and writes t
-            NttBatch bt = plain_batch(t.p, (size_t)K * N, K, B, 0);
-            bt.src = target;
-            bt.src_outer_stride = (size_t)K * N;
-            bt.src_galois_elt = galois_elt;
+        // the opening inverse transform of the items [b0, b0 + nb): out of place, the two-pass engine reads the target and writes t
+        const auto inverse_batch = [&](unsigned b0, unsigned nb) {
+            NttBatch bt = plain_batch(t.p + b0 * poly_words, poly_words, K, nb, 0);
+            bt.src = target + b0 * poly_words;
+            bt.src_outer_stride = poly_words;
+            bt.src_galois_elt = addend.galois_elt;
             if (product)
             {
                 // the target x1 y1 is formed while it is loaded; it is not stored (ks2 forms its diagonal terms from the operands too)
                 bt.prod_x = prod_xw;
                 bt.prod_y = prod_yw;
                 bt.prod_batch = B;
-                bt.prod_outer0 = 2 * B;
+                bt.prod_outer0 = 2 * B + b0;
             }
-            ck(ntt_inverse(tb, bt, 0, stream_), "ks intt target");
-        }
-        else
+            return bt;
+        };
+        if (ntt_target && !inverse_in_lane && ntt2_supports(context_.log_n()))
+            ck(ntt_inverse(tb, inverse_batch(0, B), 0, stream_), "ks intt target");
+        else if (!read_in_place && !inverse_in_lane)
         {
-            if (product)
-                throw std::invalid_argument("product");
-            ck(hipMemcpyAsync(t.p, target, (size_t)B * K * N * 8, hipMemcpyDeviceToDevice, stream_), "ks copy target");
+            ck(hipMemcpyAsync(t.p, target, (size_t)B * poly_words * 8, hipMemcpyDeviceToDevice, stream_), "ks copy target");
             if (ntt_target)
-                ck(ntt_inverse(tb, plain_batch(t.p, (size_t)K * N, K, B, 0), 0, stream_), "ks intt target");
+                ck(ntt_inverse(tb, plain_batch(t.p, poly_words, K, B, 0), 0, stream_), "ks intt target");
         }
 
-        if (key.register_order)
+        if (route.fused)
         {
             // fused path (ntt2_kernels.hip): the K(K+1) raised digits go through HBM once, between
             // the two passes, and are multiplied into the key inside the second pass
             const KsTargets &kt = ks_targets(K);
+            const size_t ks_item_words = (size_t)(K + 1) * poly_words;
             Scratch mid((size_t)plan.lanes * plan.chunk * ks_item_words);
-            Scratch inv_mid(inverse_in_lane ? (size_t)plan.lanes * plan.chunk * K * N : 1);
+            Scratch inv_mid(inverse_in_lane ? (size_t)plan.lanes * plan.chunk * poly_words : 1);
             {
                 uint64_t w = (uint64_t)plan.lanes * plan.chunk * ks_item_words, seen = g_ks_scratch_words_max.load();
                 while (w > seen && !g_ks_scratch_words_max.compare_exchange_weak(seen, w))
                     ;
             }
-            KsFusedArgs ka{};
-            ka.t = digits;
-            // the I == J shortcut of evaluator.cpp:2682-2685 (a deferred product: x1 y1 is formed where it is needed, ks2 takes it from fold_x / fold_y)
-            ka.target_ntt = ntt_target && !product ? target : nullptr;
-            ka.key = key.dev;
-            ka.mid = mid.p;
-            ka.acc = acc_out;
-            ka.targets1 = kt.dev;
-            ka.targets2 = kt.dev + 2 * (kt.n_int + kt.n_fp);
-            ka.ntargets = kt.n_int + kt.n_fp;
-            ka.n_int = kt.n_int;
-            ka.K = K;
-            ka.L = L;
-            ka.batch = B;
-            ka.j0 = j0;
-            ka.j1 = j1;
-            ka.key_digit0 = (unsigned)key.digit0;
-            ka.parts = split ? split : 1;
-            if (fold_addend && product)
-            {
-                ka.fold_x = prod_xw;
-                ka.fold_y = prod_yw;
-                ka.fold_plane = e.plane_words();
-                ka.fold_pm = klvl.dev.inv_q_last_mod_q;
-            }
-            else if (fold_addend)
-            {
-                ka.fold_c0 = galois_elt ? galois_c0 : e.plane(0);
-                ka.fold_c1 = addend1_zero ? nullptr : e.plane(1);
-                ka.fold_pm = klvl.dev.inv_q_last_mod_q;
-                ka.galois_elt = galois_elt;
-            }
+            // the two passes over the items [b0, b0 + nb), their intermediate in lane `lane`'s share of mid
+            const auto fused_args = [&](unsigned b0, unsigned nb, unsigned lane) {
+                KsFusedArgs ka{};
+                ka.t = digits + b0 * poly_words;
+                // the I == J shortcut of evaluator.cpp:2682-2685 (a deferred product: x1 y1 is formed where it is needed, ks2 takes it from fold_x / fold_y)
+                ka.target_ntt = ntt_target && !product ? target + b0 * poly_words : nullptr;
+                ka.key = key.dev;
+                ka.mid = mid.p + (size_t)lane * plan.chunk * ks_item_words;
+                ka.acc = acc_out + (size_t)b0 * 2 * (K + 1) * N;
+                ka.targets1 = kt.dev;
+                ka.targets2 = kt.dev + 2 * (kt.n_int + kt.n_fp);
+                ka.ntargets = kt.n_int + kt.n_fp;
+                ka.n_int = kt.n_int;
+                ka.K = K;
+                ka.L = L;
+                ka.batch = nb;
+                ka.j0 = j0;
+                ka.j1 = j1;
+                ka.key_digit0 = (unsigned)key.digit0;
+                ka.parts = split;
+                if (folds)
+                    ka.fold_pm = klvl.dev.inv_q_last_mod_q;
+                if (product)
+                {
+                    ka.fold_x = prod_xw + b0 * poly_words;
+                    ka.fold_y = prod_yw + b0 * poly_words;
+                    ka.fold_plane = e.plane_words();
+                }
+                else if (folds)
+                {
+                    ka.fold_c0 = (addend.galois_elt ? addend.c0 : e.plane(0)) + b0 * poly_words;
+                    ka.fold_c1 = addend.c1_zero ? nullptr : e.plane(1) + b0 * poly_words;
+                    ka.galois_elt = addend.galois_elt;
+                }
+                return ka;
+            };
             if (!chunked)
-                ck(ks_fused(tb, ka, stream_), "ks fused");
+                ck(ks_fused(tb, fused_args(0, B, 0), stream_), "ks fused");
             else
             {
-                // which pass-1 kernel: decided for the whole batch (ntt2_kernels.hip: launch_ks decides from the grid it is given)
-                ka.order1 = (size_t)B * (j1 - j0) * (N >> 12) >= 4096 ? 1 : 0;
-                KsLanes *lnp = ks_lanes();
+                KsLanes *ln = ks_lanes();
                 unsigned lanes = plan.lanes;
-                if (lanes > 1 && (!lnp || !lnp->ensure(lanes - 1)))
-                    lanes = 1;
-                KsLanes dummy_lanes_for_one_lane; // (never touched when lanes == 1)
-                KsLanes &ln = lnp ? *lnp : dummy_lanes_for_one_lane;
-                // (the two arithmetic classes of a chunk one after the other on its lane; SEALHIP_KS_CLASS_FORK=1 in development builds
-                // forks the integer class to the launcher's side stream as the unchunked path does: profiles/r05_ks_chunked.txt)
-                static const bool class_fork = shl_ab_getenv("SEALHIP_KS_CLASS_FORK") != nullptr;
-                ka.no_class_fork = lanes > 1 && !class_fork;
-                static const bool trace = shl_ab_getenv("SEALHIP_KS_TRACE") != nullptr;
-                if (trace)
+                if (lanes > 1 && (!ln || !ln->ensure(lanes - 1)))
+                    lanes = 1; // (ln is not touched from here on)
+                if (ks_switches().trace)
                     std::fprintf(stderr, "[ks] batch %u in chunks of %u on %u lane(s)\n", B, plan.chunk, lanes);
                 if (lanes > 1)
                 {
-                    ck(hipEventRecord(ln.fork, stream_), "ks lanes fork");
+                    ck(hipEventRecord(ln->fork, stream_), "ks lanes fork");
                     for (unsigned l = 1; l < lanes; l++)
-                        ck(hipStreamWaitEvent(ln.stream[l - 1], ln.fork, 0), "ks lanes fork");
+                        ck(hipStreamWaitEvent(ln->stream[l - 1], ln->fork, 0), "ks lanes fork");
                 }
-                const size_t poly_words = (size_t)K * N; // one polynomial of one item in the [batch][K][N] planes
                 unsigned c = 0;
                 //  a launch that fails half-way must not leave forked lanes running into scratch blocks that go back to
                 // the pool ordered on stream_ only: join whatever was forked before the exception travels on
                 auto join_lanes = [&](bool nothrow) {
                     for (unsigned l = 1; l < lanes; l++)
                     {
-                        const hipError_t e1 = hipEventRecord(ln.join[l - 1], ln.stream[l - 1]);
-                        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(stream_, ln.join[l - 1], 0) : e1;
+                        const hipError_t e1 = hipEventRecord(ln->join[l - 1], ln->stream[l - 1]);
+                        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(stream_, ln->join[l - 1], 0) : e1;
                         if (e2 != hipSuccess)
                         {
                             if (!nothrow)
                                 ck(e2, "ks lanes join");
-                            (void)hipStreamSynchronize(ln.stream[l - 1]); // the event path failed too: wait for the lane outright
+                            (void)hipStreamSynchronize(ln->stream[l - 1]); // the event path failed too: wait for the lane outright
                         }
                     }
                 };
                 try
                 {
-                // (The lanes run in lockstep - forked together, equal work.  A two-stage form that staggers them by construction - one
-                // producer stream for inverse transform + pass 1, the evaluator's stream consuming a ring of intermediates with pass 2
-                // - was measured too: 9.24 k ct/s against 9.27 - 9.40 k, profiles/r05_ks_chunked.txt.  Both passes need the vector
-                // ALU; side by side each runs slower by what the other takes.)
-                for (unsigned b0 = 0; b0 < B; b0 += plan.chunk, c++)
-                {
-                    const unsigned nb = B - b0 < plan.chunk ? B - b0 : plan.chunk;
-                    const unsigned l = c % lanes;
-                    hipStream_t st = l == 0 ? stream_ : ln.stream[l - 1];
-                    if (inverse_in_lane)
+                    // (The lanes run in lockstep - forked together, equal work.  A two-stage form that staggers them by construction - one
+                    // producer stream for inverse transform + pass 1, the evaluator's stream consuming a ring of intermediates with pass 2
+                    // - was measured too: 9.24 k ct/s against 9.27 - 9.40 k, profiles/r05_ks_chunked.txt.  Both passes need the vector
+                    // ALU; side by side each runs slower by what the other takes.)
+                    for (unsigned b0 = 0; b0 < B; b0 += plan.chunk, c++)
                     {
-                        NttBatch bt = plain_batch(t.p + b0 * poly_words, poly_words, K, nb, 0);
-                        bt.src = target + b0 * poly_words;
-                        bt.src_outer_stride = poly_words;
-                        bt.src_galois_elt = galois_elt;
-                        if (product)
-                        {
-                            bt.prod_x = prod_xw;
-                            bt.prod_y = prod_yw;
-                            bt.prod_batch = B;
-                            bt.prod_outer0 = 2 * B + b0;
-                        }
-                        ck(ntt2_inverse(tb, bt, 0, inv_mid.p + (size_t)l * plan.chunk * poly_words, st), "ks intt target (chunk)");
+                        const unsigned nb = B - b0 < plan.chunk ? B - b0 : plan.chunk;
+                        const unsigned l = c % lanes;
+                        hipStream_t st = l == 0 ? stream_ : ln->stream[l - 1];
+                        if (inverse_in_lane)
+                            ck(ntt2_inverse(tb, inverse_batch(b0, nb), 0, inv_mid.p + (size_t)l * plan.chunk * poly_words, st), "ks intt target (chunk)");
+                        KsFusedArgs kc = fused_args(b0, nb, l);
+                        // which pass-1 kernel: decided for the whole batch (ntt2_kernels.hip: launch_ks decides from the grid it is given)
+                        kc.order1 = (size_t)B * (j1 - j0) * (N >> 12) >= 4096 ? 1 : 0;
+                        // (the two arithmetic classes of a chunk one after the other on its lane; SEALHIP_KS_CLASS_FORK=1 in development builds
+                        // forks the integer class to the launcher's side stream as the unchunked path does: profiles/r05_ks_chunked.txt)
+                        kc.no_class_fork = lanes > 1 && !ks_switches().class_fork;
+                        ck(ks_fused(tb, kc, st), "ks fused (chunk)");
                     }
-                    KsFusedArgs kc = ka;
-                    kc.batch = nb;
-                    kc.t = digits + b0 * poly_words;
-                    kc.target_ntt = ka.target_ntt ? ka.target_ntt + b0 * poly_words : nullptr;
-                    kc.mid = mid.p + (size_t)l * plan.chunk * ks_item_words;
-                    kc.acc = acc_out + (size_t)b0 * 2 * (K + 1) * N;
-                    if (fold_addend && product)
-                    {
-                        kc.fold_x = ka.fold_x + b0 * poly_words;
-                        kc.fold_y = ka.fold_y + b0 * poly_words;
-                    }
-                    else if (fold_addend)
-                    {
-                        kc.fold_c0 = ka.fold_c0 + b0 * poly_words;
-                        kc.fold_c1 = ka.fold_c1 ? ka.fold_c1 + b0 * poly_words : nullptr;
-                    }
-                    ck(ks_fused(tb, kc, st), "ks fused (chunk)");
-                }
                 }
                 catch (...)
                 {
@@ -530,8 +573,6 @@ namespace sealhip
                 g_ks_chunks += c;
             }
         }
-        else if (split > 1 || product)
-            throw std::invalid_argument("in-launch digit groups and deferred products need the fused key-switch path");
         else
         {
             // u[b][I][J] = NTT_I(t_J mod q_I), I over the K data primes and the special prime
@@ -555,11 +596,11 @@ namespace sealhip
         }
     }
 
-    void Evaluator::switch_key_finish(Ciphertext &e, uint64_t *acc_p, unsigned parts, bool acc_has_addend, bool may_defer) const
+    void Evaluator::switch_key_finish(Ciphertext &e, uint64_t *acc, unsigned parts, bool acc_has_addend, bool may_defer) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         check_valid(e, "encrypted");
-        if (!acc_p)
+        if (!acc)
             throw std::invalid_argument("acc");
         if (!context_.using_keyswitching())
             throw std::logic_error("keyswitching is not supported by the context");
@@ -579,20 +620,15 @@ namespace sealhip
         const NttTables &tb = context_.ntt_tables();
         const ModDesc *mods = context_.dev_mods();
         const uint32_t *map = ks_comp_prime(K);
-        struct AccRef
-        {
-            uint64_t *p;
-        } acc{ acc_p };
-        // Digit-parallel callers (the sums of `parts` ranks in the caller's buffer): CKKS at the two-pass sizes takes the road of
-        // switch_key_inplace - the pass that reduces the sums adds the ciphertext's words and writes a block of the pool's, the
-        // mod-down stays pending (LazyTail) and a rescale on this evaluator folds both divisions (configs[4]: rotate + rescale)
-        static const bool lazy_ok = !std::getenv("SEALHIP_KS_EAGER_TAIL");
-        static const bool fold_ok = !shl_ab_getenv("SEALHIP_KS_NO_FOLD");
-        if (may_defer && lazy_ok && fold_ok && !acc_has_addend && scheme == Scheme::ckks && ntt2_supports(context_.log_n()) && K >= 2)
+        // Digit-parallel callers (the sums of `parts` ranks in the caller's buffer): where the route defers and folds (CKKS at the
+        // two-pass sizes) they take the road of switch_key_inplace - the pass that reduces the sums adds the ciphertext's words and
+        // writes a block of the pool's, the mod-down stays pending (LazyTail) and a rescale on this evaluator folds both divisions
+        // (configs[4]: rotate + rescale)
+        if (may_defer && !acc_has_addend && ks_route(lvl, B).fold)
         {
             const size_t words = switch_key_acc_words(e);
             uint64_t *own = DevicePool::global().alloc_words(words, stream_);
-            const hipError_t err = k_keyswitch_reduce(mods, acc.p, n_log, K, L, B, stream_, 1, e.plane(0), e.plane(1),
+            const hipError_t err = k_keyswitch_reduce(mods, acc, n_log, K, L, B, stream_, 1, e.plane(0), e.plane(1),
                                                       klvl.dev.inv_q_last_mod_q, own);
             if (err != hipSuccess)
             {
@@ -603,7 +639,7 @@ namespace sealhip
             return;
         }
         if (parts > 1)
-            ck(k_keyswitch_reduce(mods, acc.p, n_log, K, L, B, stream_), "ks reduce partial sums");
+            ck(k_keyswitch_reduce(mods, acc, n_log, K, L, B, stream_), "ks reduce partial sums");
 
         // mod-down by the special prime P and accumulate into (c0, c1) (evaluator.cpp:2806-2864)
         const uint64_t P = context_.coeff_modulus()[L - 1];
@@ -611,18 +647,18 @@ namespace sealhip
         {
             // evaluator.cpp:2762-2805: t_last = INTT_P(S_k[P]); delta = (-(t_last mod t) P^-1 mod t) P + t_last (mod q_i);
             // ct_k[i] += (S_k[q_i] - NTT_i(delta)) P^-1
-            NttBatch bi = plain_batch(acc.p + (size_t)K * N, (size_t)(K + 1) * N, 1, 2 * B, L - 1);
+            NttBatch bi = plain_batch(acc + (size_t)K * N, (size_t)(K + 1) * N, 1, 2 * B, L - 1);
             ck(ntt_inverse(tb, bi, 0, stream_), "ks intt special");
             Scratch delta((size_t)B * 2 * K * N);
             ck(k_bgv_delta(mods, host::make_mod(context_.plain_modulus()), klvl.dev.inv_q_last_mod_t, klvl.dev.q_last_mod_q,
-                           acc.p + (size_t)K * N, (size_t)(K + 1) * N, delta.p, n_log, K, (size_t)2 * B, stream_),
+                           acc + (size_t)K * N, (size_t)(K + 1) * N, delta.p, n_log, K, (size_t)2 * B, stream_),
                "ks bgv delta");
-            bgv_correct_and_combine(delta, acc.p, (size_t)(K + 1) * N, klvl.dev.inv_q_last_mod_q, K, 2 * B, e.plane(0), e.plane(1),
+            bgv_correct_and_combine(delta, acc, (size_t)(K + 1) * N, klvl.dev.inv_q_last_mod_q, K, 2 * B, e.plane(0), e.plane(1),
                                     (size_t)K * N, 2);
         }
         else if (scheme == Scheme::ckks)
         {
-            NttBatch bi = plain_batch(acc.p + (size_t)K * N, (size_t)(K + 1) * N, 1, 2 * B, L - 1);
+            NttBatch bi = plain_batch(acc + (size_t)K * N, (size_t)(K + 1) * N, 1, 2 * B, L - 1);
             ck(ntt_inverse(tb, bi, 0, stream_), "ks intt special");
             Scratch tt(ntt2_supports(context_.log_n()) ? 1 : (size_t)B * 2 * K * N);
             NttBatch b{};
@@ -632,7 +668,7 @@ namespace sealhip
             b.nouter = 2 * B;
             b.comp_prime = nullptr;
             b.prime_first = 0;
-            b.src = acc.p + (size_t)K * N;
+            b.src = acc + (size_t)K * N;
             b.src_outer_stride = (size_t)(K + 1) * N;
             b.src_ncomp = 1;
             b.src_mode = 2;
@@ -644,7 +680,7 @@ namespace sealhip
                 // the tail is the epilogue of the transform: tt is never stored
                 b.data = nullptr;
                 b.epi = acc_has_addend ? 3 : 2; // 3: acc = c + S P^-1 already (switch_key_partial, fold_addend)
-                b.epi_a = acc.p;
+                b.epi_a = acc;
                 b.epi_a_stride = (size_t)(K + 1) * N;
                 b.epi_mul = klvl.dev.inv_q_last_mod_q;
                 b.epi_out0 = e.plane(0);
@@ -655,92 +691,46 @@ namespace sealhip
             else
             {
                 ck(ntt_forward(tb, b, 1, stream_), "ks ntt correction");
-                ck(k_keyswitch_tail_ckks(mods, klvl.dev.inv_q_last_mod_q, e.plane(0), e.plane(1), acc.p, tt.p, n_log, K, B, stream_),
+                ck(k_keyswitch_tail_ckks(mods, klvl.dev.inv_q_last_mod_q, e.plane(0), e.plane(1), acc, tt.p, n_log, K, B, stream_),
                    "ks tail");
             }
         }
         else
         {
-            NttBatch bi = plain_batch(acc.p, (size_t)(K + 1) * N, K + 1, 2 * B, 0);
+            NttBatch bi = plain_batch(acc, (size_t)(K + 1) * N, K + 1, 2 * B, 0);
             bi.comp_prime = map + (size_t)(K + 1) * K;
             bi.cls_hint = ks_class_hint(K);
             ck(ntt_inverse(tb, bi, 0, stream_), "ks intt all");
             ck(k_keyswitch_tail_bfv(
-                   mods, klvl.dev.inv_q_last_mod_q, klvl.dev.round_fix, P >> 1, P, e.plane(0), e.plane(1), acc.p, n_log, K, B,
+                   mods, klvl.dev.inv_q_last_mod_q, klvl.dev.round_fix, P >> 1, P, e.plane(0), e.plane(1), acc, n_log, K, B,
                    stream_),
                "ks tail bfv");
         }
     }
 
-    // Small batches do not fill the chip: one workgroup per (target modulus, tile, batch item) is 16 (K+1) workgroups per
-    // ciphertext at N = 2^16, each looping over all K digits, and only 2 x 16 of them for the two 60-bit moduli.  Cut the
-    // digit loop into `split` in-launch groups (their partial sums are added by the reduce pass below): single-ciphertext
-    // latency of multiply+relinearize+rescale at C5 0.63 -> 0.40 ms (profiles/HISTORY.md section 5, "Small batches / latency").  SEALHIP_KS_SPLIT overrides (tests, A/B).
-    unsigned Evaluator::ks_split(const Ciphertext &e, const KSwitchKeys &keys, size_t key_index) const
-    {
-        const unsigned K = e.level()->K;
-        unsigned split = 1;
-        if (keys.context() == &context_ && key_index < keys.slots() && keys.has_key(key_index) && keys.key(key_index).register_order)
-        {
-            const size_t wgs = e.batch() * (size_t)(K + 1) * (context_.n() >> 12);
-            split = (unsigned)(2048 / (wgs ? wgs : 1)); // measured at C5: best split 4 / 4 / 2 / 1 at batch 1 / 2 / 4 / >= 8
-            // (round 6, batch 1: split 8 / 6 / 5 / 4 / 3 / 2 = 0.338 / 0.334 / 0.330 / 0.328 / 0.337 / 0.360 ms eager, 0.315 / 0.312 / 0.300 /
-            // 0.296 / 0.307 / 0.316 ms as a graph replay: the pass that adds the groups reads `split` buffers of 16 MiB)
-            if (split > 4)
-                split = 4;
-            if (const char *f = std::getenv("SEALHIP_KS_SPLIT"))
-                split = (unsigned)std::atoi(f);
-            if (split > 8)
-                split = 8; // eight canonical residues below 2^61 still fit a 64-bit word
-            if (split > K)
-                split = K;
-            if (split < 1)
-                split = 1;
-        }
-        return split;
-    }
-    // CKKS on the fused path: the sums leave the key switch with the ciphertext's words already added (c + S P^-1), so that the
-    // tail reads one operand per component instead of two - from ks2's epilogue when the digits run as one group, from the pass
-    // that adds the groups otherwise.  SEALHIP_KS_NO_FOLD=1 (development builds): the round-3 form
-    bool Evaluator::ks_folds(const KSwitchKeys &keys, size_t key_index, unsigned K) const
-    {
-        static const bool lazy_ok = !std::getenv("SEALHIP_KS_EAGER_TAIL");
-        static const bool fold_ok = !shl_ab_getenv("SEALHIP_KS_NO_FOLD");
-        return fold_ok && lazy_ok && context_.scheme() == Scheme::ckks && ntt2_supports(context_.log_n()) && K >= 2 && keys.context() == &context_ &&
-               key_index < keys.slots() && keys.has_key(key_index) && keys.key(key_index).register_order;
-    }
-
-    void Evaluator::switch_key_inplace(Ciphertext &e, const uint64_t *target, const KSwitchKeys &keys, size_t key_index, bool c1_zero_unwritten,
-                                       uint32_t galois_elt, const uint64_t *galois_c0) const
+    void Evaluator::switch_key_inplace(Ciphertext &e, const uint64_t *target, const KSwitchKeys &keys, size_t key_index, const KsRoute &route,
+                                       const KsAddend &addend) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         if (&e.context() != &context_ || !e.level())
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        const unsigned K = e.level()->K;
-        const unsigned split = ks_split(e, keys, key_index);
-        // CKKS at the two-pass sizes: leave the mod-down to whoever touches the ciphertext next (LazyTail) - a rescale on this
-        // evaluator then does both rounding divisions with one transform per component.  SEALHIP_KS_EAGER_TAIL=1: always now.
-        // BFV at the same sizes (round 4): a mod_switch_to_next on this evaluator folds the mod-down into its own division (one
-        // element-wise pass after the inverse transforms, switch_key_finish_modswitch_bfv); anything else completes it first.
-        static const bool lazy_ok = !std::getenv("SEALHIP_KS_EAGER_TAIL");
-        const Scheme sch = context_.scheme();
-        const bool defer = lazy_ok && (sch == Scheme::ckks || sch == Scheme::bfv) && ntt2_supports(context_.log_n()) && K >= 2;
-        const bool fold = ks_folds(keys, key_index, K);
-        if (galois_elt && !(fold && split == 1 && c1_zero_unwritten))
-            throw std::logic_error("the automorphism is read inside the key switch only on its un-split folded path");
-        // c1_zero_unwritten (rotations: the ciphertext is (pi(c0), 0) and its second polynomial has not been written): with the addend
-        // folded into the sums nobody reads that polynomial before the tail writes it - the zeros are neither stored nor loaded
-        if (c1_zero_unwritten && !fold)
+        const unsigned K = e.level()->K, split = route.split;
+        const bool fold = route.fold;
+        // c1 zero and unwritten (rotations: the ciphertext is (pi(c0), 0)): with the addend folded into the sums nobody reads that
+        // polynomial before the tail writes it - the zeros are neither stored nor loaded
+        if (addend.c1_zero && !fold)
             ck(hipMemsetAsync(e.plane(1), 0, e.plane_words() * 8, stream_), "zero c1");
-        const bool a1z = c1_zero_unwritten && fold;
         Scratch acc(switch_key_acc_words(e) * split);
-        switch_key_partial(e, target, keys, key_index, 0, K, acc.p, split, fold && split == 1, nullptr, a1z, galois_elt, galois_c0);
+        // (the planes are folded by ks2's epilogue when the digits run as one group, by the pass that adds the groups otherwise; a
+        // rotation's unpermuted operand can only be folded by the former, which switch_key_partial checks)
+        const bool own_planes = !addend.galois_elt && !addend.prod;
+        switch_key_partial(e, target, keys, key_index, acc.p, route, own_planes && !route.takes_product() ? KsAddend::nothing() : addend);
         if (split > 1) // several digit groups (small batches): the pass that adds them adds the ciphertext's words too
             ck(k_keyswitch_reduce(context_.dev_mods(), acc.p, (unsigned)context_.log_n(), K, context_.key_level().K, (unsigned)e.batch(),
-                                  stream_, split, fold ? e.plane(0) : nullptr, fold && !a1z ? e.plane(1) : nullptr,
+                                  stream_, split, fold ? e.plane(0) : nullptr, fold && !addend.c1_zero ? e.plane(1) : nullptr,
                                   context_.key_level().dev.inv_q_last_mod_q),
                "ks add digit groups");
-        if (defer)
+        if (route.defer)
             defer_tail(e, acc.release(), fold);
         else
             switch_key_finish(e, acc.p, 1);
@@ -759,8 +749,7 @@ namespace sealhip
         const unsigned B = (unsigned)e.batch();
         const NttTables &tb = context_.ntt_tables();
         const uint64_t P = context_.coeff_modulus()[L - 1];
-        static const bool trace = shl_ab_getenv("SEALHIP_KS_TRACE") != nullptr;
-        if (trace)
+        if (ks_switches().trace)
             std::fprintf(stderr, "[ks] folded tail (bfv)\n");
         g_tail_folded++;
         NttBatch bi = plain_batch(acc_p, (size_t)(K + 1) * N, K + 1, 2 * B, 0);
@@ -794,8 +783,7 @@ namespace sealhip
         const NttTables &tb = context_.ntt_tables();
         const uint64_t P = context_.coeff_modulus()[L - 1];
         uint64_t *c0 = e.data_, *c1 = e.data_ + (size_t)B * K * N; // no deferred tail left on e: the caller detached it
-        static const bool trace = shl_ab_getenv("SEALHIP_KS_TRACE") != nullptr;
-        if (trace)
+        if (ks_switches().trace)
             std::fprintf(stderr, acc_has_addend ? "[ks] folded tail, addend in the sums\n" : "[ks] folded tail\n");
         g_tail_folded++;
 

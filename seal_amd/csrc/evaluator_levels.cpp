@@ -9,12 +9,7 @@ namespace sealhip
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         const Scheme scheme = context_.scheme();
-        if (scheme == Scheme::bfv && e.is_ntt_form())
-            throw std::invalid_argument("BFV encrypted cannot be in NTT form");
-        if (scheme == Scheme::ckks && !e.is_ntt_form())
-            throw std::invalid_argument("CKKS encrypted must be in NTT form");
-        if (scheme == Scheme::bgv && !e.is_ntt_form())
-            throw std::invalid_argument("BGV encrypted must be in NTT form");
+        check_native_form(e);
         const Level &lvl = *e.level();
         const Level *next = context_.next_level(lvl);
         double destination_scale = 1.0;
@@ -147,13 +142,7 @@ namespace sealhip
     void Evaluator::mod_switch_drop_to_next(Ciphertext &e) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        const Scheme scheme = context_.scheme();
-        if (scheme == Scheme::bfv && e.is_ntt_form())
-            throw std::invalid_argument("BFV encrypted cannot be in NTT form");
-        if (scheme == Scheme::ckks && !e.is_ntt_form())
-            throw std::invalid_argument("CKKS encrypted must be in NTT form");
-        if (scheme == Scheme::bgv && !e.is_ntt_form())
-            throw std::invalid_argument("BGV encrypted must be in NTT form");
+        check_native_form(e);
         const Level &lvl = *e.level();
         const Level *next = context_.next_level(lvl);
         if (!scale_within_bounds(e.scale(), *next))
@@ -306,18 +295,13 @@ namespace sealhip
         if (e.size() != 2)
             throw std::invalid_argument("encrypted size must be 2");
         const Scheme scheme = context_.scheme();
-        if (scheme == Scheme::bfv && e.is_ntt_form())
-            throw std::invalid_argument("BFV encrypted cannot be in NTT form");
-        if (scheme == Scheme::ckks && !e.is_ntt_form())
-            throw std::invalid_argument("CKKS encrypted must be in NTT form");
-        if (scheme == Scheme::bgv && !e.is_ntt_form())
-            throw std::invalid_argument("BGV encrypted must be in NTT form");
+        check_native_form(e);
 
         PlaneGeom g{ (unsigned)context_.log_n(), lvl.K, (unsigned)e.batch() };
         const int ntt_form = scheme == Scheme::bfv ? 0 : 1;
         const size_t key_index = galois_index(galois_elt);
-        static const bool gather_ok = !shl_ab_getenv("SEALHIP_GALOIS_KERNELS"); // development builds: the permutation kernels always (A/B)
-        if (gather_ok && scheme == Scheme::ckks && ks_folds(galois_keys, key_index, lvl.K) && ks_split(e, galois_keys, key_index) == 1)
+        const KsRoute route = ks_route(lvl, e.batch(), galois_keys, key_index, 0, lvl.K);
+        if (route.reads_through_map())
         {
             // Round 6: batches whose key switch runs un-split with the addend folded into its sums - neither pi(c0) nor pi(c1) is ever
             // stored: the key switch's own kernels read c0 and c1 through the automorphism's index map (the opening inverse transform
@@ -338,7 +322,7 @@ namespace sealhip
             }
             try
             {
-                switch_key_inplace(dest, c1, galois_keys, key_index, true, galois_elt, c0);
+                switch_key_inplace(dest, c1, galois_keys, key_index, route, KsAddend::galois(galois_elt, c0));
                 throw_if_transparent(dest);
             }
             catch (...)
@@ -381,7 +365,7 @@ namespace sealhip
         dest.adopt(&lvl, 2, out, words);
         try
         {
-            switch_key_inplace(dest, perm.p, galois_keys, key_index, true);
+            switch_key_inplace(dest, perm.p, galois_keys, key_index, route, KsAddend::planes(true));
             throw_if_transparent(dest);
         }
         catch (...)
