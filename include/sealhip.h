@@ -568,7 +568,7 @@ SHL_FUNC SealHip_PoolStats(uint64_t *bytes_held, uint64_t *cross_stream_waits);
  *     device reports a memory fault: its handler on the stack tells that case from a C++ one) and then lets the abort proceed
  *     with the default disposition.  A later call only changes the path. */
 SHL_FUNC SealHip_InstallAbortTrace(const char *path);
-/* Environment.  The product library reads eleven variables, each exercised by a test; everything else that earlier
+/* Environment.  The product library reads twelve variables, each exercised by a test; everything else that earlier
  * rounds could switch at run time (superseded kernels, fork / no-fork of the side streams, ...) only exists in development
  * builds made with -DSEALHIP_AB_SWITCHES (seal_amd/csrc/modarith.h: shl_ab_getenv).
  *   SEALHIP_NO_FP=1                  every prime on the 64-bit integer back end (no exact double-precision arithmetic for
@@ -588,7 +588,11 @@ SHL_FUNC SealHip_InstallAbortTrace(const char *path);
  *   SEALHIP_LAZY_PRODUCT=0           tensor products are formed when Evaluator_Multiply is called (no deferred products, below)
  *   SEALHIP_LAZY_PRODUCT_MIN_WGS=<n> a product is deferred when its key switch would launch more than <n> second-pass workgroups
  *                                    (default 1024: the batches whose key switch runs as one digit group); tests reach the
- *                                    deferred form at small batches with 0, together with SEALHIP_KS_SPLIT=1 */
+ *                                    deferred form at small batches with 0, together with SEALHIP_KS_SPLIT=1
+ *   SEALHIP_TAIL_P1_ORDER=0 / 1      first pass of the rounding tails (rescale, the key switch's mod-down, the two folded into one)
+ *                                    at 2^13 <= N <= 2^16: 0 = one workgroup per target component, 1 = one workgroup per source
+ *                                    tile with the target components in a loop (default: 1 for batches whose tiles fill the chip,
+ *                                    0 below).  Same words either way; read once. */
 /* Chunked key switching (round 5).  switch_key_inplace needs K (K + 1) half-transformed digits per ciphertext between its two
  * kernels (126 MB at N = 2^16, K = 15).  For a batch of 1.5 chunks or more (2^13 <= N <= 2^16, register-order keys, one digit group) the batch is cut
  * into chunks dealt round-robin to `lanes` streams forked from and joined to the evaluator's stream: the intermediate held

@@ -127,7 +127,7 @@ namespace sealhip
             *scratch_words_max = g_ks_scratch_words_max.exchange(0); // ... since the previous query
     }
 
-    // ---- The key switch's environment switches.  This is the only place that reads them.
+    // ---- The key switch's environment switches.  This is the only place that reads them (one exception, marked).
     //   name                           build        read      set by
     //   SEALHIP_KS_SPLIT               product      per call  tests/parity_cases.py, test_emu_parity.py, test_gpu_parity.py, test_fuzz.py
     //   SEALHIP_KS_CHUNK               product      per call  tests/parity_cases.py, test_emu_parity.py
@@ -136,6 +136,8 @@ namespace sealhip
     //   SEALHIP_LAZY_PRODUCT           product      per call  tests/parity_cases.py
     //   SEALHIP_LAZY_PRODUCT_MIN_WGS   product      per call  tests/parity_cases.py, test_fuzz.py
     //   SEALHIP_KS_EAGER_TAIL          product      once      tests/parity_cases.py, dist_worker.py (fresh processes)
+    //   SEALHIP_TAIL_P1_ORDER          product      once      tests/tail_order_cases.py (fresh processes); read in ntt2_kernels.hip,
+    //                                                         src_resident(): the tails' first pass belongs to the transform engine
     //   SEALHIP_KS_NO_FOLD             development  once      tests/test_emu_parity.py (fresh process)
     //   SEALHIP_KS_TRACE               development  once      tests/test_emu_parity.py
     //   SEALHIP_KS_CLASS_FORK          development  once      - (A/B: the integer class of a chunk on the launcher's side stream)

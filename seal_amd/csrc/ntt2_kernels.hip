@@ -27,6 +27,7 @@
 #include "ntt2_device.h"
 #include <algorithm>
 #include <atomic>
+#include <cstdio>
 #include <mutex>
 #include <cstdlib>
 #include <type_traits>
@@ -485,6 +486,145 @@ namespace sealhip
                 tail2_p2_body<true, D1, 0>(a, prime, comp, outer, lds, blk.tile);
             else
                 tail2_p2_body<false, D1, 2>(a, prime, comp, outer, lds, blk.tile);
+        }
+
+        // A resident source word as the target loop sees it: opaque to the compiler, so that the target-independent half of its
+        // conversion (the two 32-bit halves as doubles, the limbs of the Barrett product) is redone per target instead of being
+        // hoisted out of the loop into two or more registers per word (ks1t_kernel's note: +68 VGPRs, a wave per SIMD less; here 250
+        // VGPRs instead of 150 for the folded tail's double-precision body, scratch for the integer one)
+        __device__ __forceinline__ uint64_t resident_word(uint64_t v)
+        {
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(v));
+#endif
+            return v;
+        }
+
+        // Pass 1 of a rounding tail with the loops exchanged, as ks1t_kernel does for the key switch: one workgroup = (column tile cg,
+        // outer item), holding the tile of its ONE source component (TWO: of both sources of the folded tail, t_P and t_last) in
+        // registers and looping over the nc target components [comp0, comp0 + nc) of its class run.  In the orders above every
+        // target's workgroup loads the same source tile again - 14 times per step at the headline, twice the bytes of the
+        // intermediate it stores - and redoes the target-independent half of the mapping (mode 2's "+ half mod src_q"; the
+        // conversion of t_last to a double when q_last < 2^52).  Per target the loop loads the modulus, its constants (scalar) and
+        // the fifteen per-thread twiddles.  Same words, same intermediate layout: pass 2 (ntt2_fwd_p2 / ntt2_tail2_p2) is unchanged.
+        // t_P may be a 60-bit residue and stays in words.  launch_fwd / launch_tail2 pick the order (src_resident()).
+        // SMALL2 (double-precision targets of the folded tail): q_last is below 2^52, t_last is converted to doubles once
+        template <bool FP, int D1, bool TWO, bool SMALL2>
+        __device__ __forceinline__ void src_p1t_body(const Tail2Args &t2, unsigned nc, uint64_t *lds)
+        {
+            static_assert(!SMALL2 || (FP && TWO), "SMALL2 is a property of the double-precision launch of the folded tail");
+            typedef Field<FP> F;
+            typedef Geo<D1> G;
+            const FwdArgs &a = t2.f;
+            const unsigned tid = threadIdx.x;
+            const unsigned grp = blockIdx.x; // outer * TILES + cg
+            if (grp >= a.nouter * G::TILES)
+                return;
+            const unsigned cg = grp % G::TILES, outer = grp / G::TILES;
+            const unsigned c = tid & (G::C - 1), rbl = tid >> G::LC;
+            const size_t col = (size_t)cg * G::C + c;
+            const uint64_t *in1 = a.src + (size_t)outer * a.src_outer_stride + col;
+            [[maybe_unused]] const uint64_t *in2 = nullptr;
+            if constexpr (TWO)
+                in2 = ((outer & 1) ? t2.x.src2_1 : t2.x.src2_0) + (size_t)(outer >> 1) * t2.x.src2_stride + col;
+            uint64_t r1[16];
+            [[maybe_unused]] uint64_t r2[16];
+#pragma unroll
+            for (int e = 0; e < 16; e++)
+            {
+                const unsigned ra = e >> (4 - G::rA), rbh = e & ((1 << (4 - G::rA)) - 1);
+                const unsigned R = ra * 16 + (rbh << G::rA) + rbl;
+                r1[e] = in1[(size_t)R * 256];
+                if constexpr (TWO)
+                    r2[e] = in2[(size_t)R * 256];
+            }
+            // the target-independent half of the mapping, once (mode 3: the producer has added the halves)
+            const bool add_half = TWO ? !t2.x.halves_added : a.src_mode == 2;
+            if (add_half)
+            {
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                {
+                    r1[e] = csub(r1[e] + a.src_half, a.src_q);
+                    if constexpr (TWO)
+                        r2[e] = csub(r2[e] + t2.x.src2_half, t2.x.src2_q);
+                }
+            }
+            if constexpr (SMALL2)
+            {
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                    r2[e] = fp_to_bits(fp_from_u52(r2[e]));
+            }
+#pragma nounroll
+            for (unsigned it = 0; it < nc; it++)
+            {
+                const unsigned comp = a.comp0 + it;
+                const unsigned prime = SHL_UNIFORM(a.comp_prime ? a.comp_prime[comp] : a.prime_first + comp);
+                uint64_t *mid_tr = a.mid + (((size_t)outer * a.ncomp + comp) << G::n);
+                auto one = [&](auto ic) {
+                    constexpr int ICLS = decltype(ic)::value;
+                    const typename F::Mod m = F::make_mod(ld_uniform_mod(&a.t.mods[prime]), ld_uniform_fpd(&a.t.fpd[prime]));
+                    const typename F::tw_t *tab = tw_table<FP>(a.t, false, prime);
+                    TwRegs<FP> tw;
+                    p1_load_tw<FP, D1>(tw, tab, tid);
+                    const SrcMap s1{ 3, 0, 0, a.src_fix[comp] };
+                    typename F::elem x[16];
+                    if constexpr (!TWO)
+                    {
+#pragma unroll
+                        for (int e = 0; e < 16; e++)
+                            x[e] = map_src<FP>(resident_word(r1[e]), s1, m); // fixed: |x| <= q/2 (integer: below 4q)
+                        p1_tile<FP, D1, 256, SEALHIP_P1_PLAIN_LEAN && FP && G::rA == 4, ICLS>(x, m, tab, tw, lds, mid_tr, cg, tid);
+                    }
+                    else
+                    {
+                        const ShoupOp pm = t2.x.pmul[comp];
+                        const uint64_t q = a.t.mods[prime].q;
+                        if constexpr (FP)
+                        {
+                            // as tail2_p1_body: v P^-1 + u with ONE fix() per coefficient
+                            const double pinv = pm.w > q / 2 ? -(double)(q - pm.w) : (double)pm.w;
+                            const double f1 = fp_from_u52(s1.fix), f2 = fp_from_u52(t2.x.src2_fix[comp]);
+#pragma unroll
+                            for (int e = 0; e < 16; e++)
+                            {
+                                const double v = F::from_any(resident_word(r1[e]), m) + f1;
+                                const double u = (SMALL2 ? fp_from_bits(r2[e]) : F::from_any(resident_word(r2[e]), m)) + f2;
+                                x[e] = fp_mulmod(v, pinv, m.q, m.qinv) + u;
+                                F::fix(x[e], m);
+                            }
+                        }
+                        else
+                        {
+                            const SrcMap s2{ 3, 0, 0, t2.x.src2_fix[comp] };
+#pragma unroll
+                            for (int e = 0; e < 16; e++)
+                            {
+                                const typename F::elem v = map_src<FP>(resident_word(r1[e]), s1, m), u = map_src<FP>(resident_word(r2[e]), s2, m);
+                                x[e] = mul_shoup(v, pm.w, pm.wq, q) + u; // below q + 2q: inside the forward input range [0, 4q)
+                            }
+                        }
+                        p1_tile<FP, D1, 256, FP && G::rA == 4, ICLS>(x, m, tab, tw, lds, mid_tr, cg, tid);
+                    }
+                };
+                if constexpr (FP)
+                    one(std::integral_constant<int, 0>());
+                else
+                    with_int_class(a.t, prime, one);
+            }
+        }
+
+        // CLS: 0 = integer back end, 1 = double precision (a mixed run keeps the target-resident kernels); TWO: the folded tail
+#ifndef SEALHIP_SRC_P1T_FP2_WGS
+#define SEALHIP_SRC_P1T_FP2_WGS 2 // workgroups per CU the folded tail's double-precision body is compiled for (150 VGPRs: three fit)
+#endif
+        template <int D1, int CLS, bool TWO, bool SMALL2 = false>
+        __global__ void __launch_bounds__(kThreads, SMALL2 ? SEALHIP_SRC_P1T_FP2_WGS : 2) ntt2_src_p1t(Tail2Args a, unsigned nc)
+        {
+            static_assert(CLS == 0 || CLS == 1, "single-class runs only");
+            HIP_DYNAMIC_SHARED(uint64_t, lds)
+            src_p1t_body<CLS == 1, D1, TWO, SMALL2>(a, nc, lds);
         }
 
         // ---------------------------------------------------------------------------------------
@@ -2028,6 +2168,50 @@ namespace sealhip
             return on;
         }
 
+        // Which order pass 1 of a mapped-source transform takes (the plain rounding tails and the folded one).  This is the only
+        // place that decides.  Source-resident (ntt2_src_p1t: the source tile in registers, the targets in the loop) when its grid
+        // of tiles x outer items fills the chip and the class run has more than one target to share the tile; target-resident
+        // (ntt2_fwd_p1 / ntt2_tail2_p1, whose grid does not shrink with the batch) otherwise: small batches, a run of one target,
+        // a mixed-class run.  SEALHIP_TAIL_P1_ORDER=0 / 1 forces the one or the other wherever the new kernel exists at all
+        // (read once; tests/test_tail_order.py, tests/test_gpu_tail_order.py in fresh processes).
+#ifndef SEALHIP_SRC_P1T_MIN_WGS
+#define SEALHIP_SRC_P1T_MIN_WGS 512 // two workgroups per CU.  Headline step at N = 2^16, order forced either way (profiles/r08_tail_source_resident.txt):
+                                    // 64 / 128 workgroups -3 % / -1 %, 256 a tie, 512 +0.6 ... +1.2 %, 1024 (rotate + rescale, batch 32) +1.2 %, 2048 / 8192 +1.6 %
+#endif
+        inline bool src_resident(unsigned tiles, unsigned nouter, const CompRun &r)
+        {
+            static const char *order_env = std::getenv("SEALHIP_TAIL_P1_ORDER");
+            // development builds: the threshold (the emulated tests cross it at batches they can finish) and one line per decision
+            static const char *min_env = shl_ab_getenv("SEALHIP_TAIL_P1_MIN_WGS");
+            static const bool trace = shl_ab_getenv("SEALHIP_TAIL_P1_TRACE") != nullptr;
+            static const size_t min_wgs = min_env ? (size_t)std::atol(min_env) : (size_t)SEALHIP_SRC_P1T_MIN_WGS;
+            bool yes = false;
+            if (r.cls != 0 && r.cls != 1)
+                yes = false;
+            else if (order_env && (order_env[0] == '0' || order_env[0] == '1'))
+                yes = order_env[0] == '1';
+            else
+                yes = r.nc > 1 && (size_t)tiles * nouter >= min_wgs;
+            if (trace)
+                std::fprintf(stderr, "[tail] pass 1 %s (%u tiles x %u items, %u targets of class %d)\n", yes ? "source-resident" : "target-resident",
+                             tiles, nouter, r.nc, r.cls);
+            return yes;
+        }
+        template <int D1, bool TWO>
+        hipError_t launch_src_p1t(const Tail2Args &g, const CompRun &r, unsigned nouter, hipStream_t st)
+        {
+            typedef Geo<D1> G;
+            const size_t l1 = G::rA > 0 ? G::lds1_words * 8 : 8;
+            const dim3 grid(G::TILES * nouter);
+            if (r.cls == 1 && TWO && !(g.x.src2_q >> 52))
+                hipLaunchKernelGGL((ntt2_src_p1t<D1, 1, TWO, TWO>), grid, dim3(kThreads), l1, st, g, r.nc);
+            else if (r.cls == 1)
+                hipLaunchKernelGGL((ntt2_src_p1t<D1, 1, TWO>), grid, dim3(kThreads), l1, st, g, r.nc);
+            else
+                hipLaunchKernelGGL((ntt2_src_p1t<D1, 0, TWO>), grid, dim3(kThreads), l1, st, g, r.nc);
+            return hipGetLastError();
+        }
+
         template <int D1>
         hipError_t launch_fwd(const FwdArgs &a, unsigned nouter, hipStream_t s)
         {
@@ -2127,7 +2311,14 @@ namespace sealhip
                         return hipGetLastError();
                     }
                 }
-                if (r.cls == 1)
+                // one source component mapped into every target (plain rescale / mod-switch, the un-deferred key-switch tail)
+                if (a.src && (a.src_mode == 2 || a.src_mode == 3) && a.src_ncomp == 1 && src_resident(G::TILES, nouter, r))
+                {
+                    hipError_t e1 = launch_src_p1t<D1, false>(Tail2Args{ g, NttTail2{} }, r, nouter, st);
+                    if (e1 != hipSuccess)
+                        return e1;
+                }
+                else if (r.cls == 1)
                     hipLaunchKernelGGL((ntt2_fwd_p1<D1, 1>), grid, dim3(kThreads), l1, st, g);
                 else if (r.cls == 0)
                     hipLaunchKernelGGL((ntt2_fwd_p1<D1, 0>), grid, dim3(kThreads), l1, st, g);
@@ -2173,7 +2364,13 @@ namespace sealhip
                 Tail2Args g = a;
                 g.f.comp0 = r.c0;
                 dim3 grid(G::TILES, r.nc, chunks);
-                if (r.cls == 1)
+                if (src_resident(G::TILES, nouter, r))
+                {
+                    hipError_t e1 = launch_src_p1t<D1, true>(g, r, nouter, st);
+                    if (e1 != hipSuccess)
+                        return e1;
+                }
+                else if (r.cls == 1)
                     hipLaunchKernelGGL((ntt2_tail2_p1<D1, 1>), grid, dim3(kThreads), l1, st, g);
                 else if (r.cls == 0)
                     hipLaunchKernelGGL((ntt2_tail2_p1<D1, 0>), grid, dim3(kThreads), l1, st, g);
