@@ -236,6 +236,32 @@ SHL_FUNC Encryptor_EncryptSymmetric(void *thisptr, void *plaintext, bool save_se
 SHL_FUNC Encryptor_SymmetricSaveSize(void *thisptr, uint64_t *parms_id, int64_t *result);
 SHL_FUNC Encryptor_EncryptZeroSymmetricSave(void *thisptr, uint64_t *parms_id, uint8_t *outptr, uint64_t size, int64_t *out_bytes);
 SHL_FUNC Encryptor_EncryptSymmetricSave(void *thisptr, void *plaintext, uint8_t *outptr, uint64_t size, int64_t *out_bytes);
+/* Whole batches in device memory (library extensions, like CKKSEncoder_EncodeDevice): `batch` fresh ciphertexts in one call,
+ * secret-key (EncryptSymmetricDevice) or public-key (EncryptDevice), without a host round trip per item.
+ * device_plain: CKKS - [batch][K][N] NTT-form words at parms_id, the layout CKKSEncoder_EncodeDevice writes and
+ *   Decryptor_DecryptBatch returns; `scale` becomes the ciphertext's scale (a normal positive number).  BFV / BGV - [batch][N]
+ *   coefficients modulo t, what BatchEncoder_EncodeDevice writes; parms_id must be NULL or the first data level and `scale` is
+ *   ignored.  NULL - encrypt zero at parms_id, at every level the per-object EncryptZero* forms accept (scale 1).  A NULL parms_id
+ *   means the first data level.  The pointer must be 16-byte aligned (SHL_E_INVALIDARG otherwise).  The words are NOT validated (as with Plaintext_SetFromDevice): CKKS words must be below their
+ *   primes and BFV / BGV coefficients below t, or the result is unspecified.
+ * destination: a Ciphertext whose batch equals `batch` (SHL_E_INVALIDARG otherwise); it is resized to size 2 at the level and its
+ *   is_ntt_form, scale and correction factor (1) are set as the per-object forms set them.  Item b lies where every batch
+ *   ciphertext keeps it: word ((p * batch + b) * K + r) * N + j.
+ * seeds: host array [batch][8], item b's bootstrap seed.  NULL: with Encryptor_SetSeed installed EVERY item restarts from that
+ *   seed (the reference's seeded factory: identical (a, e) in every item - the INSECURE warning of Encryptor_SetSeed applies, as it
+ *   does to caller-chosen seeds); otherwise every item draws 64 fresh bytes from the operating system.
+ * Item b equals, word for word, what Encryptor_EncryptSymmetric / Encryptor_Encrypt (device_plain NULL: EncryptZeroSymmetric1 /
+ * EncryptZero1) give after Encryptor_SetSeed(seeds + 8 b), hence the reference's Encryptor under Blake2xbPRNGFactory(seed_b).
+ * Both run on the NULL stream and return when the work is done; batch == 0 does nothing.  Arguments are checked as the per-object
+ * forms check them, with their HRESULTs: unknown parms_id, a level the scheme does not encrypt a plaintext at, a destination of
+ * another context or batch, device_plain overlapping the destination's words: SHL_E_INVALIDARG; a missing key:
+ * SHL_COR_E_INVALIDOPERATION; NULL thisptr / destination: SHL_E_POINTER.  A failed check leaves the destination untouched.  The batch
+ * is worked through in chunks of max(1, 256 MiB / (8 K' N)) items, K' = the primes at the level the item is encrypted at (the level
+ * above parms_id for the public-key form where there is one), which bounds the scratch of a chunk; it goes back to the pool. */
+SHL_FUNC Encryptor_EncryptSymmetricDevice(void *thisptr, const uint64_t *device_plain, uint64_t batch, uint64_t *parms_id, double scale,
+                                          const uint64_t *seeds, void *destination);
+SHL_FUNC Encryptor_EncryptDevice(void *thisptr, const uint64_t *device_plain, uint64_t batch, uint64_t *parms_id, double scale,
+                                 const uint64_t *seeds, void *destination);
 
 /* KSwitchKeys / RelinKeys / GaloisKeys (native/src/seal/c/kswitchkeys.h, relinkeys.h, galoiskeys.h).
  * A key set lives in HBM; one key (index) is uploaded as the concatenation of its decomposition
@@ -634,6 +660,9 @@ SHL_FUNC SealHip_ProductStats(uint64_t *fused, uint64_t *formed, uint64_t *dropp
  * zero before the key switch - is neither written nor read.  Same words.  Counters for tests: rotations that took that path / that ran
  * the permutation kernels. */
 SHL_FUNC SealHip_GaloisStats(uint64_t *gathered, uint64_t *permuted);
+/* sample_poly_uniform on the device (seeded streams, fresh encryptions) since the library was loaded: polynomials expanded, rejected
+ * words the host replaced in the reference's order, nanoseconds of that host walk, nanoseconds of the expansion calls altogether */
+SHL_FUNC SealHip_XofStats(uint64_t *polynomials, uint64_t *replaced_words, uint64_t *host_walk_ns, uint64_t *total_ns);
 /* stream and device memory helpers for bindings without their own runtime (a PyTorch / HIP caller passes its own streams) */
 /* one process per GPU: select the calling thread's device before creating a SEALContext (a PyTorch caller uses
  * torch.cuda.set_device instead) */

@@ -75,6 +75,7 @@ BatchEncoder_Decode2 BatchEncoder_EncodeDevice BatchEncoder_DecodeDevice
 PublicKey_Create PublicKey_Destroy PublicKey_Set PublicKey_UnsafeLoad PublicKey_Load Encryptor_Encrypt Encryptor_EncryptZero1 Encryptor_EncryptZero2 Encryptor_EncryptZeroSymmetric2
 Encryptor_Create Encryptor_Destroy Encryptor_SetSeed Encryptor_EncryptZeroSymmetric1 Encryptor_EncryptSymmetric
 Encryptor_SymmetricSaveSize Encryptor_EncryptZeroSymmetricSave Encryptor_EncryptSymmetricSave
+Encryptor_EncryptSymmetricDevice Encryptor_EncryptDevice
 Plaintext_Create1 Plaintext_Create5 Plaintext_Destroy Plaintext_Set4 Plaintext_SetFromDevice Plaintext_CoeffCount
 Plaintext_IsNTTForm Plaintext_GetParmsId Plaintext_SetParmsId Plaintext_Scale Plaintext_SetScale Plaintext_CopyToHost
 Plaintext_SaveSize Plaintext_Save Plaintext_UnsafeLoad Plaintext_Load
@@ -95,7 +96,7 @@ Comm_GetUniqueId Comm_RcclAvailable Comm_Create Comm_Destroy Comm_Info Comm_Digi
 Evaluator_RelinearizeDigitParallel Evaluator_ApplyGaloisDigitParallel Evaluator_RotateVectorDigitParallel
 Evaluator_BroadcastKeyDigits Evaluator_SwitchKeySlots Evaluator_SwitchKeyPackTargets Evaluator_SwitchKeyFinishOwned
 Evaluator_SwitchKeyAddGathered
-SealHip_ReleasePool SealHip_PoolStats SealHip_TailStats SealHip_ProductStats SealHip_GaloisStats SealHip_KsChunkStats SealHip_SetStagedHostCopies SealHip_InstallAbortTrace shl_stream_create shl_stream_destroy shl_device_count shl_set_device
+SealHip_ReleasePool SealHip_PoolStats SealHip_TailStats SealHip_ProductStats SealHip_GaloisStats SealHip_XofStats SealHip_KsChunkStats SealHip_SetStagedHostCopies SealHip_InstallAbortTrace shl_stream_create shl_stream_destroy shl_device_count shl_set_device
 shl_ntt_forward shl_ntt_inverse shl_dyadic_product shl_apply_galois shl_rns_stage shl_malloc shl_free
 shl_memcpy_h2d shl_memcpy_d2h shl_device_synchronize shl_timer_create shl_timer_destroy shl_timer_start
 shl_timer_stop

@@ -1121,6 +1121,35 @@ class Encryptor:
         N.check(N.lib().Encryptor_EncryptSymmetric(self._h, plain._h, C.c_bool(False), destination._h, None))
         return destination
 
+    def _encrypt_device(self, fn, words, batch, parms_id, scale, seeds, destination):
+        destination = destination if destination is not None else Ciphertext(self.context, batch=max(int(batch), 1))
+        pid = (C.c_uint64 * 4)(*parms_id) if parms_id is not None else None
+        sp = None
+        if seeds is not None:
+            a = np.asarray(seeds, dtype=np.uint64)
+            if a.ndim == 1 and a.size == batch and batch * 8 != a.size:   # one int per item = the first word of its seed
+                full = np.zeros((batch, 8), dtype=np.uint64)
+                full[:, 0] = a
+                a = full
+            a = np.ascontiguousarray(a.reshape(-1), dtype=np.uint64)
+            if a.size != batch * 8:
+                raise ValueError("seeds: one int or 8 words per item")
+            sp = _p(a)
+        N.check(fn(self._h, C.c_void_p(words.ptr) if words is not None else None, C.c_uint64(batch), pid, C.c_double(scale), sp, destination._h))
+        return destination
+
+    def encrypt_symmetric_device(self, words, batch, parms_id=None, scale=1.0, seeds=None, destination=None):
+        """secret-key encryption of a whole batch in device memory (sealhip.h: Encryptor_EncryptSymmetricDevice).  words: DeviceBuffer
+        of [batch][K][N] NTT-form plaintext words (CKKS: CKKSEncoder.encode_device's output) or [batch][N] coefficients modulo t
+        (BFV / BGV: BatchEncoder.encode_device's), or None: encryptions of zero.  parms_id None: the first data level.  seeds: one
+        bootstrap seed per item - `batch` ints (the first word) or a (batch, 8) array; None: the installed seed for every item
+        (INSECURE, see set_seed) or operating-system entropy per item.  -> the batch Ciphertext (`destination` reuses one)"""
+        return self._encrypt_device(N.lib().Encryptor_EncryptSymmetricDevice, words, batch, parms_id, scale, seeds, destination)
+
+    def encrypt_device(self, words, batch, parms_id=None, scale=1.0, seeds=None, destination=None):
+        """the public-key form of encrypt_symmetric_device (sealhip.h: Encryptor_EncryptDevice)"""
+        return self._encrypt_device(N.lib().Encryptor_EncryptDevice, words, batch, parms_id, scale, seeds, destination)
+
     def _save(self, parms_id, call):
         cap = C.c_int64()
         N.check(N.lib().Encryptor_SymmetricSaveSize(self._h, (C.c_uint64 * 4)(*parms_id), C.byref(cap)))
@@ -1623,6 +1652,14 @@ def galois_stats():
     a, b = C.c_uint64(), C.c_uint64()
     N.check(N.lib().SealHip_GaloisStats(C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def xof_stats():
+    """sample_poly_uniform on the device (sealhip.h: SealHip_XofStats): (polynomials expanded, rejected words replaced by the host,
+    nanoseconds of that host walk, nanoseconds of the expansion calls altogether) since the library was loaded"""
+    v = [C.c_uint64() for _ in range(4)]
+    N.check(N.lib().SealHip_XofStats(*[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
 
 
 def ks_chunk_stats():

@@ -648,5 +648,23 @@ extern "C"
         *out_bytes = (int64_t)as<Encryptor>(thisptr)->encrypt_symmetric_save(*as<Plaintext>(plaintext), outptr, (size_t)size);
         SHL_CATCH
     }
+    SHL_FUNC Encryptor_EncryptSymmetricDevice(void *thisptr, const uint64_t *device_plain, uint64_t batch, uint64_t *parms_id, double scale,
+                                              const uint64_t *seeds, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        as<Encryptor>(thisptr)->encrypt_symmetric_device(device_plain, (size_t)batch, parms_id, scale, seeds, *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
+    SHL_FUNC Encryptor_EncryptDevice(void *thisptr, const uint64_t *device_plain, uint64_t batch, uint64_t *parms_id, double scale,
+                                     const uint64_t *seeds, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        as<Encryptor>(thisptr)->encrypt_device(device_plain, (size_t)batch, parms_id, scale, seeds, *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
 
 }

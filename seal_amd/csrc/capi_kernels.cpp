@@ -162,6 +162,12 @@ extern "C"
             *scratch_bytes_max = w * 8;
         SHL_CATCH
     }
+    SHL_FUNC SealHip_XofStats(uint64_t *polynomials, uint64_t *replaced_words, uint64_t *host_walk_ns, uint64_t *total_ns)
+    {
+        SHL_TRY
+        xof_stats(polynomials, replaced_words, host_walk_ns, total_ns);
+        SHL_CATCH
+    }
     SHL_FUNC SealHip_ProductStats(uint64_t *fused, uint64_t *formed, uint64_t *dropped)
     {
         SHL_TRY

@@ -3,6 +3,7 @@
 #include "xof.h"
 #include "hostmath.h"
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -746,5 +747,312 @@ namespace sealhip
         zero(*level_for(plain), true, ct, pub);
         add_plain(plain, ct);
         return save(ct, pub, out, capacity);
+    }
+
+    // ---------------------------------------------------------------- Encryptor, whole batches in device memory
+    namespace
+    {
+        constexpr size_t kEncryptBatchScratchBytes = size_t(256) << 20; // per chunk (include/sealhip.h)
+        bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+        {
+            const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+            return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+        }
+        BfvPlainConst bfv_plain_const(const Context &ctx, const Level &lvl)
+        {
+            return BfvPlainConst{ host::make_mod(ctx.plain_modulus()), lvl.dev.q_mod_t, lvl.dev.plain_upper_half_threshold, lvl.dev.delta_mod_q };
+        }
+    } // namespace
+    size_t Encryptor::chunk_items(size_t item_words) const
+    {
+        size_t budget = kEncryptBatchScratchBytes;
+        if (const char *e = shl_ab_getenv("SEALHIP_ENCRYPT_SCRATCH_BYTES")) // development builds only: chunk edges at small N
+            budget = (size_t)std::strtoull(e, nullptr, 10);
+        return std::max<size_t>(1, std::min<size_t>(budget / (item_words * 8), 65535)); // items are the grid's y dimension
+    }
+    // where a batch is encrypted and what each scheme accepts there (level_for(parms_id) / level_for(plain) of the per-object forms)
+    const Level &Encryptor::batch_level(bool have_plain, const uint64_t *parms_id, double scale) const
+    {
+        const Level *l = parms_id ? context_.level_by_parms_id(parms_id) : &context_.first_level();
+        if (!l)
+            throw std::invalid_argument("parms_id is not valid for encryption parameters");
+        if (!have_plain)
+            return *l;
+        if (context_.scheme() == Scheme::ckks)
+        {
+            if (l->chain_index > context_.first_level().chain_index || !std::isnormal(scale) || scale <= 0)
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+        }
+        else if (l != &context_.first_level())
+            throw std::invalid_argument("plain is not valid for encryption parameters");
+        return *l;
+    }
+    void Encryptor::batch_checks(const uint64_t *plain, size_t batch, const Level &lvl, const Ciphertext &d) const
+    {
+        if (&d.context() != &context_)
+            throw std::invalid_argument("destination belongs to another context");
+        if (d.batch() != batch)
+            throw std::invalid_argument("destination's batch does not equal the number of items to encrypt");
+        if (!plain)
+            return;
+        if ((uintptr_t)plain % 16)
+            throw std::invalid_argument("device_plain must be 16-byte aligned");
+        const size_t item_words = context_.scheme() == Scheme::ckks ? lvl.K * context_.n() : context_.n();
+        if (d.has_storage() && overlap(plain, batch * item_words * 8, d.data(), d.capacity_words() * 8))
+            throw std::invalid_argument("plain and destination overlap");
+    }
+    std::vector<uint64_t> Encryptor::batch_seeds(size_t batch, const uint64_t *seeds) const
+    {
+        std::vector<uint64_t> boots(batch * 8);
+        if (seeds)
+            std::memcpy(boots.data(), seeds, batch * 64);
+        else if (seeded_)
+            for (size_t b = 0; b < batch; b++)
+                std::memcpy(boots.data() + 8 * b, seed_, 64);
+        else
+            host::random_bytes(boots.data(), batch * 64);
+        return boots;
+    }
+
+    // util::encrypt_zero_symmetric (util/rlwe.cpp:270-395) + the plaintext addition of Encryptor::encrypt_internal, `batch` times
+    void Encryptor::encrypt_symmetric_device(const uint64_t *plain, size_t batch, const uint64_t *parms_id, double scale, const uint64_t *seeds,
+                                             Ciphertext &d)
+    {
+        const Level &lvl = batch_level(plain != nullptr, parms_id, scale);
+        if (!batch)
+            return;
+        if (!sk_)
+            throw std::logic_error("secret key is not set");
+        batch_checks(plain, batch, lvl, d);
+        const size_t n = context_.n(), K = lvl.K, words = K * n;
+        const unsigned n_log = (unsigned)context_.log_n();
+        const Scheme scheme = context_.scheme();
+        const bool ntt_form = scheme != Scheme::bfv;
+        const std::vector<uint64_t> boots = batch_seeds(batch, seeds);
+        // per item as the per-object form decides: a on the device when its stream is whole PRNG buffers, the noise (bytes
+        // [64, 64 + 6n) of the bootstrap stream) when it is whole 64-byte pieces
+        const bool device_a = xof_device_ok(1, K, n);
+        const bool device_e = (6 * n) % 64 == 0 && !std::getenv("SEALHIP_ENCRYPT_HOST_SAMPLING");
+
+        ck(hipStreamSynchronize(nullptr), "encrypt sync");
+        d.resize(&lvl, 2, nullptr);
+        d.is_ntt_form() = ntt_form;
+        d.scale() = scheme == Scheme::ckks && plain ? scale : 1.0;
+        d.correction_factor() = 1;
+        uint64_t *c0 = d.plane(0), *c1 = d.plane(1);
+        const NttTables &tb = context_.ntt_tables();
+        const ModDesc *mods = context_.dev_mods();
+        const uint64_t noise_factor = scheme == Scheme::bgv ? context_.plain_modulus() : 1;
+        const bool lift = plain && scheme == Scheme::bgv;
+        const size_t chunk = std::min(chunk_items(words), batch);
+        const size_t small_stride = (n + 15) & ~size_t(15); // signed bytes per item
+        Scratch dseeds(chunk * 8), stream(device_e ? chunk * (6 * n / 8) : 1), small(chunk * small_stride / 8), lifted(lift ? chunk * words : 1);
+        int8_t *dsmall = reinterpret_cast<int8_t *>(small.p);
+        std::vector<int8_t> host_small(device_e ? 0 : chunk * small_stride);
+        std::vector<uint64_t> host_a(device_a ? 0 : words);
+        std::vector<XofJob> jobs;
+        for (size_t b0 = 0; b0 < batch; b0 += chunk)
+        {
+            const unsigned items = (unsigned)std::min(chunk, batch - b0);
+            uint64_t *c0c = c0 + b0 * words, *c1c = c1 + b0 * words;
+            // host: every item's public seed = the first 64 bytes of its bootstrap stream
+            jobs.clear();
+            for (unsigned i = 0; i < items; i++)
+            {
+                serial::Prng bootstrap(1, boots.data() + (b0 + i) * 8);
+                uint64_t pub[8];
+                bootstrap.generate(sizeof(pub), reinterpret_cast<uint8_t *>(pub));
+                if (device_a)
+                {
+                    XofJob job;
+                    std::memcpy(job.seed, pub, sizeof(job.seed));
+                    job.dst = c1c + i * words;
+                    jobs.push_back(job);
+                }
+                else
+                {
+                    serial::Prng cprng(1, pub);
+                    serial::sample_poly_uniform(cprng, context_.coeff_modulus().data(), K, n, host_a.data());
+                    ck(hipMemcpy(c1c + i * words, host_a.data(), words * 8, hipMemcpyHostToDevice), "upload a");
+                }
+                if (!device_e)
+                    serial::sample_small_cbd(bootstrap, n, host_small.data() + i * small_stride);
+            }
+            if (device_a)
+                sample_uniform_device(context_, K, jobs);
+            if (device_e)
+            {
+                ck(hipMemcpy(dseeds.p, boots.data() + b0 * 8, (size_t)items * 64, hipMemcpyHostToDevice), "upload seeds");
+                ck(k_blake2xb_stream_batch(dseeds.p, 1, 6 * n / 64, stream.p, items, nullptr), "bootstrap streams");
+                ck(k_small_from_stream_batch(reinterpret_cast<const uint8_t *>(stream.p), 6 * n, 0, 0, n, dsmall, small_stride, nullptr, items, nullptr),
+                   "sample noise");
+            }
+            else
+                ck(hipMemcpy(dsmall, host_small.data(), (size_t)items * small_stride, hipMemcpyHostToDevice), "upload noise");
+            if (ntt_form)
+            {
+                // the noise goes straight to where it is transformed and consumed: the item's c0
+                ck(k_expand_small_batch(mods, dsmall, small_stride, c0c, 0, n_log, (unsigned)K, 1, items, nullptr), "expand noise");
+                ck(ntt_forward(tb, polys(c0c, K, n, items), 0, nullptr), "ntt noise");
+                const uint64_t *m = plain ? plain + b0 * words : nullptr;
+                if (lift)
+                {
+                    // BGV: lift -> NTT -> add (Evaluator::add_plain on a fresh ciphertext, correction factor 1)
+                    ck(k_plain_lift_batch(mods, plain + b0 * n, lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log,
+                                          (unsigned)K, items, nullptr),
+                       "plain lift");
+                    ck(ntt_forward(tb, polys(lifted.p, K, n, items), 0, nullptr), "plain ntt");
+                    m = lifted.p;
+                }
+                ck(k_encrypt_sym_tail(mods, sk_, c1c, c0c, m, noise_factor, false, n_log, (unsigned)K, items, nullptr), "c0");
+            }
+            else
+            {
+                // BFV: a was sampled in NTT form; the ciphertext is returned in coefficient form
+                ck(k_encrypt_sym_tail(mods, sk_, c1c, c0c, nullptr, 1, true, n_log, (unsigned)K, items, nullptr), "a s");
+                ck(ntt_inverse(tb, polys(c0c, K, n, items), 0, nullptr), "intt a s");
+                ck(ntt_inverse(tb, polys(c1c, K, n, items), 0, nullptr), "intt a");
+                ck(k_encrypt_bfv_finish(mods, bfv_plain_const(context_, lvl), dsmall, small_stride, plain ? plain + b0 * n : nullptr, c0c, 0, 1, true,
+                                        n_log, (unsigned)K, items, nullptr),
+                   "c0");
+            }
+        }
+        ck(hipStreamSynchronize(nullptr), "encrypt sync"); // the scratch goes back to the pool
+    }
+
+    // Encryptor::encrypt_zero_internal, asymmetric branch (encryptor.cpp:139-186; util::encrypt_zero_asymmetric, rlwe.cpp:196-268)
+    // + the plaintext addition, `batch` times
+    void Encryptor::encrypt_device(const uint64_t *plain, size_t batch, const uint64_t *parms_id, double scale, const uint64_t *seeds, Ciphertext &d)
+    {
+        const Level &lvl = batch_level(plain != nullptr, parms_id, scale);
+        if (!batch)
+            return;
+        if (!pk_)
+            throw std::logic_error("public key is not set");
+        batch_checks(plain, batch, lvl, d);
+        const Level *prev = context_.level_by_chain_index(lvl.chain_index + 1);
+        const Level &at = prev ? *prev : lvl; // encrypt one level up where there is one, then switch down
+        const size_t n = context_.n(), K = at.K, L = context_.key_level().K, words = K * n;
+        const unsigned n_log = (unsigned)context_.log_n();
+        const Scheme scheme = context_.scheme();
+        const bool ntt_form = scheme != Scheme::bfv;
+        const std::vector<uint64_t> boots = batch_seeds(batch, seeds);
+        // u, e_0, e_1 = bytes [0, 4n), [4n, 10n), [10n, 16n) of the item's stream: whole 64-byte pieces from n = 4 on
+        const bool device_s = n >= 4 && !std::getenv("SEALHIP_ENCRYPT_HOST_SAMPLING");
+
+        ck(hipStreamSynchronize(nullptr), "encrypt sync");
+        d.resize(&at, 2, nullptr);
+        d.is_ntt_form() = ntt_form;
+        d.scale() = 1.0;
+        d.correction_factor() = 1;
+        const NttTables &tb = context_.ntt_tables();
+        const ModDesc *mods = context_.dev_mods();
+        const uint64_t noise_factor = scheme == Scheme::bgv ? context_.plain_modulus() : 1;
+        const size_t plane_stride = d.plane_words();
+        const size_t chunk = std::min(chunk_items(words), batch);
+        const size_t small_stride = (3 * n + 15) & ~size_t(15);
+        {
+            Scratch dseeds(chunk * 8), stream(device_s ? chunk * 2 * n : 1), small(chunk * small_stride / 8), dflags(chunk / 2 + 1), du(chunk * words);
+            int8_t *dsmall = reinterpret_cast<int8_t *>(small.p);
+            unsigned *redraw = reinterpret_cast<unsigned *>(dflags.p);
+            std::vector<unsigned> flags(chunk, 0);
+            std::vector<int8_t> host_small(3 * n);
+            for (size_t b0 = 0; b0 < batch; b0 += chunk)
+            {
+                const unsigned items = (unsigned)std::min(chunk, batch - b0);
+                uint64_t *c = d.plane(0) + b0 * words;
+                if (device_s)
+                {
+                    ck(hipMemcpy(dseeds.p, boots.data() + b0 * 8, (size_t)items * 64, hipMemcpyHostToDevice), "upload seeds");
+                    ck(hipMemsetAsync(redraw, 0, (size_t)items * 4, nullptr), "clear flags");
+                    ck(k_blake2xb_stream_batch(dseeds.p, 0, 16 * n / 64, stream.p, items, nullptr), "bootstrap streams");
+                    ck(k_small_from_stream_batch(reinterpret_cast<const uint8_t *>(stream.p), 16 * n, n, 4 * n, 2 * n, dsmall, small_stride, redraw,
+                                                 items, nullptr),
+                       "sample u, e");
+                    ck(hipMemcpy(flags.data(), redraw, (size_t)items * 4, hipMemcpyDeviceToHost), "read flags");
+                }
+                // a ternary draw the reference redraws (probability n / 2^32 per item) shifts the rest of that item's stream: such an
+                // item alone is sampled again here on the host, as every item is when the device cannot sample
+                for (unsigned i = 0; i < items; i++)
+                    if (!device_s || flags[i])
+                    {
+                        serial::Prng prng(1, boots.data() + (b0 + i) * 8);
+                        serial::sample_small_ternary(prng, n, host_small.data());
+                        serial::sample_small_cbd(prng, n, host_small.data() + n);
+                        serial::sample_small_cbd(prng, n, host_small.data() + 2 * n);
+                        ck(hipMemcpy(dsmall + i * small_stride, host_small.data(), 3 * n, hipMemcpyHostToDevice), "upload u, e");
+                    }
+                ck(k_expand_small_batch(mods, dsmall, small_stride, du.p, 0, n_log, (unsigned)K, 1, items, nullptr), "expand u");
+                ck(ntt_forward(tb, polys(du.p, K, n, items), 0, nullptr), "ntt u");
+                if (ntt_form)
+                {
+                    // e_0, e_1 go straight to where they are transformed and consumed: the item's two planes
+                    ck(k_expand_small_batch(mods, dsmall + n, small_stride, c, plane_stride, n_log, (unsigned)K, 2, items, nullptr), "expand e");
+                    if (items == batch)
+                        ck(ntt_forward(tb, polys(c, K, n, 2 * (size_t)items), 0, nullptr), "ntt noise");
+                    else
+                        for (size_t j = 0; j < 2; j++)
+                            ck(ntt_forward(tb, polys(c + j * plane_stride, K, n, items), 0, nullptr), "ntt noise");
+                    ck(k_encrypt_pk_tail(mods, pk_, L * n, du.p, c, plane_stride, noise_factor, false, n_log, (unsigned)K, items, nullptr), "pk u + e");
+                }
+                else
+                {
+                    ck(k_encrypt_pk_tail(mods, pk_, L * n, du.p, c, plane_stride, 1, true, n_log, (unsigned)K, items, nullptr), "pk u");
+                    for (size_t j = 0; j < 2; j++)
+                        ck(ntt_inverse(tb, polys(c + j * plane_stride, K, n, items), 0, nullptr), "intt pk u");
+                    ck(k_encrypt_bfv_finish(mods, bfv_plain_const(context_, at), dsmall + n, small_stride, nullptr, c, plane_stride, 2, false, n_log,
+                                            (unsigned)K, items, nullptr),
+                       "c + e");
+                }
+            }
+            ck(hipStreamSynchronize(nullptr), "encrypt sync"); // the scratch goes back to the pool
+        }
+        if (prev)
+        {
+            evaluator_.mod_switch_scale_to_next(d); // batch-aware: every item in one pass
+            evaluator_.synchronize();
+            d.scale() = 1.0;
+            d.correction_factor() = 1;
+        }
+        if (plain)
+            add_plain_batch(plain, scale, d);
+    }
+
+    // Evaluator::add_plain on fresh ciphertexts, with one plaintext per item
+    void Encryptor::add_plain_batch(const uint64_t *plain, double scale, Ciphertext &d)
+    {
+        const Level &lvl = *d.level();
+        const size_t n = context_.n(), K = lvl.K, words = K * n, batch = d.batch();
+        const unsigned n_log = (unsigned)context_.log_n();
+        const ModDesc *mods = context_.dev_mods();
+        switch (context_.scheme())
+        {
+        case Scheme::ckks:
+            d.scale() = scale;
+            ck(k_add_inplace(mods, d.plane(0), plain, batch * words, n_log, (unsigned)K, nullptr), "ckks add plain");
+            break;
+        case Scheme::bfv:
+            ck(k_encrypt_bfv_finish(mods, bfv_plain_const(context_, lvl), nullptr, 0, plain, d.plane(0), 0, 1, false, n_log, (unsigned)K,
+                                    (unsigned)batch, nullptr),
+               "bfv add plain");
+            break;
+        default:
+        {
+            const size_t chunk = std::min(chunk_items(words), batch);
+            Scratch lifted(chunk * words);
+            for (size_t b0 = 0; b0 < batch; b0 += chunk)
+            {
+                const unsigned items = (unsigned)std::min(chunk, batch - b0);
+                ck(k_plain_lift_batch(mods, plain + b0 * n, lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log, (unsigned)K,
+                                      items, nullptr),
+                   "plain lift");
+                ck(ntt_forward(context_.ntt_tables(), polys(lifted.p, K, n, items), 0, nullptr), "plain ntt");
+                ck(k_add_inplace(mods, d.plane(0) + b0 * words, lifted.p, (size_t)items * words, n_log, (unsigned)K, nullptr), "bgv add plain");
+            }
+            ck(hipStreamSynchronize(nullptr), "encrypt sync");
+            return;
+        }
+        }
+        ck(hipStreamSynchronize(nullptr), "encrypt sync");
     }
 } // namespace sealhip

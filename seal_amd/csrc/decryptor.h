@@ -4,6 +4,7 @@
 #pragma once
 #include "ckks_encoder.h"
 #include "decrypt_kernels.h"
+#include "encrypt_kernels.h"
 #include "evaluator.h"
 #include "serial.h"
 #include <mutex>
@@ -140,7 +141,23 @@ namespace sealhip
         size_t encrypt_zero_symmetric_save(const uint64_t *parms_id, uint8_t *out, size_t capacity);
         size_t encrypt_symmetric_save(const Plaintext &plain, uint8_t *out, size_t capacity);
 
+        // Whole batches in device memory (Encryptor_EncryptSymmetricDevice / Encryptor_EncryptDevice, include/sealhip.h): item b of
+        // `destination` (a batch of `batch`) is what encrypt_symmetric / encrypt [_zero when plain == null] gives under
+        // set_seed(seeds + 8 b).  plain: [batch][K][N] NTT-form words at parms_id (CKKS) or [batch][N] coefficients modulo t
+        // (BFV / BGV), device memory, not validated.  seeds: host [batch][8], or null: the installed seed for every item, or
+        // operating-system entropy per item.  One launch per step over a chunk of items (encrypt_kernels.h, xof_kernels.h);
+        // the fallbacks of the per-object forms (host sampling, rings too small for the device XOF) are taken per item.
+        void encrypt_symmetric_device(const uint64_t *plain, size_t batch, const uint64_t *parms_id, double scale, const uint64_t *seeds,
+                                      Ciphertext &destination);
+        void encrypt_device(const uint64_t *plain, size_t batch, const uint64_t *parms_id, double scale, const uint64_t *seeds,
+                            Ciphertext &destination);
+
     private:
+        const Level &batch_level(bool have_plain, const uint64_t *parms_id, double scale) const;
+        void batch_checks(const uint64_t *plain, size_t batch, const Level &lvl, const Ciphertext &destination) const;
+        std::vector<uint64_t> batch_seeds(size_t batch, const uint64_t *seeds) const;
+        size_t chunk_items(size_t item_words) const;
+        void add_plain_batch(const uint64_t *plain, double scale, Ciphertext &destination);
         friend class KeyGenerator; // keys are encryptions of zero under s (keygenerator.cpp:93-121, 322-357)
         const Level *level_for(const uint64_t *parms_id) const;
         const Level *level_for(const Plaintext &plain) const; // + the checks of Encryptor::encrypt_internal

@@ -1,6 +1,8 @@
 #include "xof.h"
 #include "pool.h"
 #include "serial.h"
+#include <atomic>
+#include <chrono>
 #include <cstring>
 #include <stdexcept>
 
@@ -13,13 +15,31 @@ namespace sealhip
             if (e != hipSuccess)
                 throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
         }
+        std::atomic<uint64_t> g_jobs{ 0 }, g_patches{ 0 }, g_walk_ns{ 0 }, g_total_ns{ 0 };
+        uint64_t ns_since(std::chrono::steady_clock::time_point t0)
+        {
+            return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        }
     } // namespace
+
+    void xof_stats(uint64_t *jobs, uint64_t *patches, uint64_t *walk_ns, uint64_t *total_ns)
+    {
+        if (jobs)
+            *jobs = g_jobs.load();
+        if (patches)
+            *patches = g_patches.load();
+        if (walk_ns)
+            *walk_ns = g_walk_ns.load();
+        if (total_ns)
+            *total_ns = g_total_ns.load();
+    }
 
     void sample_uniform_device(const Context &ctx, size_t K, const std::vector<XofJob> &jobs)
     {
         const size_t n = ctx.n(), words = K * n, njobs = jobs.size();
         if (!njobs)
             return;
+        const auto t_call = std::chrono::steady_clock::now();
         if (!xof_device_ok((uint8_t)jobs[0].prng_type, K, n))
             throw std::logic_error("polynomial is not a whole number of PRNG buffers");
         const size_t map_words = words / 32; // unsigned words of the rejection bitmap per job
@@ -43,6 +63,7 @@ namespace sealhip
         }
         std::vector<uint32_t> map(njobs * map_words);
         ck(hipMemcpy(map.data(), dmap.p, map.size() * 4, hipMemcpyDeviceToHost), "download bitmap");
+        const auto t_walk = std::chrono::steady_clock::now();
 
         // the replacements: per polynomial the stream continues after its K*N words; rejected positions take the next accepted
         // words in (component, coefficient) order - the loop of sample_poly_uniform (util/rlwe.cpp:170-190)
@@ -72,6 +93,9 @@ namespace sealhip
                 }
             }
         }
+        g_walk_ns += ns_since(t_walk);
+        g_jobs += njobs;
+        g_patches += patches.size();
         if (!patches.empty())
         {
             Scratch dp(patches.size() * sizeof(XofPatch) / 8);
@@ -79,5 +103,6 @@ namespace sealhip
             ck(k_apply_patches(reinterpret_cast<const XofPatch *>(dp.p), patches.size(), nullptr), "patch");
             ck(hipStreamSynchronize(nullptr), "xof sync");
         }
+        g_total_ns += ns_since(t_call);
     }
 } // namespace sealhip

@@ -15,4 +15,7 @@ namespace sealhip
     // dst_j = sample_poly_uniform(Blake2xbPRNG(seed_j) or Shake256PRNG(seed_j), XofJob::prng_type) over the first K primes of the context, every job [K][N] words in HBM.
     // Synchronous (returns when the words are in place).
     void sample_uniform_device(const Context &ctx, size_t K, const std::vector<XofJob> &jobs);
+    // (SealHip_XofStats: since the library was loaded - polynomials expanded, rejected words replaced, nanoseconds the host
+    // spent on the bitmap and the replacement walk, nanoseconds inside sample_uniform_device altogether)
+    void xof_stats(uint64_t *jobs, uint64_t *patches, uint64_t *walk_ns, uint64_t *total_ns);
 } // namespace sealhip

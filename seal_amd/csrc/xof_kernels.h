@@ -45,5 +45,12 @@ namespace sealhip
     // ternary draw would have been redrawn by the reference (the caller then samples on the host)
     hipError_t k_small_from_stream(const uint8_t *stream, size_t n_ternary, size_t cbd_offset, size_t n_cbd, int8_t *small, unsigned *redraw,
                                    hipStream_t s);
+    // The two kernels above for `items` independent streams in one launch (Encryptor's batch forms, decryptor.h).  seeds: a DEVICE
+    // array [items][8]; out: [items][8 * pieces] words, item b = pieces first_piece .. of the stream of seeds[b].
+    hipError_t k_blake2xb_stream_batch(const uint64_t *seeds, uint64_t first_piece, size_t pieces, uint64_t *out, unsigned items, hipStream_t s);
+    // streams: [items][stream_bytes]; small: [items][small_stride] signed bytes (n_ternary + n_cbd used); redraw: one flag per
+    // item (zeroed by the caller; may be null when n_ternary == 0), raised where item b alone has to be resampled on the host
+    hipError_t k_small_from_stream_batch(const uint8_t *streams, size_t stream_bytes, size_t n_ternary, size_t cbd_offset, size_t n_cbd,
+                                         int8_t *small, size_t small_stride, unsigned *redraw, unsigned items, hipStream_t s);
     hipError_t k_apply_patches(const XofPatch *patches, size_t count, hipStream_t s);
 } // namespace sealhip

@@ -268,6 +268,42 @@ namespace sealhip
             }
         }
 
+        // the two kernels above over `gridDim.y` independent streams: item b = blockIdx.y reads its seed from seeds[b]
+        __global__ void __launch_bounds__(kBlock) blake2xb_stream_batch_kernel(const uint64_t *seeds, uint64_t first_piece, size_t pieces, uint64_t *out)
+        {
+            const size_t p = blockIdx.x * (size_t)kBlock + threadIdx.x;
+            if (p >= pieces)
+                return;
+            uint64_t h[8];
+            stream_piece(seeds + 8 * (size_t)blockIdx.y, first_piece + p, h);
+            uint64_t *dst = out + ((size_t)blockIdx.y * pieces + p) * 8;
+#pragma unroll
+            for (int t = 0; t < 8; t++)
+                dst[t] = h[t];
+        }
+        __global__ void __launch_bounds__(kBlock) small_from_stream_batch_kernel(
+            const uint8_t *streams, size_t stream_bytes, size_t n_ternary, size_t cbd_offset, size_t n_cbd, int8_t *small, size_t small_stride,
+            unsigned *redraw)
+        {
+            const size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x;
+            const uint8_t *stream = streams + (size_t)blockIdx.y * stream_bytes;
+            int8_t *out = small + (size_t)blockIdx.y * small_stride;
+            if (k < n_ternary)
+            {
+                const uint8_t *b = stream + 4 * k;
+                const uint32_t g = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+                const uint64_t product = (uint64_t)g * 3u;
+                if ((uint32_t)product < 1u)
+                    atomicOr(redraw + blockIdx.y, 1u);
+                out[k] = (int8_t)((int)(product >> 32) - 1);
+            }
+            else if (k < n_ternary + n_cbd)
+            {
+                const uint8_t *b = stream + cbd_offset + 6 * (k - n_ternary);
+                out[k] = (int8_t)(__popc(b[0]) + __popc(b[1]) + __popc(b[2] & 0x1Fu) - __popc(b[3]) - __popc(b[4]) - __popc(b[5] & 0x1Fu));
+            }
+        }
+
         __global__ void __launch_bounds__(kBlock) apply_patches_kernel(const XofPatch *patches, size_t count)
         {
             const size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x;
@@ -311,6 +347,24 @@ namespace sealhip
             return hipSuccess;
         hipLaunchKernelGGL(small_from_stream_kernel, dim3((unsigned)((work + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, stream, n_ternary,
                            cbd_offset, n_cbd, small, redraw);
+        return hipGetLastError();
+    }
+    hipError_t k_blake2xb_stream_batch(const uint64_t *seeds, uint64_t first_piece, size_t pieces, uint64_t *out, unsigned items, hipStream_t s)
+    {
+        if (!pieces || !items)
+            return hipSuccess;
+        hipLaunchKernelGGL(blake2xb_stream_batch_kernel, dim3((unsigned)((pieces + kBlock - 1) / kBlock), items), dim3(kBlock), 0, s, seeds,
+                           first_piece, pieces, out);
+        return hipGetLastError();
+    }
+    hipError_t k_small_from_stream_batch(const uint8_t *streams, size_t stream_bytes, size_t n_ternary, size_t cbd_offset, size_t n_cbd,
+                                         int8_t *small, size_t small_stride, unsigned *redraw, unsigned items, hipStream_t s)
+    {
+        const size_t work = n_ternary + n_cbd;
+        if (!work || !items)
+            return hipSuccess;
+        hipLaunchKernelGGL(small_from_stream_batch_kernel, dim3((unsigned)((work + kBlock - 1) / kBlock), items), dim3(kBlock), 0, s, streams,
+                           stream_bytes, n_ternary, cbd_offset, n_cbd, small, small_stride, redraw);
         return hipGetLastError();
     }
     hipError_t k_apply_patches(const XofPatch *patches, size_t count, hipStream_t s)
