@@ -269,8 +269,9 @@ SHL_FUNC Encryptor_EncryptDevice(void *thisptr, const uint64_t *device_plain, ui
  * (KSwitchKeys::keys_[index][digit].data(), native/src/seal/kswitchkeys.h:340). */
 /* Plaintext (native/src/seal/c/plaintext.h:16-75; class seal::Plaintext, native/src/seal/plaintext.h), device resident.
  * Coefficient form: `count` coefficients modulo t (BFV/BGV), parms_id = zero.  NTT form: K*N words at a level
- * (Plaintext_Set4 the words, then Plaintext_SetParmsId; CKKS plaintexts are always in this form).  One plaintext is
- * applied to every item of a ciphertext batch.  Create1 takes the context where sealc takes a pool handle. */
+ * (Plaintext_Set4 the words, then Plaintext_SetParmsId; CKKS plaintexts are always in this form).  One Plaintext handle is
+ * applied to every item of a ciphertext batch; for one plaintext per item see Evaluator_AddPlainDevice / SubPlainDevice /
+ * MultiplyPlainDevice, which take the plaintexts as raw device words.  Create1 takes the context where sealc takes a pool handle. */
 SHL_FUNC Plaintext_Create1(void *context, void **plaintext);
 SHL_FUNC Plaintext_Create5(void *copy, void **plaintext);
 SHL_FUNC Plaintext_Destroy(void *thisptr);
@@ -367,6 +368,45 @@ SHL_FUNC Evaluator_Exponentiate(void *thisptr, void *encrypted, uint64_t exponen
 SHL_FUNC Evaluator_TransformToNTT1(void *thisptr, void *plain, uint64_t *parms_id, void *destination_ntt, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext2(void *thisptr, void *plain, void *destination);
 SHL_FUNC Evaluator_ModSwitchTo2(void *thisptr, void *plain, uint64_t *parms_id, void *destination);
+/* One plaintext PER ITEM of a device-resident batch (library extensions, like Encryptor_EncryptDevice): plaintext b is applied to
+ * item b of `encrypted`, where a Plaintext handle is applied to every item.
+ * device_plain: `batch` plaintexts in device memory, 16-byte aligned, batch == the ciphertext's batch.
+ *   plain_is_ntt false - [batch][N] coefficients modulo t, what BatchEncoder_EncodeDevice writes (BFV / BGV only);
+ *   plain_is_ntt true  - [batch][K][N] NTT-form words at the ciphertext's own level, what CKKSEncoder_EncodeDevice and
+ *                        Evaluator_TransformPlainToNTTDevice write (CKKS plaintexts are always in this form).
+ *   The words are NOT validated (as with Plaintext_SetFromDevice): out of range, the result is unspecified.
+ * scale: the plaintexts' common scale for CKKS (a normal positive number): AddPlainDevice / SubPlainDevice require it to be close
+ *   to the ciphertext's, MultiplyPlainDevice multiplies the scales and checks the bound.  Ignored for BFV / BGV.
+ * Item b of the result equals, word for word, Evaluator_AddPlain / SubPlain / MultiplyPlain on a batch of one with a Plaintext that
+ * holds item b's words, hence the reference's add_plain_inplace / sub_plain_inplace / multiply_plain_inplace; is_ntt_form, scale and
+ * correction factor of the result are what those leave.  The accepted combinations of forms are theirs too: CKKS NTT x NTT; BFV
+ * add / sub coefficient x coefficient; BGV add / sub NTT ciphertext x coefficient plaintext (the plaintext is multiplied by the
+ * ciphertext's correction factor modulo t before the lift); multiply every combination of forms except a coefficient-form
+ * plaintext for CKKS.  A coefficient-form ciphertext times coefficient-form plaintexts reproduces the reference's monomial branch
+ * PER ITEM (a plaintext with one non-zero coefficient is multiplied in as the raw coefficient under the fast plain lift; a batch
+ * may mix such items with others): all items are decided by one statistics kernel and ONE read-back, so this combination
+ * synchronises the evaluator's stream once and cannot be recorded by Evaluator_BeginCapture, exactly like the per-object form; every
+ * other combination is enqueued without a host round trip and records.
+ * destination == encrypted works in place.  Otherwise `encrypted` is only read and the result is written straight into
+ * `destination`, which takes the ciphertext's shape and metadata (no copy of the operand first); a call that fails its argument
+ * checks leaves it untouched.  Checks and HRESULTs are those of the per-object forms (invalid ciphertext, wrong form for the
+ * scheme, scale mismatch / out of bounds: SHL_E_INVALIDARG; NULL handles: SHL_E_POINTER), and SHL_E_INVALIDARG for: batch == 0 or
+ * != the ciphertext's batch, a NULL or misaligned device_plain, device_plain overlapping the words of `encrypted` or `destination`.
+ * With Evaluator_SetTransparentCheck on, the result is checked over the whole batch.
+ * The lifted plaintexts of a BFV / BGV call ([batch][K][N] words) are scratch: the batch is worked through in chunks of
+ * max(1, 256 MiB / (8 K N)) items and the scratch goes back to the pool. */
+SHL_FUNC Evaluator_AddPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, bool plain_is_ntt,
+                                  double scale, void *destination);
+SHL_FUNC Evaluator_SubPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, bool plain_is_ntt,
+                                  double scale, void *destination);
+SHL_FUNC Evaluator_MultiplyPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, bool plain_is_ntt,
+                                       double scale, void *destination);
+/* [batch][N] coefficients modulo t -> [batch][K][N] NTT-form words at parms_id, item for item Evaluator_TransformToNTT1 (centred
+ * lift, forward transform): plaintexts that are used many times are lifted and transformed once and then passed with
+ * plain_is_ntt = true.  BFV / BGV; CKKS is refused as the per-object form refuses it.  SHL_E_INVALIDARG for an unknown parms_id,
+ * batch == 0, a NULL or misaligned (16 bytes) device pointer, input overlapping output.  Enqueued on the evaluator's stream. */
+SHL_FUNC Evaluator_TransformPlainToNTTDevice(void *thisptr, const uint64_t *device_coefficients, uint64_t batch, uint64_t *parms_id,
+                                             uint64_t *device_words);
 SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *pool);
 SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *pool);

@@ -1382,6 +1382,43 @@ class Evaluator:
         N.check(N.lib().Evaluator_TransformToNTT1(self._h, plain._h, pid, plain._h, None))
         return plain
 
+    # ---- one plaintext per item of a device-resident batch (sealhip.h: Evaluator_AddPlainDevice ...)
+    def _pl_device(self, fn, a, words, plain_is_ntt, scale, destination):
+        batch = a.batch()
+        need = batch * a.poly_modulus_degree() * (a.coeff_modulus_size() if plain_is_ntt else 1)
+        if isinstance(words, DeviceBuffer) and words.words < need:
+            # the level of raw words is the number of them: [batch][K][N] at the ciphertext's level, [batch][N] coefficients
+            raise ValueError("%d plaintext words for a batch of %d at this level: %d needed" % (words.words, batch, need))
+        d = a if destination is None else destination
+        ptr = words.ptr if isinstance(words, DeviceBuffer) else words
+        N.check(fn(self._h, a._h, C.c_void_p(ptr), C.c_uint64(batch), C.c_bool(plain_is_ntt), C.c_double(scale), d._h))
+        return d
+
+    def add_plain_device(self, a, words, plain_is_ntt, scale=1.0, destination=None):
+        """item b of `a` + plaintext b (sealhip.h: Evaluator_AddPlainDevice).  words: DeviceBuffer of [batch][N] coefficients modulo
+        t (plain_is_ntt False; BatchEncoder.encode_device's output) or [batch][K][N] NTT-form words at the ciphertext's level
+        (plain_is_ntt True; CKKSEncoder.encode_device's or transform_plain_to_ntt_device's).  scale: the plaintexts' common scale
+        (CKKS).  destination None: in place; otherwise `a` is only read.  -> the result Ciphertext"""
+        return self._pl_device(N.lib().Evaluator_AddPlainDevice, a, words, plain_is_ntt, scale, destination)
+
+    def sub_plain_device(self, a, words, plain_is_ntt, scale=1.0, destination=None):
+        """item b of `a` - plaintext b (sealhip.h: Evaluator_SubPlainDevice); arguments as add_plain_device"""
+        return self._pl_device(N.lib().Evaluator_SubPlainDevice, a, words, plain_is_ntt, scale, destination)
+
+    def multiply_plain_device(self, a, words, plain_is_ntt, scale=1.0, destination=None):
+        """item b of `a` * plaintext b (sealhip.h: Evaluator_MultiplyPlainDevice); arguments as add_plain_device.  CKKS: the
+        scales are multiplied.  Coefficient-form ciphertext and plaintexts (BFV): synchronises once, cannot be captured"""
+        return self._pl_device(N.lib().Evaluator_MultiplyPlainDevice, a, words, plain_is_ntt, scale, destination)
+
+    def transform_plain_to_ntt_device(self, coefficients, batch, parms_id, out=None):
+        """[batch][N] coefficients modulo t -> DeviceBuffer of [batch][K][N] NTT-form words at parms_id (BFV / BGV): plaintexts that
+        are multiplied in many times are lifted and transformed once (sealhip.h: Evaluator_TransformPlainToNTTDevice)"""
+        K = len(self.context.coeff_modulus_at(self.context.chain_index(parms_id)))
+        out = out if out is not None else DeviceBuffer(max(batch * K * self.context.n, 1))
+        pid = (C.c_uint64 * 4)(*parms_id)
+        N.check(N.lib().Evaluator_TransformPlainToNTTDevice(self._h, C.c_void_p(coefficients.ptr), C.c_uint64(batch), pid, C.c_void_p(out.ptr)))
+        return out
+
     def mod_switch_plain_to_next_inplace(self, plain):
         N.check(N.lib().Evaluator_ModSwitchToNext2(self._h, plain._h, plain._h))
         return plain

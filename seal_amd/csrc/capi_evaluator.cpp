@@ -224,6 +224,33 @@ extern "C"
         as<Evaluator>(thisptr)->multiply_plain_inplace(prepare_dest(encrypted, destination), *as<Plaintext>(plain));
         SHL_CATCH
     }
+    // one plaintext per item, raw device words (library extensions): no copy into the destination first - the host code shapes it
+#define EV_PLAIN_DEVICE(fn, call)                                                                                          \
+    SHL_FUNC fn(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, bool plain_is_ntt, double scale, \
+                void *destination)                                                                                         \
+    {                                                                                                                      \
+        IfNullRet(thisptr, SHL_E_POINTER);                                                                                 \
+        IfNullRet(encrypted, SHL_E_POINTER);                                                                               \
+        IfNullRet(destination, SHL_E_POINTER);                                                                             \
+        SHL_TRY                                                                                                            \
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());                                                        \
+        as<Evaluator>(thisptr)->call(*as<Ciphertext>(encrypted), device_plain, (size_t)batch, plain_is_ntt, scale,         \
+                                     *as<Ciphertext>(destination));                                                        \
+        SHL_CATCH                                                                                                          \
+    }
+    EV_PLAIN_DEVICE(Evaluator_AddPlainDevice, add_plain_device)
+    EV_PLAIN_DEVICE(Evaluator_SubPlainDevice, sub_plain_device)
+    EV_PLAIN_DEVICE(Evaluator_MultiplyPlainDevice, multiply_plain_device)
+    SHL_FUNC Evaluator_TransformPlainToNTTDevice(void *thisptr, const uint64_t *device_coefficients, uint64_t batch, uint64_t *parms_id,
+                                                 uint64_t *device_words)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(parms_id, SHL_E_POINTER);
+        SHL_TRY
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->transform_plain_to_ntt_device(device_coefficients, (size_t)batch, parms_id, device_words);
+        SHL_CATCH
+    }
     static Plaintext &prepare_plain_dest(void *plain, void *destination)
     {
         Plaintext *src = as<Plaintext>(plain), *dst = as<Plaintext>(destination);

@@ -898,7 +898,7 @@ namespace sealhip
                 if (lift)
                 {
                     // BGV: lift -> NTT -> add (Evaluator::add_plain on a fresh ciphertext, correction factor 1)
-                    ck(k_plain_lift_batch(mods, plain + b0 * n, lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log,
+                    ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), 1, plain + b0 * n, lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log,
                                           (unsigned)K, items, nullptr),
                        "plain lift");
                     ck(ntt_forward(tb, polys(lifted.p, K, n, items), 0, nullptr), "plain ntt");
@@ -1043,7 +1043,7 @@ namespace sealhip
             for (size_t b0 = 0; b0 < batch; b0 += chunk)
             {
                 const unsigned items = (unsigned)std::min(chunk, batch - b0);
-                ck(k_plain_lift_batch(mods, plain + b0 * n, lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log, (unsigned)K,
+                ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), 1, plain + b0 * n, lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log, (unsigned)K,
                                       items, nullptr),
                    "plain lift");
                 ck(ntt_forward(context_.ntt_tables(), polys(lifted.p, K, n, items), 0, nullptr), "plain ntt");

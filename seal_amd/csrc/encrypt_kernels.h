@@ -39,7 +39,8 @@ namespace sealhip
     hipError_t k_encrypt_bfv_finish(const ModDesc *mods, const BfvPlainConst &pc, const int8_t *small, size_t small_stride, const uint64_t *m,
                                     uint64_t *c, size_t plane_stride, unsigned planes, bool negate, unsigned n_log, unsigned K, unsigned items,
                                     hipStream_t s);
-    // BGV: out[b][r][j] = the centred lift of m[b][j] (coefficients modulo t) to q_r - k_plain_lift with scale_by = 1 for every item
-    hipError_t k_plain_lift_batch(const ModDesc *mods, const uint64_t *m, uint64_t threshold, const uint64_t *inc, uint64_t *out, unsigned n_log,
-                                  unsigned K, unsigned items, hipStream_t s);
+    // BFV / BGV: out[b][r][j] = the centred lift of m[b][j] (coefficients modulo t) to q_r - k_plain_lift for every item; scale_by != 1
+    // first multiplies m[b][j] by it modulo t (BGV add_plain: the ciphertext's correction factor)
+    hipError_t k_plain_lift_batch(const ModDesc *mods, const ModDesc &t, uint64_t scale_by, const uint64_t *m, uint64_t threshold,
+                                  const uint64_t *inc, uint64_t *out, unsigned n_log, unsigned K, unsigned items, hipStream_t s);
 } // namespace sealhip

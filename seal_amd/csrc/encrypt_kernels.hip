@@ -1,5 +1,5 @@
 // See encrypt_kernels.h.  One thread = two adjacent words of every operand (N is even, rows are 16-byte aligned).
-#include "encrypt_kernels.h"
+#include "stream_device.h"
 
 namespace sealhip
 {
@@ -14,32 +14,6 @@ namespace sealhip
             if (b == 0)
                 b = 1;
             return (unsigned)b;
-        }
-        // two adjacent words with one 16-byte access; NT: the non-temporal hint (read once / written once)
-        template <bool NT>
-        __device__ __forceinline__ void ld2(const uint64_t *p, uint64_t &a, uint64_t &b)
-        {
-#if defined(__HIP_DEVICE_COMPILE__)
-            typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-            const u64x2 *q = reinterpret_cast<const u64x2 *>(p);
-            const u64x2 v = NT ? __builtin_nontemporal_load(q) : *q;
-            a = v.x;
-            b = v.y;
-#else
-            a = p[0];
-            b = p[1];
-#endif
-        }
-        __device__ __forceinline__ void st2_nt(uint64_t *p, uint64_t a, uint64_t b)
-        {
-#if defined(__HIP_DEVICE_COMPILE__)
-            typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-            const u64x2 v = { a, b };
-            __builtin_nontemporal_store(v, reinterpret_cast<u64x2 *>(p));
-#else
-            p[0] = a;
-            p[1] = b;
-#endif
         }
         __device__ __forceinline__ uint64_t lift_small(int v, uint64_t q)
         {
@@ -143,37 +117,6 @@ namespace sealhip
             }
         }
 
-        // floor((hi:lo) / t) for a quotient below 2^64, with t's Barrett constant floor(2^128 / t) (as poly_kernels.hip divides)
-        __device__ __forceinline__ uint64_t div128_by(uint64_t lo, uint64_t hi, const ModDesc &t)
-        {
-            uint64_t t1 = mul_hi64(lo, t.ratio_lo);
-            uint64_t a_lo, a_hi, b_lo, b_hi;
-            mul_wide(lo, t.ratio_hi, a_lo, a_hi);
-            mul_wide(hi, t.ratio_lo, b_lo, b_hi);
-            uint64_t mid = t1 + a_lo;
-            uint64_t c = mid < t1;
-            uint64_t mid2 = mid + b_lo;
-            c += mid2 < mid;
-            uint64_t qest = hi * t.ratio_hi + a_hi + b_hi + c; // low by at most 2
-            uint64_t r = lo - qest * t.q;
-            while (r >= t.q)
-            {
-                r -= t.q;
-                qest++;
-            }
-            return qest;
-        }
-        // round(m * Q / t) mod q_r as multiply_add_plain_with_scaling_variant forms it: m * floor(Q / t) + floor((m * (Q mod t) + (t + 1) / 2) / t)
-        __device__ __forceinline__ uint64_t bfv_scaled(uint64_t mv, const BfvPlainConst &pc, uint64_t delta, const ModDesc &md)
-        {
-            uint64_t lo, hi;
-            mul_wide(mv, pc.q_mod_t, lo, hi);
-            lo += pc.threshold;
-            hi += lo < pc.threshold;
-            const uint64_t fix = div128_by(lo, hi, pc.t);
-            return add_mod(mul_mod(mv, delta, md), barrett64(fix, md), md.q);
-        }
-
         // pairs = planes * items * K * N / 2
         __global__ void __launch_bounds__(kBlock) encrypt_bfv_finish_kernel(
             const ModDesc *mods, BfvPlainConst pc, const int8_t *small, size_t small_stride, const uint64_t *m, uint64_t *c, size_t plane_stride,
@@ -215,16 +158,22 @@ namespace sealhip
 
         // pairs = items * K * N / 2
         __global__ void __launch_bounds__(kBlock) plain_lift_batch_kernel(
-            const ModDesc *mods, const uint64_t *m, uint64_t threshold, const uint64_t *inc, uint64_t *out, size_t pairs, unsigned n_log, unsigned K)
+            const ModDesc *mods, ModDesc t, uint64_t scale_by, const uint64_t *m, uint64_t threshold, const uint64_t *inc, uint64_t *out,
+            size_t pairs, unsigned n_log, unsigned K)
         {
             const size_t nmask = (size_t(1) << n_log) - 1;
-            for (size_t t = blockIdx.x * (size_t)kBlock + threadIdx.x; t < pairs; t += (size_t)gridDim.x * kBlock)
+            for (size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x; w < pairs; w += (size_t)gridDim.x * kBlock)
             {
-                const size_t i = 2 * t, row = i >> n_log; // b * K + r
+                const size_t i = 2 * w, row = i >> n_log; // b * K + r
                 const unsigned r = (unsigned)(row % K);
                 const ModDesc md = mods[r];
                 uint64_t m0, m1;
                 ld2<false>(m + ((row / K) << n_log) + (i & nmask), m0, m1);
+                if (scale_by != 1)
+                {
+                    m0 = mul_mod(m0, scale_by, t);
+                    m1 = mul_mod(m1, scale_by, t);
+                }
                 uint64_t v0 = barrett64(m0, md), v1 = barrett64(m1, md);
                 const uint64_t up = inc[r];
                 if (m0 >= threshold)
@@ -285,13 +234,14 @@ namespace sealhip
                            pairs, negate, n_log, K, items);
         return hipGetLastError();
     }
-    hipError_t k_plain_lift_batch(const ModDesc *mods, const uint64_t *m, uint64_t threshold, const uint64_t *inc, uint64_t *out, unsigned n_log,
-                                  unsigned K, unsigned items, hipStream_t s)
+    hipError_t k_plain_lift_batch(const ModDesc *mods, const ModDesc &t, uint64_t scale_by, const uint64_t *m, uint64_t threshold,
+                                  const uint64_t *inc, uint64_t *out, unsigned n_log, unsigned K, unsigned items, hipStream_t s)
     {
         const size_t pairs = (((size_t)items * K) << n_log) / 2;
         if (!pairs)
             return hipSuccess;
-        hipLaunchKernelGGL(plain_lift_batch_kernel, dim3(grid_for(pairs)), dim3(kBlock), 0, s, mods, m, threshold, inc, out, pairs, n_log, K);
+        hipLaunchKernelGGL(plain_lift_batch_kernel, dim3(grid_for(pairs)), dim3(kBlock), 0, s, mods, t, scale_by, m, threshold, inc, out, pairs, n_log,
+                           K);
         return hipGetLastError();
     }
 } // namespace sealhip

@@ -1,5 +1,6 @@
 // Evaluator, part 1: construction, streams and graph capture, deferred key-switch tails, negate / add / sub, transforms, plaintext operands, multiply
 #include "evaluator_common.h"
+#include "plain_batch_kernels.h"
 #include <atomic>
 
 namespace sealhip
@@ -695,37 +696,42 @@ namespace sealhip
         check_valid(plain);
         addsub_plain(e, plain, 1);
     }
-    void Evaluator::addsub_plain(Ciphertext &e, const Plaintext &plain, int op) const
+    void Evaluator::check_addsub_plain_forms(const Ciphertext &e, bool plain_is_ntt, const Level *plain_level, double plain_scale) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         const Scheme scheme = context_.scheme();
         if (scheme == Scheme::bfv)
         {
             if (e.is_ntt_form())
                 throw std::invalid_argument("BFV encrypted cannot be in NTT form");
-            if (plain.is_ntt_form())
+            if (plain_is_ntt)
                 throw std::invalid_argument("BFV plain cannot be in NTT form");
         }
         else if (scheme == Scheme::ckks)
         {
             if (!e.is_ntt_form())
                 throw std::invalid_argument("CKKS encrypted must be in NTT form");
-            if (!plain.is_ntt_form())
+            if (!plain_is_ntt)
                 throw std::invalid_argument("CKKS plain must be in NTT form");
-            if (e.level() != plain.level())
+            if (e.level() != plain_level)
                 throw std::invalid_argument("encrypted and plain parameter mismatch");
-            if (!are_close(e.scale(), plain.scale()))
+            if (!are_close(e.scale(), plain_scale))
                 throw std::invalid_argument("scale mismatch");
         }
         else
         {
             if (!e.is_ntt_form())
                 throw std::invalid_argument("BGV encrypted must be in NTT form");
-            if (plain.is_ntt_form())
+            if (plain_is_ntt)
                 throw std::invalid_argument("BGV plain cannot be in NTT form");
         }
         if (e.size() < 1)
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
+    }
+    void Evaluator::addsub_plain(Ciphertext &e, const Plaintext &plain, int op) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        const Scheme scheme = context_.scheme();
+        check_addsub_plain_forms(e, plain.is_ntt_form(), plain.level(), plain.scale());
         const Level &lvl = *e.level();
         const unsigned n_log = (unsigned)context_.log_n();
         const ModDesc *mods = context_.dev_mods();
@@ -865,6 +871,247 @@ namespace sealhip
             transform_from_ntt_inplace(e);
         }
         throw_if_transparent(e);
+    }
+
+    // ---- one plaintext per item of a device-resident batch (include/sealhip.h: Evaluator_AddPlainDevice ...; plain_batch_kernels.h)
+    namespace
+    {
+        constexpr size_t kPlainBatchScratchBytes = size_t(256) << 20; // per chunk of lifted plaintexts (include/sealhip.h)
+        bool words_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+        {
+            const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+            return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+        }
+        // items whose lifted plaintexts [K][N] fit the scratch of one chunk
+        size_t plain_chunk_items(size_t item_words)
+        {
+            size_t budget = kPlainBatchScratchBytes;
+            if (const char *e = shl_ab_getenv("SEALHIP_PLAIN_SCRATCH_BYTES")) // development builds only: chunk edges at small N
+                budget = (size_t)std::strtoull(e, nullptr, 10);
+            return std::max<size_t>(1, budget / (item_words * 8));
+        }
+    } // namespace
+    void Evaluator::check_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
+                                       const Ciphertext &dest) const
+    {
+        check_valid(e, "encrypted");
+        if (!plain)
+            throw std::invalid_argument("device_plain is null");
+        if ((uintptr_t)plain % 16)
+            throw std::invalid_argument("device_plain must be 16-byte aligned");
+        if (!batch || batch != e.batch())
+            throw std::invalid_argument("batch does not equal the ciphertext's batch");
+        if (context_.scheme() == Scheme::ckks)
+        {
+            if (!plain_is_ntt)
+                throw std::invalid_argument("CKKS plain must be in NTT form");
+            if (!std::isnormal(scale) || scale <= 0) // is_metadata_valid_for(Plaintext)
+                throw std::invalid_argument("plain is not valid for encryption parameters");
+        }
+        const size_t plain_bytes = batch * (plain_is_ntt ? (size_t)e.level()->K * context_.n() : context_.n()) * 8;
+        if (e.has_storage() && words_overlap(plain, plain_bytes, e.data(), e.capacity_words() * 8))
+            throw std::invalid_argument("device_plain and encrypted overlap");
+        if (&dest != &e && dest.has_storage() && words_overlap(plain, plain_bytes, dest.data_, dest.capacity_words() * 8))
+            throw std::invalid_argument("device_plain and destination overlap");
+    }
+    uint64_t *Evaluator::begin_result(const Ciphertext &e, Ciphertext &dest) const
+    {
+        if (&dest == &e)
+            return dest.data();
+        e.settle(); // the operand's words are read by what follows
+        if (dest.ctx_ != e.ctx_ || dest.batch_ != e.batch_)
+        {
+            dest.release();
+            dest.ctx_ = e.ctx_;
+            dest.batch_ = e.batch_;
+        }
+        dest.reshape_uninitialized(e.level(), e.size());
+        dest.is_ntt_form() = e.is_ntt_form();
+        dest.scale() = e.scale();
+        dest.correction_factor() = e.correction_factor();
+        return dest.data_;
+    }
+
+    void Evaluator::add_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
+                                     Ciphertext &dest) const
+    {
+        addsub_plain_device(e, plain, batch, plain_is_ntt, scale, 0, dest);
+    }
+    void Evaluator::sub_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
+                                     Ciphertext &dest) const
+    {
+        addsub_plain_device(e, plain, batch, plain_is_ntt, scale, 1, dest);
+    }
+    void Evaluator::addsub_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale, int op,
+                                        Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_plain_device(e, plain, batch, plain_is_ntt, scale, dest);
+        check_addsub_plain_forms(e, plain_is_ntt, e.level(), scale);
+        const Level &lvl = *e.level();
+        const size_t n = context_.n(), words = (size_t)lvl.K * n;
+        const unsigned n_log = (unsigned)context_.log_n(), K = lvl.K;
+        const ModDesc *mods = context_.dev_mods();
+        const uint64_t *a = e.plane(0);
+        uint64_t *r = begin_result(e, dest);
+        if (&dest != &e && e.size() > 1) // the other polynomials pass through
+            ck(hipMemcpyAsync(r + e.plane_words(), e.plane(1), (e.size() - 1) * e.plane_words() * 8, hipMemcpyDeviceToDevice, stream_),
+               "add/sub plain: copy c1..");
+        switch (context_.scheme())
+        {
+        case Scheme::bfv:
+        {
+            const BfvPlainConst pc{ host::make_mod(context_.plain_modulus()), lvl.dev.q_mod_t, lvl.dev.plain_upper_half_threshold,
+                                    lvl.dev.delta_mod_q };
+            ck(k_bfv_addsub_plain_batch(mods, pc, plain, a, r, op, n_log, K, (unsigned)batch, stream_), "bfv add/sub plain (per item)");
+            break;
+        }
+        case Scheme::ckks:
+            ck(k_addsub_plain_batch(mods, a, plain, r, op, n_log, K, (unsigned)batch, stream_), "ckks add/sub plain (per item)");
+            break;
+        case Scheme::bgv:
+        {
+            // plain_b * correction_factor mod t, lifted and transformed at the ciphertext's level (evaluator.cpp:1836-1847), a chunk at a time
+            const size_t chunk = std::min(plain_chunk_items(words), batch);
+            Scratch lifted(chunk * words);
+            for (size_t b0 = 0; b0 < batch; b0 += chunk)
+            {
+                const unsigned items = (unsigned)std::min(chunk, batch - b0);
+                ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), e.correction_factor(), plain + b0 * n,
+                                      lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log, K, items, stream_),
+                   "plain lift (per item)");
+                ck(ntt_forward(context_.ntt_tables(), plain_batch(lifted.p, words, K, items, 0), 0, stream_), "plain ntt (per item)");
+                ck(k_addsub_plain_batch(mods, a + b0 * words, lifted.p, r + b0 * words, op, n_log, K, items, stream_),
+                   "bgv add/sub plain (per item)");
+            }
+            break;
+        }
+        default:
+            throw std::invalid_argument("unsupported scheme");
+        }
+        throw_if_transparent(dest);
+    }
+
+    void Evaluator::multiply_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
+                                          Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_plain_device(e, plain, batch, plain_is_ntt, scale, dest);
+        const Level &lvl = *e.level();
+        const bool ckks = context_.scheme() == Scheme::ckks;
+        // (BFV / BGV plaintexts have scale 1: multiply_plain_ntt's scale update and bound check do nothing for them)
+        const double new_scale = ckks ? e.scale() * scale : e.scale();
+        if (ckks && !scale_within_bounds(new_scale, lvl))
+            throw std::invalid_argument("scale out of bounds");
+        const size_t n = context_.n(), words = (size_t)lvl.K * n, size = e.size(), plane = e.plane_words();
+        const unsigned n_log = (unsigned)context_.log_n(), K = lvl.K;
+        const ModDesc *mods = context_.dev_mods();
+        const NttTables &tb = context_.ntt_tables();
+        const bool ct_ntt = e.is_ntt_form();
+
+        // multiply_plain_normal's monomial branch (mul_plain_monomial above), decided for every item at once: one launch, one read-back
+        std::unique_ptr<Scratch> stats;
+        size_t monomials = 0;
+        if (!ct_ntt && !plain_is_ntt && size)
+        {
+            stats.reset(new Scratch(3 * batch));
+            ck(k_plain_stats_batch(plain, stats->p, n_log, (unsigned)batch, stream_), "plain stats (per item)");
+            std::vector<uint64_t> st(3 * batch);
+            ck(hipMemcpyAsync(st.data(), stats->p, st.size() * 8, hipMemcpyDeviceToHost, stream_), "plain stats read");
+            ck(hipStreamSynchronize(stream_), "plain stats sync");
+            for (size_t b = 0; b < batch; b++)
+                monomials += st[3 * b] == 1;
+        }
+
+        const uint64_t *src = e.data();
+        // the monomial product permutes: in place it goes through a fresh slab, as mul_plain_monomial's does
+        uint64_t *fresh = (&dest == &e && monomials) ? DevicePool::global().alloc_words(e.word_count()) : nullptr;
+        uint64_t *res = fresh ? fresh : begin_result(e, dest);
+        try
+        {
+            if (monomials < batch && size)
+            {
+                // the other items (and, unused, the monomial ones among them): lift and transform the plaintexts at the ciphertext's
+                // level and multiply in the NTT domain - multiply_plain_normal / multiply_plain_ntt and the mixed-form branches
+                // (evaluator.cpp:2006-2017)
+                if (!ct_ntt)
+                {
+                    NttBatch cb = plain_batch(res, words, K, (unsigned)(size * batch), 0);
+                    if (res != src) // out of place: the first pass reads the operand itself (NttBatch::src, mode 0) - no copy
+                    {
+                        cb.src = src;
+                        cb.src_outer_stride = words;
+                        cb.src_ncomp = K;
+                        cb.src_mode = 0;
+                    }
+                    ck(ntt_forward(tb, cb, 0, stream_), "multiply_plain ntt (per item)");
+                }
+                const uint64_t *a = ct_ntt ? src : res;
+                if (plain_is_ntt)
+                    ck(k_dyadic_plain_batch(mods, a, plane, plain, res, plane, (unsigned)size, n_log, K, (unsigned)batch, stream_),
+                       "multiply_plain (per item)");
+                else
+                {
+                    const size_t chunk = std::min(plain_chunk_items(words), batch);
+                    Scratch lifted(chunk * words);
+                    for (size_t b0 = 0; b0 < batch; b0 += chunk)
+                    {
+                        const unsigned items = (unsigned)std::min(chunk, batch - b0);
+                        ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), 1, plain + b0 * n,
+                                              lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log, K, items, stream_),
+                           "plain lift (per item)");
+                        ck(ntt_forward(tb, plain_batch(lifted.p, words, K, items, 0), 0, stream_), "plain ntt (per item)");
+                        ck(k_dyadic_plain_batch(mods, a + b0 * words, plane, lifted.p, res + b0 * words, plane, (unsigned)size, n_log, K, items,
+                                                stream_),
+                           "multiply_plain (per item)");
+                    }
+                }
+                if (!ct_ntt)
+                    ck(ntt_inverse(tb, plain_batch(res, words, K, (unsigned)(size * batch), 0), 0, stream_), "multiply_plain intt (per item)");
+            }
+            if (monomials)
+            {
+                bool fast_lift = true; // qualifiers.using_fast_plain_lift: t smaller than every prime of this level
+                for (unsigned i = 0; i < K; i++)
+                    fast_lift = fast_lift && context_.plain_modulus() < context_.coeff_modulus()[i];
+                ck(k_negacyclic_mul_mono_batch(mods, stats->p, lvl.dev.plain_upper_half_threshold, fast_lift ? nullptr : lvl.dev.upper_half_inc,
+                                               src, plane, res, plane, (unsigned)size, n_log, K, (unsigned)batch, stream_),
+                   "multiply_plain monomial (per item)");
+            }
+        }
+        catch (...)
+        {
+            DevicePool::global().free_words(fresh);
+            throw;
+        }
+        if (fresh)
+            dest.adopt(&lvl, size, fresh, e.word_count());
+        dest.scale() = new_scale;
+        throw_if_transparent(dest);
+    }
+
+    void Evaluator::transform_plain_to_ntt_device(const uint64_t *coefficients, size_t batch, const uint64_t *parms_id, uint64_t *out) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        if (!coefficients || !out)
+            throw std::invalid_argument("device pointer is null");
+        if ((uintptr_t)coefficients % 16 || (uintptr_t)out % 16)
+            throw std::invalid_argument("device pointers must be 16-byte aligned");
+        if (!batch)
+            throw std::invalid_argument("batch cannot be zero");
+        const Level *lvl = context_.level_by_parms_id(parms_id);
+        if (!lvl)
+            throw std::invalid_argument("parms_id is not valid for the current context");
+        if (context_.scheme() == Scheme::ckks)
+            throw std::invalid_argument("CKKS plain must be in NTT form");
+        const size_t n = context_.n(), words = (size_t)lvl->K * n;
+        if (words_overlap(coefficients, batch * n * 8, out, batch * words * 8))
+            throw std::invalid_argument("device_coefficients and device_words overlap");
+        ck(k_plain_lift_batch(context_.dev_mods(), host::make_mod(context_.plain_modulus()), 1, coefficients,
+                              lvl->dev.plain_upper_half_threshold, lvl->dev.upper_half_inc, out, (unsigned)context_.log_n(), lvl->K,
+                              (unsigned)batch, stream_),
+           "plain lift (per item)");
+        ck(ntt_forward(context_.ntt_tables(), plain_batch(out, words, lvl->K, (unsigned)batch, 0), 0, stream_), "plain ntt (per item)");
     }
 
     void Evaluator::add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const

@@ -199,7 +199,8 @@ namespace sealhip
 
     // seal::Plaintext (plaintext.h) resident in HBM: either coeff_count <= N coefficients modulo t (BFV/BGV,
     // parms_id_zero) or, in NTT form, K*N words at a level (CKKS always; BFV/BGV after transform_to_ntt_inplace).
-    // One plaintext is applied to every item of a ciphertext batch.
+    // One Plaintext object is applied to every item of a ciphertext batch; one plaintext per item is what the Evaluator's *_device
+    // forms take, as raw device words.
     class Plaintext
     {
     public:
@@ -321,6 +322,21 @@ namespace sealhip
         void transform_to_ntt_inplace(Plaintext &plain, const uint64_t *parms_id) const;
         void mod_switch_to_next_inplace(Plaintext &plain) const;
         void mod_switch_to_inplace(Plaintext &plain, const uint64_t *parms_id) const;
+        // One plaintext PER ITEM of a device-resident batch (include/sealhip.h: Evaluator_AddPlainDevice ...): plain = `batch` plaintexts
+        // in device memory, [batch][N] coefficients modulo t (plain_is_ntt false; BFV / BGV) or [batch][K][N] NTT-form words at the
+        // ciphertext's level (plain_is_ntt true; CKKS always), item b for item b of `encrypted`.  Item b of the result equals, word for
+        // word, add_plain_inplace / sub_plain_inplace / multiply_plain_inplace on a batch of one with plaintext b; the form checks,
+        // metadata updates and exception classes are theirs.  destination may be encrypted (in place); otherwise encrypted is only
+        // read and a call that fails its checks leaves destination untouched.  `scale`: the plaintexts' common scale (CKKS).
+        void add_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
+                              Ciphertext &destination) const;
+        void sub_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
+                              Ciphertext &destination) const;
+        void multiply_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
+                                   Ciphertext &destination) const;
+        // transform_to_ntt_inplace(Plaintext) for `batch` plaintexts: [batch][N] coefficients modulo t -> [batch][K][N] NTT-form words
+        // at parms_id (centred lift, forward transform); BFV / BGV
+        void transform_plain_to_ntt_device(const uint64_t *coefficients, size_t batch, const uint64_t *parms_id, uint64_t *words) const;
         void add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const;
         void multiply_many(const std::vector<const Ciphertext *> &encrypteds, const KSwitchKeys &relin_keys, Ciphertext &destination) const;
         void exponentiate_inplace(Ciphertext &encrypted, uint64_t exponent, const KSwitchKeys &relin_keys) const;
@@ -417,6 +433,13 @@ namespace sealhip
         void bgv_multiply(Ciphertext &e1, const Ciphertext &e2) const;
         void check_valid(const Plaintext &plain) const;
         void addsub_plain(Ciphertext &encrypted, const Plaintext &plain, int op) const;
+        // what add_plain / sub_plain accept per scheme (shared by the per-object and the per-item forms)
+        void check_addsub_plain_forms(const Ciphertext &encrypted, bool plain_is_ntt, const Level *plain_level, double plain_scale) const;
+        void check_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
+                                const Ciphertext &destination) const;
+        uint64_t *begin_result(const Ciphertext &encrypted, Ciphertext &destination) const; // destination shaped like encrypted, words undefined
+        void addsub_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale, int op,
+                                 Ciphertext &destination) const;
         bool mul_plain_monomial(Ciphertext &encrypted, const Plaintext &plain) const;
         void plain_to_rns(const Plaintext &plain, const Level &lvl, uint64_t scale_by, uint64_t *out) const;
         void multiply_plain_ntt(Ciphertext &encrypted_ntt, const uint64_t *plain_rns, const Level *plain_level, double plain_scale) const;

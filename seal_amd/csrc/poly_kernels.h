@@ -44,7 +44,7 @@ namespace sealhip
     // util/polyarithsmallmod.h:440-448 / .cpp:197-224); r may be a.
     hipError_t k_mul_scalar(
         const ModDesc *mods, const uint64_t *a, uint64_t *r, uint64_t scalar, PlaneGeom g, unsigned planes, hipStream_t s);
-    // ---- plaintext operands (one polynomial applied to every batch item)
+    // ---- plaintext operands (one polynomial applied to every batch item; one plaintext per item: plain_batch_kernels.h)
     // r[item][k] = a[item][k] .* p[k]: multiply_plain_ntt (evaluator.cpp:2157-2194); items = size * batch
     hipError_t k_dyadic_plain(const ModDesc *mods, const uint64_t *a, const uint64_t *p, uint64_t *r, unsigned n_log, unsigned K,
                               size_t items, hipStream_t s);
