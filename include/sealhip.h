@@ -407,6 +407,35 @@ SHL_FUNC Evaluator_MultiplyPlainDevice(void *thisptr, void *encrypted, const uin
  * batch == 0, a NULL or misaligned (16 bytes) device pointer, input overlapping output.  Enqueued on the evaluator's stream. */
 SHL_FUNC Evaluator_TransformPlainToNTTDevice(void *thisptr, const uint64_t *device_coefficients, uint64_t batch, uint64_t *parms_id,
                                              uint64_t *device_words);
+/* Sums over the ITEMS of a device-resident batch (library extensions): the one thing the per-item forms above do not do is combine
+ * items - the aggregation sum_b ct_b, its weighted form, and the encrypted matrix-vector / database dot product
+ * sum_b ct_b (.) pt_b with one plaintext per row, optionally in groups of rows.
+ * encrypted: a batch of B items, any size >= 2, at any level.  group = g >= 1 must divide B.  destination: ANOTHER handle whose batch
+ * is B / g, made with Ciphertext_CreateBatch (the convention of Encryptor_EncryptDevice's destination); it is resized to the operand's
+ * size and level.  Output item o is the sum over the input items o g .. o g + g - 1: g = B gives one ciphertext; g = 1 is a copy for
+ * SumItems and the words of MultiplyPlainDevice for DotPlainDevice.  `encrypted` is only read.
+ * Evaluator_SumItems: item o equals, word for word, Evaluator_AddMany over batch-of-one ciphertexts holding those items, hence the
+ *   reference's add_many (evaluator.cpp:242-261).  Every form and scheme Evaluator_Add accepts; the items of a batch share scale and
+ *   correction factor, so the reference's CKKS scale check and BGV correction-factor branch are the equal case.  is_ntt_form, scale
+ *   and correction factor of the result are the operand's.
+ * Evaluator_DotPlainDevice: device_plain = [B][K][N] NTT-form words at the ciphertext's level (what CKKSEncoder_EncodeDevice and
+ *   Evaluator_TransformPlainToNTTDevice write), 16-byte aligned, batch == B, NOT validated like the other *Device forms.  The
+ *   ciphertext must be in NTT form: CKKS, BGV, or BFV after Evaluator_TransformToNTT2.  Item o equals Evaluator_MultiplyPlainDevice
+ *   with plain_is_ntt = true followed by the sum above, hence the reference's multiply_plain_inplace (evaluator.cpp:2157-2194) per
+ *   item and then add_many; scale handling (CKKS: the scales are multiplied), the scale-bound check and the metadata are those of
+ *   that composition.  Coefficient-form plaintexts are deliberately NOT accepted - run Evaluator_TransformPlainToNTTDevice first:
+ *   the coefficient x coefficient monomial branch of the product is per item and data dependent and has no place in a reduction.
+ * SHL_E_POINTER: NULL handles.  SHL_E_INVALIDARG: an invalid ciphertext; g == 0 or g does not divide B; batch != B; the destination's
+ * batch != B / g; destination == encrypted; a NULL or misaligned device_plain; device_plain overlapping the words of `encrypted` or
+ * `destination`; a ciphertext in coefficient form (DotPlainDevice); a scale out of bounds.  A failed check leaves the destination
+ * untouched.  With Evaluator_SetTransparentCheck on, the result batch is checked.
+ * Both calls are enqueued on the evaluator's stream without a host round trip and record under Evaluator_BeginCapture.  Terms are
+ * accumulated as plain integers and reduced once per 16 (sums) / 256 (products) of them: with primes below 2^60 that many fit 64 /
+ * 128 bits.  A small result (fewer than 2^17 output pairs, at least 8 items per group) is computed in up to 64 slices of the group
+ * by separate workgroups into pool scratch of slices x one result batch, which a second launch adds; the words do not depend on it. */
+SHL_FUNC Evaluator_SumItems(void *thisptr, void *encrypted, uint64_t group, void *destination);
+SHL_FUNC Evaluator_DotPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, uint64_t group, double scale,
+                                  void *destination);
 SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *pool);
 SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *pool);
@@ -498,6 +527,14 @@ SHL_FUNC shl_ntt_forward(void *context, uint64_t *data, uint64_t polys, uint64_t
 SHL_FUNC shl_ntt_inverse(void *context, uint64_t *data, uint64_t polys, uint64_t comps, uint64_t first_prime, int lazy, void *stream);
 /* dyadic_product_coeffmod (util/polyarithsmallmod.cpp:226-284): r = a .* b, operands may be lazy (< 4q) */
 SHL_FUNC shl_dyadic_product(void *context, const uint64_t *a, const uint64_t *b, uint64_t *r, uint64_t polys, uint64_t comps, uint64_t first_prime, void *stream);
+/* The kernels of Evaluator_SumItems (plain == NULL) / Evaluator_DotPlainDevice on raw words at one level: a = [size][batch][K][N],
+ * plain = [batch][K][N], r = [size][batch / group][K][N], r distinct from the operands.  slices: 0 = the library's rule, 1 = one
+ * launch, 2 .. min(group, 64) = that cut of the group, with scratch of slices * size * (batch / group) * K * N words.  slices_used
+ * (may be NULL) receives the slices run; r == NULL only answers that.  Nothing is validated beyond the shape. */
+SHL_FUNC shl_reduce_items(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *plain, uint64_t *r, uint64_t size,
+                          uint64_t batch, uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream);
+/* terms the lazy accumulators of those kernels take between two reductions (sums: 16; products: 256) */
+SHL_FUNC shl_reduce_flush_intervals(uint64_t *sum_terms, uint64_t *dot_terms);
 /* GaloisTool::apply_galois (ntt_form == 0, util/galois.cpp:148) / apply_galois_ntt (!= 0, galois.cpp:192) */
 SHL_FUNC shl_apply_galois(void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys, void *stream);
 /* RNSTool stages (util/rns.cpp) on one level, `polys` polynomials each [comps][N]:

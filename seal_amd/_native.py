@@ -82,6 +82,7 @@ Plaintext_SaveSize Plaintext_Save Plaintext_UnsafeLoad Plaintext_Load
 Evaluator_AddMany Evaluator_AddPlain Evaluator_SubPlain Evaluator_MultiplyMany Evaluator_MultiplyPlain Evaluator_Exponentiate
 Evaluator_TransformToNTT1 Evaluator_ModSwitchToNext2 Evaluator_ModSwitchTo2
 Evaluator_AddPlainDevice Evaluator_SubPlainDevice Evaluator_MultiplyPlainDevice Evaluator_TransformPlainToNTTDevice
+Evaluator_SumItems Evaluator_DotPlainDevice shl_reduce_items shl_reduce_flush_intervals
 KSwitchKeys_Create1 KSwitchKeys_Destroy KSwitchKeys_Size KSwitchKeys_SetKey KSwitchKeys_SetKeyFromDevice
 KSwitchKeys_SetKeyDigits KSwitchKeys_HasKey KSwitchKeys_DeviceBytes RelinKeys_GetIndex GaloisKeys_GetIndex GaloisTool_GetEltFromStep
 Evaluator_Create Evaluator_Destroy Evaluator_SetStream Evaluator_Synchronize Evaluator_CopyTo Evaluator_SetTransparentCheck

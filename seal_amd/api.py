@@ -1419,6 +1419,38 @@ class Evaluator:
         N.check(N.lib().Evaluator_TransformPlainToNTTDevice(self._h, C.c_void_p(coefficients.ptr), C.c_uint64(batch), pid, C.c_void_p(out.ptr)))
         return out
 
+    # ---- sums over the items of a device-resident batch (sealhip.h: Evaluator_SumItems / Evaluator_DotPlainDevice)
+    def _reduce_dest(self, a, group, destination):
+        batch = a.batch()
+        group = batch if group is None else group
+        if destination is None:
+            if group < 1 or batch % group:
+                raise ValueError("group %r does not divide the batch of %d" % (group, batch))
+            destination = Ciphertext(self.context, batch=batch // group)
+        return group, destination
+
+    def sum_items(self, a, group=None, destination=None):
+        """item o of the result = the sum of the items o * group .. o * group + group - 1 of `a` (sealhip.h: Evaluator_SumItems).
+        group None: the whole batch, one ciphertext.  destination None: a new Ciphertext of batch // group items; otherwise a
+        handle of that batch, distinct from `a`.  `a` is only read.  -> the destination"""
+        group, d = self._reduce_dest(a, group, destination)
+        N.check(N.lib().Evaluator_SumItems(self._h, a._h, C.c_uint64(group), d._h))
+        return d
+
+    def dot_plain_device(self, a, words, scale=1.0, group=None, destination=None):
+        """item o of the result = the sum over the items b of group o of item b of `a` * plaintext b (sealhip.h:
+        Evaluator_DotPlainDevice).  words: DeviceBuffer of [batch][K][N] NTT-form words at the ciphertext's level
+        (CKKSEncoder.encode_device's or transform_plain_to_ntt_device's); `a` in NTT form.  scale: the plaintexts' common scale
+        (CKKS; the scales are multiplied).  group, destination: as sum_items.  -> the destination"""
+        batch = a.batch()
+        need = batch * a.poly_modulus_degree() * a.coeff_modulus_size()
+        if isinstance(words, DeviceBuffer) and words.words < need:
+            raise ValueError("%d plaintext words for a batch of %d at this level: %d needed" % (words.words, batch, need))
+        group, d = self._reduce_dest(a, group, destination)
+        ptr = words.ptr if isinstance(words, DeviceBuffer) else words
+        N.check(N.lib().Evaluator_DotPlainDevice(self._h, a._h, C.c_void_p(ptr), C.c_uint64(batch), C.c_uint64(group), C.c_double(scale), d._h))
+        return d
+
     def mod_switch_plain_to_next_inplace(self, plain):
         N.check(N.lib().Evaluator_ModSwitchToNext2(self._h, plain._h, plain._h))
         return plain

@@ -1,0 +1,41 @@
+// Kernels of the Evaluator's reductions over the items of a batch (evaluator.h: sum_items / dot_plain_device): output item o is the
+// sum of the `group` input items o * group .. o * group + group - 1, or of their dyadic products with one NTT-form plaintext per
+// item.  HBM-streaming like plain_batch_kernels.h and with its conventions: one thread moves two adjacent words per operand with one
+// 16-byte access, flat grids (one thread per output pair, no loop over the grid), one ModDesc per prime, and the non-temporal hint
+// on every ciphertext and plaintext word - each is read once.
+// Layouts: a ciphertext plane is [batch][K][N], so the items of a group are `group` consecutive [K][N] blocks of each plane; the
+// plaintexts are [batch][K][N]; the result's planes are [batch / group][K][N].  The result must not be an operand.
+// Accumulation is lazy (batch_reduce_kernels.hip: kSumFlush, kDotFlush): terms are added as plain integers and reduced once per
+// flush interval.  Every result is the canonical residue of an exactly specified integer, so it does not depend on the schedule:
+// the words are those of add_many (evaluator.cpp:242-261) over multiply_plain (evaluator.cpp:2157-2194).
+// Small results: one thread per output pair is too few threads when the result is small (N = 8192, K = 3, one output item: 24 k),
+// so below a threshold the group is cut into `slices` runs of consecutive items, each reduced by workgroups of its own (the slow grid
+// dimension) into scratch [slices][size][batch / group][K][N], and a second launch of the sum kernel adds the slices.  No atomics:
+// modular addition is exact and associative, the words do not depend on the cut.
+#pragma once
+#include "encrypt_kernels.h"
+
+namespace sealhip
+{
+    // terms a lazy accumulator takes between two reductions (derived in batch_reduce_kernels.hip from "primes are below 2^60")
+    unsigned batch_reduce_sum_flush();
+    unsigned batch_reduce_dot_flush();
+    // The library's rule: slices for a launch of `threads` threads (one per output pair: sum_items size * out_items * K * N / 2,
+    // dot_plain_device out_items * K * N / 2) that each add `group` terms.  1 = one launch, no scratch.
+    unsigned batch_reduce_slices(size_t threads, size_t group);
+    // words of scratch a call with `slices` > 1 needs
+    inline size_t batch_reduce_scratch_words(unsigned slices, unsigned size, size_t out_items, unsigned n_log, unsigned K)
+    {
+        return slices > 1 ? (((size_t)slices * size * out_items * K) << n_log) : 0;
+    }
+
+    // r[p][o][k][j] = sum_i a[p][o * group + i][k][j] mod q_k, p < size.  Plane p of the source is a + p * a_stride, of the result
+    // r + p * r_stride.  slices: 1, or the cut described above with scratch of batch_reduce_scratch_words words (2 <= slices <= group).
+    hipError_t k_sum_items(const ModDesc *mods, const uint64_t *a, size_t a_stride, uint64_t *r, size_t r_stride, unsigned size, unsigned n_log,
+                           unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch, hipStream_t s);
+    // r[p][o][k][j] = sum_i a[p][o * group + i][k][j] * pl[o * group + i][k][j] mod q_k.  A thread keeps its two plaintext words in
+    // registers over the planes (up to three at a time): the plaintexts cross HBM once for size <= 3.
+    hipError_t k_dot_plain_items(const ModDesc *mods, const uint64_t *a, size_t a_stride, const uint64_t *pl, uint64_t *r, size_t r_stride,
+                                 unsigned size, unsigned n_log, unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch,
+                                 hipStream_t s);
+} // namespace sealhip

@@ -251,6 +251,29 @@ extern "C"
         as<Evaluator>(thisptr)->transform_plain_to_ntt_device(device_coefficients, (size_t)batch, parms_id, device_words);
         SHL_CATCH
     }
+    // sums over the items of a batch (library extensions): the destination is another handle, shaped by the host code
+    SHL_FUNC Evaluator_SumItems(void *thisptr, void *encrypted, uint64_t group, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->sum_items(*as<Ciphertext>(encrypted), (size_t)group, *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
+    SHL_FUNC Evaluator_DotPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, uint64_t group, double scale,
+                                      void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->dot_plain_device(*as<Ciphertext>(encrypted), device_plain, (size_t)batch, (size_t)group, scale,
+                                                 *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
     static Plaintext &prepare_plain_dest(void *plain, void *destination)
     {
         Plaintext *src = as<Plaintext>(plain), *dst = as<Plaintext>(destination);

@@ -1,5 +1,6 @@
 // extern "C" layer, part 4: the per-kernel seam (NTT, dyadic products, RNS stages on raw device buffers; include/sealhip.h)
 #include "capi_common.h"
+#include "batch_reduce_kernels.h"
 
 extern "C"
 {
@@ -52,6 +53,48 @@ extern "C"
             throw std::out_of_range("first_prime + comps");
         hip_ok(k_dyadic(c->dev_mods(), a, b, r, (unsigned)c->log_n(), (unsigned)comps, (unsigned)first_prime, polys, (hipStream_t)stream), "dyadic");
         SHL_CATCH
+    }
+    SHL_FUNC shl_reduce_items(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *plain, uint64_t *r, uint64_t size,
+                              uint64_t batch, uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        SHL_TRY
+        auto c = as<Context>(context);
+        auto l = c->level_by_chain_index(chain_index);
+        if (!l)
+            throw std::out_of_range("chain_index");
+        if (!group || batch % group || !size || size > 16)
+            throw std::invalid_argument("group must divide batch; 1 <= size <= 16");
+        const size_t out_items = batch / group, words = (size_t)l->K * c->n();
+        const unsigned n_log = (unsigned)c->log_n();
+        if (!slices)
+            slices = batch_reduce_slices((plain ? 1 : size) * out_items * words / 2, group);
+        if (slices > group || slices > 64)
+            throw std::invalid_argument("1 <= slices <= min(group, 64)");
+        if (slices_used)
+            *slices_used = slices;
+        if (!r) // a query: the slices the library would use, hence the scratch to pass
+            return SHL_S_OK;
+        IfNullRet(a, SHL_E_POINTER);
+        if (slices > 1 && !scratch)
+            throw std::invalid_argument("scratch is null");
+        if (plain)
+            hip_ok(k_dot_plain_items(c->dev_mods(), a, batch * words, plain, r, out_items * words, (unsigned)size, n_log, l->K, out_items, group,
+                                     (unsigned)slices, scratch, (hipStream_t)stream),
+                   "dot_plain (items)");
+        else
+            hip_ok(k_sum_items(c->dev_mods(), a, batch * words, r, out_items * words, (unsigned)size, n_log, l->K, out_items, group,
+                               (unsigned)slices, scratch, (hipStream_t)stream),
+                   "sum (items)");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_reduce_flush_intervals(uint64_t *sum_terms, uint64_t *dot_terms)
+    {
+        IfNullRet(sum_terms, SHL_E_POINTER);
+        IfNullRet(dot_terms, SHL_E_POINTER);
+        *sum_terms = batch_reduce_sum_flush();
+        *dot_terms = batch_reduce_dot_flush();
+        return SHL_S_OK;
     }
     SHL_FUNC shl_apply_galois(
         void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys,

@@ -1,6 +1,7 @@
 // Evaluator, part 1: construction, streams and graph capture, deferred key-switch tails, negate / add / sub, transforms, plaintext operands, multiply
 #include "evaluator_common.h"
 #include "plain_batch_kernels.h"
+#include "batch_reduce_kernels.h"
 #include <atomic>
 
 namespace sealhip
@@ -1112,6 +1113,72 @@ namespace sealhip
                               (unsigned)batch, stream_),
            "plain lift (per item)");
         ck(ntt_forward(context_.ntt_tables(), plain_batch(out, words, lvl->K, (unsigned)batch, 0), 0, stream_), "plain ntt (per item)");
+    }
+
+    // ---- sums over the items of a device-resident batch (include/sealhip.h: Evaluator_SumItems / Evaluator_DotPlainDevice)
+    void Evaluator::check_reduce_items(const Ciphertext &e, size_t group, const Ciphertext &dest) const
+    {
+        if (&dest == &e)
+            throw std::invalid_argument("destination must be different from encrypted");
+        if (!group || e.batch() % group)
+            throw std::invalid_argument("group must divide the ciphertext's batch");
+        if (dest.batch() != e.batch() / group)
+            throw std::invalid_argument("destination's batch does not equal the ciphertext's batch divided by group");
+    }
+    void Evaluator::reduce_items(const Ciphertext &e, const uint64_t *plain, size_t group, double new_scale, Ciphertext &dest) const
+    {
+        e.settle(); // the operand's words are read by what follows
+        const Level &lvl = *e.level();
+        const size_t size = e.size(), out_items = e.batch() / group;
+        const unsigned n_log = (unsigned)context_.log_n(), K = lvl.K;
+        if (dest.ctx_ != e.ctx_)
+        {
+            dest.release();
+            dest.ctx_ = e.ctx_;
+        }
+        dest.reshape_uninitialized(&lvl, size);
+        dest.is_ntt_form() = e.is_ntt_form();
+        dest.scale() = new_scale;
+        dest.correction_factor() = e.correction_factor();
+        // one thread per output pair: the sum has the planes in its grid, the product loops over them
+        const size_t threads = (plain ? 1 : size) * dest.plane_words() / 2;
+        const unsigned slices = batch_reduce_slices(threads, group);
+        std::unique_ptr<Scratch> scratch;
+        if (slices > 1)
+            scratch.reset(new Scratch(batch_reduce_scratch_words(slices, (unsigned)size, out_items, n_log, K)));
+        uint64_t *sp = scratch ? scratch->p : nullptr;
+        if (plain)
+            ck(k_dot_plain_items(context_.dev_mods(), e.data_, e.plane_words(), plain, dest.data_, dest.plane_words(), (unsigned)size, n_log, K,
+                                 out_items, group, slices, sp, stream_),
+               "dot_plain (items)");
+        else
+            ck(k_sum_items(context_.dev_mods(), e.data_, e.plane_words(), dest.data_, dest.plane_words(), (unsigned)size, n_log, K, out_items,
+                           group, slices, sp, stream_),
+               "sum (items)");
+        throw_if_transparent(dest);
+    }
+    void Evaluator::sum_items(const Ciphertext &e, size_t group, Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_valid(e, "encrypted");
+        check_reduce_items(e, group, dest);
+        reduce_items(e, nullptr, group, e.scale(), dest);
+    }
+    void Evaluator::dot_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, size_t group, double scale,
+                                     Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_plain_device(e, plain, batch, true, scale, dest);
+        check_reduce_items(e, group, dest);
+        // coefficient-form operands have no place in a reduction: the monomial branch of multiply_plain_normal is per item and data
+        // dependent (include/sealhip.h)
+        if (!e.is_ntt_form())
+            throw std::invalid_argument("encrypted must be in NTT form");
+        const bool ckks = context_.scheme() == Scheme::ckks;
+        const double new_scale = ckks ? e.scale() * scale : e.scale(); // as multiply_plain_device
+        if (ckks && !scale_within_bounds(new_scale, *e.level()))
+            throw std::invalid_argument("scale out of bounds");
+        reduce_items(e, plain, group, new_scale, dest);
     }
 
     void Evaluator::add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const

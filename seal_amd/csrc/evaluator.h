@@ -337,6 +337,15 @@ namespace sealhip
         // transform_to_ntt_inplace(Plaintext) for `batch` plaintexts: [batch][N] coefficients modulo t -> [batch][K][N] NTT-form words
         // at parms_id (centred lift, forward transform); BFV / BGV
         void transform_plain_to_ntt_device(const uint64_t *coefficients, size_t batch, const uint64_t *parms_id, uint64_t *words) const;
+        // Reductions over the ITEMS of a device-resident batch (include/sealhip.h: Evaluator_SumItems / Evaluator_DotPlainDevice;
+        // batch_reduce_kernels.h).  `group` divides encrypted's batch B; destination is another object whose batch is B / group; item o
+        // of it becomes the sum of the items o * group .. o * group + group - 1 - word for word add_many over batches of one holding
+        // them - or, for dot_plain_device, of their products with the NTT-form plaintexts plain [B][K][N] (multiply_plain_device with
+        // plain_is_ntt = true, then that sum; scale handling and bound check are its).  encrypted is only read; a call that fails
+        // its checks leaves destination untouched.
+        void sum_items(const Ciphertext &encrypted, size_t group, Ciphertext &destination) const;
+        void dot_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, size_t group, double scale,
+                              Ciphertext &destination) const;
         void add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const;
         void multiply_many(const std::vector<const Ciphertext *> &encrypteds, const KSwitchKeys &relin_keys, Ciphertext &destination) const;
         void exponentiate_inplace(Ciphertext &encrypted, uint64_t exponent, const KSwitchKeys &relin_keys) const;
@@ -438,6 +447,9 @@ namespace sealhip
         void check_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
                                 const Ciphertext &destination) const;
         uint64_t *begin_result(const Ciphertext &encrypted, Ciphertext &destination) const; // destination shaped like encrypted, words undefined
+        void check_reduce_items(const Ciphertext &encrypted, size_t group, const Ciphertext &destination) const;
+        // destination (batch / group items) <- the sums; plain null: of the items, else of their products with the plaintexts
+        void reduce_items(const Ciphertext &encrypted, const uint64_t *plain, size_t group, double new_scale, Ciphertext &destination) const;
         void addsub_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale, int op,
                                  Ciphertext &destination) const;
         bool mul_plain_monomial(Ciphertext &encrypted, const Plaintext &plain) const;
