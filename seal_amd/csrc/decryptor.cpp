@@ -1,5 +1,6 @@
 // See decryptor.h.  Reference: native/src/seal/decryptor.cpp.
 #include "decryptor.h"
+#include "evaluator_common.h"
 #include "xof.h"
 #include "hostmath.h"
 #include <algorithm>
@@ -11,11 +12,6 @@ namespace sealhip
 {
     namespace
     {
-        void ck(hipError_t e, const char *what)
-        {
-            if (e != hipSuccess)
-                throw std::runtime_error(std::string("HIP failure in ") + what + ": " + hipGetErrorString(e));
-        }
         NttBatch polys(uint64_t *data, size_t K, size_t n, size_t count)
         {
             NttBatch b{};
@@ -753,15 +749,6 @@ namespace sealhip
     namespace
     {
         constexpr size_t kEncryptBatchScratchBytes = size_t(256) << 20; // per chunk (include/sealhip.h)
-        bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-        {
-            const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-            return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-        }
-        BfvPlainConst bfv_plain_const(const Context &ctx, const Level &lvl)
-        {
-            return BfvPlainConst{ host::make_mod(ctx.plain_modulus()), lvl.dev.q_mod_t, lvl.dev.plain_upper_half_threshold, lvl.dev.delta_mod_q };
-        }
     } // namespace
     size_t Encryptor::chunk_items(size_t item_words) const
     {
@@ -798,7 +785,7 @@ namespace sealhip
         if ((uintptr_t)plain % 16)
             throw std::invalid_argument("device_plain must be 16-byte aligned");
         const size_t item_words = context_.scheme() == Scheme::ckks ? lvl.K * context_.n() : context_.n();
-        if (d.has_storage() && overlap(plain, batch * item_words * 8, d.data(), d.capacity_words() * 8))
+        if (d.has_storage() && words_overlap(plain, batch * item_words * 8, d.data(), d.capacity_words() * 8))
             throw std::invalid_argument("plain and destination overlap");
     }
     std::vector<uint64_t> Encryptor::batch_seeds(size_t batch, const uint64_t *seeds) const
@@ -898,8 +885,8 @@ namespace sealhip
                 if (lift)
                 {
                     // BGV: lift -> NTT -> add (Evaluator::add_plain on a fresh ciphertext, correction factor 1)
-                    ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), 1, plain + b0 * n, lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log,
-                                          (unsigned)K, items, nullptr),
+                    ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), 1, plain + b0 * n, n, n, lvl.dev.plain_upper_half_threshold,
+                                          lvl.dev.upper_half_inc, lifted.p, n_log, (unsigned)K, items, nullptr),
                        "plain lift");
                     ck(ntt_forward(tb, polys(lifted.p, K, n, items), 0, nullptr), "plain ntt");
                     m = lifted.p;
@@ -1015,44 +1002,12 @@ namespace sealhip
             d.correction_factor() = 1;
         }
         if (plain)
-            add_plain_batch(plain, scale, d);
-    }
-
-    // Evaluator::add_plain on fresh ciphertexts, with one plaintext per item
-    void Encryptor::add_plain_batch(const uint64_t *plain, double scale, Ciphertext &d)
-    {
-        const Level &lvl = *d.level();
-        const size_t n = context_.n(), K = lvl.K, words = K * n, batch = d.batch();
-        const unsigned n_log = (unsigned)context_.log_n();
-        const ModDesc *mods = context_.dev_mods();
-        switch (context_.scheme())
         {
-        case Scheme::ckks:
-            d.scale() = scale;
-            ck(k_add_inplace(mods, d.plane(0), plain, batch * words, n_log, (unsigned)K, nullptr), "ckks add plain");
-            break;
-        case Scheme::bfv:
-            ck(k_encrypt_bfv_finish(mods, bfv_plain_const(context_, lvl), nullptr, 0, plain, d.plane(0), 0, 1, false, n_log, (unsigned)K,
-                                    (unsigned)batch, nullptr),
-               "bfv add plain");
-            break;
-        default:
-        {
-            const size_t chunk = std::min(chunk_items(words), batch);
-            Scratch lifted(chunk * words);
-            for (size_t b0 = 0; b0 < batch; b0 += chunk)
-            {
-                const unsigned items = (unsigned)std::min(chunk, batch - b0);
-                ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), 1, plain + b0 * n, lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log, (unsigned)K,
-                                      items, nullptr),
-                   "plain lift");
-                ck(ntt_forward(context_.ntt_tables(), polys(lifted.p, K, n, items), 0, nullptr), "plain ntt");
-                ck(k_add_inplace(mods, d.plane(0) + b0 * words, lifted.p, (size_t)items * words, n_log, (unsigned)K, nullptr), "bgv add plain");
-            }
-            ck(hipStreamSynchronize(nullptr), "encrypt sync");
-            return;
+            // Evaluator::add_plain on fresh ciphertexts, with one plaintext per item
+            if (scheme == Scheme::ckks)
+                d.scale() = scale;
+            evaluator_.add_plain_device(d, plain, batch, scheme == Scheme::ckks, scale, d);
+            evaluator_.synchronize();
         }
-        }
-        ck(hipStreamSynchronize(nullptr), "encrypt sync");
     }
 } // namespace sealhip

@@ -157,7 +157,6 @@ namespace sealhip
         void batch_checks(const uint64_t *plain, size_t batch, const Level &lvl, const Ciphertext &destination) const;
         std::vector<uint64_t> batch_seeds(size_t batch, const uint64_t *seeds) const;
         size_t chunk_items(size_t item_words) const;
-        void add_plain_batch(const uint64_t *plain, double scale, Ciphertext &destination);
         friend class KeyGenerator; // keys are encryptions of zero under s (keygenerator.cpp:93-121, 322-357)
         const Level *level_for(const uint64_t *parms_id) const;
         const Level *level_for(const Plaintext &plain) const; // + the checks of Encryptor::encrypt_internal

@@ -7,7 +7,7 @@
 // Every result is the canonical residue of an exactly specified integer: the words equal those of the per-object chain
 // (k_dyadic, k_expand_small, k_neg_add_noise, Evaluator::add_plain) whatever the order of the additions.
 #pragma once
-#include "context.h"
+#include "plain_batch_kernels.h" // BfvPlainConst; the per-item lift of the BGV plaintexts (k_plain_lift_batch)
 
 namespace sealhip
 {
@@ -28,19 +28,8 @@ namespace sealhip
     //   c_p <- c_p + e_p            e_p[b][j] = small[b][p * N + j]; small == null: no noise
     //   c_p <- -c_p                 when negate (the symmetric form)
     //   c_0 <- c_0 + scaled(m_b)    m = [items][N] coefficients modulo t or null: multiply_add_plain_with_scaling_variant
-    //                               (util/scalingvariant.cpp:70-115), per item what k_bfv_addsub_plain adds for one plaintext
-    struct BfvPlainConst
-    {
-        ModDesc t;
-        uint64_t q_mod_t;
-        uint64_t threshold;    // plain_upper_half_threshold = (t + 1) / 2
-        const uint64_t *delta; // [K] floor(Q / t) mod q_r (LevelDev::delta_mod_q)
-    };
+    //                               (util/scalingvariant.cpp:70-115), what k_bfv_addsub_plain_batch adds
     hipError_t k_encrypt_bfv_finish(const ModDesc *mods, const BfvPlainConst &pc, const int8_t *small, size_t small_stride, const uint64_t *m,
                                     uint64_t *c, size_t plane_stride, unsigned planes, bool negate, unsigned n_log, unsigned K, unsigned items,
                                     hipStream_t s);
-    // BFV / BGV: out[b][r][j] = the centred lift of m[b][j] (coefficients modulo t) to q_r - k_plain_lift for every item; scale_by != 1
-    // first multiplies m[b][j] by it modulo t (BGV add_plain: the ciphertext's correction factor)
-    hipError_t k_plain_lift_batch(const ModDesc *mods, const ModDesc &t, uint64_t scale_by, const uint64_t *m, uint64_t threshold,
-                                  const uint64_t *inc, uint64_t *out, unsigned n_log, unsigned K, unsigned items, hipStream_t s);
 } // namespace sealhip

@@ -155,34 +155,6 @@ namespace sealhip
                 st2_nt(cp, v0, v1);
             }
         }
-
-        // pairs = items * K * N / 2
-        __global__ void __launch_bounds__(kBlock) plain_lift_batch_kernel(
-            const ModDesc *mods, ModDesc t, uint64_t scale_by, const uint64_t *m, uint64_t threshold, const uint64_t *inc, uint64_t *out,
-            size_t pairs, unsigned n_log, unsigned K)
-        {
-            const size_t nmask = (size_t(1) << n_log) - 1;
-            for (size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x; w < pairs; w += (size_t)gridDim.x * kBlock)
-            {
-                const size_t i = 2 * w, row = i >> n_log; // b * K + r
-                const unsigned r = (unsigned)(row % K);
-                const ModDesc md = mods[r];
-                uint64_t m0, m1;
-                ld2<false>(m + ((row / K) << n_log) + (i & nmask), m0, m1);
-                if (scale_by != 1)
-                {
-                    m0 = mul_mod(m0, scale_by, t);
-                    m1 = mul_mod(m1, scale_by, t);
-                }
-                uint64_t v0 = barrett64(m0, md), v1 = barrett64(m1, md);
-                const uint64_t up = inc[r];
-                if (m0 >= threshold)
-                    v0 = add_mod(v0, up, md.q);
-                if (m1 >= threshold)
-                    v1 = add_mod(v1, up, md.q);
-                st2_nt(out + i, v0, v1);
-            }
-        }
     } // namespace
 
     hipError_t k_expand_small_batch(const ModDesc *mods, const int8_t *small, size_t small_stride, uint64_t *dst, size_t poly_stride,
@@ -232,16 +204,6 @@ namespace sealhip
             return hipSuccess;
         hipLaunchKernelGGL(encrypt_bfv_finish_kernel, dim3(grid_for(pairs)), dim3(kBlock), 0, s, mods, pc, small, small_stride, m, c, plane_stride,
                            pairs, negate, n_log, K, items);
-        return hipGetLastError();
-    }
-    hipError_t k_plain_lift_batch(const ModDesc *mods, const ModDesc &t, uint64_t scale_by, const uint64_t *m, uint64_t threshold,
-                                  const uint64_t *inc, uint64_t *out, unsigned n_log, unsigned K, unsigned items, hipStream_t s)
-    {
-        const size_t pairs = (((size_t)items * K) << n_log) / 2;
-        if (!pairs)
-            return hipSuccess;
-        hipLaunchKernelGGL(plain_lift_batch_kernel, dim3(grid_for(pairs)), dim3(kBlock), 0, s, mods, t, scale_by, m, threshold, inc, out, pairs, n_log,
-                           K);
         return hipGetLastError();
     }
 } // namespace sealhip

@@ -616,15 +616,73 @@ namespace sealhip
             throw std::invalid_argument("plain is not valid for encryption parameters");
     }
 
-    // coefficients modulo t -> [K][N] residues of the centred lift (evaluator.cpp:2098-2125, 2243-2282), times scale_by mod t
-    void Evaluator::plain_to_rns(const Plaintext &plain, const Level &lvl, uint64_t scale_by, uint64_t *out) const
+    // ---- plaintext operands.  One code path serves a Plaintext handle (one plaintext for every item of the batch) and raw device
+    // words with one plaintext per item (include/sealhip.h: Evaluator_AddPlainDevice ...): the shared plaintext is the per-item one
+    // whose item stride is zero (plain_batch_kernels.h).
+    struct Evaluator::PlainOperand
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (context_.scheme() == Scheme::ckks)
-            throw std::invalid_argument("CKKS plain must be in NTT form");
-        ck(k_plain_lift(context_.dev_mods(), host::make_mod(context_.plain_modulus()), plain.data(), plain.coeff_count(), scale_by,
-                        lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, out, (unsigned)context_.log_n(), lvl.K, stream_),
-           "plain lift");
+        const uint64_t *words;
+        size_t stride;      // words from one item's plaintext to the next; 0 = one plaintext shared by every item
+        size_t coeff_count; // coefficient form: the words one plaintext holds (<= N)
+        bool ntt;
+        const Level *level; // of the words in NTT form; per item: the ciphertext's
+        double scale;
+        PlainOperand(const Plaintext &p)
+            : words(p.data()), stride(0), coeff_count(p.coeff_count()), ntt(p.is_ntt_form()), level(p.level()), scale(p.scale())
+        {
+        }
+        // one plaintext per item of a batch: [batch][N] coefficients, or [batch][K][N] words at lvl (BFV / BGV plaintexts have scale 1)
+        PlainOperand(const Context &ctx, const Level *lvl, const uint64_t *plain, bool plain_is_ntt, double plain_scale)
+            : words(plain), stride(plain_is_ntt ? lvl->K * ctx.n() : ctx.n()), coeff_count(ctx.n()), ntt(plain_is_ntt), level(lvl),
+              scale(ctx.scheme() == Scheme::ckks ? plain_scale : 1.0)
+        {
+        }
+    };
+    namespace
+    {
+        constexpr size_t kPlainBatchScratchBytes = size_t(256) << 20; // per chunk of lifted plaintexts (include/sealhip.h)
+        // items whose lifted plaintexts [K][N] fit the scratch of one chunk
+        size_t plain_chunk_items(size_t item_words)
+        {
+            size_t budget = kPlainBatchScratchBytes;
+            if (const char *e = shl_ab_getenv("SEALHIP_PLAIN_SCRATCH_BYTES")) // development builds only: chunk edges at small N
+                budget = (size_t)std::strtoull(e, nullptr, 10);
+            return std::max<size_t>(1, budget / (item_words * 8));
+        }
+        // qualifiers.using_fast_plain_lift: t smaller than every prime of the level
+        bool fast_plain_lift(const Context &ctx, const Level &lvl)
+        {
+            bool fast = true;
+            for (unsigned i = 0; i < lvl.K; i++)
+                fast = fast && ctx.plain_modulus() < ctx.coeff_modulus()[i];
+            return fast;
+        }
+    } // namespace
+
+    // Coefficient-form plaintexts -> NTT-form words [K][N] at lvl (the centred lift of evaluator.cpp:2098-2125, 2243-2282, times
+    // scale_by modulo t, then the forward transform), a chunk at a time: use(b0, items, lifted, stride) applies the chunk to the
+    // `items` ciphertext items from b0 on, item b with the words at lifted + (b - b0) * stride.  A shared plaintext is one chunk of
+    // one plaintext for all `batch` items (stride 0).  out: where the words go instead of a chunk's scratch - all of them at once.
+    template <class Use>
+    void Evaluator::lift_chunks(const PlainOperand &plain, const Level &lvl, uint64_t scale_by, size_t batch, uint64_t *out, Use use) const
+    {
+        const size_t words = (size_t)lvl.K * context_.n(), count = plain.stride ? batch : 1;
+        const size_t chunk = out ? count : std::min(plain_chunk_items(words), count);
+        std::unique_ptr<Scratch> scratch(out ? nullptr : new Scratch(chunk * words));
+        uint64_t *lifted = out ? out : scratch->p;
+        for (size_t b0 = 0; b0 < count; b0 += chunk)
+        {
+            const unsigned items = (unsigned)std::min(chunk, count - b0);
+            ck(k_plain_lift_batch(context_.dev_mods(), host::make_mod(context_.plain_modulus()), scale_by, plain.words + b0 * plain.stride,
+                                  plain.stride, plain.coeff_count, lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted,
+                                  (unsigned)context_.log_n(), lvl.K, items, stream_),
+               "plain lift");
+            ck(ntt_forward(context_.ntt_tables(), plain_batch(lifted, words, lvl.K, items, 0), 0, stream_), "plain ntt");
+            if (plain.stride)
+                use(b0, items, lifted, words);
+            else
+                use(0, (unsigned)batch, lifted, 0);
+        }
     }
 
     void Evaluator::transform_to_ntt_inplace(Plaintext &plain, const uint64_t *parms_id) const
@@ -636,12 +694,13 @@ namespace sealhip
             throw std::invalid_argument("parms_id is not valid for the current context");
         if (plain.is_ntt_form())
             throw std::invalid_argument("plain is already in NTT form");
+        if (context_.scheme() == Scheme::ckks)
+            throw std::invalid_argument("CKKS plain must be in NTT form");
         const size_t words = (size_t)lvl->K * context_.n();
         uint64_t *out = DevicePool::global().alloc_words(words);
         try
         {
-            plain_to_rns(plain, *lvl, 1, out);
-            ck(ntt_forward(context_.ntt_tables(), plain_batch(out, words, lvl->K, 1, 0), 0, stream_), "plain ntt");
+            lift_chunks(plain, *lvl, 1, 1, out, [](size_t, unsigned, const uint64_t *, size_t) {});
         }
         catch (...)
         {
@@ -688,14 +747,21 @@ namespace sealhip
         // add_plain_inplace / sub_plain_inplace share everything but the sign
         check_valid(e, "encrypted");
         check_valid(plain);
-        addsub_plain(e, plain, 0);
+        addsub_plain(e, plain, 0, e);
     }
     void Evaluator::sub_plain_inplace(Ciphertext &e, const Plaintext &plain) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         check_valid(e, "encrypted");
         check_valid(plain);
-        addsub_plain(e, plain, 1);
+        addsub_plain(e, plain, 1, e);
+    }
+    void Evaluator::multiply_plain_inplace(Ciphertext &e, const Plaintext &plain) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_valid(e, "encrypted");
+        check_valid(plain);
+        multiply_plain(e, plain, e);
     }
     void Evaluator::check_addsub_plain_forms(const Ciphertext &e, bool plain_is_ntt, const Level *plain_level, double plain_scale) const
     {
@@ -728,170 +794,6 @@ namespace sealhip
         if (e.size() < 1)
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
     }
-    void Evaluator::addsub_plain(Ciphertext &e, const Plaintext &plain, int op) const
-    {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        const Scheme scheme = context_.scheme();
-        check_addsub_plain_forms(e, plain.is_ntt_form(), plain.level(), plain.scale());
-        const Level &lvl = *e.level();
-        const unsigned n_log = (unsigned)context_.log_n();
-        const ModDesc *mods = context_.dev_mods();
-        switch (scheme)
-        {
-        case Scheme::bfv:
-            // multiply_add/sub_plain_with_scaling_variant (util/scalingvariant.cpp:70-175)
-            ck(k_bfv_addsub_plain(mods, host::make_mod(context_.plain_modulus()), plain.data(), plain.coeff_count(), lvl.dev.q_mod_t,
-                                  lvl.dev.plain_upper_half_threshold, lvl.dev.delta_mod_q, e.plane(0), op, n_log, lvl.K, e.batch(), stream_),
-               "bfv add/sub plain");
-            break;
-        case Scheme::ckks:
-            ck(k_addsub_plain(mods, e.plane(0), plain.data(), op, n_log, lvl.K, e.batch(), stream_), "ckks add/sub plain");
-            break;
-        case Scheme::bgv:
-        {
-            // plain * correction_factor mod t, lifted and transformed at the ciphertext's level (evaluator.cpp:1836-1847)
-            Scratch tmp((size_t)lvl.K * context_.n());
-            plain_to_rns(plain, lvl, e.correction_factor(), tmp.p);
-            ck(ntt_forward(context_.ntt_tables(), plain_batch(tmp.p, (size_t)lvl.K * context_.n(), lvl.K, 1, 0), 0, stream_), "plain ntt");
-            ck(k_addsub_plain(mods, e.plane(0), tmp.p, op, n_log, lvl.K, e.batch(), stream_), "bgv add/sub plain");
-            break;
-        }
-        default:
-            throw std::invalid_argument("unsupported scheme");
-        }
-        throw_if_transparent(e);
-    }
-
-    void Evaluator::multiply_plain_ntt(Ciphertext &e, const uint64_t *plain_rns, const Level *plain_level, double plain_scale) const
-    {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        // multiply_plain_ntt (evaluator.cpp:2157-2194)
-        if (e.level() != plain_level)
-            throw std::invalid_argument("encrypted_ntt and plain_ntt parameter mismatch");
-        const Level &lvl = *e.level();
-        ck(k_dyadic_plain(context_.dev_mods(), e.data(), plain_rns, e.data(), (unsigned)context_.log_n(), lvl.K, e.size() * e.batch(), stream_),
-           "multiply_plain");
-        e.scale() *= plain_scale;
-        if (!scale_within_bounds(e.scale(), lvl))
-            throw std::invalid_argument("scale out of bounds");
-    }
-
-    // The monomial shortcut of multiply_plain_normal (evaluator.cpp:2051-2095).  It is not merely faster: with the
-    // "fast plain lift" (t below every q_i) the reference multiplies by the RAW coefficient even when it lies in the
-    // upper half, i.e. by m instead of m - t; the ciphertext words differ from the generic path (by t * ct * x^e), so
-    // the branch has to be reproduced.  Costs one 24-byte read-back per coefficient-form multiply_plain.
-    bool Evaluator::mul_plain_monomial(Ciphertext &e, const Plaintext &plain) const
-    {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        const Level &lvl = *e.level();
-        Scratch stats(3);
-        ck(k_plain_stats(plain.data(), plain.coeff_count(), stats.p, stream_), "plain stats");
-        uint64_t st[3];
-        ck(hipMemcpyAsync(st, stats.p, 24, hipMemcpyDeviceToHost, stream_), "plain stats read");
-        ck(hipStreamSynchronize(stream_), "plain stats sync");
-        if (st[0] != 1)
-            return false;
-        const size_t mono_exponent = (size_t)st[1] - 1;
-        const uint64_t c = st[2], t = context_.plain_modulus();
-        const std::vector<uint64_t> &q = context_.coeff_modulus();
-        bool fast_lift = true; // qualifiers.using_fast_plain_lift: t smaller than every prime of this level
-        for (unsigned i = 0; i < lvl.K; i++)
-            fast_lift = fast_lift && t < q[i];
-        std::vector<uint64_t> sc(lvl.K);
-        for (unsigned i = 0; i < lvl.K; i++)
-        {
-            sc[i] = c % q[i];
-            if (c >= lvl.dev.plain_upper_half_threshold && !fast_lift)
-                sc[i] = (sc[i] + (q[i] - t % q[i]) % q[i]) % q[i]; // (c + Q - t) mod q_i
-        }
-        Scratch dsc(lvl.K);
-        ck(hipMemcpyAsync(dsc.p, sc.data(), lvl.K * 8, hipMemcpyHostToDevice, stream_), "mono scalars");
-        const size_t words = e.word_count();
-        uint64_t *out = DevicePool::global().alloc_words(words);
-        ck(k_negacyclic_mul_mono(context_.dev_mods(), e.data(), out, dsc.p, mono_exponent, (unsigned)context_.log_n(), lvl.K,
-                                 e.size() * e.batch(), stream_),
-           "multiply_plain monomial");
-        ck(hipStreamSynchronize(stream_), "mono sync"); // sc lives on this stack frame
-        const size_t size = e.size();
-        e.adopt(&lvl, size, out, words);
-        if (context_.scheme() == Scheme::ckks)
-        {
-            e.scale() *= plain.scale();
-            if (!scale_within_bounds(e.scale(), lvl))
-                throw std::invalid_argument("scale out of bounds");
-        }
-        return true;
-    }
-
-    void Evaluator::multiply_plain_inplace(Ciphertext &e, const Plaintext &plain) const
-    {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        check_valid(e, "encrypted");
-        check_valid(plain);
-        const Level &lvl = *e.level();
-        const size_t pw = (size_t)lvl.K * context_.n();
-        if (e.is_ntt_form() && plain.is_ntt_form())
-            multiply_plain_ntt(e, plain.data(), plain.level(), plain.scale());
-        else if (!plain.is_ntt_form())
-        {
-            // multiply_plain_normal (evaluator.cpp:2021-2155) and the "encrypted in NTT form, plain not" branch (2006-2011):
-            // lift the plaintext at the ciphertext's level, transform it, and multiply in the NTT domain.  The reference's
-            // monomial shortcut computes the same product, so the canonical result is identical.
-            const bool ct_ntt = e.is_ntt_form();
-            const unsigned items = (unsigned)(e.size() * e.batch());
-            if (!ct_ntt && mul_plain_monomial(e, plain))
-            {
-                throw_if_transparent(e);
-                return;
-            }
-            Scratch tmp(pw);
-            plain_to_rns(plain, lvl, 1, tmp.p);
-            ck(ntt_forward(context_.ntt_tables(), plain_batch(tmp.p, pw, lvl.K, 1, 0), 0, stream_), "plain ntt");
-            if (!ct_ntt)
-                ck(ntt_forward(context_.ntt_tables(), plain_batch(e.data(), pw, lvl.K, items, 0), 1, stream_), "multiply_plain ntt");
-            if (ct_ntt)
-                multiply_plain_ntt(e, tmp.p, &lvl, plain.scale());
-            else
-            {
-                ck(k_dyadic_plain(context_.dev_mods(), e.data(), tmp.p, e.data(), (unsigned)context_.log_n(), lvl.K, items, stream_),
-                   "multiply_plain");
-                ck(ntt_inverse(context_.ntt_tables(), plain_batch(e.data(), pw, lvl.K, items, 0), 0, stream_), "multiply_plain intt");
-                if (context_.scheme() == Scheme::ckks)
-                {
-                    e.scale() *= plain.scale();
-                    if (!scale_within_bounds(e.scale(), lvl))
-                        throw std::invalid_argument("scale out of bounds");
-                }
-            }
-        }
-        else
-        {
-            // encrypted not in NTT form, plain in NTT form (evaluator.cpp:2012-2017)
-            transform_to_ntt_inplace(e);
-            multiply_plain_ntt(e, plain.data(), plain.level(), plain.scale());
-            transform_from_ntt_inplace(e);
-        }
-        throw_if_transparent(e);
-    }
-
-    // ---- one plaintext per item of a device-resident batch (include/sealhip.h: Evaluator_AddPlainDevice ...; plain_batch_kernels.h)
-    namespace
-    {
-        constexpr size_t kPlainBatchScratchBytes = size_t(256) << 20; // per chunk of lifted plaintexts (include/sealhip.h)
-        bool words_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-        {
-            const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-            return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-        }
-        // items whose lifted plaintexts [K][N] fit the scratch of one chunk
-        size_t plain_chunk_items(size_t item_words)
-        {
-            size_t budget = kPlainBatchScratchBytes;
-            if (const char *e = shl_ab_getenv("SEALHIP_PLAIN_SCRATCH_BYTES")) // development builds only: chunk edges at small N
-                budget = (size_t)std::strtoull(e, nullptr, 10);
-            return std::max<size_t>(1, budget / (item_words * 8));
-        }
-    } // namespace
     void Evaluator::check_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
                                        const Ciphertext &dest) const
     {
@@ -936,22 +838,32 @@ namespace sealhip
     void Evaluator::add_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
                                      Ciphertext &dest) const
     {
-        addsub_plain_device(e, plain, batch, plain_is_ntt, scale, 0, dest);
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_plain_device(e, plain, batch, plain_is_ntt, scale, dest);
+        addsub_plain(e, PlainOperand(context_, e.level(), plain, plain_is_ntt, scale), 0, dest);
     }
     void Evaluator::sub_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
                                      Ciphertext &dest) const
     {
-        addsub_plain_device(e, plain, batch, plain_is_ntt, scale, 1, dest);
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_plain_device(e, plain, batch, plain_is_ntt, scale, dest);
+        addsub_plain(e, PlainOperand(context_, e.level(), plain, plain_is_ntt, scale), 1, dest);
     }
-    void Evaluator::addsub_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale, int op,
-                                        Ciphertext &dest) const
+    void Evaluator::multiply_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
+                                          Ciphertext &dest) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         check_plain_device(e, plain, batch, plain_is_ntt, scale, dest);
-        check_addsub_plain_forms(e, plain_is_ntt, e.level(), scale);
+        multiply_plain(e, PlainOperand(context_, e.level(), plain, plain_is_ntt, scale), dest);
+    }
+
+    // dest <- e (+/-) plain (op 0 add, 1 sub); dest may be e
+    void Evaluator::addsub_plain(const Ciphertext &e, const PlainOperand &plain, int op, Ciphertext &dest) const
+    {
+        check_addsub_plain_forms(e, plain.ntt, plain.level, plain.scale);
         const Level &lvl = *e.level();
-        const size_t n = context_.n(), words = (size_t)lvl.K * n;
-        const unsigned n_log = (unsigned)context_.log_n(), K = lvl.K;
+        const size_t words = (size_t)lvl.K * context_.n();
+        const unsigned n_log = (unsigned)context_.log_n(), K = lvl.K, batch = (unsigned)e.batch();
         const ModDesc *mods = context_.dev_mods();
         const uint64_t *a = e.plane(0);
         uint64_t *r = begin_result(e, dest);
@@ -961,80 +873,76 @@ namespace sealhip
         switch (context_.scheme())
         {
         case Scheme::bfv:
-        {
-            const BfvPlainConst pc{ host::make_mod(context_.plain_modulus()), lvl.dev.q_mod_t, lvl.dev.plain_upper_half_threshold,
-                                    lvl.dev.delta_mod_q };
-            ck(k_bfv_addsub_plain_batch(mods, pc, plain, a, r, op, n_log, K, (unsigned)batch, stream_), "bfv add/sub plain (per item)");
+            // multiply_add/sub_plain_with_scaling_variant (util/scalingvariant.cpp:70-175)
+            ck(k_bfv_addsub_plain_batch(mods, bfv_plain_const(context_, lvl), plain.words, plain.stride, plain.coeff_count, a, r, op, n_log, K,
+                                        batch, stream_),
+               "bfv add/sub plain");
             break;
-        }
         case Scheme::ckks:
-            ck(k_addsub_plain_batch(mods, a, plain, r, op, n_log, K, (unsigned)batch, stream_), "ckks add/sub plain (per item)");
+            ck(k_addsub_plain_batch(mods, a, plain.words, plain.stride, r, op, n_log, K, batch, stream_), "ckks add/sub plain");
             break;
         case Scheme::bgv:
-        {
-            // plain_b * correction_factor mod t, lifted and transformed at the ciphertext's level (evaluator.cpp:1836-1847), a chunk at a time
-            const size_t chunk = std::min(plain_chunk_items(words), batch);
-            Scratch lifted(chunk * words);
-            for (size_t b0 = 0; b0 < batch; b0 += chunk)
-            {
-                const unsigned items = (unsigned)std::min(chunk, batch - b0);
-                ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), e.correction_factor(), plain + b0 * n,
-                                      lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log, K, items, stream_),
-                   "plain lift (per item)");
-                ck(ntt_forward(context_.ntt_tables(), plain_batch(lifted.p, words, K, items, 0), 0, stream_), "plain ntt (per item)");
-                ck(k_addsub_plain_batch(mods, a + b0 * words, lifted.p, r + b0 * words, op, n_log, K, items, stream_),
-                   "bgv add/sub plain (per item)");
-            }
+            // plain * correction_factor mod t, lifted and transformed at the ciphertext's level (evaluator.cpp:1836-1847)
+            lift_chunks(plain, lvl, e.correction_factor(), batch, nullptr, [&](size_t b0, unsigned items, const uint64_t *lifted, size_t stride) {
+                ck(k_addsub_plain_batch(mods, a + b0 * words, lifted, stride, r + b0 * words, op, n_log, K, items, stream_), "bgv add/sub plain");
+            });
             break;
-        }
         default:
             throw std::invalid_argument("unsupported scheme");
         }
         throw_if_transparent(dest);
     }
 
-    void Evaluator::multiply_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
-                                          Ciphertext &dest) const
+    // dest <- e * plain; dest may be e.  multiply_plain_ntt (evaluator.cpp:2157-2194), multiply_plain_normal (2021-2155) and the
+    // mixed-form branches (2006-2017): whatever the forms, the product is taken in the NTT domain - a coefficient-form plaintext is
+    // lifted and transformed at the ciphertext's level, a coefficient-form ciphertext is transformed and transformed back - except
+    // for the monomial shortcut of multiply_plain_normal (2051-2095), which is not merely faster: with the "fast plain lift" (t
+    // below every q_i) the reference multiplies by the RAW coefficient even when it lies in the upper half, i.e. by m instead of
+    // m - t; the ciphertext words differ from the generic path (by t * ct * x^e), so the branch is reproduced, per item.  Costs one
+    // read-back of 24 bytes per plaintext for a coefficient-form product.
+    void Evaluator::multiply_plain(const Ciphertext &e, const PlainOperand &plain, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        check_plain_device(e, plain, batch, plain_is_ntt, scale, dest);
         const Level &lvl = *e.level();
-        const bool ckks = context_.scheme() == Scheme::ckks;
-        // (BFV / BGV plaintexts have scale 1: multiply_plain_ntt's scale update and bound check do nothing for them)
-        const double new_scale = ckks ? e.scale() * scale : e.scale();
-        if (ckks && !scale_within_bounds(new_scale, lvl))
-            throw std::invalid_argument("scale out of bounds");
-        const size_t n = context_.n(), words = (size_t)lvl.K * n, size = e.size(), plane = e.plane_words();
+        const bool ckks = context_.scheme() == Scheme::ckks, ct_ntt = e.is_ntt_form();
+        if (plain.ntt && plain.level != &lvl)
+            throw std::invalid_argument("encrypted_ntt and plain_ntt parameter mismatch");
+        const size_t words = (size_t)lvl.K * context_.n(), size = e.size(), plane = e.plane_words(), batch = e.batch();
         const unsigned n_log = (unsigned)context_.log_n(), K = lvl.K;
         const ModDesc *mods = context_.dev_mods();
         const NttTables &tb = context_.ntt_tables();
-        const bool ct_ntt = e.is_ntt_form();
 
-        // multiply_plain_normal's monomial branch (mul_plain_monomial above), decided for every item at once: one launch, one read-back
+        // the monomial branch, decided for every plaintext at once: one launch, one read-back
         std::unique_ptr<Scratch> stats;
         size_t monomials = 0;
-        if (!ct_ntt && !plain_is_ntt && size)
+        if (!ct_ntt && !plain.ntt && size)
         {
-            stats.reset(new Scratch(3 * batch));
-            ck(k_plain_stats_batch(plain, stats->p, n_log, (unsigned)batch, stream_), "plain stats (per item)");
-            std::vector<uint64_t> st(3 * batch);
+            const size_t count = plain.stride ? batch : 1;
+            stats.reset(new Scratch(3 * count));
+            ck(k_plain_stats_batch(plain.words, plain.stride, plain.coeff_count, stats->p, (unsigned)count, stream_), "plain stats");
+            std::vector<uint64_t> st(3 * count);
             ck(hipMemcpyAsync(st.data(), stats->p, st.size() * 8, hipMemcpyDeviceToHost, stream_), "plain stats read");
             ck(hipStreamSynchronize(stream_), "plain stats sync");
-            for (size_t b = 0; b < batch; b++)
+            for (size_t b = 0; b < count; b++)
                 monomials += st[3 * b] == 1;
+            if (!plain.stride)
+                monomials *= batch;
         }
+        if (ckks && !plain.ntt && monomials < batch)
+            throw std::invalid_argument("CKKS plain must be in NTT form");
+        // as the reference: the scale is the plaintext's business wherever multiply_plain_ntt does the work, and in CKKS
+        const bool scaled = ckks || ct_ntt || plain.ntt;
+        const double new_scale = scaled ? e.scale() * plain.scale : e.scale();
+        if (scaled && !scale_within_bounds(new_scale, lvl))
+            throw std::invalid_argument("scale out of bounds");
 
         const uint64_t *src = e.data();
-        // the monomial product permutes: in place it goes through a fresh slab, as mul_plain_monomial's does
+        // the monomial product permutes: in place it goes through a fresh slab
         uint64_t *fresh = (&dest == &e && monomials) ? DevicePool::global().alloc_words(e.word_count()) : nullptr;
         uint64_t *res = fresh ? fresh : begin_result(e, dest);
         try
         {
             if (monomials < batch && size)
             {
-                // the other items (and, unused, the monomial ones among them): lift and transform the plaintexts at the ciphertext's
-                // level and multiply in the NTT domain - multiply_plain_normal / multiply_plain_ntt and the mixed-form branches
-                // (evaluator.cpp:2006-2017)
                 if (!ct_ntt)
                 {
                     NttBatch cb = plain_batch(res, words, K, (unsigned)(size * batch), 0);
@@ -1045,40 +953,29 @@ namespace sealhip
                         cb.src_ncomp = K;
                         cb.src_mode = 0;
                     }
-                    ck(ntt_forward(tb, cb, 0, stream_), "multiply_plain ntt (per item)");
+                    // (a shared coefficient-form plaintext has always met lazy words here, the other shapes canonical ones: the
+                    // product is the same canonical residue)
+                    ck(ntt_forward(tb, cb, !plain.stride && !plain.ntt ? 1 : 0, stream_), "multiply_plain ntt");
                 }
                 const uint64_t *a = ct_ntt ? src : res;
-                if (plain_is_ntt)
-                    ck(k_dyadic_plain_batch(mods, a, plane, plain, res, plane, (unsigned)size, n_log, K, (unsigned)batch, stream_),
-                       "multiply_plain (per item)");
-                else
-                {
-                    const size_t chunk = std::min(plain_chunk_items(words), batch);
-                    Scratch lifted(chunk * words);
-                    for (size_t b0 = 0; b0 < batch; b0 += chunk)
-                    {
-                        const unsigned items = (unsigned)std::min(chunk, batch - b0);
-                        ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), 1, plain + b0 * n,
-                                              lvl.dev.plain_upper_half_threshold, lvl.dev.upper_half_inc, lifted.p, n_log, K, items, stream_),
-                           "plain lift (per item)");
-                        ck(ntt_forward(tb, plain_batch(lifted.p, words, K, items, 0), 0, stream_), "plain ntt (per item)");
-                        ck(k_dyadic_plain_batch(mods, a + b0 * words, plane, lifted.p, res + b0 * words, plane, (unsigned)size, n_log, K, items,
-                                                stream_),
-                           "multiply_plain (per item)");
-                    }
-                }
+                if (plain.ntt)
+                    ck(k_dyadic_plain_batch(mods, a, plane, plain.words, plain.stride, res, plane, (unsigned)size, n_log, K, (unsigned)batch,
+                                            stream_),
+                       "multiply_plain");
+                else // (the monomial items among them are overwritten below)
+                    lift_chunks(plain, lvl, 1, batch, nullptr, [&](size_t b0, unsigned items, const uint64_t *lifted, size_t stride) {
+                        ck(k_dyadic_plain_batch(mods, a + b0 * words, plane, lifted, stride, res + b0 * words, plane, (unsigned)size, n_log, K,
+                                                items, stream_),
+                           "multiply_plain");
+                    });
                 if (!ct_ntt)
-                    ck(ntt_inverse(tb, plain_batch(res, words, K, (unsigned)(size * batch), 0), 0, stream_), "multiply_plain intt (per item)");
+                    ck(ntt_inverse(tb, plain_batch(res, words, K, (unsigned)(size * batch), 0), 0, stream_), "multiply_plain intt");
             }
             if (monomials)
-            {
-                bool fast_lift = true; // qualifiers.using_fast_plain_lift: t smaller than every prime of this level
-                for (unsigned i = 0; i < K; i++)
-                    fast_lift = fast_lift && context_.plain_modulus() < context_.coeff_modulus()[i];
-                ck(k_negacyclic_mul_mono_batch(mods, stats->p, lvl.dev.plain_upper_half_threshold, fast_lift ? nullptr : lvl.dev.upper_half_inc,
-                                               src, plane, res, plane, (unsigned)size, n_log, K, (unsigned)batch, stream_),
-                   "multiply_plain monomial (per item)");
-            }
+                ck(k_negacyclic_mul_mono_batch(mods, stats->p, plain.stride ? 3 : 0, lvl.dev.plain_upper_half_threshold,
+                                               fast_plain_lift(context_, lvl) ? nullptr : lvl.dev.upper_half_inc, src, plane, res, plane,
+                                               (unsigned)size, n_log, K, (unsigned)batch, stream_),
+                   "multiply_plain monomial");
         }
         catch (...)
         {
@@ -1105,14 +1002,10 @@ namespace sealhip
             throw std::invalid_argument("parms_id is not valid for the current context");
         if (context_.scheme() == Scheme::ckks)
             throw std::invalid_argument("CKKS plain must be in NTT form");
-        const size_t n = context_.n(), words = (size_t)lvl->K * n;
-        if (words_overlap(coefficients, batch * n * 8, out, batch * words * 8))
+        const size_t n = context_.n();
+        if (words_overlap(coefficients, batch * n * 8, out, batch * lvl->K * n * 8))
             throw std::invalid_argument("device_coefficients and device_words overlap");
-        ck(k_plain_lift_batch(context_.dev_mods(), host::make_mod(context_.plain_modulus()), 1, coefficients,
-                              lvl->dev.plain_upper_half_threshold, lvl->dev.upper_half_inc, out, (unsigned)context_.log_n(), lvl->K,
-                              (unsigned)batch, stream_),
-           "plain lift (per item)");
-        ck(ntt_forward(context_.ntt_tables(), plain_batch(out, words, lvl->K, (unsigned)batch, 0), 0, stream_), "plain ntt (per item)");
+        lift_chunks(PlainOperand(context_, lvl, coefficients, false, 1.0), *lvl, 1, batch, out, [](size_t, unsigned, const uint64_t *, size_t) {});
     }
 
     // ---- sums over the items of a device-resident batch (include/sealhip.h: Evaluator_SumItems / Evaluator_DotPlainDevice)

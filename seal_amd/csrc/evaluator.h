@@ -441,7 +441,12 @@ namespace sealhip
         void bfv_multiply_to(const Ciphertext &e1, const Ciphertext &e2, Ciphertext &dst) const;
         void bgv_multiply(Ciphertext &e1, const Ciphertext &e2) const;
         void check_valid(const Plaintext &plain) const;
-        void addsub_plain(Ciphertext &encrypted, const Plaintext &plain, int op) const;
+        // plaintext operands (evaluator.cpp): a Plaintext handle or raw device words with one plaintext per item, one code path
+        struct PlainOperand;
+        void addsub_plain(const Ciphertext &encrypted, const PlainOperand &plain, int op, Ciphertext &destination) const;
+        void multiply_plain(const Ciphertext &encrypted, const PlainOperand &plain, Ciphertext &destination) const;
+        template <class Use>
+        void lift_chunks(const PlainOperand &plain, const Level &lvl, uint64_t scale_by, size_t batch, uint64_t *out, Use use) const;
         // what add_plain / sub_plain accept per scheme (shared by the per-object and the per-item forms)
         void check_addsub_plain_forms(const Ciphertext &encrypted, bool plain_is_ntt, const Level *plain_level, double plain_scale) const;
         void check_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
@@ -450,11 +455,6 @@ namespace sealhip
         void check_reduce_items(const Ciphertext &encrypted, size_t group, const Ciphertext &destination) const;
         // destination (batch / group items) <- the sums; plain null: of the items, else of their products with the plaintexts
         void reduce_items(const Ciphertext &encrypted, const uint64_t *plain, size_t group, double new_scale, Ciphertext &destination) const;
-        void addsub_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale, int op,
-                                 Ciphertext &destination) const;
-        bool mul_plain_monomial(Ciphertext &encrypted, const Plaintext &plain) const;
-        void plain_to_rns(const Plaintext &plain, const Level &lvl, uint64_t scale_by, uint64_t *out) const;
-        void multiply_plain_ntt(Ciphertext &encrypted_ntt, const uint64_t *plain_rns, const Level *plain_level, double plain_scale) const;
         void bgv_correct_and_combine(
             Scratch &delta, const uint64_t *a, size_t a_stride, const ShoupOp *mul, unsigned ncomp, size_t items, uint64_t *out0,
             uint64_t *out1, size_t out_stride, int epi) const;

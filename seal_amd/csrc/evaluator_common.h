@@ -1,6 +1,7 @@
 #pragma once
-// Shared by objects.cpp and the evaluator*.cpp files: small host helpers (each translation unit gets its own copy).
+// Shared by objects.cpp, the evaluator*.cpp files and decryptor.cpp: small host helpers (each translation unit gets its own copy).
 #include "evaluator.h"
+#include "plain_batch_kernels.h"
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -88,6 +89,18 @@ namespace sealhip
                 }
             }
             f = host::mulmod(e1, c1, t);
+        }
+
+        // do [a, a + a_bytes) and [b, b + b_bytes) share a byte?
+        bool words_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+        {
+            const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+            return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+        }
+        // the constants of the BFV plaintext scaling at a level
+        BfvPlainConst bfv_plain_const(const Context &ctx, const Level &lvl)
+        {
+            return BfvPlainConst{ host::make_mod(ctx.plain_modulus()), lvl.dev.q_mod_t, lvl.dev.plain_upper_half_threshold, lvl.dev.delta_mod_q };
         }
 
         NttBatch plain_batch(uint64_t *data, size_t outer_stride, unsigned ncomp, unsigned nouter, unsigned prime_first)

@@ -2,7 +2,7 @@
 // 16-byte accesses (two adjacent words per thread and per operand, with or without the non-temporal hint) and the per-coefficient
 // BFV scaling of a plaintext.  Include from a .hip file only, inside nothing; everything lives in an unnamed namespace.
 #pragma once
-#include "encrypt_kernels.h"
+#include "plain_batch_kernels.h"
 
 namespace sealhip
 {
@@ -35,7 +35,7 @@ namespace sealhip
 #endif
         }
 
-        // floor((hi:lo) / t) for a quotient below 2^64, with t's Barrett constant floor(2^128 / t) (as poly_kernels.hip divides)
+        // floor((hi:lo) / t) for a quotient below 2^64, with t's Barrett constant floor(2^128 / t)
         __device__ __forceinline__ uint64_t div128_by(uint64_t lo, uint64_t hi, const ModDesc &t)
         {
             uint64_t t1 = mul_hi64(lo, t.ratio_lo);

@@ -222,11 +222,13 @@ def case_host_sampling_equals_device(scheme, n, bits, batch, monkeypatch):
 
 
 def case_chunks(scheme, n, bits, batch, per_chunk, monkeypatch, with_ref=False):
-    """a scratch cap that makes chunks of `per_chunk` items (development builds: SEALHIP_ENCRYPT_SCRATCH_BYTES): every item on
-    both sides of every chunk edge equals the per-object form"""
+    """a scratch cap that makes chunks of `per_chunk` items (development builds: SEALHIP_ENCRYPT_SCRATCH_BYTES for the Encryptor's
+    own chunks, SEALHIP_PLAIN_SCRATCH_BYTES for the Evaluator's plaintext addition after a public-key encryption, at the first
+    level): every item on both sides of every chunk edge equals the per-object form"""
     side = Side(scheme, n, bits)
     K_top = side.K_at(side.first, True)
     monkeypatch.setenv("SEALHIP_ENCRYPT_SCRATCH_BYTES", str(per_chunk * 8 * K_top * n))
+    monkeypatch.setenv("SEALHIP_PLAIN_SCRATCH_BYTES", str(per_chunk * 8 * side.K(side.first) * n))
     assert (batch - 1) // per_chunk >= 2, "at least two chunk edges"
     case_per_item_seeds(scheme, n, bits, batch, side=side, levels=[side.first])
 

@@ -1,8 +1,10 @@
 """One plaintext per item of a device-resident batch (Evaluator_AddPlainDevice / SubPlainDevice / MultiplyPlainDevice /
 TransformPlainToNTTDevice), shared by the CPU (emulated kernels) and `-m gpu` suites.  Byte equality, per item, against two
 yardsticks: the REAL reference (oracle/_ref) where it is built - add_plain_inplace / sub_plain_inplace / multiply_plain_inplace /
-transform_to_ntt_inplace on its own objects - and the library's per-object forms on batches of one, which are unchanged and
-proven against the reference (parity_cases.case_plain_ops).  TEST INFRASTRUCTURE: the reference is the checker."""
+transform_to_ntt_inplace on its own objects - and the library's per-object forms on batches of one.  The per-object and the
+per-item forms share their kernels and their host path (a shared plaintext is a per-item one with item stride 0), so agreement
+between the two proves little by itself: the independent yardsticks are the reference here and parity_cases.case_plain_ops.
+TEST INFRASTRUCTURE: the reference is the checker."""
 import ctypes as C
 
 import numpy as np
@@ -156,6 +158,56 @@ def case_branches(scheme, n, bits, tbits=20, size=2, seed=9):
         c = side.dev_ct(x, ci, ct_ntt)
         side.call(op, c, buf, False)
         side.check((scheme, "branches", op, ct_ntt, "fast lift" if fast else "general lift"), c, op, x, pl, ci, ct_ntt, False)
+    return fast
+
+
+C_ABI = {"add": "Evaluator_AddPlain", "sub": "Evaluator_SubPlain", "multiply": "Evaluator_MultiplyPlain"}
+
+
+def case_shared_plaintext(scheme, n, bits, tbits, batch=3, size=2, seed=19):
+    """ONE Plaintext handle of coeff_count 1, 5, N - 1 and N words applied to a batch (item stride 0): every item, in place and
+    out of place through the C ABI, carries the words of the REFERENCE's own add / sub / multiply_plain_inplace on that item.
+    Coefficients beyond coeff_count act as zero and are never read.  Among the plaintexts the 5-coefficient monomial with an
+    upper-half coefficient: the raw coefficient under the fast plain lift, the increment per prime otherwise.  -> fast lift?"""
+    side = Side(scheme, n, bits, tbits)
+    ref, t, ci = side.ref, side.t, side.first
+    assert ref is not None, "this case compares with the reference alone"
+    rng = np.random.default_rng(seed)
+    fast = all(t < q for q in side.ctx.coeff_modulus_at(ci))
+    plains = []
+    for cc in (1, 5, n - 1, n):
+        w = rng.integers(1, t, cc, dtype=np.uint64)
+        w[-1] = t - 1 - cc            # upper half, and the last word the plaintext holds
+        w[0] = (t + 1) // 2 - (cc & 1)   # the threshold itself / the value below it
+        plains.append(w)
+    mono = np.zeros(5, dtype=np.uint64)
+    mono[4] = t - 2
+    plains.append(mono)
+    todo = [c for c in combos(scheme) if not c[2]] + [("multiply", False, False)]
+    for op, ct_ntt, _ in dict.fromkeys(todo):
+        for w in plains:
+            x = side.rand_ct(rng, ci, batch, size)
+            want = []
+            for b in range(batch):
+                r = ref.ct(ci, x[:, b], ct_ntt, side.scale, side.cf)
+                getattr(ref, REF_OP[op])(r, ref.pt(w))
+                want.append((r.data(), r.info()))
+            pt = S.Plaintext.from_numpy(side.ctx, w)
+            assert pt.coeff_count() == w.size
+            c = side.dev_ct(x, ci, ct_ntt)
+            src = side.dev_ct(x, ci, ct_ntt)
+            dest = S.Ciphertext(side.ctx, batch=batch)
+            getattr(side.ev, "%s_plain_inplace" % op)(c, pt)
+            side.ev._pl(C_ABI[op], src, pt, dest, pool=op == "multiply")
+            assert np.array_equal(src.to_numpy(), x), ("encrypted changed", scheme, op, ct_ntt, w.size)
+            for what, got_ct in (("in place", c), ("out of place", dest)):
+                got = got_ct.to_numpy()
+                assert got.shape == x.shape, (what, got.shape)
+                for b in range(batch):
+                    words, i = want[b]
+                    assert np.array_equal(got[:, b], words), (what, scheme, op, ct_ntt, "coeff_count", w.size, "item", b, "fast" if fast else "general")
+                    assert (got_ct.is_ntt_form(), got_ct.scale(), got_ct.correction_factor()) == \
+                        (i["is_ntt_form"], i["scale"], i["correction_factor"]), (what, "metadata")
     return fast
 
 

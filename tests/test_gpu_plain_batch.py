@@ -54,6 +54,16 @@ def test_branches_general_lift(gpu, scheme):
     assert not PB.case_branches(scheme, 8192, [30, 30, 30, 60], tbits=40)
 
 
+@needs_ref
+@pytest.mark.parametrize("scheme", ["bfv", "bgv"])
+@pytest.mark.parametrize("bits,tbits,fast", [([40, 40, 60], 20, True), ([30, 30, 60], 40, False)])
+def test_shared_plaintext(gpu, scheme, bits, tbits, fast):
+    """one Plaintext of 1, 5, N - 1 and N coefficients for a batch of 3 at N = 64, two primes, against the reference item by item;
+    t below every prime (fast plain lift) and above them (general lift)"""
+    import plain_batch_cases as PB
+    assert PB.case_shared_plaintext(scheme, 64, bits, tbits) == fast
+
+
 @pytest.mark.parametrize("scheme", ["bfv", "bgv"])
 def test_transform(gpu, scheme):
     import plain_batch_cases as PB
