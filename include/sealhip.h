@@ -436,6 +436,30 @@ SHL_FUNC Evaluator_TransformPlainToNTTDevice(void *thisptr, const uint64_t *devi
 SHL_FUNC Evaluator_SumItems(void *thisptr, void *encrypted, uint64_t group, void *destination);
 SHL_FUNC Evaluator_DotPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, uint64_t group, double scale,
                                   void *destination);
+/* The ciphertext x ciphertext reduction over the ITEMS of two device-resident batches (library extension): sum_b x_b (x) y_b - an
+ * encrypted inner product, an encrypted matrix times an encrypted vector with one ciphertext per row or column, a squared distance
+ * sum_b (x_b)^2.  The sum is formed BEFORE relinearising (relinearisation is linear): one Evaluator_Relinearize on the result serves a
+ * whole group.  No product is stored: each operand word crosses HBM once and the result is written once.
+ * encrypted1, encrypted2: batches of B items, CKKS or BGV, both of size 2, in NTT form, at the same level; they may be the same
+ * handle (the sum of squares; the operand is then read once).  group = g >= 1 must divide B.  destination: ANOTHER handle whose batch
+ * is B / g, made with Ciphertext_CreateBatch, different from both operands; it is resized to size 3 at the operands' level.
+ * Output item o equals, word for word, Evaluator_Multiply on batches of one holding the items o g .. o g + g - 1 followed by
+ * Evaluator_AddMany over the products, hence the reference's multiply (evaluator.cpp ckks_multiply / bgv_multiply) and then add_many.
+ * g = 1 gives exactly Evaluator_Multiply's words.  is_ntt_form is true; CKKS: scale = scale1 * scale2 with the reference's
+ * scale-bound check; BGV: correction factor = cf1 * cf2 mod t (the items of a batch share it, so the sum is the equal-factor case);
+ * parms_id is the operands'.
+ * BFV is refused (SHL_E_INVALIDARG, "unsupported scheme"): its product rounds per item (BEHZ), sum_b round(.) is not round(sum_b .),
+ * so a fused form could not give the reference's words.  Sizes other than 2 x 2 are refused with SHL_E_INVALIDARG: the sum is taken
+ * before relinearising, on fresh or relinearised operands, and those have size 2.
+ * SHL_E_POINTER: NULL handles.  SHL_E_INVALIDARG: an invalid ciphertext; mismatched levels or batches; a ciphertext in coefficient
+ * form; g == 0 or g does not divide B; the destination's batch != B / g; destination == an operand; a scale out of bounds.  A failed
+ * check leaves the destination untouched.  With Evaluator_SetTransparentCheck on, the result batch is checked.
+ * Operands with a deferred key-switch tail or a deferred product pending are settled before they are read; the result is stored at
+ * once (never a deferred product).  Enqueued on the evaluator's stream without a host round trip; records under
+ * Evaluator_BeginCapture.  Products are accumulated as plain 128-bit integers and reduced once per 128 items (the middle polynomial
+ * adds two products per item, and 256 products of words below 2^60 fit 128 bits).  A small result is computed in slices by the rule
+ * of Evaluator_SumItems, with pool scratch of slices x 3 x one result plane. */
+SHL_FUNC Evaluator_DotItems(void *thisptr, void *encrypted1, void *encrypted2, uint64_t group, void *destination);
 SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *pool);
 SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *pool);
@@ -535,6 +559,13 @@ SHL_FUNC shl_reduce_items(void *context, uint64_t chain_index, const uint64_t *a
                           uint64_t batch, uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream);
 /* terms the lazy accumulators of those kernels take between two reductions (sums: 16; products: 256) */
 SHL_FUNC shl_reduce_flush_intervals(uint64_t *sum_terms, uint64_t *dot_terms);
+/* The kernels of Evaluator_DotItems on raw words at one level: x, y = [2][batch][K][N], r = [3][batch / group][K][N], r distinct
+ * from the operands; y == x selects the square kernel (x is read once).  slices, scratch (slices * 3 * (batch / group) * K * N
+ * words), slices_used and r == NULL: as shl_reduce_items.  Nothing is validated beyond the shape. */
+SHL_FUNC shl_dot_items(void *context, uint64_t chain_index, const uint64_t *x, const uint64_t *y, uint64_t *r, uint64_t batch,
+                       uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream);
+/* items the lazy accumulators of that kernel take between two reductions (128: the middle polynomial adds two products per item) */
+SHL_FUNC shl_dot_items_flush_interval(uint64_t *items);
 /* GaloisTool::apply_galois (ntt_form == 0, util/galois.cpp:148) / apply_galois_ntt (!= 0, galois.cpp:192) */
 SHL_FUNC shl_apply_galois(void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys, void *stream);
 /* RNSTool stages (util/rns.cpp) on one level, `polys` polynomials each [comps][N]:

@@ -83,6 +83,7 @@ Evaluator_AddMany Evaluator_AddPlain Evaluator_SubPlain Evaluator_MultiplyMany E
 Evaluator_TransformToNTT1 Evaluator_ModSwitchToNext2 Evaluator_ModSwitchTo2
 Evaluator_AddPlainDevice Evaluator_SubPlainDevice Evaluator_MultiplyPlainDevice Evaluator_TransformPlainToNTTDevice
 Evaluator_SumItems Evaluator_DotPlainDevice shl_reduce_items shl_reduce_flush_intervals
+Evaluator_DotItems shl_dot_items shl_dot_items_flush_interval
 KSwitchKeys_Create1 KSwitchKeys_Destroy KSwitchKeys_Size KSwitchKeys_SetKey KSwitchKeys_SetKeyFromDevice
 KSwitchKeys_SetKeyDigits KSwitchKeys_HasKey KSwitchKeys_DeviceBytes RelinKeys_GetIndex GaloisKeys_GetIndex GaloisTool_GetEltFromStep
 Evaluator_Create Evaluator_Destroy Evaluator_SetStream Evaluator_Synchronize Evaluator_CopyTo Evaluator_SetTransparentCheck

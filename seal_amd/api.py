@@ -1451,6 +1451,14 @@ class Evaluator:
         N.check(N.lib().Evaluator_DotPlainDevice(self._h, a._h, C.c_void_p(ptr), C.c_uint64(batch), C.c_uint64(group), C.c_double(scale), d._h))
         return d
 
+    def dot_items(self, a, b, group=None, destination=None):
+        """item o of the result = the sum over the items i of group o of the tensor product a_i (x) b_i, size 3, not relinearised
+        (sealhip.h: Evaluator_DotItems).  a, b: batches of size-2 ciphertexts in NTT form at one level (CKKS, BGV); `b is a` is the sum
+        of squares.  group, destination: as sum_items; the destination is distinct from both operands.  -> the destination"""
+        group, d = self._reduce_dest(a, group, destination)
+        N.check(N.lib().Evaluator_DotItems(self._h, a._h, b._h, C.c_uint64(group), d._h))
+        return d
+
     def mod_switch_plain_to_next_inplace(self, plain):
         N.check(N.lib().Evaluator_ModSwitchToNext2(self._h, plain._h, plain._h))
         return plain

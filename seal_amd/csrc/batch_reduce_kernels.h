@@ -1,6 +1,6 @@
-// Kernels of the Evaluator's reductions over the items of a batch (evaluator.h: sum_items / dot_plain_device): output item o is the
-// sum of the `group` input items o * group .. o * group + group - 1, or of their dyadic products with one NTT-form plaintext per
-// item.  HBM-streaming like plain_batch_kernels.h and with its conventions: one thread moves two adjacent words per operand with one
+// Kernels of the Evaluator's reductions over the items of a batch (evaluator.h: sum_items / dot_plain_device / dot_items): output
+// item o is the sum of the `group` input items o * group .. o * group + group - 1, of their dyadic products with one NTT-form
+// plaintext per item, or of the size-2 x size-2 tensor products of the items of two batches.  HBM-streaming like plain_batch_kernels.h and with its conventions: one thread moves two adjacent words per operand with one
 // 16-byte access, flat grids (one thread per output pair, no loop over the grid), one ModDesc per prime, and the non-temporal hint
 // on every ciphertext and plaintext word - each is read once.
 // Layouts: a ciphertext plane is [batch][K][N], so the items of a group are `group` consecutive [K][N] blocks of each plane; the
@@ -20,8 +20,9 @@ namespace sealhip
     // terms a lazy accumulator takes between two reductions (derived in batch_reduce_kernels.hip from "primes are below 2^60")
     unsigned batch_reduce_sum_flush();
     unsigned batch_reduce_dot_flush();
+    unsigned batch_reduce_dot_items_flush(); // items, not products: the middle polynomial of a ciphertext product takes two per item
     // The library's rule: slices for a launch of `threads` threads (one per output pair: sum_items size * out_items * K * N / 2,
-    // dot_plain_device out_items * K * N / 2) that each add `group` terms.  1 = one launch, no scratch.
+    // dot_plain_device and dot_items out_items * K * N / 2) that each add `group` terms.  1 = one launch, no scratch.
     unsigned batch_reduce_slices(size_t threads, size_t group);
     // words of scratch a call with `slices` > 1 needs
     inline size_t batch_reduce_scratch_words(unsigned slices, unsigned size, size_t out_items, unsigned n_log, unsigned K)
@@ -38,4 +39,13 @@ namespace sealhip
     hipError_t k_dot_plain_items(const ModDesc *mods, const uint64_t *a, size_t a_stride, const uint64_t *pl, uint64_t *r, size_t r_stride,
                                  unsigned size, unsigned n_log, unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch,
                                  hipStream_t s);
+    // Ciphertext x ciphertext, both of size 2 and in NTT form: x, y = [2][batch][K][N] (planes x_stride / y_stride words apart),
+    // r = [3][batch / group][K][N]:
+    //   r[0][o] = sum_i x0 y0,  r[1][o] = sum_i (x0 y1 + x1 y0),  r[2][o] = sum_i x1 y1   over the items o * group + i, mod q_k
+    // - the words of multiply (evaluator.cpp ckks_multiply / bgv_multiply, 2 x 2) per item and then add_many.  Each operand word
+    // crosses HBM once: 4 plane-items read per item, no product is stored.  y == x (same pointer and stride) is the sum of squares
+    // and reads 2.  slices, scratch: as above with size 3.
+    hipError_t k_dot_items(const ModDesc *mods, const uint64_t *x, size_t x_stride, const uint64_t *y, size_t y_stride, uint64_t *r,
+                           size_t r_stride, unsigned n_log, unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch,
+                           hipStream_t s);
 } // namespace sealhip

@@ -25,6 +25,10 @@ namespace sealhip
         static_assert(kDotFlush == 256 && (unsigned __int128)((uint64_t(1) << kPrimeBits) - 1) * ((uint64_t(1) << kPrimeBits) - 1) <=
                                               ~(unsigned __int128)0 / kDotFlush,
                       "kDotFlush products of words below 2^60 must fit 128 bits");
+        // the ciphertext x ciphertext product's middle polynomial takes TWO products per item (x0 y1 + x1 y0), so a run of it is half
+        // as many items; the outer two sums are flushed at the same interval
+        constexpr unsigned kDotItemsFlush = kDotFlush / 2;
+        static_assert(kDotItemsFlush == 128 && 2 * kDotItemsFlush <= kDotFlush, "two products per item: kDotFlush of them in kDotItemsFlush items");
 
         // ---- the cut of a small result (tuning values; tools/batch_reduce_rate.py sweeps them, DESIGN.md has the table)
         constexpr size_t kSliceBelowThreads = size_t(1) << 17; // launches of fewer threads than this are cut
@@ -167,6 +171,96 @@ namespace sealhip
             }
         }
 
+        // ---- ciphertext x ciphertext: r[.][o] = sum_i x[.][o g + i] (x) y[.][o g + i], the size-2 x size-2 tensor product
+        struct DotItemsGeom
+        {
+            size_t x_plane, y_plane;     // words between the two planes of each operand
+            size_t dst_plane, dst_slice; // as SumGeom
+            size_t pairs;                // out_items * K * N / 2
+            size_t words;                // K * N: one item of one plane
+            unsigned group, per_slice;   // slice s adds the items [s * per_slice, min(group, (s + 1) * per_slice)) of every group
+            unsigned n_log, K;
+        };
+        __device__ __forceinline__ void add128(U128 &acc, uint64_t lo, uint64_t hi)
+        {
+            acc.lo += lo;
+            acc.hi += hi + (acc.lo < lo);
+        }
+
+        // c0 += x0 y0, c1 += x0 y1 + x1 y0, c2 += x1 y1 per item, as plain 128-bit integers for kDotItemsFlush items at a time.
+        // SQUARE: y is x - two loads per item, and the middle sum takes the one product x0 x1 twice (the same integer as x0 y1 + x1 y0)
+        template <bool SQUARE, bool FINAL>
+        __global__ void __launch_bounds__(kBlock) dot_items_kernel(const ModDesc *mods, const uint64_t *x, const uint64_t *y, uint64_t *dst,
+                                                                   DotItemsGeom g)
+        {
+            const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
+            if (w >= g.pairs)
+                return;
+            const size_t i = 2 * w, j = i & ((size_t(1) << g.n_log) - 1);
+            const unsigned row = (unsigned)(i >> g.n_log); // o * K + k
+            const unsigned k = row % g.K, o = row / g.K;
+            const ModDesc md = mods[k];
+            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.group - t0 < g.per_slice ? g.group : t0 + g.per_slice;
+            const size_t inner = ((size_t)k << g.n_log) + j;
+            const size_t first = ((size_t)o * g.group + t0) * g.words + inner; // item o * group + t0, component k, coefficient j
+            const uint64_t *xp = x + first, *yp = y + first;
+            uint64_t tot[3][2];
+            for (unsigned p = 0; p < 3; p++)
+                tot[p][0] = tot[p][1] = 0;
+            for (unsigned t = t0; t < t1;)
+            {
+                const unsigned end = t1 - t < kDotItemsFlush ? t1 : t + kDotItemsFlush;
+                U128 acc[3][2];
+                for (unsigned p = 0; p < 3; p++)
+                    acc[p][0] = acc[p][1] = U128{ 0, 0 };
+#pragma unroll 2
+                for (; t < end; t++, xp += g.words, yp += g.words)
+                {
+                    uint64_t x0[2], x1[2];
+                    ld2<true>(xp, x0[0], x0[1]);
+                    ld2<true>(xp + g.x_plane, x1[0], x1[1]);
+                    if (SQUARE)
+                    {
+                        for (unsigned l = 0; l < 2; l++)
+                        {
+                            uint64_t lo, hi;
+                            mul_wide(x0[l], x1[l], lo, hi);
+                            mac128(acc[0][l], x0[l], x0[l]);
+                            add128(acc[1][l], lo, hi);
+                            add128(acc[1][l], lo, hi);
+                            mac128(acc[2][l], x1[l], x1[l]);
+                        }
+                    }
+                    else
+                    {
+                        uint64_t y0[2], y1[2];
+                        ld2<true>(yp, y0[0], y0[1]);
+                        ld2<true>(yp + g.y_plane, y1[0], y1[1]);
+                        for (unsigned l = 0; l < 2; l++)
+                        {
+                            mac128(acc[0][l], x0[l], y0[l]);
+                            mac128(acc[1][l], x0[l], y1[l]);
+                            mac128(acc[1][l], x1[l], y0[l]);
+                            mac128(acc[2][l], x1[l], y1[l]);
+                        }
+                    }
+                }
+                for (unsigned p = 0; p < 3; p++)
+                {
+                    tot[p][0] = add_mod(tot[p][0], barrett128(acc[p][0].lo, acc[p][0].hi, md), md.q);
+                    tot[p][1] = add_mod(tot[p][1], barrett128(acc[p][1].lo, acc[p][1].hi, md), md.q);
+                }
+            }
+            uint64_t *d = dst + blockIdx.y * g.dst_slice + (((size_t)o * g.K) << g.n_log) + inner;
+            for (unsigned p = 0; p < 3; p++)
+            {
+                if (FINAL)
+                    st2_nt(d + p * g.dst_plane, tot[p][0], tot[p][1]);
+                else
+                    st2(d + p * g.dst_plane, tot[p][0], tot[p][1]);
+            }
+        }
+
         // one thread per pair, rows numbered in 32 bits: false when the launch would not fit
         inline bool flat_grid(size_t pairs, unsigned n_log, unsigned &blocks)
         {
@@ -215,6 +309,19 @@ namespace sealhip
                 hipLaunchKernelGGL((dot_plain_items_kernel<SIZE, false>), dim3(blocks, slices), dim3(kBlock), 0, s, mods, a, pl, dst, g);
             return hipGetLastError();
         }
+        template <bool SQUARE>
+        hipError_t launch_dot_items(const ModDesc *mods, const uint64_t *x, const uint64_t *y, uint64_t *dst, const DotItemsGeom &g,
+                                    unsigned slices, bool final, hipStream_t s)
+        {
+            unsigned blocks;
+            if (!flat_grid(g.pairs, g.n_log, blocks))
+                return hipErrorInvalidValue;
+            if (final)
+                hipLaunchKernelGGL((dot_items_kernel<SQUARE, true>), dim3(blocks, slices), dim3(kBlock), 0, s, mods, x, y, dst, g);
+            else
+                hipLaunchKernelGGL((dot_items_kernel<SQUARE, false>), dim3(blocks, slices), dim3(kBlock), 0, s, mods, x, y, dst, g);
+            return hipGetLastError();
+        }
     } // namespace
 
     unsigned batch_reduce_sum_flush()
@@ -224,6 +331,10 @@ namespace sealhip
     unsigned batch_reduce_dot_flush()
     {
         return kDotFlush;
+    }
+    unsigned batch_reduce_dot_items_flush()
+    {
+        return kDotItemsFlush;
     }
     unsigned batch_reduce_slices(size_t threads, size_t group)
     {
@@ -284,5 +395,26 @@ namespace sealhip
         if (final)
             return hipSuccess;
         return combine_slices(mods, scratch, r, r_stride, size, n_log, K, out_items, slices, s);
+    }
+
+    hipError_t k_dot_items(const ModDesc *mods, const uint64_t *x, size_t x_stride, const uint64_t *y, size_t y_stride, uint64_t *r,
+                           size_t r_stride, unsigned n_log, unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch,
+                           hipStream_t s)
+    {
+        const size_t words = (size_t)K << n_log, out_plane = out_items * words;
+        if (!out_plane || !group)
+            return hipSuccess;
+        unsigned per_slice;
+        if (!cut(group, slices, per_slice) || out_items > 0xffffffffu || (slices > 1 && !scratch))
+            return hipErrorInvalidValue;
+        const bool final = slices == 1, square = x == y && x_stride == y_stride;
+        uint64_t *dst = final ? r : scratch;
+        const DotItemsGeom g{ x_stride, y_stride, final ? r_stride : out_plane, final ? 0 : 3 * out_plane, out_plane / 2, words, (unsigned)group,
+                              per_slice, n_log, K };
+        hipError_t e = square ? launch_dot_items<true>(mods, x, y, dst, g, slices, final, s)
+                              : launch_dot_items<false>(mods, x, y, dst, g, slices, final, s);
+        if (e != hipSuccess || final)
+            return e;
+        return combine_slices(mods, scratch, r, r_stride, 3, n_log, K, out_items, slices, s);
     }
 } // namespace sealhip

@@ -274,6 +274,18 @@ extern "C"
                                                  *as<Ciphertext>(destination));
         SHL_CATCH
     }
+    SHL_FUNC Evaluator_DotItems(void *thisptr, void *encrypted1, void *encrypted2, uint64_t group, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted1, SHL_E_POINTER);
+        IfNullRet(encrypted2, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->dot_items(*as<Ciphertext>(encrypted1), *as<Ciphertext>(encrypted2), (size_t)group,
+                                          *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
     static Plaintext &prepare_plain_dest(void *plain, void *destination)
     {
         Plaintext *src = as<Plaintext>(plain), *dst = as<Plaintext>(destination);

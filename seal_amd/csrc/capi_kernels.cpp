@@ -96,6 +96,42 @@ extern "C"
         *dot_terms = batch_reduce_dot_flush();
         return SHL_S_OK;
     }
+    SHL_FUNC shl_dot_items(void *context, uint64_t chain_index, const uint64_t *x, const uint64_t *y, uint64_t *r, uint64_t batch,
+                           uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        SHL_TRY
+        auto c = as<Context>(context);
+        auto l = c->level_by_chain_index(chain_index);
+        if (!l)
+            throw std::out_of_range("chain_index");
+        if (!group || batch % group)
+            throw std::invalid_argument("group must divide batch");
+        const size_t out_items = batch / group, words = (size_t)l->K * c->n();
+        const unsigned n_log = (unsigned)c->log_n();
+        if (!slices)
+            slices = batch_reduce_slices(out_items * words / 2, group);
+        if (slices > group || slices > 64)
+            throw std::invalid_argument("1 <= slices <= min(group, 64)");
+        if (slices_used)
+            *slices_used = slices;
+        if (!r) // a query: the slices the library would use, hence the scratch to pass
+            return SHL_S_OK;
+        IfNullRet(x, SHL_E_POINTER);
+        IfNullRet(y, SHL_E_POINTER);
+        if (slices > 1 && !scratch)
+            throw std::invalid_argument("scratch is null");
+        hip_ok(k_dot_items(c->dev_mods(), x, batch * words, y, batch * words, r, out_items * words, n_log, l->K, out_items, group,
+                           (unsigned)slices, scratch, (hipStream_t)stream),
+               "dot (items)");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_dot_items_flush_interval(uint64_t *items)
+    {
+        IfNullRet(items, SHL_E_POINTER);
+        *items = batch_reduce_dot_items_flush();
+        return SHL_S_OK;
+    }
     SHL_FUNC shl_apply_galois(
         void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys,
         void *stream)

@@ -1074,6 +1074,57 @@ namespace sealhip
         reduce_items(e, plain, group, new_scale, dest);
     }
 
+    // sum over the items of a group of the 2 x 2 tensor products (include/sealhip.h: Evaluator_DotItems): the checks and metadata of
+    // multiply (ckks_multiply / bgv_multiply at 2 x 2) and of sum_items, one kernel and no stored product
+    void Evaluator::dot_items(const Ciphertext &e1, const Ciphertext &e2, size_t group, Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_valid(e1, "encrypted1");
+        check_valid(e2, "encrypted2");
+        const Scheme scheme = context_.scheme();
+        // BFV's product rounds per item (BEHZ): the sum of the rounded products is not the rounded sum
+        if (scheme != Scheme::ckks && scheme != Scheme::bgv)
+            throw std::invalid_argument("unsupported scheme");
+        if (e1.level() != e2.level())
+            throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
+        if (e1.batch() != e2.batch())
+            throw std::invalid_argument("batch mismatch");
+        if (!(e1.is_ntt_form() && e2.is_ntt_form()))
+            throw std::invalid_argument("encrypted1 or encrypted2 must be in NTT form");
+        if (e1.size() != 2 || e2.size() != 2)
+            throw std::invalid_argument("encrypted1 and encrypted2 must have size 2");
+        check_reduce_items(e1, group, dest);
+        if (&dest == &e2)
+            throw std::invalid_argument("destination must be different from encrypted");
+        const Level &lvl = *e1.level();
+        const bool ckks = scheme == Scheme::ckks;
+        const double new_scale = ckks ? e1.scale() * e2.scale() : e1.scale();
+        if (ckks && !scale_within_bounds(new_scale, lvl))
+            throw std::invalid_argument("scale out of bounds");
+        const uint64_t cf = ckks ? 1 : host::mulmod(e1.correction_factor(), e2.correction_factor(), context_.plain_modulus());
+        // operands first: whatever is pending on them (a key-switch tail, a product of their own) is settled before their words are read
+        const uint64_t *xw = e1.data(), *yw = &e1 == &e2 ? xw : e2.data();
+        const size_t out_items = e1.batch() / group;
+        const unsigned n_log = (unsigned)context_.log_n(), K = lvl.K;
+        if (dest.ctx_ != e1.ctx_)
+        {
+            dest.release();
+            dest.ctx_ = e1.ctx_;
+        }
+        dest.reshape_uninitialized(&lvl, 3);
+        dest.is_ntt_form() = true;
+        dest.scale() = new_scale;
+        dest.correction_factor() = cf;
+        const unsigned slices = batch_reduce_slices(dest.plane_words() / 2, group);
+        std::unique_ptr<Scratch> scratch;
+        if (slices > 1)
+            scratch.reset(new Scratch(batch_reduce_scratch_words(slices, 3, out_items, n_log, K)));
+        ck(k_dot_items(context_.dev_mods(), xw, e1.plane_words(), yw, e2.plane_words(), dest.data_, dest.plane_words(), n_log, K, out_items,
+                       group, slices, scratch ? scratch->p : nullptr, stream_),
+           "dot (items)");
+        throw_if_transparent(dest);
+    }
+
     void Evaluator::add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)

@@ -346,6 +346,11 @@ namespace sealhip
         void sum_items(const Ciphertext &encrypted, size_t group, Ciphertext &destination) const;
         void dot_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, size_t group, double scale,
                               Ciphertext &destination) const;
+        // The ciphertext x ciphertext reduction (include/sealhip.h: Evaluator_DotItems): item o of destination becomes the sum over the
+        // items o * group .. o * group + group - 1 of the 2 x 2 tensor products encrypted1_b (x) encrypted2_b - word for word multiply
+        // on batches of one and add_many over the products, without storing a product.  CKKS and BGV, both operands of size 2 and in
+        // NTT form; encrypted1 and encrypted2 may be the same object; destination is another object (size 3 afterwards).
+        void dot_items(const Ciphertext &encrypted1, const Ciphertext &encrypted2, size_t group, Ciphertext &destination) const;
         void add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const;
         void multiply_many(const std::vector<const Ciphertext *> &encrypteds, const KSwitchKeys &relin_keys, Ciphertext &destination) const;
         void exponentiate_inplace(Ciphertext &encrypted, uint64_t exponent, const KSwitchKeys &relin_keys) const;
