@@ -1,16 +1,17 @@
 // Kernels of the Evaluator's reductions over the items of a batch (evaluator.h: sum_items / dot_plain_device / dot_items): output
 // item o is the sum of the `group` input items o * group .. o * group + group - 1, of their dyadic products with one NTT-form
-// plaintext per item, or of the size-2 x size-2 tensor products of the items of two batches.  HBM-streaming like plain_batch_kernels.h and with its conventions: one thread moves two adjacent words per operand with one
+// plaintext per item, or of the size-2 x size-2 tensor products of the items of two batches.
+// HBM-streaming like plain_batch_kernels.h and with its conventions: one thread moves two adjacent words per operand with one
 // 16-byte access, flat grids (one thread per output pair, no loop over the grid), one ModDesc per prime, and the non-temporal hint
 // on every ciphertext and plaintext word - each is read once.
 // Layouts: a ciphertext plane is [batch][K][N], so the items of a group are `group` consecutive [K][N] blocks of each plane; the
 // plaintexts are [batch][K][N]; the result's planes are [batch / group][K][N].  The result must not be an operand.
 // Accumulation is lazy (batch_reduce_kernels.hip: kSumFlush, kDotFlush): terms are added as plain integers and reduced once per
 // flush interval.  Every result is the canonical residue of an exactly specified integer, so it does not depend on the schedule:
-// the words are those of add_many (evaluator.cpp:242-261) over multiply_plain (evaluator.cpp:2157-2194).
+// the words are those of the reference's Evaluator::add_many over Evaluator::multiply_plain_inplace.
 // Small results: one thread per output pair is too few threads when the result is small (N = 8192, K = 3, one output item: 24 k),
 // so below a threshold the group is cut into `slices` runs of consecutive items, each reduced by workgroups of its own (the slow grid
-// dimension) into scratch [slices][size][batch / group][K][N], and a second launch of the sum kernel adds the slices.  No atomics:
+// dimension) into scratch [slices][size][batch / group][K][N], and a second launch, of the sum over the slices, adds them.  No atomics:
 // modular addition is exact and associative, the words do not depend on the cut.
 #pragma once
 #include "encrypt_kernels.h"

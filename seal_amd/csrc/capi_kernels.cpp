@@ -2,6 +2,41 @@
 #include "capi_common.h"
 #include "batch_reduce_kernels.h"
 
+namespace
+{
+    // The prologue of the raw seams of the batch reductions (shl_reduce_items, shl_dot_items): level, group and cut are checked -
+    // slices == 0 asks for the library's rule over grid_planes * (one result plane) / 2 threads -, *slices_used is set, a call
+    // without a result is the query and ends there; otherwise launch(context, level, out_items, words per item, slices) runs
+    template <class Launch>
+    SHL_HRESULT raw_reduce(void *context, uint64_t chain_index, bool size_ok, const char *shape, uint64_t grid_planes, uint64_t batch,
+                           uint64_t group, uint64_t slices, uint64_t *slices_used, const uint64_t *r, bool operands, const uint64_t *scratch,
+                           Launch launch)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        SHL_TRY
+        auto c = as<Context>(context);
+        auto l = c->level_by_chain_index(chain_index);
+        if (!l)
+            throw std::out_of_range("chain_index");
+        if (!group || batch % group || !size_ok)
+            throw std::invalid_argument(shape);
+        const size_t out_items = batch / group, words = (size_t)l->K * c->n();
+        if (!slices)
+            slices = batch_reduce_slices(grid_planes * out_items * words / 2, group);
+        if (slices > group || slices > 64)
+            throw std::invalid_argument("1 <= slices <= min(group, 64)");
+        if (slices_used)
+            *slices_used = slices;
+        if (!r) // a query: the slices the library would use, hence the scratch to pass
+            return SHL_S_OK;
+        IfNullRet(operands, SHL_E_POINTER);
+        if (slices > 1 && !scratch)
+            throw std::invalid_argument("scratch is null");
+        launch(c, l, out_items, words, (unsigned)slices);
+        SHL_CATCH
+    }
+} // namespace
+
 extern "C"
 {
     // ------------------------------------------------------------------ per-kernel seam
@@ -57,36 +92,18 @@ extern "C"
     SHL_FUNC shl_reduce_items(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *plain, uint64_t *r, uint64_t size,
                               uint64_t batch, uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream)
     {
-        IfNullRet(context, SHL_E_POINTER);
-        SHL_TRY
-        auto c = as<Context>(context);
-        auto l = c->level_by_chain_index(chain_index);
-        if (!l)
-            throw std::out_of_range("chain_index");
-        if (!group || batch % group || !size || size > 16)
-            throw std::invalid_argument("group must divide batch; 1 <= size <= 16");
-        const size_t out_items = batch / group, words = (size_t)l->K * c->n();
-        const unsigned n_log = (unsigned)c->log_n();
-        if (!slices)
-            slices = batch_reduce_slices((plain ? 1 : size) * out_items * words / 2, group);
-        if (slices > group || slices > 64)
-            throw std::invalid_argument("1 <= slices <= min(group, 64)");
-        if (slices_used)
-            *slices_used = slices;
-        if (!r) // a query: the slices the library would use, hence the scratch to pass
-            return SHL_S_OK;
-        IfNullRet(a, SHL_E_POINTER);
-        if (slices > 1 && !scratch)
-            throw std::invalid_argument("scratch is null");
-        if (plain)
-            hip_ok(k_dot_plain_items(c->dev_mods(), a, batch * words, plain, r, out_items * words, (unsigned)size, n_log, l->K, out_items, group,
-                                     (unsigned)slices, scratch, (hipStream_t)stream),
-                   "dot_plain (items)");
-        else
-            hip_ok(k_sum_items(c->dev_mods(), a, batch * words, r, out_items * words, (unsigned)size, n_log, l->K, out_items, group,
-                               (unsigned)slices, scratch, (hipStream_t)stream),
-                   "sum (items)");
-        SHL_CATCH
+        return raw_reduce(context, chain_index, size && size <= 16, "group must divide batch; 1 <= size <= 16", plain ? 1 : size, batch, group,
+                          slices, slices_used, r, a, scratch, [&](Context *c, const Level *l, size_t out_items, size_t words, unsigned cut) {
+                              const unsigned n_log = (unsigned)c->log_n();
+                              if (plain)
+                                  hip_ok(k_dot_plain_items(c->dev_mods(), a, batch * words, plain, r, out_items * words, (unsigned)size, n_log, l->K,
+                                                           out_items, group, cut, scratch, (hipStream_t)stream),
+                                         "dot_plain (items)");
+                              else
+                                  hip_ok(k_sum_items(c->dev_mods(), a, batch * words, r, out_items * words, (unsigned)size, n_log, l->K, out_items,
+                                                     group, cut, scratch, (hipStream_t)stream),
+                                         "sum (items)");
+                          });
     }
     SHL_FUNC shl_reduce_flush_intervals(uint64_t *sum_terms, uint64_t *dot_terms)
     {
@@ -99,32 +116,12 @@ extern "C"
     SHL_FUNC shl_dot_items(void *context, uint64_t chain_index, const uint64_t *x, const uint64_t *y, uint64_t *r, uint64_t batch,
                            uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream)
     {
-        IfNullRet(context, SHL_E_POINTER);
-        SHL_TRY
-        auto c = as<Context>(context);
-        auto l = c->level_by_chain_index(chain_index);
-        if (!l)
-            throw std::out_of_range("chain_index");
-        if (!group || batch % group)
-            throw std::invalid_argument("group must divide batch");
-        const size_t out_items = batch / group, words = (size_t)l->K * c->n();
-        const unsigned n_log = (unsigned)c->log_n();
-        if (!slices)
-            slices = batch_reduce_slices(out_items * words / 2, group);
-        if (slices > group || slices > 64)
-            throw std::invalid_argument("1 <= slices <= min(group, 64)");
-        if (slices_used)
-            *slices_used = slices;
-        if (!r) // a query: the slices the library would use, hence the scratch to pass
-            return SHL_S_OK;
-        IfNullRet(x, SHL_E_POINTER);
-        IfNullRet(y, SHL_E_POINTER);
-        if (slices > 1 && !scratch)
-            throw std::invalid_argument("scratch is null");
-        hip_ok(k_dot_items(c->dev_mods(), x, batch * words, y, batch * words, r, out_items * words, n_log, l->K, out_items, group,
-                           (unsigned)slices, scratch, (hipStream_t)stream),
-               "dot (items)");
-        SHL_CATCH
+        return raw_reduce(context, chain_index, true, "group must divide batch", 1, batch, group, slices, slices_used, r, x && y, scratch,
+                          [&](Context *c, const Level *l, size_t out_items, size_t words, unsigned cut) {
+                              hip_ok(k_dot_items(c->dev_mods(), x, batch * words, y, batch * words, r, out_items * words, (unsigned)c->log_n(), l->K,
+                                                 out_items, group, cut, scratch, (hipStream_t)stream),
+                                     "dot (items)");
+                          });
     }
     SHL_FUNC shl_dot_items_flush_interval(uint64_t *items)
     {

@@ -1018,36 +1018,29 @@ namespace sealhip
         if (dest.batch() != e.batch() / group)
             throw std::invalid_argument("destination's batch does not equal the ciphertext's batch divided by group");
     }
-    void Evaluator::reduce_items(const Ciphertext &e, const uint64_t *plain, size_t group, double new_scale, Ciphertext &dest) const
+    // The one host path of the reductions, after their checks and with the operands settled: dest becomes `size` planes of
+    // e.batch() / group items at e's level with the given metadata, the cut is the library's rule for grid_planes * (one result plane)
+    // / 2 threads, and launch(out_items, slices, scratch) starts the kernels
+    template <class Launch>
+    void Evaluator::reduce_items(const Ciphertext &e, size_t group, size_t size, size_t grid_planes, bool ntt_form, double scale,
+                                 uint64_t correction_factor, Ciphertext &dest, const char *what, Launch launch) const
     {
-        e.settle(); // the operand's words are read by what follows
         const Level &lvl = *e.level();
-        const size_t size = e.size(), out_items = e.batch() / group;
-        const unsigned n_log = (unsigned)context_.log_n(), K = lvl.K;
+        const size_t out_items = e.batch() / group;
         if (dest.ctx_ != e.ctx_)
         {
             dest.release();
             dest.ctx_ = e.ctx_;
         }
         dest.reshape_uninitialized(&lvl, size);
-        dest.is_ntt_form() = e.is_ntt_form();
-        dest.scale() = new_scale;
-        dest.correction_factor() = e.correction_factor();
-        // one thread per output pair: the sum has the planes in its grid, the product loops over them
-        const size_t threads = (plain ? 1 : size) * dest.plane_words() / 2;
-        const unsigned slices = batch_reduce_slices(threads, group);
+        dest.is_ntt_form() = ntt_form;
+        dest.scale() = scale;
+        dest.correction_factor() = correction_factor;
+        const unsigned slices = batch_reduce_slices(grid_planes * dest.plane_words() / 2, group);
         std::unique_ptr<Scratch> scratch;
         if (slices > 1)
-            scratch.reset(new Scratch(batch_reduce_scratch_words(slices, (unsigned)size, out_items, n_log, K)));
-        uint64_t *sp = scratch ? scratch->p : nullptr;
-        if (plain)
-            ck(k_dot_plain_items(context_.dev_mods(), e.data_, e.plane_words(), plain, dest.data_, dest.plane_words(), (unsigned)size, n_log, K,
-                                 out_items, group, slices, sp, stream_),
-               "dot_plain (items)");
-        else
-            ck(k_sum_items(context_.dev_mods(), e.data_, e.plane_words(), dest.data_, dest.plane_words(), (unsigned)size, n_log, K, out_items,
-                           group, slices, sp, stream_),
-               "sum (items)");
+            scratch.reset(new Scratch(batch_reduce_scratch_words(slices, (unsigned)size, out_items, (unsigned)context_.log_n(), lvl.K)));
+        ck(launch(out_items, slices, scratch ? scratch->p : nullptr), what);
         throw_if_transparent(dest);
     }
     void Evaluator::sum_items(const Ciphertext &e, size_t group, Ciphertext &dest) const
@@ -1055,7 +1048,13 @@ namespace sealhip
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         check_valid(e, "encrypted");
         check_reduce_items(e, group, dest);
-        reduce_items(e, nullptr, group, e.scale(), dest);
+        e.settle(); // the operand's words are read by what follows
+        // one thread per output pair, the planes in the grid
+        reduce_items(e, group, e.size(), e.size(), e.is_ntt_form(), e.scale(), e.correction_factor(), dest, "sum (items)",
+                     [&](size_t out_items, unsigned slices, uint64_t *scratch) {
+                         return k_sum_items(context_.dev_mods(), e.data_, e.plane_words(), dest.data_, dest.plane_words(), (unsigned)e.size(),
+                                            (unsigned)context_.log_n(), e.level()->K, out_items, group, slices, scratch, stream_);
+                     });
     }
     void Evaluator::dot_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, size_t group, double scale,
                                      Ciphertext &dest) const
@@ -1071,7 +1070,14 @@ namespace sealhip
         const double new_scale = ckks ? e.scale() * scale : e.scale(); // as multiply_plain_device
         if (ckks && !scale_within_bounds(new_scale, *e.level()))
             throw std::invalid_argument("scale out of bounds");
-        reduce_items(e, plain, group, new_scale, dest);
+        e.settle(); // the operand's words are read by what follows
+        // one thread per output pair of one plane: the product loops over the planes
+        reduce_items(e, group, e.size(), 1, e.is_ntt_form(), new_scale, e.correction_factor(), dest, "dot_plain (items)",
+                     [&](size_t out_items, unsigned slices, uint64_t *scratch) {
+                         return k_dot_plain_items(context_.dev_mods(), e.data_, e.plane_words(), plain, dest.data_, dest.plane_words(),
+                                                  (unsigned)e.size(), (unsigned)context_.log_n(), e.level()->K, out_items, group, slices, scratch,
+                                                  stream_);
+                     });
     }
 
     // sum over the items of a group of the 2 x 2 tensor products (include/sealhip.h: Evaluator_DotItems): the checks and metadata of
@@ -1104,25 +1110,10 @@ namespace sealhip
         const uint64_t cf = ckks ? 1 : host::mulmod(e1.correction_factor(), e2.correction_factor(), context_.plain_modulus());
         // operands first: whatever is pending on them (a key-switch tail, a product of their own) is settled before their words are read
         const uint64_t *xw = e1.data(), *yw = &e1 == &e2 ? xw : e2.data();
-        const size_t out_items = e1.batch() / group;
-        const unsigned n_log = (unsigned)context_.log_n(), K = lvl.K;
-        if (dest.ctx_ != e1.ctx_)
-        {
-            dest.release();
-            dest.ctx_ = e1.ctx_;
-        }
-        dest.reshape_uninitialized(&lvl, 3);
-        dest.is_ntt_form() = true;
-        dest.scale() = new_scale;
-        dest.correction_factor() = cf;
-        const unsigned slices = batch_reduce_slices(dest.plane_words() / 2, group);
-        std::unique_ptr<Scratch> scratch;
-        if (slices > 1)
-            scratch.reset(new Scratch(batch_reduce_scratch_words(slices, 3, out_items, n_log, K)));
-        ck(k_dot_items(context_.dev_mods(), xw, e1.plane_words(), yw, e2.plane_words(), dest.data_, dest.plane_words(), n_log, K, out_items,
-                       group, slices, scratch ? scratch->p : nullptr, stream_),
-           "dot (items)");
-        throw_if_transparent(dest);
+        reduce_items(e1, group, 3, 1, true, new_scale, cf, dest, "dot (items)", [&](size_t out_items, unsigned slices, uint64_t *scratch) {
+            return k_dot_items(context_.dev_mods(), xw, e1.plane_words(), yw, e2.plane_words(), dest.data_, dest.plane_words(),
+                               (unsigned)context_.log_n(), lvl.K, out_items, group, slices, scratch, stream_);
+        });
     }
 
     void Evaluator::add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const

@@ -458,8 +458,10 @@ namespace sealhip
                                 const Ciphertext &destination) const;
         uint64_t *begin_result(const Ciphertext &encrypted, Ciphertext &destination) const; // destination shaped like encrypted, words undefined
         void check_reduce_items(const Ciphertext &encrypted, size_t group, const Ciphertext &destination) const;
-        // destination (batch / group items) <- the sums; plain null: of the items, else of their products with the plaintexts
-        void reduce_items(const Ciphertext &encrypted, const uint64_t *plain, size_t group, double new_scale, Ciphertext &destination) const;
+        // destination <- `size` planes of batch / group items with this metadata, filled by launch(out_items, slices, scratch)
+        template <class Launch>
+        void reduce_items(const Ciphertext &encrypted, size_t group, size_t size, size_t grid_planes, bool ntt_form, double scale,
+                          uint64_t correction_factor, Ciphertext &destination, const char *what, Launch launch) const;
         void bgv_correct_and_combine(
             Scratch &delta, const uint64_t *a, size_t a_stride, const ShoupOp *mul, unsigned ncomp, size_t items, uint64_t *out0,
             uint64_t *out1, size_t out_stride, int epi) const;

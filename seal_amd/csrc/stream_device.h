@@ -23,6 +23,17 @@ namespace sealhip
             b = p[1];
 #endif
         }
+        __device__ __forceinline__ void st2(uint64_t *p, uint64_t a, uint64_t b)
+        {
+#if defined(__HIP_DEVICE_COMPILE__)
+            typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+            const u64x2 v = { a, b };
+            *reinterpret_cast<u64x2 *>(p) = v;
+#else
+            p[0] = a;
+            p[1] = b;
+#endif
+        }
         __device__ __forceinline__ void st2_nt(uint64_t *p, uint64_t a, uint64_t b)
         {
 #if defined(__HIP_DEVICE_COMPILE__)

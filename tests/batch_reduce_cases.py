@@ -208,6 +208,36 @@ def case_sliced(scheme, n, bits, batch, group, slice_counts, size=3, seed=67):
         check(side, (scheme, "sliced", plain is not None), out, x, plain, ci, True, group)
 
 
+def case_plane_counts(n, bits, sizes=(1, 4, 5), batch=6, group=3, patterns=("max", "random"), seed=79):
+    """plane counts the Evaluator's cases do not reach, through the raw seam: one plane (the product's single-plane kernel), four and
+    five (the product takes its planes three at a time, then one or two; the sum has all of them in its grid), in one launch and in
+    two slices - which do not divide the group of three, so the second slice is short.  Every word equals the sum formed with
+    Python integers"""
+    side = Side("ckks", n, bits)
+    rng = np.random.default_rng(seed)
+    ci, out_items = side.first, batch // group
+    q = [int(v) for v in side.q(ci)]
+    K = len(q)
+    for size in sizes:
+        for pattern in patterns:
+            xc = _columns(side, ci, pattern, rng, (size, batch))    # [size][batch][K][2]
+            pc = _columns(side, ci, pattern, rng, (batch,))
+            x = np.ascontiguousarray(np.tile(xc, n // 2))
+            pl = np.ascontiguousarray(np.tile(pc, n // 2))
+            assert np.array_equal(x[..., -2:], xc) and x.shape == (size, batch, K, n)
+            xo, po = xc.astype(object), pc.astype(object)
+            want_sum = np.zeros((size, out_items, K, 2), dtype=np.uint64)
+            want_dot = np.zeros((size, out_items, K, 2), dtype=np.uint64)
+            for o in range(out_items):
+                sl = slice(o * group, (o + 1) * group)
+                for k in range(K):
+                    want_sum[:, o, k] = (xo[:, sl, k].sum(axis=1) % q[k]).astype(np.uint64)
+                    want_dot[:, o, k] = ((xo[:, sl, k] * po[None, sl, k]).sum(axis=1) % q[k]).astype(np.uint64)
+            for slices in (1, 2):
+                assert np.array_equal(raw_reduce(side, ci, x, None, group, slices), np.tile(want_sum, n // 2)), ("sum", size, pattern, slices)
+                assert np.array_equal(raw_reduce(side, ci, x, pl, group, slices), np.tile(want_dot, n // 2)), ("dot", size, pattern, slices)
+
+
 def case_natural_slices(scheme, n, bits, group, size=2, seed=71):
     """no forcing: by the documented rule a batch of one group is cut (asserted from the rule, not assumed), several groups of the
     same size are not (fewer items per launch than the rule asks for would be: checked too); the first group's words agree"""

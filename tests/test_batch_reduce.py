@@ -56,6 +56,13 @@ def test_sliced(emu, scheme):
     BR.case_sliced(scheme, 1024, [60, 40, 60], batch=46, group=23, slice_counts=(2, 3, 4, 5, 23))
 
 
+@pytest.mark.parametrize("n,bits", SIZES[:2])
+def test_plane_counts(emu, n, bits):
+    """sizes 1, 4 and 5, in one launch and in two slices of a group of three"""
+    import batch_reduce_cases as BR
+    BR.case_plane_counts(n, bits)
+
+
 def test_natural_slices(emu):
     """N = 1024, K = 2: 1024 output pairs per item, so one group of 16 is cut and 128 of them are not"""
     import batch_reduce_cases as BR

@@ -66,6 +66,13 @@ def test_sliced(gpu, scheme):
     BR.case_sliced(scheme, *MID, batch=46, group=23, slice_counts=(2, 3, 4, 5, 23), size=2)
 
 
+@pytest.mark.parametrize("n,bits", [(8, [30, 30, 30]), (1024, [60, 40, 60])])
+def test_plane_counts(gpu, n, bits):
+    """sizes 1, 4 and 5, in one launch and in two slices of a group of three"""
+    import batch_reduce_cases as BR
+    BR.case_plane_counts(n, bits)
+
+
 def test_natural_slices(gpu):
     """N = 8192, K = 3: 12288 output pairs per item, so one group of 16 is cut and 11 of them are not (asserted inside)"""
     import batch_reduce_cases as BR

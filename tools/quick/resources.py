@@ -13,7 +13,7 @@ dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, t
 KEYS = ["VGPRs", "AGPRs", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]", r"LDS Size \[bytes/block\]"]
 print("vgpr agpr scratch occ     lds  kernel")
 for b, d in zip(blocks, dem):
-    d = re.sub(r"^void sealhip::\(anonymous namespace\)::", "", d)
+    d = re.sub(r"^void ", "", d.replace("sealhip::(anonymous namespace)::", ""))
     d = re.sub(r"\(.*$", "", d)
     if flt and flt not in d:
         continue
