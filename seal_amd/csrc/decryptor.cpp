@@ -420,7 +420,13 @@ namespace sealhip
         ck(hipMemcpy(values, out.p, n * 8, hipMemcpyDeviceToHost), "download values");
     }
 
-    // ---------------------------------------------------------------- Encryptor (secret-key encryption)
+    // ---------------------------------------------------------------- Encryptor
+    // the switch that sends every draw of u, e (and of the KeyGenerator's s) to the host samplers, which otherwise only a ternary
+    // redraw (one item in 2^16 at N = 2^16) and the rings too small for whole 64-byte pieces reach: tests run that branch with it
+    bool encrypt_host_sampling()
+    {
+        return std::getenv("SEALHIP_ENCRYPT_HOST_SAMPLING") != nullptr;
+    }
     Encryptor::Encryptor(const Context &context, const PublicKey *public_key, const SecretKey *secret_key)
         : context_(context), evaluator_(context)
     {
@@ -440,97 +446,13 @@ namespace sealhip
             ck(hipMemcpy(pk_, public_key->data(), 2 * words * 8, hipMemcpyDeviceToDevice), "copy public key");
         }
     }
-    void Encryptor::bootstrap_seed(uint64_t *seed8) const
-    {
-        if (seeded_)
-            std::memcpy(seed8, seed_, 64);
-        else
-            host::random_bytes(seed8, 64);
-    }
-
-    // util::encrypt_zero_asymmetric (util/rlwe.cpp:196-268) at `lvl`
-    void Encryptor::zero_asymmetric_at(const Level &lvl, Ciphertext &d, bool host_sampling)
-    {
-        const size_t n = context_.n(), K = lvl.K, L = context_.key_level().K, words = K * n;
-        const unsigned n_log = (unsigned)context_.log_n();
-        const Scheme scheme = context_.scheme();
-        const bool ntt_form = scheme != Scheme::bfv;
-        // u <- R_3, then e_0, e_1 <- chi, all from one PRNG, in this order: bytes [0, 4n), [4n, 10n), [10n, 16n) of its stream, which
-        // the device produces itself (xof_kernels.h) - unless a ternary draw has to be redrawn (probability n / 2^32), which shifts
-        // everything after it: then the sampling is repeated here on the host, as it is for rings too small for whole 64-byte pieces
-        uint64_t boot[8];
-        bootstrap_seed(boot);
-        if (n < 4 || std::getenv("SEALHIP_ENCRYPT_HOST_SAMPLING")) // (the switch: tests run the host branch, otherwise one call in 2^16)
-            host_sampling = true;
-
-        ck(hipStreamSynchronize(nullptr), "encrypt sync");
-        d.resize(&lvl, 2, nullptr);
-        d.is_ntt_form() = ntt_form;
-        d.scale() = 1.0;
-        d.correction_factor() = 1;
-        const NttTables &tb = context_.ntt_tables();
-        const ModDesc *mods = context_.dev_mods();
-        const size_t small_words = (3 * n + 7) / 8;
-        Scratch du(words), de(2 * words), ds(small_words + 1), stream(host_sampling ? 1 : 2 * n);
-        int8_t *dsmall = reinterpret_cast<int8_t *>(ds.p);
-        unsigned *redraw = reinterpret_cast<unsigned *>(ds.p + small_words);
-        if (host_sampling)
-        {
-            // (N signed bytes each; the device replicates them into the RNS components)
-            serial::Prng prng(1, boot);
-            std::vector<int8_t> small(3 * n);
-            serial::sample_small_ternary(prng, n, small.data());
-            serial::sample_small_cbd(prng, n, small.data() + n);
-            serial::sample_small_cbd(prng, n, small.data() + 2 * n);
-            ck(hipMemcpy(ds.p, small.data(), 3 * n, hipMemcpyHostToDevice), "upload u, e");
-        }
-        else
-        {
-            XofSeed seed;
-            std::memcpy(seed.w, boot, sizeof(seed.w));
-            ck(hipMemsetAsync(redraw, 0, 8, nullptr), "clear flag");
-            ck(k_blake2xb_stream(seed, 0, 16 * n / 64, stream.p, nullptr), "bootstrap stream");
-            ck(k_small_from_stream(reinterpret_cast<const uint8_t *>(stream.p), n, 4 * n, 2 * n, dsmall, redraw, nullptr), "sample u, e");
-        }
-        ck(k_expand_small(mods, dsmall, du.p, n_log, (unsigned)K, 1, nullptr), "expand u");
-        ck(k_expand_small(mods, dsmall + n, de.p, n_log, (unsigned)K, 2, nullptr), "expand e");
-        ck(ntt_forward(tb, polys(du.p, K, n, 1), 0, nullptr), "ntt u");
-        for (size_t j = 0; j < 2; j++)
-            ck(k_dyadic(mods, du.p, pk_ + j * L * n, d.plane(j), n_log, (unsigned)K, 0, 1, nullptr), "pk u");
-        if (ntt_form)
-            ck(ntt_forward(tb, polys(de.p, K, n, 2), 0, nullptr), "ntt noise");
-        else
-            ck(ntt_inverse(tb, polys(d.data(), K, n, 2), 0, nullptr), "intt pk u");
-        ck(k_neg_add_noise(mods, d.data(), de.p, scheme == Scheme::bgv ? context_.plain_modulus() : 1, 2 * words, n_log, (unsigned)K, nullptr,
-                           false),
-           "c + e");
-        unsigned flag = 0;
-        if (!host_sampling)
-            ck(hipMemcpy(&flag, redraw, sizeof(flag), hipMemcpyDeviceToHost), "read flag");
-        ck(hipStreamSynchronize(nullptr), "encrypt sync");
-        if (flag)
-            zero_asymmetric_at(lvl, d, true);
-    }
-    // Encryptor::encrypt_zero_internal, asymmetric branch (encryptor.cpp:139-186): encrypt one level up, switch down
+    // Encryptor::encrypt_zero_internal, asymmetric branch (encryptor.cpp:139-186), one ciphertext
     void Encryptor::zero_asymmetric(const Level &lvl, Ciphertext &d)
     {
         if (!pk_)
             throw std::logic_error("public key is not set");
-        if (&d.context() != &context_)
-            throw std::invalid_argument("destination belongs to another context");
-        if (d.batch() != 1)
-            throw std::invalid_argument("Encryptor encrypts one ciphertext at a time: destination must be a batch of one");
-        const Level *prev = context_.level_by_chain_index(lvl.chain_index + 1);
-        if (!prev)
-        {
-            zero_asymmetric_at(lvl, d);
-            return;
-        }
-        zero_asymmetric_at(*prev, d);
-        evaluator_.mod_switch_scale_to_next(d);
-        evaluator_.synchronize();
-        d.scale() = 1.0;             // destination.scale() = temp.scale(), .correction_factor() = temp.correction_factor()
-        d.correction_factor() = 1;
+        one_destination(d);
+        asymmetric(lvl, 1, batch_seeds(1, nullptr).data(), d);
     }
     void Encryptor::encrypt_zero(const uint64_t *parms_id, Ciphertext &destination)
     {
@@ -591,100 +513,23 @@ namespace sealhip
         return &context_.first_level();
     }
 
-    // util::encrypt_zero_symmetric (util/rlwe.cpp:270-395)
-    void Encryptor::zero(const Level &lvl, bool save_seed, Ciphertext &d, uint64_t *public_seed, bool host_sampling, bool key_form)
+    void Encryptor::one_destination(const Ciphertext &d) const
     {
-        if (!sk_)
-            throw std::logic_error("secret key is not set");
         if (&d.context() != &context_)
             throw std::invalid_argument("destination belongs to another context");
         if (d.batch() != 1)
             throw std::invalid_argument("Encryptor encrypts one ciphertext at a time: destination must be a batch of one");
-        const size_t n = context_.n(), K = lvl.K, words = K * n;
-        const unsigned n_log = (unsigned)context_.log_n();
-        const Scheme scheme = context_.scheme();
-        const bool ntt_form = key_form || scheme != Scheme::bfv;
+    }
+    // util::encrypt_zero_symmetric (util/rlwe.cpp:270-395), one ciphertext
+    void Encryptor::zero(const Level &lvl, bool save_seed, Ciphertext &d, uint64_t *public_seed, bool key_form)
+    {
+        if (!sk_)
+            throw std::logic_error("secret key is not set");
+        one_destination(d);
         // a polynomial too small to hold the seed is saved in full (rlwe.cpp:298-306): 16 + 1 + 64 bytes -> 11 words, plus a marker
-        if (save_seed && words < 12)
+        if (save_seed && lvl.K * context_.n() < 12)
             save_seed = false;
-
-        // host: the reference's randomness, in the reference's order
-        uint64_t boot_seed[8];
-        bootstrap_seed(boot_seed);
-        serial::Prng bootstrap(1, boot_seed);
-        uint64_t pub[8];
-        bootstrap.generate(sizeof(pub), reinterpret_cast<uint8_t *>(pub));
-        serial::Prng cprng(1, pub);
-        // a = sample_poly_uniform(cprng): on the device when the stream is whole PRNG buffers (xof.h), else here
-        const bool device_a = xof_device_ok(1, K, n);
-        std::vector<uint64_t> a(device_a ? 0 : words);
-        // the noise: bytes [64, 64 + 6n) of the bootstrap stream, sampled on the device when they are whole 64-byte pieces
-        const bool device_e = !host_sampling && (6 * n) % 64 == 0 && !std::getenv("SEALHIP_ENCRYPT_HOST_SAMPLING");
-        std::vector<int8_t> noise(device_e ? 0 : n);
-        if (!device_a)
-            serial::sample_poly_uniform(cprng, context_.coeff_modulus().data(), K, n, a.data());
-        if (!device_e)
-            serial::sample_small_cbd(bootstrap, n, noise.data());
-        if (public_seed)
-            std::memcpy(public_seed, pub, sizeof(pub));
-
-        // device: c1 = a, c0 = -(a s + e) (BGV: e -> t e)
-        ck(hipStreamSynchronize(nullptr), "encrypt sync");
-        d.resize(&lvl, 2, nullptr);
-        d.is_ntt_form() = ntt_form;
-        d.scale() = 1.0;
-        d.correction_factor() = 1;
-        uint64_t *c0 = d.plane(0), *c1 = d.plane(1);
-        const NttTables &tb = context_.ntt_tables();
-        const ModDesc *mods = context_.dev_mods();
-        Scratch e(words), ds((n + 7) / 8 + 1), stream(device_e ? 6 * n / 8 : 1);
-        if (device_a)
-        {
-            XofJob job;
-            std::memcpy(job.seed, pub, sizeof(job.seed));
-            job.dst = c1;
-            sample_uniform_device(context_, K, { job });
-        }
-        else
-            ck(hipMemcpy(c1, a.data(), words * 8, hipMemcpyHostToDevice), "upload a");
-        if (device_e)
-        {
-            XofSeed seed;
-            std::memcpy(seed.w, boot_seed, sizeof(seed.w));
-            ck(k_blake2xb_stream(seed, 1, 6 * n / 64, stream.p, nullptr), "bootstrap stream");
-            ck(k_small_from_stream(reinterpret_cast<const uint8_t *>(stream.p), 0, 0, n, reinterpret_cast<int8_t *>(ds.p),
-                                   reinterpret_cast<unsigned *>(ds.p + (n + 7) / 8), nullptr),
-               "sample noise");
-        }
-        else
-            ck(hipMemcpy(ds.p, noise.data(), n, hipMemcpyHostToDevice), "upload noise");
-        ck(k_expand_small(mods, reinterpret_cast<const int8_t *>(ds.p), e.p, n_log, (unsigned)K, 1, nullptr), "expand noise");
-        if (ntt_form)
-        {
-            ck(k_dyadic(mods, sk_, c1, c0, n_log, (unsigned)K, 0, 1, nullptr), "a s");
-            ck(ntt_forward(tb, polys(e.p, K, n, 1), 0, nullptr), "ntt noise");
-            ck(k_neg_add_noise(mods, c0, e.p, scheme == Scheme::bgv ? context_.plain_modulus() : 1, words, n_log, (unsigned)K, nullptr), "c0");
-        }
-        else if (save_seed)
-        {
-            // a was sampled in coefficient form (it is what the seed re-expands to): transform a copy for the product
-            Scratch an(words);
-            ck(hipMemcpyAsync(an.p, c1, words * 8, hipMemcpyDeviceToDevice, nullptr), "copy a");
-            ck(ntt_forward(tb, polys(an.p, K, n, 1), 0, nullptr), "ntt a");
-            ck(k_dyadic(mods, sk_, an.p, c0, n_log, (unsigned)K, 0, 1, nullptr), "a s");
-            ck(ntt_inverse(tb, polys(c0, K, n, 1), 0, nullptr), "intt a s");
-            ck(k_neg_add_noise(mods, c0, e.p, 1, words, n_log, (unsigned)K, nullptr), "c0");
-            ck(hipStreamSynchronize(nullptr), "encrypt sync");
-        }
-        else
-        {
-            // a was sampled in NTT form; the ciphertext is returned in coefficient form
-            ck(k_dyadic(mods, sk_, c1, c0, n_log, (unsigned)K, 0, 1, nullptr), "a s");
-            ck(ntt_inverse(tb, polys(c0, K, n, 1), 0, nullptr), "intt a s");
-            ck(k_neg_add_noise(mods, c0, e.p, 1, words, n_log, (unsigned)K, nullptr), "c0");
-            ck(ntt_inverse(tb, polys(c1, K, n, 1), 0, nullptr), "intt a");
-        }
-        ck(hipStreamSynchronize(nullptr), "encrypt sync"); // e goes back to the pool
+        symmetric(lvl, nullptr, 1, batch_seeds(1, nullptr).data(), d, SymmetricForm{ key_form, save_seed, public_seed });
     }
 
     void Encryptor::add_plain(const Plaintext &plain, Ciphertext &d)
@@ -745,7 +590,7 @@ namespace sealhip
         return save(ct, pub, out, capacity);
     }
 
-    // ---------------------------------------------------------------- Encryptor, whole batches in device memory
+    // ---------------------------------------------------------------- Encryptor: the two bodies, over `batch` items in device memory
     namespace
     {
         constexpr size_t kEncryptBatchScratchBytes = size_t(256) << 20; // per chunk (include/sealhip.h)
@@ -801,7 +646,6 @@ namespace sealhip
         return boots;
     }
 
-    // util::encrypt_zero_symmetric (util/rlwe.cpp:270-395) + the plaintext addition of Encryptor::encrypt_internal, `batch` times
     void Encryptor::encrypt_symmetric_device(const uint64_t *plain, size_t batch, const uint64_t *parms_id, double scale, const uint64_t *seeds,
                                              Ciphertext &d)
     {
@@ -811,20 +655,31 @@ namespace sealhip
         if (!sk_)
             throw std::logic_error("secret key is not set");
         batch_checks(plain, batch, lvl, d);
+        symmetric(lvl, plain, batch, batch_seeds(batch, seeds).data(), d, SymmetricForm{});
+        if (plain && context_.scheme() == Scheme::ckks)
+            d.scale() = scale;
+    }
+
+    // util::encrypt_zero_symmetric (util/rlwe.cpp:270-395) + the plaintext addition of Encryptor::encrypt_internal, `batch` times;
+    // item b draws from the PRNG seeded with boots[8 b ..]
+    void Encryptor::symmetric(const Level &lvl, const uint64_t *plain, size_t batch, const uint64_t *boots, Ciphertext &d,
+                              const SymmetricForm &form)
+    {
         const size_t n = context_.n(), K = lvl.K, words = K * n;
         const unsigned n_log = (unsigned)context_.log_n();
         const Scheme scheme = context_.scheme();
-        const bool ntt_form = scheme != Scheme::bfv;
-        const std::vector<uint64_t> boots = batch_seeds(batch, seeds);
-        // per item as the per-object form decides: a on the device when its stream is whole PRNG buffers, the noise (bytes
-        // [64, 64 + 6n) of the bootstrap stream) when it is whole 64-byte pieces
+        const bool ntt_form = form.key_form || scheme != Scheme::bfv;
+        // BFV with the seed saved: the seed must re-expand to c1, so a is sampled in coefficient form (rlwe.cpp:337-345)
+        const bool coeff_a = form.save_seed && !ntt_form;
+        // a on the device when its stream is whole PRNG buffers (xof.h), the noise (bytes [64, 64 + 6n) of the bootstrap stream)
+        // when it is whole 64-byte pieces; otherwise from the host samplers
         const bool device_a = xof_device_ok(1, K, n);
-        const bool device_e = (6 * n) % 64 == 0 && !std::getenv("SEALHIP_ENCRYPT_HOST_SAMPLING");
+        const bool device_e = (6 * n) % 64 == 0 && !encrypt_host_sampling();
 
         ck(hipStreamSynchronize(nullptr), "encrypt sync");
         d.resize(&lvl, 2, nullptr);
         d.is_ntt_form() = ntt_form;
-        d.scale() = scheme == Scheme::ckks && plain ? scale : 1.0;
+        d.scale() = 1.0;
         d.correction_factor() = 1;
         uint64_t *c0 = d.plane(0), *c1 = d.plane(1);
         const NttTables &tb = context_.ntt_tables();
@@ -833,7 +688,8 @@ namespace sealhip
         const bool lift = plain && scheme == Scheme::bgv;
         const size_t chunk = std::min(chunk_items(words), batch);
         const size_t small_stride = (n + 15) & ~size_t(15); // signed bytes per item
-        Scratch dseeds(chunk * 8), stream(device_e ? chunk * (6 * n / 8) : 1), small(chunk * small_stride / 8), lifted(lift ? chunk * words : 1);
+        Scratch dseeds(chunk * 8), stream(device_e ? chunk * (6 * n / 8) : 1), small(chunk * small_stride / 8), lifted(lift ? chunk * words : 1),
+            a_ntt(coeff_a ? chunk * words : 1);
         int8_t *dsmall = reinterpret_cast<int8_t *>(small.p);
         std::vector<int8_t> host_small(device_e ? 0 : chunk * small_stride);
         std::vector<uint64_t> host_a(device_a ? 0 : words);
@@ -846,9 +702,11 @@ namespace sealhip
             jobs.clear();
             for (unsigned i = 0; i < items; i++)
             {
-                serial::Prng bootstrap(1, boots.data() + (b0 + i) * 8);
+                serial::Prng bootstrap(1, boots + (b0 + i) * 8);
                 uint64_t pub[8];
                 bootstrap.generate(sizeof(pub), reinterpret_cast<uint8_t *>(pub));
+                if (form.public_seed)
+                    std::memcpy(form.public_seed + (b0 + i) * 8, pub, sizeof(pub));
                 if (device_a)
                 {
                     XofJob job;
@@ -869,7 +727,7 @@ namespace sealhip
                 sample_uniform_device(context_, K, jobs);
             if (device_e)
             {
-                ck(hipMemcpy(dseeds.p, boots.data() + b0 * 8, (size_t)items * 64, hipMemcpyHostToDevice), "upload seeds");
+                ck(hipMemcpy(dseeds.p, boots + b0 * 8, (size_t)items * 64, hipMemcpyHostToDevice), "upload seeds");
                 ck(k_blake2xb_stream_batch(dseeds.p, 1, 6 * n / 64, stream.p, items, nullptr), "bootstrap streams");
                 ck(k_small_from_stream_batch(reinterpret_cast<const uint8_t *>(stream.p), 6 * n, 0, 0, n, dsmall, small_stride, nullptr, items, nullptr),
                    "sample noise");
@@ -895,10 +753,17 @@ namespace sealhip
             }
             else
             {
-                // BFV: a was sampled in NTT form; the ciphertext is returned in coefficient form
-                ck(k_encrypt_sym_tail(mods, sk_, c1c, c0c, nullptr, 1, true, n_log, (unsigned)K, items, nullptr), "a s");
+                // BFV: the ciphertext is returned in coefficient form.  a was sampled in NTT form and is transformed back after the
+                // product - unless it is c1 as sampled (coeff_a): then a scratch copy is transformed for the product
+                if (coeff_a)
+                {
+                    ck(hipMemcpyAsync(a_ntt.p, c1c, (size_t)items * words * 8, hipMemcpyDeviceToDevice, nullptr), "copy a");
+                    ck(ntt_forward(tb, polys(a_ntt.p, K, n, items), 0, nullptr), "ntt a");
+                }
+                ck(k_encrypt_sym_tail(mods, sk_, coeff_a ? a_ntt.p : c1c, c0c, nullptr, 1, true, n_log, (unsigned)K, items, nullptr), "a s");
                 ck(ntt_inverse(tb, polys(c0c, K, n, items), 0, nullptr), "intt a s");
-                ck(ntt_inverse(tb, polys(c1c, K, n, items), 0, nullptr), "intt a");
+                if (!coeff_a)
+                    ck(ntt_inverse(tb, polys(c1c, K, n, items), 0, nullptr), "intt a");
                 ck(k_encrypt_bfv_finish(mods, bfv_plain_const(context_, lvl), dsmall, small_stride, plain ? plain + b0 * n : nullptr, c0c, 0, 1, true,
                                         n_log, (unsigned)K, items, nullptr),
                    "c0");
@@ -907,8 +772,6 @@ namespace sealhip
         ck(hipStreamSynchronize(nullptr), "encrypt sync"); // the scratch goes back to the pool
     }
 
-    // Encryptor::encrypt_zero_internal, asymmetric branch (encryptor.cpp:139-186; util::encrypt_zero_asymmetric, rlwe.cpp:196-268)
-    // + the plaintext addition, `batch` times
     void Encryptor::encrypt_device(const uint64_t *plain, size_t batch, const uint64_t *parms_id, double scale, const uint64_t *seeds, Ciphertext &d)
     {
         const Level &lvl = batch_level(plain != nullptr, parms_id, scale);
@@ -917,15 +780,30 @@ namespace sealhip
         if (!pk_)
             throw std::logic_error("public key is not set");
         batch_checks(plain, batch, lvl, d);
+        asymmetric(lvl, batch, batch_seeds(batch, seeds).data(), d);
+        if (plain)
+        {
+            // Evaluator::add_plain on fresh ciphertexts, with one plaintext per item
+            const bool ckks = context_.scheme() == Scheme::ckks;
+            if (ckks)
+                d.scale() = scale;
+            evaluator_.add_plain_device(d, plain, batch, ckks, scale, d);
+            evaluator_.synchronize();
+        }
+    }
+
+    // Encryptor::encrypt_zero_internal, asymmetric branch (encryptor.cpp:139-186; util::encrypt_zero_asymmetric, rlwe.cpp:196-268),
+    // `batch` times: encrypt one level up where there is one, then switch down
+    void Encryptor::asymmetric(const Level &lvl, size_t batch, const uint64_t *boots, Ciphertext &d)
+    {
         const Level *prev = context_.level_by_chain_index(lvl.chain_index + 1);
-        const Level &at = prev ? *prev : lvl; // encrypt one level up where there is one, then switch down
+        const Level &at = prev ? *prev : lvl;
         const size_t n = context_.n(), K = at.K, L = context_.key_level().K, words = K * n;
         const unsigned n_log = (unsigned)context_.log_n();
         const Scheme scheme = context_.scheme();
         const bool ntt_form = scheme != Scheme::bfv;
-        const std::vector<uint64_t> boots = batch_seeds(batch, seeds);
         // u, e_0, e_1 = bytes [0, 4n), [4n, 10n), [10n, 16n) of the item's stream: whole 64-byte pieces from n = 4 on
-        const bool device_s = n >= 4 && !std::getenv("SEALHIP_ENCRYPT_HOST_SAMPLING");
+        const bool device_s = n >= 4 && !encrypt_host_sampling();
 
         ck(hipStreamSynchronize(nullptr), "encrypt sync");
         d.resize(&at, 2, nullptr);
@@ -950,7 +828,7 @@ namespace sealhip
                 uint64_t *c = d.plane(0) + b0 * words;
                 if (device_s)
                 {
-                    ck(hipMemcpy(dseeds.p, boots.data() + b0 * 8, (size_t)items * 64, hipMemcpyHostToDevice), "upload seeds");
+                    ck(hipMemcpy(dseeds.p, boots + b0 * 8, (size_t)items * 64, hipMemcpyHostToDevice), "upload seeds");
                     ck(hipMemsetAsync(redraw, 0, (size_t)items * 4, nullptr), "clear flags");
                     ck(k_blake2xb_stream_batch(dseeds.p, 0, 16 * n / 64, stream.p, items, nullptr), "bootstrap streams");
                     ck(k_small_from_stream_batch(reinterpret_cast<const uint8_t *>(stream.p), 16 * n, n, 4 * n, 2 * n, dsmall, small_stride, redraw,
@@ -963,7 +841,7 @@ namespace sealhip
                 for (unsigned i = 0; i < items; i++)
                     if (!device_s || flags[i])
                     {
-                        serial::Prng prng(1, boots.data() + (b0 + i) * 8);
+                        serial::Prng prng(1, boots + (b0 + i) * 8);
                         serial::sample_small_ternary(prng, n, host_small.data());
                         serial::sample_small_cbd(prng, n, host_small.data() + n);
                         serial::sample_small_cbd(prng, n, host_small.data() + 2 * n);
@@ -998,16 +876,8 @@ namespace sealhip
         {
             evaluator_.mod_switch_scale_to_next(d); // batch-aware: every item in one pass
             evaluator_.synchronize();
-            d.scale() = 1.0;
+            d.scale() = 1.0; // destination.scale() = temp.scale(), .correction_factor() = temp.correction_factor()
             d.correction_factor() = 1;
-        }
-        if (plain)
-        {
-            // Evaluator::add_plain on fresh ciphertexts, with one plaintext per item
-            if (scheme == Scheme::ckks)
-                d.scale() = scale;
-            evaluator_.add_plain_device(d, plain, batch, scheme == Scheme::ckks, scale, d);
-            evaluator_.synchronize();
         }
     }
 } // namespace sealhip

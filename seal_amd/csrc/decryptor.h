@@ -106,14 +106,17 @@ namespace sealhip
         uint32_t *map_ = nullptr; // matrix_reps_index_map_, device
     };
 
-    // seal::Encryptor, the secret-key half (native/src/seal/encryptor.h: encrypt_symmetric / encrypt_zero_symmetric and their
-    // Serializable<> forms; encryptor.cpp:116-330, util/rlwe.cpp:270-395).  The randomness is the reference's: a bootstrap
-    // Blake2xb PRNG yields the public seed of c_1 = a (expanded by sample_poly_uniform) and the centred-binomial noise e
-    // (sample_poly_cbd); both are sampled on the device from the reference's byte streams (xof_kernels.h; the host keeps the
-    // same samplers, serial.h, for the cases the kernels leave out) and c_0 = -(a s + e) [+ the plaintext] is computed there too.
-    // Public-key encryption (encrypt / encrypt_zero; util::encrypt_zero_asymmetric, rlwe.cpp:196-268) follows the same pattern with
-    // u <- ternary (serial.h: sample_poly_ternary, tied to libstdc++'s uniform_int_distribution), c_j = pk_j u + e_j at the level
-    // above and one modulus switch down (encryptor.cpp:139-186).
+    // seal::Encryptor (native/src/seal/encryptor.h; encryptor.cpp:116-330, util/rlwe.cpp:196-395).  One path: a secret-key body
+    // (util::encrypt_zero_symmetric) and a public-key body (util::encrypt_zero_asymmetric at the level above, then one modulus switch
+    // down, encryptor.cpp:139-186) over `batch` items in device memory; the batch forms call them with the caller's batch and the
+    // per-object forms - and the KeyGenerator, whose keys are encryptions of zero - with a batch of one.  The randomness is the
+    // reference's: per item a bootstrap Blake2xb PRNG yields the public seed of c_1 = a (expanded by sample_poly_uniform) and the
+    // centred-binomial noise e (sample_poly_cbd), or u <- ternary, e_0, e_1 (serial.h: sample_poly_ternary, tied to libstdc++'s
+    // uniform_int_distribution).  They are sampled on the device from the reference's byte streams (xof_kernels.h), one launch per
+    // step over a chunk of items; what the kernels leave out - rings too small for whole PRNG buffers or whole 64-byte pieces, an
+    // item whose ternary draw the reference redraws - comes per item from the same samplers on the host (serial.h).
+    // c_0 = -(a s + e) [+ the plaintext], c_j = pk_j u + e_j are computed on the device too (encrypt_kernels.h).
+    bool encrypt_host_sampling(); // SEALHIP_ENCRYPT_HOST_SAMPLING (include/sealhip.h): every small polynomial from the host samplers
     class Encryptor
     {
     public:
@@ -145,8 +148,7 @@ namespace sealhip
         // `destination` (a batch of `batch`) is what encrypt_symmetric / encrypt [_zero when plain == null] gives under
         // set_seed(seeds + 8 b).  plain: [batch][K][N] NTT-form words at parms_id (CKKS) or [batch][N] coefficients modulo t
         // (BFV / BGV), device memory, not validated.  seeds: host [batch][8], or null: the installed seed for every item, or
-        // operating-system entropy per item.  One launch per step over a chunk of items (encrypt_kernels.h, xof_kernels.h);
-        // the fallbacks of the per-object forms (host sampling, rings too small for the device XOF) are taken per item.
+        // operating-system entropy per item.
         void encrypt_symmetric_device(const uint64_t *plain, size_t batch, const uint64_t *parms_id, double scale, const uint64_t *seeds,
                                       Ciphertext &destination);
         void encrypt_device(const uint64_t *plain, size_t batch, const uint64_t *parms_id, double scale, const uint64_t *seeds,
@@ -160,12 +162,21 @@ namespace sealhip
         friend class KeyGenerator; // keys are encryptions of zero under s (keygenerator.cpp:93-121, 322-357)
         const Level *level_for(const uint64_t *parms_id) const;
         const Level *level_for(const Plaintext &plain) const; // + the checks of Encryptor::encrypt_internal
-        // key_form: NTT form whatever the scheme - how KeyGenerator calls encrypt_zero_symmetric (is_ntt_form = true)
-        void zero(const Level &lvl, bool save_seed, Ciphertext &destination, uint64_t *public_seed, bool host_sampling = false,
-                  bool key_form = false);
+        struct SymmetricForm
+        {
+            bool key_form = false;           // NTT form whatever the scheme: how KeyGenerator calls encrypt_zero_symmetric
+            bool save_seed = false;          // c_1 is what the public seed expands to (BFV: a sampled in coefficient form)
+            uint64_t *public_seed = nullptr; // out, host [batch][8]: every item's public seed
+        };
+        // the two bodies: `batch` fresh ciphertexts at lvl into destination, item b from the bootstrap seed boots[8 b ..];
+        // plain as for encrypt_symmetric_device, or null
+        void symmetric(const Level &lvl, const uint64_t *plain, size_t batch, const uint64_t *boots, Ciphertext &destination,
+                       const SymmetricForm &form);
+        void asymmetric(const Level &lvl, size_t batch, const uint64_t *boots, Ciphertext &destination);
+        // the per-object forms: argument checks, then a body at batch one
+        void one_destination(const Ciphertext &destination) const;
+        void zero(const Level &lvl, bool save_seed, Ciphertext &destination, uint64_t *public_seed, bool key_form = false);
         void zero_asymmetric(const Level &lvl, Ciphertext &destination);
-        void zero_asymmetric_at(const Level &lvl, Ciphertext &destination, bool host_sampling = false); // util::encrypt_zero_asymmetric
-        void bootstrap_seed(uint64_t *seed8) const;
         uint64_t *pk_ = nullptr; // [2][L][N], NTT form
         void add_plain(const Plaintext &plain, Ciphertext &destination);
         size_t save(const Ciphertext &ct, const uint64_t *public_seed, uint8_t *out, size_t capacity) const;

@@ -1,11 +1,12 @@
-// Kernels of the Encryptor's batch forms (decryptor.h: encrypt_symmetric_device / encrypt_device): `items` independent fresh
-// ciphertexts per launch, every item with its own randomness and its own plaintext.  Element-wise and HBM-streaming: each thread
-// moves two adjacent words per operand with one 16-byte access; operands that are read once and results that are written once
-// carry the non-temporal hint, so that what the whole batch shares (s, the public key) stays in the L2.
+// Kernels of the Encryptor's two bodies (decryptor.h: symmetric / asymmetric): `items` independent fresh ciphertexts per launch,
+// every item with its own randomness and its own plaintext; the per-object forms and the KeyGenerator run them with items = 1.
+// Element-wise and HBM-streaming: each thread moves two adjacent words per operand with one 16-byte access; operands that are read
+// once and results that are written once carry the non-temporal hint, so that what the whole batch shares (s, the public key)
+// stays in the L2.  N >= 2 (the Context's constructor enforces it) and rows of N * 8 bytes in 16-byte aligned slabs: a pair never
+// straddles two rows and every access is aligned, down to N = 2 (one pair per row).
 // Layouts: a ciphertext plane chunk is [items][K][N]; keys are [L][N] at the key level (component r of a level = prime r);
 // the small polynomials are signed bytes, item b at small + b * small_stride.
-// Every result is the canonical residue of an exactly specified integer: the words equal those of the per-object chain
-// (k_dyadic, k_expand_small, k_neg_add_noise, Evaluator::add_plain) whatever the order of the additions.
+// Every result is the canonical residue of an exactly specified integer, whatever the order of the additions.
 #pragma once
 #include "plain_batch_kernels.h" // BfvPlainConst; the per-item lift of the BGV plaintexts (k_plain_lift_batch)
 

@@ -1,4 +1,5 @@
-// See encrypt_kernels.h.  One thread = two adjacent words of every operand (N is even, rows are 16-byte aligned).
+// See encrypt_kernels.h.  One thread = two adjacent words of every operand: N >= 2 is a power of two and rows are 16-byte aligned,
+// so a pair lies inside one row down to N = 2 (tests: the ring sizes 2 and 8 of test_encrypt_at_sampling_thresholds).
 #include "stream_device.h"
 
 namespace sealhip

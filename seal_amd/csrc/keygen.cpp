@@ -3,7 +3,6 @@
 #include "poly_kernels.h"
 #include "pool.h"
 #include "xof.h"
-#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 
@@ -70,11 +69,11 @@ namespace sealhip
             host::random_bytes(seed, sizeof(seed));
         uint64_t *s = sk_.allocate();
         const size_t small_words = (n + 7) / 8;
-        Scratch ds(small_words + 1), stream(n >= 16 ? n / 2 : 1);
+        Scratch ds(small_words + 1), stream(n >= 16 ? n / 2 : 1), dseed(8);
         int8_t *dsmall = reinterpret_cast<int8_t *>(ds.p);
         unsigned *redraw = reinterpret_cast<unsigned *>(ds.p + small_words);
         // the 4 n bytes of the ternary draws come off the device's BLAKE2Xb unless one of them has to be redrawn (see Encryptor)
-        bool host_sampling = n < 16 || std::getenv("SEALHIP_ENCRYPT_HOST_SAMPLING");
+        bool host_sampling = n < 16 || encrypt_host_sampling();
         for (;;)
         {
             if (host_sampling)
@@ -86,13 +85,12 @@ namespace sealhip
             }
             else
             {
-                XofSeed xs;
-                std::memcpy(xs.w, seed, sizeof(xs.w));
+                ck(hipMemcpy(dseed.p, seed, sizeof(seed), hipMemcpyHostToDevice), "upload seed");
                 ck(hipMemsetAsync(redraw, 0, 8, nullptr), "clear flag");
-                ck(k_blake2xb_stream(xs, 0, 4 * n / 64, stream.p, nullptr), "secret key stream");
-                ck(k_small_from_stream(reinterpret_cast<const uint8_t *>(stream.p), n, 0, 0, dsmall, redraw, nullptr), "sample s");
+                ck(k_blake2xb_stream_batch(dseed.p, 0, 4 * n / 64, stream.p, 1, nullptr), "secret key stream");
+                ck(k_small_from_stream_batch(reinterpret_cast<const uint8_t *>(stream.p), 0, n, 0, 0, dsmall, 0, redraw, 1, nullptr), "sample s");
             }
-            ck(k_expand_small(context_.dev_mods(), dsmall, s, n_log, (unsigned)L, 1, nullptr), "expand s");
+            ck(k_expand_small_batch(context_.dev_mods(), dsmall, 0, s, 0, n_log, (unsigned)L, 1, 1, nullptr), "expand s");
             unsigned flag = 0;
             if (!host_sampling)
                 ck(hipMemcpy(&flag, redraw, sizeof(flag), hipMemcpyDeviceToHost), "read flag");
@@ -101,7 +99,8 @@ namespace sealhip
             host_sampling = true;
         }
         ck(ntt_forward(context_.ntt_tables(), polys(s, L, n, 1), 0, nullptr), "ntt s");
-        // the draws s was made from go back to the pool cleared (the reference's seal_memzero of its secret-key copies)
+        // the seed and the draws s was made from go back to the pool cleared (the reference's seal_memzero of its secret-key copies)
+        ck(hipMemsetAsync(dseed.p, 0, sizeof(seed), nullptr), "clear seed");
         ck(hipMemsetAsync(ds.p, 0, (small_words + 1) * 8, nullptr), "clear s bytes");
         if (n >= 16)
             ck(hipMemsetAsync(stream.p, 0, n / 2 * 8, nullptr), "clear stream");
@@ -116,7 +115,7 @@ namespace sealhip
         const Level &kl = context_.key_level();
         const size_t words = kl.K * context_.n();
         Ciphertext ct(context_, 1);
-        encryptor_->zero(kl, false, ct, nullptr, false, true);
+        encryptor_->zero(kl, false, ct, nullptr, true);
         uint64_t *pk = destination.allocate();
         ck(hipMemcpy(pk, ct.plane(0), words * 8, hipMemcpyDeviceToDevice), "copy c0");
         ck(hipMemcpy(pk + words, ct.plane(1), words * 8, hipMemcpyDeviceToDevice), "copy c1");
@@ -142,7 +141,7 @@ namespace sealhip
         for (size_t j = 0; j < digits; j++)
         {
             // digit j = an encryption of zero under s with (special prime mod q_j) * new_key added into component j of c_0
-            encryptor_->zero(kl, false, ct, public_seeds ? public_seeds + 8 * j : nullptr, false, true);
+            encryptor_->zero(kl, false, ct, public_seeds ? public_seeds + 8 * j : nullptr, true);
             uint64_t *dj = out + j * 2 * words;
             ck(hipMemcpyAsync(dj, ct.plane(0), words * 8, hipMemcpyDeviceToDevice, nullptr), "copy c0");
             ck(hipMemcpyAsync(dj + words, ct.plane(1), words * 8, hipMemcpyDeviceToDevice, nullptr), "copy c1");

@@ -154,7 +154,7 @@ namespace sealhip
         }
         namespace
         {
-            // the small value replicated into every RNS component, negative values as q_j + v (what k_expand_small does on the device)
+            // the small value replicated into every RNS component, negative values as q_j + v (what k_expand_small_batch does on the device)
             void replicate(const int8_t *small, const uint64_t *primes, size_t K, size_t N, uint64_t *dst)
             {
                 for (size_t j = 0; j < K; j++)

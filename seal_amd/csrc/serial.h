@@ -143,7 +143,7 @@ namespace sealhip
         // what the reference build in this image uses (checked byte for byte in tests/decrypt_cases.py).
         void sample_poly_ternary(Prng &prng, const uint64_t *primes, size_t K, size_t N, uint64_t *dst);
         // the same two distributions as N signed bytes (ternary: -1, 0, 1; cbd: -21 .. 21) - what the Encryptor uploads; the device
-        // replicates them into the RNS components (decrypt_kernels.h: k_expand_small)
+        // replicates them into the RNS components (encrypt_kernels.h: k_expand_small_batch)
         void sample_small_ternary(Prng &prng, size_t N, int8_t *dst);
         void sample_small_cbd(Prng &prng, size_t N, int8_t *dst);
         // Serializable<Ciphertext>::save of a seeded ciphertext (ciphertext.cpp:171-196): members, DynArray with c_0 only, then

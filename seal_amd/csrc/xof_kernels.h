@@ -34,22 +34,14 @@ namespace sealhip
     // written from FIPS 202, the 25 lanes in registers).
     hipError_t k_shake256_uniform(const ModDesc *mods, const XofJob *jobs, unsigned njobs, unsigned *reject, unsigned n_log, unsigned K,
                                   hipStream_t s);
-    // the raw PRNG stream of `seed`: 64-byte pieces first_piece .. first_piece + pieces - 1 (piece p = bytes 64 p .. of the stream)
-    struct XofSeed
-    {
-        uint64_t w[8];
-    };
-    hipError_t k_blake2xb_stream(const XofSeed &seed, uint64_t first_piece, size_t pieces, uint64_t *out, hipStream_t s);
-    // sample_poly_ternary / sample_poly_cbd as signed bytes from a stream in HBM: small[0 .. n_ternary) from the 4-byte draws at
-    // stream + 4 k, small[n_ternary .. n_ternary + n_cbd) from the 6-byte draws at stream + cbd_offset + 6 k; *redraw is set when a
-    // ternary draw would have been redrawn by the reference (the caller then samples on the host)
-    hipError_t k_small_from_stream(const uint8_t *stream, size_t n_ternary, size_t cbd_offset, size_t n_cbd, int8_t *small, unsigned *redraw,
-                                   hipStream_t s);
-    // The two kernels above for `items` independent streams in one launch (Encryptor's batch forms, decryptor.h).  seeds: a DEVICE
-    // array [items][8]; out: [items][8 * pieces] words, item b = pieces first_piece .. of the stream of seeds[b].
+    // The raw PRNG streams of `items` seeds in one launch (Encryptor, decryptor.h; KeyGenerator's secret key with items = 1).
+    // seeds: a DEVICE array [items][8]; out: [items][8 * pieces] words, item b = the 64-byte pieces first_piece ..
+    // first_piece + pieces - 1 of the stream of seeds[b] (piece p = bytes 64 p .. of the stream).
     hipError_t k_blake2xb_stream_batch(const uint64_t *seeds, uint64_t first_piece, size_t pieces, uint64_t *out, unsigned items, hipStream_t s);
-    // streams: [items][stream_bytes]; small: [items][small_stride] signed bytes (n_ternary + n_cbd used); redraw: one flag per
-    // item (zeroed by the caller; may be null when n_ternary == 0), raised where item b alone has to be resampled on the host
+    // sample_poly_ternary / sample_poly_cbd as signed bytes from streams in HBM, [items][stream_bytes]: small[b][0 .. n_ternary)
+    // from the 4-byte draws at 4 k of stream b, small[b][n_ternary .. n_ternary + n_cbd) from the 6-byte draws at cbd_offset + 6 k;
+    // small: [items][small_stride] signed bytes.  redraw: one flag per item (zeroed by the caller; may be null when n_ternary == 0),
+    // raised where a ternary draw would have been redrawn by the reference: item b alone has to be resampled on the host
     hipError_t k_small_from_stream_batch(const uint8_t *streams, size_t stream_bytes, size_t n_ternary, size_t cbd_offset, size_t n_cbd,
                                          int8_t *small, size_t small_stride, unsigned *redraw, unsigned items, hipStream_t s);
     hipError_t k_apply_patches(const XofPatch *patches, size_t count, hipStream_t s);

@@ -230,45 +230,8 @@ namespace sealhip
             }
         }
 
-        // the raw stream: pieces first_piece .. first_piece + pieces - 1 -> out[8 * pieces]
-        __global__ void __launch_bounds__(kBlock) blake2xb_stream_kernel(XofSeed seed, uint64_t first_piece, size_t pieces, uint64_t *out)
-        {
-            const size_t p = blockIdx.x * (size_t)kBlock + threadIdx.x;
-            if (p >= pieces)
-                return;
-            uint64_t h[8];
-            stream_piece(seed.w, first_piece + p, h);
-#pragma unroll
-            for (int t = 0; t < 8; t++)
-                out[p * 8 + t] = h[t];
-        }
-
-        // The Encryptor's small samplers over a stream already in HBM (util/rlwe.cpp:24-43, 120-150; serial.h for the ternary draw):
-        // thread k < n_ternary: coefficient k of a ternary polynomial from the 4 bytes at 4 k; the others: coefficient of a
-        // centred-binomial polynomial from the 6 bytes at cbd_offset + 6 (k - n_ternary).  A ternary draw the reference would
-        // redraw (g * 3 mod 2^32 == 0: probability 2^-32) shifts the rest of the stream: it raises *redraw and the caller
-        // repeats the sampling on the host.
-        __global__ void __launch_bounds__(kBlock) small_from_stream_kernel(
-            const uint8_t *stream, size_t n_ternary, size_t cbd_offset, size_t n_cbd, int8_t *small, unsigned *redraw)
-        {
-            const size_t k = blockIdx.x * (size_t)kBlock + threadIdx.x;
-            if (k < n_ternary)
-            {
-                const uint8_t *b = stream + 4 * k;
-                const uint32_t g = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-                const uint64_t product = (uint64_t)g * 3u;
-                if ((uint32_t)product < 1u)
-                    atomicOr(redraw, 1u);
-                small[k] = (int8_t)((int)(product >> 32) - 1);
-            }
-            else if (k < n_ternary + n_cbd)
-            {
-                const uint8_t *b = stream + cbd_offset + 6 * (k - n_ternary);
-                small[k] = (int8_t)(__popc(b[0]) + __popc(b[1]) + __popc(b[2] & 0x1Fu) - __popc(b[3]) - __popc(b[4]) - __popc(b[5] & 0x1Fu));
-            }
-        }
-
-        // the two kernels above over `gridDim.y` independent streams: item b = blockIdx.y reads its seed from seeds[b]
+        // the raw streams of `gridDim.y` seeds: item b = blockIdx.y, pieces first_piece .. first_piece + pieces - 1 of seeds[b]
+        // -> out[b][8 * pieces]
         __global__ void __launch_bounds__(kBlock) blake2xb_stream_batch_kernel(const uint64_t *seeds, uint64_t first_piece, size_t pieces, uint64_t *out)
         {
             const size_t p = blockIdx.x * (size_t)kBlock + threadIdx.x;
@@ -281,6 +244,11 @@ namespace sealhip
             for (int t = 0; t < 8; t++)
                 dst[t] = h[t];
         }
+        // The Encryptor's small samplers over streams already in HBM (util/rlwe.cpp:24-43, 120-150; serial.h for the ternary draw),
+        // item b = blockIdx.y.  Thread k < n_ternary: coefficient k of a ternary polynomial from the 4 bytes at 4 k; the others:
+        // coefficient of a centred-binomial polynomial from the 6 bytes at cbd_offset + 6 (k - n_ternary).  A ternary draw the
+        // reference would redraw (g * 3 mod 2^32 == 0: probability 2^-32) shifts the rest of the stream: it raises redraw[b] and the
+        // caller repeats the sampling of that item on the host.
         __global__ void __launch_bounds__(kBlock) small_from_stream_batch_kernel(
             const uint8_t *streams, size_t stream_bytes, size_t n_ternary, size_t cbd_offset, size_t n_cbd, int8_t *small, size_t small_stride,
             unsigned *redraw)
@@ -329,24 +297,6 @@ namespace sealhip
         if (!buffers || !njobs)
             return hipSuccess;
         hipLaunchKernelGGL(shake256_uniform_kernel, dim3((unsigned)((buffers + 63) / 64), njobs), dim3(64), 0, s, mods, jobs, reject, n_log, K);
-        return hipGetLastError();
-    }
-    hipError_t k_blake2xb_stream(const XofSeed &seed, uint64_t first_piece, size_t pieces, uint64_t *out, hipStream_t s)
-    {
-        if (!pieces)
-            return hipSuccess;
-        hipLaunchKernelGGL(blake2xb_stream_kernel, dim3((unsigned)((pieces + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, seed, first_piece,
-                           pieces, out);
-        return hipGetLastError();
-    }
-    hipError_t k_small_from_stream(const uint8_t *stream, size_t n_ternary, size_t cbd_offset, size_t n_cbd, int8_t *small, unsigned *redraw,
-                                   hipStream_t s)
-    {
-        const size_t work = n_ternary + n_cbd;
-        if (!work)
-            return hipSuccess;
-        hipLaunchKernelGGL(small_from_stream_kernel, dim3((unsigned)((work + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, stream, n_ternary,
-                           cbd_offset, n_cbd, small, redraw);
         return hipGetLastError();
     }
     hipError_t k_blake2xb_stream_batch(const uint64_t *seeds, uint64_t first_piece, size_t pieces, uint64_t *out, unsigned items, hipStream_t s)

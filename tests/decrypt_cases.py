@@ -170,9 +170,19 @@ def case_encrypt_symmetric(scheme, n, bits, seed=0x5EA1):
         rpt = ref.batch_encode(rng.integers(0, t, n, dtype=np.uint64))
     pt = S.Plaintext(d.ctx)
     pt.load_bytes(ref.pt_save(rpt))
-    assert enc.encrypt_symmetric_save(pt) == ref.encrypt_symmetric_save(rpt, True), "seeded encryption of a plaintext"
+    seeded = enc.encrypt_symmetric_save(pt)
+    assert seeded == ref.encrypt_symmetric_save(rpt, True), "seeded encryption of a plaintext"
     ct = enc.encrypt_symmetric(pt)
     assert ct.save_bytes() == ref.encrypt_symmetric_save(rpt, False), "encryption of a plaintext"
+    # the saved seed re-expands to the c1 that c0 was computed with: the stream loads to the reference's words and decrypts to the
+    # plaintext.  CKKS / BGV: these are the words of encrypt_symmetric.  Not BFV: the reference samples a in coefficient form
+    # when the seed is saved and in NTT form otherwise (util/rlwe.cpp:337-345), two different encryptions of the same plaintext
+    back = S.Ciphertext(d.ctx)
+    assert back.load_bytes(seeded) == len(seeded)
+    assert np.array_equal(back.to_numpy()[:, 0], ref.ct_load(seeded)[0].data()), "the seeded stream loads to the reference's words"
+    if scheme != "bfv":
+        assert np.array_equal(back.to_numpy(), ct.to_numpy()), "the seeded stream loads to the words of encrypt_symmetric"
+    assert np.array_equal(dec.decrypt(back).to_numpy(), dec.decrypt(ct).to_numpy()), "decrypt(load(seeded stream))"
     _same_plain(dec.decrypt(ct), ref.decrypt(ref.ct_load(ct.save_bytes())[0]), "decrypt(encrypt(plain))")
     # fresh entropy: different bytes every time, same plaintext after the reference decrypts the stream
     enc.set_seed(None)

@@ -1,7 +1,8 @@
 """Batched encryption in device memory (Encryptor_EncryptSymmetricDevice / Encryptor_EncryptDevice), shared by the CPU
 (emulated kernels) and `-m gpu` suites.  Two yardsticks: the REAL reference (oracle/_ref) where it is built - every item equals
-the bytes of seal::Encryptor under the same seeded factory - and the per-object Encryptor_EncryptSymmetric / Encryptor_Encrypt,
-which are unchanged and proven against the reference (decrypt_cases.py): item b equals them under set_seed(seeds[b]).
+the bytes of seal::Encryptor under the same seeded factory - and the per-object Encryptor_EncryptSymmetric / Encryptor_Encrypt:
+item b equals them under set_seed(seeds[b]).  The per-object forms are the batch path at batch one, so that comparison pins
+seeds and metadata; the arithmetic is checked by the reference, here and in decrypt_cases.py.
 TEST INFRASTRUCTURE: the reference is the checker."""
 import ctypes as C
 
@@ -224,13 +225,17 @@ def case_host_sampling_equals_device(scheme, n, bits, batch, monkeypatch):
 def case_chunks(scheme, n, bits, batch, per_chunk, monkeypatch, with_ref=False):
     """a scratch cap that makes chunks of `per_chunk` items (development builds: SEALHIP_ENCRYPT_SCRATCH_BYTES for the Encryptor's
     own chunks, SEALHIP_PLAIN_SCRATCH_BYTES for the Evaluator's plaintext addition after a public-key encryption, at the first
-    level): every item on both sides of every chunk edge equals the per-object form"""
+    level): every item on both sides of every chunk edge equals the per-object form - or, with_ref, carries the reference's bytes
+    (the per-object forms are the same code at batch one: only the reference checks the arithmetic)"""
     side = Side(scheme, n, bits)
     K_top = side.K_at(side.first, True)
     monkeypatch.setenv("SEALHIP_ENCRYPT_SCRATCH_BYTES", str(per_chunk * 8 * K_top * n))
     monkeypatch.setenv("SEALHIP_PLAIN_SCRATCH_BYTES", str(per_chunk * 8 * side.K(side.first) * n))
     assert (batch - 1) // per_chunk >= 2, "at least two chunk edges"
-    case_per_item_seeds(scheme, n, bits, batch, side=side, levels=[side.first])
+    if with_ref:
+        case_reference_parity(scheme, n, bits, batch)
+    else:
+        case_per_item_seeds(scheme, n, bits, batch, side=side, levels=[side.first])
 
 
 def _expect(exc, call, what):

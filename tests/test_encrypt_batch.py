@@ -54,6 +54,14 @@ def test_chunks(emu, monkeypatch, scheme, per_chunk):
     EB.case_chunks(scheme, 1024, [60, 40, 60], 7, per_chunk, monkeypatch)
 
 
+@needs_ref
+@pytest.mark.parametrize("scheme", SCHEMES)
+@pytest.mark.parametrize("per_chunk", [1, 3])
+def test_chunks_against_reference(emu, monkeypatch, scheme, per_chunk):
+    import encrypt_batch_cases as EB
+    EB.case_chunks(scheme, 1024, [60, 40, 60], 7, per_chunk, monkeypatch, with_ref=True)
+
+
 @pytest.mark.parametrize("scheme", SCHEMES)
 def test_errors(emu, scheme):
     import encrypt_batch_cases as EB

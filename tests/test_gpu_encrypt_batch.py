@@ -47,6 +47,13 @@ def test_small_ring_fallbacks(gpu, scheme):
     EB.case_per_item_seeds(scheme, 8, [30, 30, 30], batch=3)
 
 
+@needs_ref
+@pytest.mark.parametrize("scheme", SCHEMES)
+def test_small_ring_fallbacks_against_reference(gpu, scheme):
+    import encrypt_batch_cases as EB
+    EB.case_reference_parity(scheme, 8, [30, 30, 30], batch=3)
+
+
 @pytest.mark.parametrize("scheme", SCHEMES)
 def test_fresh_entropy(gpu, scheme):
     import encrypt_batch_cases as EB

@@ -97,6 +97,24 @@ def test_encrypt_asymmetric(gpu, scheme, n, bits):
     DC.case_encrypt_asymmetric(scheme, n, bits)
 
 
+THRESHOLDS = [2, 8, 32, 1024]   # test_serialization.py: the ring sizes at which the Encryptor changes samplers
+
+
+@pytest.mark.parametrize("scheme", ["ckks", "bfv", "bgv"])
+@pytest.mark.parametrize("n", THRESHOLDS)
+def test_encrypt_at_sampling_thresholds(gpu, scheme, n):
+    import decrypt_cases as DC
+    DC.case_encrypt_symmetric(scheme, n, [30, 30, 30])
+    DC.case_encrypt_asymmetric(scheme, n, [30, 30, 30])
+
+
+@pytest.mark.parametrize("scheme", ["ckks", "bfv", "bgv"])
+@pytest.mark.parametrize("n", THRESHOLDS[1:])   # 8 is the smallest ring on which case_keygen's rotation by two steps exists
+def test_keygen_at_sampling_thresholds(gpu, scheme, n):
+    import decrypt_cases as DC
+    DC.case_keygen(scheme, n, [30, 30, 30])
+
+
 @pytest.mark.parametrize("n,bits", [(8192, [60, 40, 40, 60]), (32768, [60, 50, 50, 50, 60]), (65536, [60] + [50] * 14 + [60])])   # the last two reach the multi-precision branch (scale 2^150)
 def test_ckks_encoder(gpu, n, bits):
     import decrypt_cases as DC

@@ -148,6 +148,30 @@ def test_keygen(emu, scheme, n, bits):
     DC.case_keygen(scheme, n, bits)
 
 
+# the ring sizes at which the Encryptor changes samplers: 2 = below the device's ternary sampler, one 16-byte pair per row;
+# 8 = a and the noise from the host, u from the device; 32 = the noise is whole 64-byte pieces, a still from the host;
+# 1024 = everything on the device
+THRESHOLDS = [2, 8, 32, 1024]
+
+
+@needs_ref
+@pytest.mark.parametrize("scheme", ["ckks", "bfv", "bgv"])
+@pytest.mark.parametrize("n", THRESHOLDS)
+def test_encrypt_at_sampling_thresholds(emu, scheme, n):
+    import decrypt_cases as DC
+    DC.case_encrypt_symmetric(scheme, n, [30, 30, 30])
+    DC.case_encrypt_asymmetric(scheme, n, [30, 30, 30])
+
+
+@needs_ref
+@pytest.mark.parametrize("scheme", ["ckks", "bfv", "bgv"])
+@pytest.mark.parametrize("n", THRESHOLDS[1:])   # 8 is the smallest ring on which case_keygen's rotation by two steps exists
+def test_keygen_at_sampling_thresholds(emu, scheme, n):
+    """keys are zero encryptions in NTT form whatever the scheme, and their seeded streams the save_seed form"""
+    import decrypt_cases as DC
+    DC.case_keygen(scheme, n, [30, 30, 30])
+
+
 @needs_ref
 def test_encrypt_with_host_sampling(emu, monkeypatch):
     """u, e are normally drawn on the device from the bootstrap stream; the host branch (taken when a ternary draw is redrawn) must
