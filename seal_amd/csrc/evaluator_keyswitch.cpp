@@ -468,6 +468,8 @@ namespace sealhip
             // the two passes, and are multiplied into the key inside the second pass
             const KsTargets &kt = ks_targets(K);
             const size_t ks_item_words = (size_t)(K + 1) * poly_words;
+            if (ks_switches().trace) // tests: how many digit groups ran
+                std::fprintf(stderr, "[ks] split %u (K %u, digits %u..%u)\n", split, K, j0, j1);
             Scratch mid((size_t)plan.lanes * plan.chunk * ks_item_words);
             Scratch inv_mid(inverse_in_lane ? (size_t)plan.lanes * plan.chunk * poly_words : 1);
             {

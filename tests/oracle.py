@@ -84,6 +84,22 @@ class Oracle:
             return self.ref.key("galois", (elt - 1) >> 1)
         return self._rand_key(("galois", elt))
 
+    def set_key(self, kind, elt_or_0, words):
+        """replace the relinearisation key (kind 'relin', 0) or the Galois key of element `elt_or_0` (kind 'galois') with the
+        caller's words [digits][2][L][N], each below its prime; relin_key() / galois_key() then return them.  A Galois key must
+        exist already (galois_elts at construction)."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        assert w.shape == (self.L - 1, 2, self.L, self.n), w.shape
+        assert (w < np.array(self.primes, dtype=np.uint64)[None, None, :, None]).all(), "key words must be canonical"
+        if kind == "galois":
+            assert elt_or_0 in self.galois_elts, "no Galois key for element %d" % elt_or_0
+        else:
+            assert kind == "relin" and elt_or_0 == 0
+        if self.kind == "reference":
+            self.ref.set_key(kind, (elt_or_0 - 1) >> 1 if kind == "galois" else 0, w)
+        else:
+            self._keys[(kind, elt_or_0)] = w.copy()
+
     def _rand_key(self, name):
         if name not in self._keys:
             K = self.L - 1

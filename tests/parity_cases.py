@@ -54,6 +54,32 @@ def case_ntt(n, bits, polys=2, seed=1):
     _eq(lz % q, inv, "lazy inverse mod q")
 
 
+def case_ntt_many_polys(n=8, bits=(30, 30), polys=66000, check=(0, 65534, 65535, 65536, 65999), seed=17):
+    """more than 65535 polynomials in one call: the launcher cuts the outer dimension into grids of 65535 at most (ntt_kernels.hip:
+    run()) and the second grid starts at polynomial 65535.  The polynomials on either side of the cut and the last one against the
+    oracle, both directions; the round trip on the whole buffer."""
+    primes = coeff_modulus_create(n, list(bits))
+    o = Oracle("ckks", n, primes)
+    d = DeviceSide("ckks", n, primes)
+    L = len(primes)
+    assert polys > 65535 and max(check) < polys
+    rng = np.random.default_rng(seed)
+    x = np.stack([rng.integers(0, primes[i], (polys, n), dtype=np.uint64) for i in range(L)], axis=1)  # [polys][L][n]
+    buf = S.DeviceBuffer.from_numpy(x)
+    S.ntt_forward(d.ctx, buf, polys, L)
+    fwd = buf.to_numpy(x.shape)
+    for p in check:
+        _eq(fwd[p], o.ntt(0, x[p], "fwd"), "forward, polynomial %d of %d" % (p, polys))
+    S.ntt_inverse(d.ctx, buf, polys, L)
+    _eq(buf.to_numpy(x.shape), x, "inverse(forward(x)) == x over %d polynomials" % polys)
+    S.ntt_inverse(d.ctx, buf, polys, L)
+    inv = buf.to_numpy(x.shape)
+    for p in check:
+        _eq(inv[p], o.ntt(0, x[p], "inv"), "inverse, polynomial %d of %d" % (p, polys))
+    S.ntt_forward(d.ctx, buf, polys, L)
+    _eq(buf.to_numpy(x.shape), x, "forward(inverse(x)) == x over %d polynomials" % polys)
+
+
 # ---- dyadic product: native/tests/seal/util/polyarithsmallmod.cpp:545-641
 def case_dyadic(n, bits, seed=2):
     primes = coeff_modulus_create(n, bits)
@@ -652,13 +678,17 @@ def case_bgv_pipeline(n, primes, t, batch=2, seed=6):
 # ---- digit-parallel key switching (sealhip.h section 1b) emulated in ONE process: the digits are split
 #      over `parts` virtual ranks, each with only its key slice resident; the partial sums are added on the host (what the
 #      all-reduce does) and every result must equal the single-GPU relinearize / rotate AND the oracle, bit for bit.
-def case_digit_parallel(scheme, n, primes, t=0, parts=2, batch=2, seed=7):
+def case_digit_parallel(scheme, n, primes, t=0, parts=2, batch=2, seed=7, key_pattern=None):
+    """key_pattern: both keys are extreme_key words of that pattern on the oracle and on the device instead of generated ones"""
     from seal_amd import shard
     L = len(primes)
     K = L - 1
     probe = Oracle(scheme, n, primes, t)
     elt = probe.galois_elt_from_step(1)
     o = Oracle(scheme, n, primes, t, galois_elts=[elt])
+    if key_pattern is not None:
+        o.set_key("relin", 0, extreme_key(primes, K, n, key_pattern, seed=seed))
+        o.set_key("galois", elt, extreme_key(primes, K, n, key_pattern, seed=seed + 1))
     d = DeviceSide(scheme, n, primes, t)
     d.upload_keys(o)
     rlk_words, glk_words = o.relin_key(), o.galois_key(elt)
@@ -1393,6 +1423,17 @@ def extreme_slab(primes, n, pattern, seed=0):
         else:
             raise ValueError(pattern)
     return out
+
+
+KEY_PATTERNS = ("qm1", "half", "half1", "alt", "mix4", "one", "zero")
+
+
+def extreme_key(primes, K, n, pattern, seed=0):
+    """a switching key [K][2][L][n] of extreme_slab words over all L primes of the key level (seeded per digit and polynomial):
+    every word at 0, 1, floor(q/2), floor(q/2)+1 or q-1 - the ends and the middle of the range key_layout_kernel folds into
+    balanced doubles (primes below 2^50) or stores next to floor(w 2^64 / q) (51 to 60 bits)"""
+    assert pattern in KEY_PATTERNS, pattern
+    return np.stack([np.stack([extreme_slab(primes, n, pattern, seed=(seed * 64 + j) * 2 + k) for k in range(2)]) for j in range(K)])
 
 
 def case_extremes_ntt(n, bits, polys):

@@ -234,6 +234,35 @@ def case_key_save(scheme, n, bits, steps=(1,)):
         assert _outcome(lambda: part.save_bytes()) == S.LogicError
 
 
+def case_key_words_survive_save(n=8192, bits=(50, 59, 57, 60)):
+    """structured key words (parity_cases.extreme_key: every word at 0, 1, floor(q/2), floor(q/2)+1 or q-1) set on both sides: the
+    device's saved RelinKeys / GaloisKeys stream is the reference's, and the words read back through KSwitchKeys::data() are the words
+    that were set - key_unlayout_kernel's balanced double -> [0, q) path (the 50-bit primes; the edge is floor(q/2) / floor(q/2)+1)
+    and its pair -> word path (51 to 60 bits)"""
+    from parity_cases import KEY_PATTERNS, extreme_key
+    primes, t, ref, d = setup("ckks", n, list(bits))
+    L, K = len(primes), len(primes) - 1
+    elt = ref.galois_elt_from_step(1)
+    ref.keygen_relin()
+    ref.keygen_galois_elts([elt])
+    gidx = S.GaloisKeys.get_index(elt)
+    rlk, glk = S.RelinKeys(d.ctx), S.GaloisKeys(d.ctx)
+    shape = ref.keys_save_mode("galois", 0)  # the reference's object has a slot per odd element (all but one empty): take its shape
+    assert glk.load_bytes(shape) == len(shape)
+    for pattern in KEY_PATTERNS:
+        for kind, index, seed, keys in (("relin", 0, 3, rlk), ("galois", gidx, 5, glk)):
+            words = extreme_key(primes, K, n, pattern, seed=seed)
+            ref.set_key(kind, index, words)
+            keys.set_key(index, words)
+            assert keys.save_bytes() == ref.keys_save_mode(kind, 0), "%s keys of pattern %s: the saved stream" % (kind, pattern)
+            digits = keys.key_list(index)
+            assert len(digits) == K
+            for j, dg in enumerate(digits):
+                got = dg.words(L, n)
+                assert np.array_equal(got, words[j]), "%s key of pattern %s, digit %d: %d words differ from the words that were set" % (
+                    kind, pattern, j, np.count_nonzero(got != words[j]))
+
+
 def _walk_key_digits(stream):
     """offsets (start, size) of every digit (a framed seeded or full ciphertext) inside a KSwitchKeys stream"""
     pos = 16 + 32

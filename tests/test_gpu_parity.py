@@ -39,6 +39,12 @@ def test_ntt(gpu, n, bits, polys):
     P.case_ntt(n, bits, polys=polys)
 
 
+def test_ntt_more_polynomials_than_one_grid(gpu):
+    """66000 polynomials at N = 8: the launcher's loop over grids of 65535 outer items takes its second iteration.  (The two-pass
+    engine has the same loop; reaching it needs 4 GB per component and is left out.)"""
+    P.case_ntt_many_polys()
+
+
 # single-launch transforms (N = 2^13, 2^14): batches large enough that every workgroup loops with the next
 # transform in flight, and a forced one-workgroup-per-component loop
 @pytest.mark.parametrize("n,bits,polys,chunks", [

@@ -40,6 +40,10 @@ def test_key_save(gpu, scheme, n, bits):
     SC.case_key_save(scheme, n, bits)
 
 
+def test_key_words_survive_save(gpu):
+    SC.case_key_words_survive_save()
+
+
 def test_key_stream_headline_size(gpu):
     """BASELINE's headline parameters: CKKS N = 65536, {60, 14 x 50, 60}; seeded RelinKeys + GaloisKeys streams"""
     SC.case_key_streams("ckks", 65536, [60] + [50] * 14 + [60], True)
