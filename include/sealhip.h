@@ -460,6 +460,57 @@ SHL_FUNC Evaluator_DotPlainDevice(void *thisptr, void *encrypted, const uint64_t
  * adds two products per item, and 256 products of words below 2^60 fit 128 bits).  A small result is computed in slices by the rule
  * of Evaluator_SumItems, with pool scratch of slices x 3 x one result plane. */
 SHL_FUNC Evaluator_DotItems(void *thisptr, void *encrypted1, void *encrypted2, uint64_t group, void *destination);
+/* Item maps (library extensions): the three reductions above over the items a device-resident CSR list names, instead of over
+ * consecutive groups - select, repeat, permute or compact the items of a batch on the device (a gather), sum groups of unequal length
+ * (aggregation by bucket, federated sums with drop-outs), multiply a sparse plaintext matrix with a vector of ciphertexts (row o
+ * adds the few items its non-zeros name), or sum x_i (x) y_j over a list of pairs (i, j).
+ * ItemMap_Create: row_offsets is a host array of rows + 1 entries, first_items and second_items host arrays of
+ *   terms = row_offsets[rows] entries.  Term t of row o (row_offsets[o] <= t < row_offsets[o + 1]) names item first_items[t] of the
+ *   first operand and second_items[t] of the second; second_items == NULL means "the same list", and second_batch must then equal
+ *   first_batch.  Everything is validated once, here, with SHL_E_INVALIDARG: rows >= 1; row_offsets[0] == 0 and strictly increasing (an
+ *   empty row would be a transparent ciphertext, and add_many of nothing throws in the reference); rows and terms below 2^32; every
+ *   item number below its batch; NULL arrays.  The lists are uploaded once, as 32-bit words, each 16-byte aligned, with a plain
+ *   synchronous copy after draining the device: this is not a hot-path call.  The calls below read them from HBM and make no host
+ *   transfer, so they record under Evaluator_BeginCapture and one map serves many calls (a fixed sparse matrix).
+ * ItemMap_Destroy gives the lists back through the stream-aware device pool and drains nothing: a block that work may still read is
+ *   not handed to another user before that user has waited for every stream registered with the pool and for the NULL stream, so a
+ *   map may be destroyed right after the call that used it - but not before the last launch of a graph that recorded it.
+ * ItemMap_Info: any of the outputs may be NULL.
+ * The three calls: the output is a batch of `rows` items; destination is ANOTHER handle made with Ciphertext_CreateBatch(rows),
+ * distinct from every operand.
+ * Evaluator_SumItemsMapped: item o = sum_t ct[first[t]].  Only the first list is used; every size, form and scheme Evaluator_SumItems
+ *   accepts; encrypted's batch must equal first_batch.  A map whose rows all have one term is a gather: the words are copied exactly,
+ *   because the canonical residue of one canonical word is that word.
+ * Evaluator_DotPlainMapped: item o = sum_t ct[first[t]] (.) pt[second[t]].  device_plain = [plain_count][K][N] NTT-form words at the
+ *   ciphertext's level, plain_count == second_batch, which may differ from the ciphertext's batch (weights per non-zero, or weights
+ *   shared per column).  The ciphertext is in NTT form; scale, alignment, overlap and "NOT validated" exactly as
+ *   Evaluator_DotPlainDevice.
+ * Evaluator_DotItemsMapped: item o = sum_t x[first[t]] (x) y[second[t]], size 3, not relinearised.  CKKS / BGV, size 2 x 2, NTT form,
+ *   the same level; BFV is refused as Evaluator_DotItems refuses it.  x's batch must equal first_batch and y's second_batch; the two
+ *   may differ.  The square kernel (x read once) applies when encrypted1 == encrypted2 and the map has no second list.
+ * Output item o equals, word for word, the per-object forms on batches of one holding the named items followed by Evaluator_AddMany,
+ * hence the reference's multiply_plain_inplace / multiply and then add_many: a modular sum does not depend on which items it is told
+ * to add.  An item named twice is added twice.  Metadata (scale product and its bound check, correction factor, is_ntt_form,
+ * parms_id), the settle-before-read rules for operands with a deferred tail or a pending product, Evaluator_SetTransparentCheck and
+ * "a failed check leaves the destination untouched" are those of the contiguous forms, and so are their SHL_E_POINTER /
+ * SHL_E_INVALIDARG cases, with these instead of the group's: an operand's batch != the map's, plain_count != second_batch, the
+ * destination's batch != rows, a map of another context.
+ * The calls are enqueued on the evaluator's stream without a host round trip.  The kernels are those of the contiguous forms with
+ * another walk: from N = 128 on a wavefront never leaves its row and reads offsets and item numbers through the scalar cache, one
+ * 4-byte load per wavefront, list and term; on smaller rings every lane reads its own.  A small result is cut as for
+ * Evaluator_SumItems: WHETHER to cut, and into how many slices, follows from the mean row - that rule asked with
+ * ceil(terms / rows) items per group; the slices are then sized from the longest row, per_slice = ceil(longest_row / slices), and
+ * ceil(longest_row / per_slice) of them run.  Slice s of row o adds the terms [off[o] + s per_slice, min(off[o + 1], off[o] + (s + 1)
+ * per_slice)) and writes zeros where that is empty; the words do not depend on it.  A very skewed map (one long row among short
+ * ones) is balanced by this cut and by nothing else. */
+SHL_FUNC ItemMap_Create(void *context, uint64_t rows, const uint64_t *row_offsets, const uint64_t *first_items, const uint64_t *second_items,
+                        uint64_t first_batch, uint64_t second_batch, void **item_map);
+SHL_FUNC ItemMap_Destroy(void *thisptr);
+SHL_FUNC ItemMap_Info(void *thisptr, uint64_t *rows, uint64_t *terms, uint64_t *longest_row, uint64_t *first_batch, uint64_t *second_batch);
+SHL_FUNC Evaluator_SumItemsMapped(void *thisptr, void *encrypted, void *item_map, void *destination);
+SHL_FUNC Evaluator_DotPlainMapped(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t plain_count, void *item_map,
+                                  double scale, void *destination);
+SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination);
 SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *pool);
 SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *pool);
@@ -566,6 +617,16 @@ SHL_FUNC shl_dot_items(void *context, uint64_t chain_index, const uint64_t *x, c
                        uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream);
 /* items the lazy accumulators of that kernel take between two reductions (128: the middle polynomial adds two products per item) */
 SHL_FUNC shl_dot_items_flush_interval(uint64_t *items);
+/* The kernels of the *Mapped reductions on raw words at one level.  kind 0: the sum, a = [size][a_batch][K][N], b unused; kind 1:
+ * the plaintext dot product, a as before, b = [b_batch][K][N]; kind 2: the ciphertext dot product, a = [2][a_batch][K][N],
+ * b = [2][b_batch][K][N], size ignored (the result has 3 planes; b == a with a one-list map selects the square kernel).
+ * r = [size or 3][rows][K][N], distinct from the operands.  a_batch / b_batch must be the map's first_batch / second_batch.  slices:
+ * 0 = the library's rule (above), 1 = one launch, 2 .. min(longest_row, 64) = that cut of the longest row, with scratch of
+ * slices * (size or 3) * rows * K * N words; the slices run are ceil(longest_row / ceil(longest_row / slices)).  slices_used (may be
+ * NULL) receives them; r == NULL only answers that.  Nothing is validated beyond the shape. */
+SHL_FUNC shl_reduce_mapped(void *context, uint64_t chain_index, int kind, const uint64_t *a, uint64_t a_batch, const uint64_t *b,
+                           uint64_t b_batch, uint64_t *r, uint64_t size, void *item_map, uint64_t slices, uint64_t *scratch,
+                           uint64_t *slices_used, void *stream);
 /* GaloisTool::apply_galois (ntt_form == 0, util/galois.cpp:148) / apply_galois_ntt (!= 0, galois.cpp:192) */
 SHL_FUNC shl_apply_galois(void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys, void *stream);
 /* RNSTool stages (util/rns.cpp) on one level, `polys` polynomials each [comps][N]:

@@ -84,6 +84,7 @@ Evaluator_TransformToNTT1 Evaluator_ModSwitchToNext2 Evaluator_ModSwitchTo2
 Evaluator_AddPlainDevice Evaluator_SubPlainDevice Evaluator_MultiplyPlainDevice Evaluator_TransformPlainToNTTDevice
 Evaluator_SumItems Evaluator_DotPlainDevice shl_reduce_items shl_reduce_flush_intervals
 Evaluator_DotItems shl_dot_items shl_dot_items_flush_interval
+ItemMap_Create ItemMap_Destroy ItemMap_Info Evaluator_SumItemsMapped Evaluator_DotPlainMapped Evaluator_DotItemsMapped shl_reduce_mapped
 KSwitchKeys_Create1 KSwitchKeys_Destroy KSwitchKeys_Size KSwitchKeys_SetKey KSwitchKeys_SetKeyFromDevice
 KSwitchKeys_SetKeyDigits KSwitchKeys_HasKey KSwitchKeys_DeviceBytes RelinKeys_GetIndex GaloisKeys_GetIndex GaloisTool_GetEltFromStep
 Evaluator_Create Evaluator_Destroy Evaluator_SetStream Evaluator_Synchronize Evaluator_CopyTo Evaluator_SetTransparentCheck

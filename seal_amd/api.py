@@ -1182,6 +1182,62 @@ class Graph:
             self._h = None
 
 
+class ItemMap:
+    """a device-resident CSR list of item numbers (sealhip.h: ItemMap_Create): which items of a batch - or which pairs of items of
+    two - the terms of each output item of Evaluator.sum_items_mapped / dot_plain_mapped / dot_items_mapped are.
+    rows: a list of rows, each a list of item numbers (or of (first, second) pairs), or the CSR triple given with row_offsets=.
+    second: None = one list for both operands; otherwise the second operand's item numbers, shaped like `rows` (a flat list with
+    row_offsets=).  first_batch / second_batch: the operands' batches (second_batch None: first_batch)."""
+
+    def __init__(self, context, rows, first_batch, second=None, second_batch=None, row_offsets=None):
+        self.context = context
+        if row_offsets is None:
+            rows = [list(r) for r in rows]
+            if second is None and rows and rows[0] and isinstance(rows[0][0], (tuple, list)):
+                second = [[t[1] for t in r] for r in rows]
+                rows = [[t[0] for t in r] for r in rows]
+            row_offsets = [0]
+            for r in rows:
+                row_offsets.append(row_offsets[-1] + len(r))
+            first = [i for r in rows for i in r]
+            if second is not None:
+                if [len(r) for r in second] != [len(r) for r in rows]:
+                    raise ValueError("the second list is not shaped like the first")
+                second = [i for r in second for i in r]
+        else:
+            row_offsets, first = list(row_offsets), list(rows)
+            second = None if second is None else list(second)
+        if not row_offsets or (second is not None and len(second) != len(first)):
+            raise ValueError("row_offsets is empty, or the lists differ in length")
+        if len(first) < row_offsets[-1]:
+            raise ValueError("fewer item numbers than row_offsets[-1]")
+        nrows = len(row_offsets) - 1
+        second_batch = first_batch if second_batch is None else second_batch
+        off = (C.c_uint64 * len(row_offsets))(*row_offsets)
+        f = (C.c_uint64 * max(len(first), 1))(*first)
+        s2 = (C.c_uint64 * max(len(second), 1))(*second) if second is not None else None
+        self._h = C.c_void_p()
+        N.check(N.lib().ItemMap_Create(context._h, C.c_uint64(nrows), off, f, s2, C.c_uint64(first_batch), C.c_uint64(second_batch),
+                                       C.byref(self._h)))
+
+    def info(self):
+        """-> (rows, terms, longest_row, first_batch, second_batch)"""
+        v = [C.c_uint64() for _ in range(5)]
+        N.check(N.lib().ItemMap_Info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def rows(self):
+        return self.info()[0]
+
+    def destroy(self):
+        """give the lists back now (sealhip.h: ItemMap_Destroy is safe while work that reads them is queued)"""
+        if getattr(self, "_h", None):
+            N.lib().ItemMap_Destroy(self._h)
+            self._h = None
+
+    __del__ = destroy
+
+
 class Evaluator:
     """seal::Evaluator's hot-path surface (evaluator.h:79-1387), in-place and destination forms."""
 
@@ -1457,6 +1513,41 @@ class Evaluator:
         of squares.  group, destination: as sum_items; the destination is distinct from both operands.  -> the destination"""
         group, d = self._reduce_dest(a, group, destination)
         N.check(N.lib().Evaluator_DotItems(self._h, a._h, b._h, C.c_uint64(group), d._h))
+        return d
+
+    # ---- the same reductions over the items an ItemMap names (sealhip.h: Evaluator_SumItemsMapped ...)
+    def _mapped_dest(self, item_map, destination):
+        return Ciphertext(self.context, batch=item_map.rows()) if destination is None else destination
+
+    def sum_items_mapped(self, a, item_map, destination=None):
+        """item o of the result = the sum over the terms t of row o of item first[t] of `a` (sealhip.h: Evaluator_SumItemsMapped).
+        destination None: a new Ciphertext of item_map.rows() items; otherwise a handle of that batch, distinct from `a`"""
+        d = self._mapped_dest(item_map, destination)
+        N.check(N.lib().Evaluator_SumItemsMapped(self._h, a._h, item_map._h, d._h))
+        return d
+
+    def gather_items(self, a, indices, destination=None):
+        """item o of the result = item indices[o] of `a`, word for word: select, repeat, permute, compact (sum_items_mapped with
+        one-term rows).  The map made here is given back when this returns, which is safe for the queued call but not for the
+        replays of a recording: under capture() make the ItemMap yourself, keep it, and call sum_items_mapped"""
+        return self.sum_items_mapped(a, ItemMap(self.context, [[i] for i in indices], a.batch()), destination)
+
+    def dot_plain_mapped(self, a, words, plain_count, item_map, scale=1.0, destination=None):
+        """item o of the result = the sum over the terms t of row o of item first[t] of `a` * plaintext second[t] (sealhip.h:
+        Evaluator_DotPlainMapped).  words: DeviceBuffer of [plain_count][K][N] NTT-form words at the ciphertext's level"""
+        need = plain_count * a.poly_modulus_degree() * a.coeff_modulus_size()
+        if isinstance(words, DeviceBuffer) and words.words < need:
+            raise ValueError("%d plaintext words for %d plaintexts at this level: %d needed" % (words.words, plain_count, need))
+        d = self._mapped_dest(item_map, destination)
+        ptr = words.ptr if isinstance(words, DeviceBuffer) else words
+        N.check(N.lib().Evaluator_DotPlainMapped(self._h, a._h, C.c_void_p(ptr), C.c_uint64(plain_count), item_map._h, C.c_double(scale), d._h))
+        return d
+
+    def dot_items_mapped(self, a, b, item_map, destination=None):
+        """item o of the result = the sum over the terms t of row o of a[first[t]] (x) b[second[t]], size 3, not relinearised
+        (sealhip.h: Evaluator_DotItemsMapped); `b is a` with a one-list map is the sum of squares"""
+        d = self._mapped_dest(item_map, destination)
+        N.check(N.lib().Evaluator_DotItemsMapped(self._h, a._h, b._h, item_map._h, d._h))
         return d
 
     def mod_switch_plain_to_next_inplace(self, plain):

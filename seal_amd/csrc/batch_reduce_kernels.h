@@ -13,6 +13,12 @@
 // so below a threshold the group is cut into `slices` runs of consecutive items, each reduced by workgroups of its own (the slow grid
 // dimension) into scratch [slices][size][batch / group][K][N], and a second launch, of the sum over the slices, adds them.  No atomics:
 // modular addition is exact and associative, the words do not depend on the cut.
+// Item maps (evaluator.h: ItemMap; include/sealhip.h: Evaluator_SumItemsMapped ...): the same kernels with another walk.  Instead of
+// the items o * group + t, term t of output item (row) o is the item a CSR list names: rows [off[o], off[o + 1]) of two lists of
+// 32-bit item numbers in HBM, one per operand.  Rows may differ in length; the kernels read the lists (through the scalar cache
+// from N = 128 on, where a wave never leaves its row) and nothing else changes - a modular sum does not depend on which items it is
+// told to add, so the words are still those of add_many over the per-object forms on the named items.  A cut slices every row at
+// the same positions, sized from the longest row; slices past the end of a shorter row store zeros.
 #pragma once
 #include "encrypt_kernels.h"
 
@@ -25,28 +31,51 @@ namespace sealhip
     // The library's rule: slices for a launch of `threads` threads (one per output pair: sum_items size * out_items * K * N / 2,
     // dot_plain_device and dot_items out_items * K * N / 2) that each add `group` terms.  1 = one launch, no scratch.
     unsigned batch_reduce_slices(size_t threads, size_t group);
+
+    // Which operand items the terms of an output item are.  ItemWalk(group): the consecutive items o * group .. o * group + group - 1
+    // of both operands.  Mapped (offsets != nullptr; device pointers, 32-bit words; rows = the output items): term t of row o,
+    // offsets[o] <= t < offsets[o + 1], is item first[t] of the first operand and second[t] of the second (second == first: one
+    // list).  Item numbers are NOT checked by the kernels: ItemMap_Create does that once.
+    struct ItemWalk
+    {
+        size_t longest = 0; // terms of the longest row: what a cut slices
+        size_t mean = 0;    // ceil(terms / rows): what the library's rule is asked with
+        const uint32_t *offsets = nullptr, *first = nullptr, *second = nullptr;
+        ItemWalk() = default;
+        explicit ItemWalk(size_t group) : longest(group), mean(group) {}
+        ItemWalk(size_t longest_row, size_t mean_row, const uint32_t *off, const uint32_t *f, const uint32_t *s)
+            : longest(longest_row), mean(mean_row), offsets(off), first(f), second(s)
+        {}
+        bool mapped() const { return offsets != nullptr; }
+    };
+    // The rule for a walk: whether to cut, and into how many slices, is decided from the MEAN work per thread
+    // (batch_reduce_slices(threads, walk.mean)); the slices are then sized from the longest row - per_slice = ceil(longest / slices) -
+    // and the count is what that leaves non-empty.  Consecutive groups: mean = longest = group, the rule above.  A very skewed map
+    // (one long row among short ones) is balanced by this cut and by nothing else.
+    unsigned batch_reduce_slices(size_t threads, const ItemWalk &walk);
     // words of scratch a call with `slices` > 1 needs
     inline size_t batch_reduce_scratch_words(unsigned slices, unsigned size, size_t out_items, unsigned n_log, unsigned K)
     {
         return slices > 1 ? (((size_t)slices * size * out_items * K) << n_log) : 0;
     }
 
-    // r[p][o][k][j] = sum_i a[p][o * group + i][k][j] mod q_k, p < size.  Plane p of the source is a + p * a_stride, of the result
-    // r + p * r_stride.  slices: 1, or the cut described above with scratch of batch_reduce_scratch_words words (2 <= slices <= group).
+    // r[p][o][k][j] = sum_i a[p][o * group + i][k][j] mod q_k, p < size (written for consecutive groups here and below; with a mapped
+    // walk the items are the named ones).  Plane p of the source is a + p * a_stride, of the result r + p * r_stride.  slices: 1, or
+    // the cut described above with scratch of batch_reduce_scratch_words words (2 <= slices <= walk.longest).
     hipError_t k_sum_items(const ModDesc *mods, const uint64_t *a, size_t a_stride, uint64_t *r, size_t r_stride, unsigned size, unsigned n_log,
-                           unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch, hipStream_t s);
+                           unsigned K, size_t out_items, const ItemWalk &walk, unsigned slices, uint64_t *scratch, hipStream_t s);
     // r[p][o][k][j] = sum_i a[p][o * group + i][k][j] * pl[o * group + i][k][j] mod q_k.  A thread keeps its two plaintext words in
     // registers over the planes (up to three at a time): the plaintexts cross HBM once for size <= 3.
     hipError_t k_dot_plain_items(const ModDesc *mods, const uint64_t *a, size_t a_stride, const uint64_t *pl, uint64_t *r, size_t r_stride,
-                                 unsigned size, unsigned n_log, unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch,
-                                 hipStream_t s);
+                                 unsigned size, unsigned n_log, unsigned K, size_t out_items, const ItemWalk &walk, unsigned slices,
+                                 uint64_t *scratch, hipStream_t s);
     // Ciphertext x ciphertext, both of size 2 and in NTT form: x, y = [2][batch][K][N] (planes x_stride / y_stride words apart),
     // r = [3][batch / group][K][N]:
     //   r[0][o] = sum_i x0 y0,  r[1][o] = sum_i (x0 y1 + x1 y0),  r[2][o] = sum_i x1 y1   over the items o * group + i, mod q_k
     // - the words of multiply (evaluator.cpp ckks_multiply / bgv_multiply, 2 x 2) per item and then add_many.  Each operand word
-    // crosses HBM once: 4 plane-items read per item, no product is stored.  y == x (same pointer and stride) is the sum of squares
-    // and reads 2.  slices, scratch: as above with size 3.
+    // crosses HBM once: 4 plane-items read per item, no product is stored.  y == x (same pointer and stride, and one list of items
+    // when the walk is mapped) is the sum of squares and reads 2.  slices, scratch: as above with size 3.
     hipError_t k_dot_items(const ModDesc *mods, const uint64_t *x, size_t x_stride, const uint64_t *y, size_t y_stride, uint64_t *r,
-                           size_t r_stride, unsigned n_log, unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch,
-                           hipStream_t s);
+                           size_t r_stride, unsigned n_log, unsigned K, size_t out_items, const ItemWalk &walk, unsigned slices,
+                           uint64_t *scratch, hipStream_t s);
 } // namespace sealhip

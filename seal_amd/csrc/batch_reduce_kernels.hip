@@ -1,6 +1,7 @@
 // See batch_reduce_kernels.h.  One thread = two adjacent words of one output row (N is even, rows are 16-byte aligned); the grid is
 // flat in x (one thread per output pair) and, when the group is cut, the slices sit in y.  There is one kernel, reduce_items_kernel:
-// what a reduction adds per term is its Term (SumTerm, DotPlainTerm, DotItemsTerm), everything else exists once.
+// what a reduction adds per term is its Term (SumTerm, DotPlainTerm, DotItemsTerm), which items its terms are is its Walk
+// (ConsecutiveWalk, MappedWalk), everything else exists once.
 #include "batch_reduce_kernels.h"
 #include "stream_device.h"
 #include <algorithm>
@@ -47,6 +48,35 @@ namespace sealhip
             size_t pairs;                         // grid planes * out_items * K * N / 2
             unsigned out_items, terms, per_slice; // slice s adds the terms [s * per_slice, min(terms, (s + 1) * per_slice))
             unsigned n_log, K;
+        };
+
+        // ---- the walks: which operand items the terms of output item o are.  A Walk gives the slice's range of terms [t0, t1) of
+        // a row and moves the operand pointers from term to term; the kernel does not know which one it runs with.
+        // Consecutive groups: term t of output item o is item o * group + t of both operands (the strides are ReduceGeom's item, term)
+        struct ConsecutiveWalk
+        {
+            static constexpr bool kMapped = false;
+        };
+        // An item map (batch_reduce_kernels.h: ItemWalk): row o has the terms off[o] .. off[o + 1] - 1 of two lists of item numbers,
+        // 32-bit words in HBM; term t is item first[t] of the first operand and second[t] of the second.  Here ReduceGeom's term is
+        // the words of one item ([K][N], below 2^32) and item, terms are not used: an operand address costs one 32 x 32 -> 64
+        // multiply-add per term.  per_slice is sized from the longest row; a slice past the end of a short row adds nothing and
+        // stores zeros.
+        // UNIFORM: a wave covers 128 consecutive words and rows are N words, so from N = 128 on a wave never leaves its row - the row
+        // number is moved to an SGPR and offsets and item numbers are read through the constant address space (scalar loads, one per
+        // wave and term, uniform trip counts).  Below that the lanes of a wave sit in rows of different length: per-lane loads,
+        // divergent trip counts and flushes.
+        template <bool UNIFORM>
+        struct MappedWalk
+        {
+            static constexpr bool kMapped = true, kUniform = UNIFORM;
+            const uint32_t *off, *first, *second;
+            static __device__ __forceinline__ unsigned ld(const uint32_t *p, unsigned i)
+            {
+                if (UNIFORM)
+                    return SHL_UCONST32(p)[i];
+                return p[i];
+            }
         };
 
         // ---- the terms.  A Term has kOut result planes per thread, kFlush terms between two reductions of its accumulators (Acc,
@@ -156,30 +186,72 @@ namespace sealhip
             }
         };
 
+        // waves per SIMD a kernel is built for: its term's - except on the per-lane walk, which exists for the rings below N = 128 and
+        // keeps a term index, two list pointers and two more addresses per lane: at the 7 waves of DotPlainTerm<2> (72 registers) it
+        // spills, so it is built for 5 waves at most (96 registers; that term takes 90 there, and spills again at 4 and at 6)
+        template <class Term, class Walk>
+        constexpr unsigned walk_waves()
+        {
+            if constexpr (Walk::kMapped)
+                return !Walk::kUniform && Term::kWaves > 5 ? 5 : Term::kWaves;
+            else
+                return Term::kWaves;
+        }
+
         // FINAL: the result is the ciphertext (written once: non-temporal) and not scratch that the next launch reads
-        template <class Term, bool FINAL>
-        __global__ void __launch_bounds__(kBlock, Term::kWaves) reduce_items_kernel(const ModDesc *mods, const uint64_t *a, const uint64_t *b, uint64_t *dst,
-                                                                      ReduceGeom g)
+        template <class Term, bool FINAL, class Walk>
+        __global__ void __launch_bounds__(kBlock, (walk_waves<Term, Walk>())) reduce_items_kernel(const ModDesc *mods, const uint64_t *a, const uint64_t *b, uint64_t *dst,
+                                                                      ReduceGeom g, Walk walk)
         {
             const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
             if (w >= g.pairs)
                 return;
             const size_t i = 2 * w, j = i & ((size_t(1) << g.n_log) - 1);
-            const unsigned row = (unsigned)(i >> g.n_log); // (p * out_items + o) * K + k
+            unsigned row = (unsigned)(i >> g.n_log); // (p * out_items + o) * K + k
+            if constexpr (Walk::kMapped)
+            {
+                if (Walk::kUniform)
+                    row = SHL_UNIFORM(row);
+            }
             const unsigned k = row % g.K, po = row / g.K, o = po % g.out_items, p = po / g.out_items;
             const ModDesc md = mods[k];
-            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.terms - t0 < g.per_slice ? g.terms : t0 + g.per_slice;
-            const size_t inner = ((size_t)k << g.n_log) + j;
-            const size_t first = o * g.item + t0 * g.term + inner; // output item o, term t0, component k, coefficient j
-            const uint64_t *ap = a + p * g.a_plane + first, *bp = b + p * g.b_plane + first;
+            unsigned t0, t1;
+            size_t inner; // component k, coefficient j
+            const uint64_t *ap, *bp;
+            if constexpr (Walk::kMapped)
+            {
+                // the slice's part of row o: [off + s * per_slice, min(off + len, off + (s + 1) * per_slice)), empty past the row's end
+                const unsigned off = Walk::ld(walk.off, o), len = Walk::ld(walk.off, o + 1) - off;
+                const unsigned s0 = blockIdx.y * g.per_slice, r0 = s0 < len ? s0 : len;
+                t0 = off + r0;
+                t1 = len - r0 < g.per_slice ? off + len : t0 + g.per_slice;
+                inner = ((size_t)k << g.n_log) + j;
+                ap = a + p * g.a_plane + inner; // item 0: a term adds its item number times the words of an item
+                bp = b + p * g.b_plane + inner;
+            }
+            else
+            {
+                t0 = blockIdx.y * g.per_slice;
+                t1 = g.terms - t0 < g.per_slice ? g.terms : t0 + g.per_slice;
+                inner = ((size_t)k << g.n_log) + j;
+                const size_t first = o * g.item + t0 * g.term + inner; // output item o, term t0, component k, coefficient j
+                ap = a + p * g.a_plane + first;
+                bp = b + p * g.b_plane + first;
+            }
+            const size_t step = Walk::kMapped ? 0 : g.term; // consecutive items: the pointers walk; a map: they stay at item 0
             uint64_t tot[Term::kOut][2] = {};
             for (unsigned t = t0; t < t1;)
             {
                 const unsigned end = t1 - t < Term::kFlush ? t1 : t + Term::kFlush;
                 typename Term::Acc acc[Term::kOut][2] = {};
 #pragma unroll Term::kUnroll
-                for (; t < end; t++, ap += g.term, bp += g.term)
-                    Term::add(acc, ap, bp, g);
+                for (; t < end; t++, ap += step, bp += step)
+                {
+                    if constexpr (Walk::kMapped) // g.term: the words of one item, below 2^32
+                        Term::add(acc, ap + (size_t)Walk::ld(walk.first, t) * (unsigned)g.term, bp + (size_t)Walk::ld(walk.second, t) * (unsigned)g.term, g);
+                    else
+                        Term::add(acc, ap, bp, g);
+                }
                 for (unsigned q = 0; q < Term::kOut; q++)
                     for (unsigned l = 0; l < 2; l++)
                         tot[q][l] = add_mod(tot[q][l], Term::reduce(acc[q][l], md), md.q);
@@ -211,45 +283,61 @@ namespace sealhip
             return true;
         }
 
-        template <class Term>
-        hipError_t launch_reduce(const ModDesc *mods, const uint64_t *a, const uint64_t *b, uint64_t *dst, const ReduceGeom &g, unsigned slices,
-                                 bool final, hipStream_t s)
+        template <class Term, class Walk>
+        hipError_t launch_walk(const ModDesc *mods, const uint64_t *a, const uint64_t *b, uint64_t *dst, const ReduceGeom &g, unsigned slices,
+                               bool final, hipStream_t s, const Walk &walk)
         {
             unsigned blocks;
             if (!flat_grid(g.pairs, g.n_log, blocks))
                 return hipErrorInvalidValue;
             if (final)
-                hipLaunchKernelGGL((reduce_items_kernel<Term, true>), dim3(blocks, slices), dim3(kBlock), 0, s, mods, a, b, dst, g);
+                hipLaunchKernelGGL((reduce_items_kernel<Term, true, Walk>), dim3(blocks, slices), dim3(kBlock), 0, s, mods, a, b, dst, g, walk);
             else if constexpr (Term::kOperands)
-                hipLaunchKernelGGL((reduce_items_kernel<Term, false>), dim3(blocks, slices), dim3(kBlock), 0, s, mods, a, b, dst, g);
+                hipLaunchKernelGGL((reduce_items_kernel<Term, false, Walk>), dim3(blocks, slices), dim3(kBlock), 0, s, mods, a, b, dst, g, walk);
             else
                 return hipErrorInvalidValue; // the slices are added into the result and nowhere else
             return hipGetLastError();
         }
+        // the one launch: the walk picks the kernel's mode - consecutive groups, or a map read per wave (N >= 128) or per lane
+        template <class Term>
+        hipError_t launch_reduce(const ModDesc *mods, const uint64_t *a, const uint64_t *b, uint64_t *dst, const ReduceGeom &g, unsigned slices,
+                                 bool final, hipStream_t s, const ItemWalk &walk)
+        {
+            if constexpr (Term::kOperands)
+            {
+                if (walk.mapped() && g.n_log >= 7)
+                    return launch_walk<Term>(mods, a, b, dst, g, slices, final, s, MappedWalk<true>{ walk.offsets, walk.first, walk.second });
+                if (walk.mapped())
+                    return launch_walk<Term>(mods, a, b, dst, g, slices, final, s, MappedWalk<false>{ walk.offsets, walk.first, walk.second });
+            }
+            else if (walk.mapped())
+                return hipErrorInvalidValue; // slice scratch is consecutive
+            return launch_walk<Term>(mods, a, b, dst, g, slices, final, s, ConsecutiveWalk{});
+        }
 
         // The host path of every reduction: r [size][out_items][K][N] (planes r_stride words apart) from operands whose planes are
-        // a_plane / b_plane words apart and whose items are [K][N] blocks.  launch(g, dst, slices, final) starts the reduction's own
-        // kernels over grid_planes planes per launch; with slices > 1 they fill scratch [slices][size][out_items][K][N] and the sum
-        // of the slices follows.
+        // a_plane / b_plane words apart and whose items are [K][N] blocks, the terms of an output item being what `walk` says.
+        // launch(g, dst, slices, final) starts the reduction's own kernels over grid_planes planes per launch; with slices > 1 (a cut
+        // of the longest row) they fill scratch [slices][size][out_items][K][N] and the sum of the slices follows.
         template <class Launch>
         hipError_t reduce_items(const ModDesc *mods, size_t a_plane, size_t b_plane, uint64_t *r, size_t r_stride, unsigned size,
-                                unsigned grid_planes, unsigned n_log, unsigned K, size_t out_items, size_t group, unsigned slices,
+                                unsigned grid_planes, unsigned n_log, unsigned K, size_t out_items, const ItemWalk &walk, unsigned slices,
                                 uint64_t *scratch, hipStream_t s, Launch launch)
         {
-            const size_t words = (size_t)K << n_log, out_plane = out_items * words;
+            const size_t words = (size_t)K << n_log, out_plane = out_items * words, group = walk.longest;
             if (!size || !out_plane || !group)
                 return hipSuccess;
             unsigned per_slice;
-            if (!cut(group, slices, per_slice) || out_items > 0xffffffffu || (slices > 1 && !scratch))
+            if (!cut(group, slices, per_slice) || out_items > 0xffffffffu || (slices > 1 && !scratch) || (walk.mapped() && words > 0xffffffffu))
                 return hipErrorInvalidValue;
             const bool final = slices == 1;
-            const ReduceGeom g{ a_plane, b_plane, group * words, words, final ? r_stride : out_plane, final ? 0 : size * out_plane,
-                                grid_planes * out_plane / 2, (unsigned)out_items, (unsigned)group, per_slice, n_log, K };
+            const ReduceGeom g{ a_plane, b_plane, walk.mapped() ? 0 : group * words, words, final ? r_stride : out_plane, final ? 0 : size * out_plane,
+                                grid_planes * out_plane / 2, (unsigned)out_items, walk.mapped() ? 0u : (unsigned)group, per_slice, n_log, K };
             const hipError_t e = launch(g, final ? r : scratch, slices, final);
             if (e != hipSuccess || final)
                 return e;
             const ReduceGeom c{ out_plane, 0, words, size * out_plane, r_stride, 0, size * out_plane / 2, (unsigned)out_items, slices, slices, n_log, K };
-            return launch_reduce<SumTerm<false>>(mods, scratch, scratch, r, c, 1, true, s);
+            return launch_reduce<SumTerm<false>>(mods, scratch, scratch, r, c, 1, true, s, ItemWalk(slices));
         }
     } // namespace
 
@@ -274,21 +362,27 @@ namespace sealhip
         cut(group, slices, per_slice);
         return slices;
     }
+    unsigned batch_reduce_slices(size_t threads, const ItemWalk &walk)
+    {
+        unsigned slices = batch_reduce_slices(threads, walk.mean), per_slice;
+        cut(walk.longest, slices, per_slice); // mean <= longest: the slices of the mean row fit the longest one
+        return slices;
+    }
 
     hipError_t k_sum_items(const ModDesc *mods, const uint64_t *a, size_t a_stride, uint64_t *r, size_t r_stride, unsigned size, unsigned n_log,
-                           unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch, hipStream_t s)
+                           unsigned K, size_t out_items, const ItemWalk &walk, unsigned slices, uint64_t *scratch, hipStream_t s)
     {
-        return reduce_items(mods, a_stride, 0, r, r_stride, size, size, n_log, K, out_items, group, slices, scratch, s,
+        return reduce_items(mods, a_stride, 0, r, r_stride, size, size, n_log, K, out_items, walk, slices, scratch, s,
                             [=](const ReduceGeom &g, uint64_t *dst, unsigned ns, bool final) {
-                                return launch_reduce<SumTerm<true>>(mods, a, a, dst, g, ns, final, s);
+                                return launch_reduce<SumTerm<true>>(mods, a, a, dst, g, ns, final, s, walk);
                             });
     }
 
     hipError_t k_dot_plain_items(const ModDesc *mods, const uint64_t *a, size_t a_stride, const uint64_t *pl, uint64_t *r, size_t r_stride,
-                                 unsigned size, unsigned n_log, unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch,
-                                 hipStream_t s)
+                                 unsigned size, unsigned n_log, unsigned K, size_t out_items, const ItemWalk &walk, unsigned slices,
+                                 uint64_t *scratch, hipStream_t s)
     {
-        return reduce_items(mods, a_stride, 0, r, r_stride, size, 1, n_log, K, out_items, group, slices, scratch, s,
+        return reduce_items(mods, a_stride, 0, r, r_stride, size, 1, n_log, K, out_items, walk, slices, scratch, s,
                             [=](const ReduceGeom &g, uint64_t *dst, unsigned ns, bool final) -> hipError_t {
                                 // three planes at a time, then two or one: the plaintexts are read once for size <= 3
                                 for (unsigned p = 0; p < size;)
@@ -296,9 +390,9 @@ namespace sealhip
                                     const unsigned take = std::min(3u, size - p);
                                     const uint64_t *ap = a + p * a_stride;
                                     uint64_t *dp = dst + p * g.dst_plane;
-                                    const hipError_t e = take == 3   ? launch_reduce<DotPlainTerm<3>>(mods, ap, pl, dp, g, ns, final, s)
-                                                         : take == 2 ? launch_reduce<DotPlainTerm<2>>(mods, ap, pl, dp, g, ns, final, s)
-                                                                     : launch_reduce<DotPlainTerm<1>>(mods, ap, pl, dp, g, ns, final, s);
+                                    const hipError_t e = take == 3   ? launch_reduce<DotPlainTerm<3>>(mods, ap, pl, dp, g, ns, final, s, walk)
+                                                         : take == 2 ? launch_reduce<DotPlainTerm<2>>(mods, ap, pl, dp, g, ns, final, s, walk)
+                                                                     : launch_reduce<DotPlainTerm<1>>(mods, ap, pl, dp, g, ns, final, s, walk);
                                     if (e != hipSuccess)
                                         return e;
                                     p += take;
@@ -308,13 +402,15 @@ namespace sealhip
     }
 
     hipError_t k_dot_items(const ModDesc *mods, const uint64_t *x, size_t x_stride, const uint64_t *y, size_t y_stride, uint64_t *r,
-                           size_t r_stride, unsigned n_log, unsigned K, size_t out_items, size_t group, unsigned slices, uint64_t *scratch,
-                           hipStream_t s)
+                           size_t r_stride, unsigned n_log, unsigned K, size_t out_items, const ItemWalk &walk, unsigned slices,
+                           uint64_t *scratch, hipStream_t s)
     {
-        return reduce_items(mods, x_stride, y_stride, r, r_stride, 3, 1, n_log, K, out_items, group, slices, scratch, s,
+        // the square: one operand and one list of items
+        const bool square = x == y && x_stride == y_stride && walk.first == walk.second;
+        return reduce_items(mods, x_stride, y_stride, r, r_stride, 3, 1, n_log, K, out_items, walk, slices, scratch, s,
                             [=](const ReduceGeom &g, uint64_t *dst, unsigned ns, bool final) {
-                                return x == y && x_stride == y_stride ? launch_reduce<DotItemsTerm<true>>(mods, x, y, dst, g, ns, final, s)
-                                                                      : launch_reduce<DotItemsTerm<false>>(mods, x, y, dst, g, ns, final, s);
+                                return square ? launch_reduce<DotItemsTerm<true>>(mods, x, y, dst, g, ns, final, s, walk)
+                                              : launch_reduce<DotItemsTerm<false>>(mods, x, y, dst, g, ns, final, s, walk);
                             });
     }
 } // namespace sealhip

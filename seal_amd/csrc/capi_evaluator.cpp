@@ -286,6 +286,76 @@ extern "C"
                                           *as<Ciphertext>(destination));
         SHL_CATCH
     }
+    // item maps (library extensions): a CSR list of item numbers in device memory, and the three reductions over the items it names
+    SHL_FUNC ItemMap_Create(void *context, uint64_t rows, const uint64_t *row_offsets, const uint64_t *first_items, const uint64_t *second_items,
+                            uint64_t first_batch, uint64_t second_batch, void **item_map)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        IfNullRet(item_map, SHL_E_POINTER);
+        SHL_TRY
+        *item_map = new ItemMap(*as<Context>(context), rows, row_offsets, first_items, second_items, first_batch, second_batch);
+        SHL_CATCH
+    }
+    SHL_FUNC ItemMap_Destroy(void *thisptr)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        SHL_TRY
+        delete as<ItemMap>(thisptr);
+        SHL_CATCH
+    }
+    SHL_FUNC ItemMap_Info(void *thisptr, uint64_t *rows, uint64_t *terms, uint64_t *longest_row, uint64_t *first_batch, uint64_t *second_batch)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        const ItemMap *m = as<ItemMap>(thisptr);
+        if (rows)
+            *rows = m->rows();
+        if (terms)
+            *terms = m->terms();
+        if (longest_row)
+            *longest_row = m->longest_row();
+        if (first_batch)
+            *first_batch = m->first_batch();
+        if (second_batch)
+            *second_batch = m->second_batch();
+        return SHL_S_OK;
+    }
+    SHL_FUNC Evaluator_SumItemsMapped(void *thisptr, void *encrypted, void *item_map, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted, SHL_E_POINTER);
+        IfNullRet(item_map, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->sum_items_mapped(*as<Ciphertext>(encrypted), *as<ItemMap>(item_map), *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
+    SHL_FUNC Evaluator_DotPlainMapped(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t plain_count, void *item_map,
+                                      double scale, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted, SHL_E_POINTER);
+        IfNullRet(item_map, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->dot_plain_mapped(*as<Ciphertext>(encrypted), device_plain, (size_t)plain_count, *as<ItemMap>(item_map), scale,
+                                                 *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
+    SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted1, SHL_E_POINTER);
+        IfNullRet(encrypted2, SHL_E_POINTER);
+        IfNullRet(item_map, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->dot_items_mapped(*as<Ciphertext>(encrypted1), *as<Ciphertext>(encrypted2), *as<ItemMap>(item_map),
+                                                 *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
     static Plaintext &prepare_plain_dest(void *plain, void *destination)
     {
         Plaintext *src = as<Plaintext>(plain), *dst = as<Plaintext>(destination);

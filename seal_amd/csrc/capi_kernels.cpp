@@ -4,13 +4,13 @@
 
 namespace
 {
-    // The prologue of the raw seams of the batch reductions (shl_reduce_items, shl_dot_items): level, group and cut are checked -
-    // slices == 0 asks for the library's rule over grid_planes * (one result plane) / 2 threads -, *slices_used is set, a call
-    // without a result is the query and ends there; otherwise launch(context, level, out_items, words per item, slices) runs
+    // The prologue of the raw seams of the batch reductions (shl_reduce_items, shl_dot_items, shl_reduce_mapped): level and cut are
+    // checked - slices == 0 asks for the library's rule over grid_planes * (one result plane) / 2 threads and this walk -, *slices_used
+    // is set, a call without a result is the query and ends there; otherwise launch(context, level, words per item, slices) runs
     template <class Launch>
-    SHL_HRESULT raw_reduce(void *context, uint64_t chain_index, bool size_ok, const char *shape, uint64_t grid_planes, uint64_t batch,
-                           uint64_t group, uint64_t slices, uint64_t *slices_used, const uint64_t *r, bool operands, const uint64_t *scratch,
-                           Launch launch)
+    SHL_HRESULT raw_reduce(void *context, uint64_t chain_index, const char *shape_error, uint64_t grid_planes, uint64_t out_items,
+                           const ItemWalk &walk, uint64_t slices, uint64_t *slices_used, const uint64_t *r, bool operands,
+                           const uint64_t *scratch, Launch launch)
     {
         IfNullRet(context, SHL_E_POINTER);
         SHL_TRY
@@ -18,13 +18,13 @@ namespace
         auto l = c->level_by_chain_index(chain_index);
         if (!l)
             throw std::out_of_range("chain_index");
-        if (!group || batch % group || !size_ok)
-            throw std::invalid_argument(shape);
-        const size_t out_items = batch / group, words = (size_t)l->K * c->n();
+        if (shape_error)
+            throw std::invalid_argument(shape_error);
+        const size_t words = (size_t)l->K * c->n();
         if (!slices)
-            slices = batch_reduce_slices(grid_planes * out_items * words / 2, group);
-        if (slices > group || slices > 64)
-            throw std::invalid_argument("1 <= slices <= min(group, 64)");
+            slices = batch_reduce_slices(grid_planes * out_items * words / 2, walk);
+        if (slices > walk.longest || slices > 64)
+            throw std::invalid_argument("1 <= slices <= min(group or longest row, 64)");
         if (slices_used)
             *slices_used = slices;
         if (!r) // a query: the slices the library would use, hence the scratch to pass
@@ -32,8 +32,20 @@ namespace
         IfNullRet(operands, SHL_E_POINTER);
         if (slices > 1 && !scratch)
             throw std::invalid_argument("scratch is null");
-        launch(c, l, out_items, words, (unsigned)slices);
+        launch(c, l, words, (unsigned)slices);
         SHL_CATCH
+    }
+    // consecutive groups: the shape is checked here
+    template <class Launch>
+    SHL_HRESULT raw_reduce(void *context, uint64_t chain_index, bool size_ok, const char *shape, uint64_t grid_planes, uint64_t batch,
+                           uint64_t group, uint64_t slices, uint64_t *slices_used, const uint64_t *r, bool operands, const uint64_t *scratch,
+                           Launch launch)
+    {
+        const bool bad = !group || batch % group || !size_ok;
+        const size_t out_items = bad ? 0 : batch / group;
+        const ItemWalk walk(group);
+        return raw_reduce(context, chain_index, bad ? shape : nullptr, grid_planes, out_items, walk, slices, slices_used, r, operands, scratch,
+                          [&](Context *c, const Level *l, size_t words, unsigned cut) { launch(c, l, out_items, words, walk, cut); });
     }
 } // namespace
 
@@ -93,15 +105,15 @@ extern "C"
                               uint64_t batch, uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream)
     {
         return raw_reduce(context, chain_index, size && size <= 16, "group must divide batch; 1 <= size <= 16", plain ? 1 : size, batch, group,
-                          slices, slices_used, r, a, scratch, [&](Context *c, const Level *l, size_t out_items, size_t words, unsigned cut) {
+                          slices, slices_used, r, a, scratch, [&](Context *c, const Level *l, size_t out_items, size_t words, const ItemWalk &walk, unsigned cut) {
                               const unsigned n_log = (unsigned)c->log_n();
                               if (plain)
                                   hip_ok(k_dot_plain_items(c->dev_mods(), a, batch * words, plain, r, out_items * words, (unsigned)size, n_log, l->K,
-                                                           out_items, group, cut, scratch, (hipStream_t)stream),
+                                                           out_items, walk, cut, scratch, (hipStream_t)stream),
                                          "dot_plain (items)");
                               else
                                   hip_ok(k_sum_items(c->dev_mods(), a, batch * words, r, out_items * words, (unsigned)size, n_log, l->K, out_items,
-                                                     group, cut, scratch, (hipStream_t)stream),
+                                                     walk, cut, scratch, (hipStream_t)stream),
                                          "sum (items)");
                           });
     }
@@ -117,9 +129,9 @@ extern "C"
                            uint64_t group, uint64_t slices, uint64_t *scratch, uint64_t *slices_used, void *stream)
     {
         return raw_reduce(context, chain_index, true, "group must divide batch", 1, batch, group, slices, slices_used, r, x && y, scratch,
-                          [&](Context *c, const Level *l, size_t out_items, size_t words, unsigned cut) {
+                          [&](Context *c, const Level *l, size_t out_items, size_t words, const ItemWalk &walk, unsigned cut) {
                               hip_ok(k_dot_items(c->dev_mods(), x, batch * words, y, batch * words, r, out_items * words, (unsigned)c->log_n(), l->K,
-                                                 out_items, group, cut, scratch, (hipStream_t)stream),
+                                                 out_items, walk, cut, scratch, (hipStream_t)stream),
                                      "dot (items)");
                           });
     }
@@ -128,6 +140,35 @@ extern "C"
         IfNullRet(items, SHL_E_POINTER);
         *items = batch_reduce_dot_items_flush();
         return SHL_S_OK;
+    }
+    SHL_FUNC shl_reduce_mapped(void *context, uint64_t chain_index, int kind, const uint64_t *a, uint64_t a_batch, const uint64_t *b,
+                               uint64_t b_batch, uint64_t *r, uint64_t size, void *item_map, uint64_t slices, uint64_t *scratch,
+                               uint64_t *slices_used, void *stream)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        IfNullRet(item_map, SHL_E_POINTER);
+        const ItemMap *m = as<ItemMap>(item_map);
+        const bool two = kind != 0; // a second operand: the plaintexts, or y
+        const bool bad = kind < 0 || kind > 2 || !size || size > 16 || a_batch != m->first_batch() || (two && b_batch != m->second_batch());
+        const size_t rows = m->rows();
+        const ItemWalk walk = m->walk();
+        return raw_reduce(context, chain_index, bad ? "kind 0 .. 2; 1 <= size <= 16; the batches are the map's" : nullptr, kind == 0 ? size : 1, rows, walk, slices, slices_used, r, a && (b || !two), scratch,
+                          [&](Context *c, const Level *l, size_t words, unsigned cut) {
+                              const unsigned n_log = (unsigned)c->log_n();
+                              hipStream_t s = (hipStream_t)stream;
+                              if (kind == 0)
+                                  hip_ok(k_sum_items(c->dev_mods(), a, a_batch * words, r, rows * words, (unsigned)size, n_log, l->K, rows, walk, cut,
+                                                     scratch, s),
+                                         "sum (mapped)");
+                              else if (kind == 1)
+                                  hip_ok(k_dot_plain_items(c->dev_mods(), a, a_batch * words, b, r, rows * words, (unsigned)size, n_log, l->K, rows,
+                                                           walk, cut, scratch, s),
+                                         "dot_plain (mapped)");
+                              else
+                                  hip_ok(k_dot_items(c->dev_mods(), a, a_batch * words, b, b_batch * words, r, rows * words, n_log, l->K, rows, walk,
+                                                     cut, scratch, s),
+                                         "dot (mapped)");
+                          });
     }
     SHL_FUNC shl_apply_galois(
         void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys,

@@ -795,14 +795,14 @@ namespace sealhip
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
     }
     void Evaluator::check_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
-                                       const Ciphertext &dest) const
+                                       const Ciphertext &dest, bool per_item) const
     {
         check_valid(e, "encrypted");
         if (!plain)
             throw std::invalid_argument("device_plain is null");
         if ((uintptr_t)plain % 16)
             throw std::invalid_argument("device_plain must be 16-byte aligned");
-        if (!batch || batch != e.batch())
+        if (!batch || (per_item && batch != e.batch()))
             throw std::invalid_argument("batch does not equal the ciphertext's batch");
         if (context_.scheme() == Scheme::ckks)
         {
@@ -1008,25 +1008,101 @@ namespace sealhip
         lift_chunks(PlainOperand(context_, lvl, coefficients, false, 1.0), *lvl, 1, batch, out, [](size_t, unsigned, const uint64_t *, size_t) {});
     }
 
-    // ---- sums over the items of a device-resident batch (include/sealhip.h: Evaluator_SumItems / Evaluator_DotPlainDevice)
-    void Evaluator::check_reduce_items(const Ciphertext &e, size_t group, const Ciphertext &dest) const
+    // ---- sums over the items of a device-resident batch (include/sealhip.h: Evaluator_SumItems / Evaluator_DotPlainDevice /
+    // Evaluator_DotItems and their *Mapped forms).  A call is "rows output items and a walk": consecutive groups or an ItemMap
+    ItemMap::ItemMap(const Context &context, uint64_t rows, const uint64_t *row_offsets, const uint64_t *first_items, const uint64_t *second_items,
+                     uint64_t first_batch, uint64_t second_batch)
+        : ctx_(&context), rows_((size_t)rows), first_batch_((size_t)first_batch), second_batch_((size_t)second_batch)
+    {
+        if (!row_offsets || !first_items)
+            throw std::invalid_argument("row_offsets or first_items is null");
+        if (!rows || rows >= (uint64_t(1) << 32))
+            throw std::invalid_argument("1 <= rows < 2^32");
+        if (row_offsets[0])
+            throw std::invalid_argument("row_offsets[0] must be 0");
+        for (uint64_t o = 0; o < rows; o++)
+        {
+            if (row_offsets[o + 1] <= row_offsets[o]) // add_many of nothing throws in the reference; the sum would be transparent
+                throw std::invalid_argument("row_offsets must increase strictly: a row cannot be empty");
+            longest_ = std::max<size_t>(longest_, (size_t)(row_offsets[o + 1] - row_offsets[o]));
+        }
+        const uint64_t terms = row_offsets[rows];
+        if (terms >= (uint64_t(1) << 32))
+            throw std::invalid_argument("terms < 2^32");
+        if (!second_items && second_batch != first_batch)
+            throw std::invalid_argument("one list of items: second_batch must equal first_batch");
+        for (uint64_t t = 0; t < terms; t++)
+            if (first_items[t] >= first_batch || (second_items && second_items[t] >= second_batch))
+                throw std::invalid_argument("an item number is not below its batch");
+        terms_ = (size_t)terms;
+        // [rows + 1 offsets][terms][terms], each list padded to 16 bytes
+        const auto pad4 = [](size_t n) { return (n + 3) & ~size_t(3); };
+        const size_t off_at = 0, first_at = pad4(rows_ + 1), second_at = first_at + pad4(terms_);
+        std::vector<uint32_t> host(second_items ? second_at + pad4(terms_) : second_at, 0);
+        for (size_t o = 0; o <= rows_; o++)
+            host[off_at + o] = (uint32_t)row_offsets[o];
+        for (size_t t = 0; t < terms_; t++)
+        {
+            host[first_at + t] = (uint32_t)first_items[t];
+            if (second_items)
+                host[second_at + t] = (uint32_t)second_items[t];
+        }
+        block_ = DevicePool::global().alloc_words(host.size() / 2);
+        try
+        {
+            ck(hipDeviceSynchronize(), "ItemMap upload"); // not a hot-path call: whatever used the block before is done
+            copy_h2d(block_, host.data(), host.size() * 4);
+        }
+        catch (...)
+        {
+            DevicePool::global().free_words(block_);
+            throw;
+        }
+        const uint32_t *base = reinterpret_cast<const uint32_t *>(block_);
+        offsets_ = base + off_at;
+        first_ = base + first_at;
+        second_ = second_items ? base + second_at : first_;
+    }
+    ItemMap::~ItemMap()
+    {
+        DevicePool::global().free_words(block_); // tagged by the pool: work that still reads the lists is waited for by the next user
+    }
+    ItemWalk ItemMap::walk() const
+    {
+        return ItemWalk(longest_, (terms_ + rows_ - 1) / rows_, offsets_, first_, second_);
+    }
+
+    ItemWalk Evaluator::consecutive_walk(const Ciphertext &e, size_t group, size_t &rows) const
+    {
+        if (!group || e.batch() % group)
+            throw std::invalid_argument("group must divide the ciphertext's batch");
+        rows = e.batch() / group;
+        return ItemWalk(group);
+    }
+    ItemWalk Evaluator::mapped_walk(const Ciphertext &e, const ItemMap &map, size_t &rows) const
+    {
+        if (map.context() != &context_)
+            throw std::invalid_argument("item_map is not valid for the current context");
+        if (e.batch() != map.first_batch())
+            throw std::invalid_argument("the ciphertext's batch does not equal the map's first_batch");
+        rows = map.rows();
+        return map.walk();
+    }
+    void Evaluator::check_reduce_items(const Ciphertext &e, size_t rows, const Ciphertext &dest) const
     {
         if (&dest == &e)
             throw std::invalid_argument("destination must be different from encrypted");
-        if (!group || e.batch() % group)
-            throw std::invalid_argument("group must divide the ciphertext's batch");
-        if (dest.batch() != e.batch() / group)
-            throw std::invalid_argument("destination's batch does not equal the ciphertext's batch divided by group");
+        if (dest.batch() != rows)
+            throw std::invalid_argument("destination's batch does not equal the number of output items");
     }
-    // The one host path of the reductions, after their checks and with the operands settled: dest becomes `size` planes of
-    // e.batch() / group items at e's level with the given metadata, the cut is the library's rule for grid_planes * (one result plane)
-    // / 2 threads, and launch(out_items, slices, scratch) starts the kernels
+    // The one host path of the reductions, after their checks and with the operands settled: dest becomes `size` planes of `rows`
+    // items at e's level with the given metadata, the cut is the library's rule for grid_planes * (one result plane) / 2 threads and
+    // this walk, and launch(slices, scratch) starts the kernels
     template <class Launch>
-    void Evaluator::reduce_items(const Ciphertext &e, size_t group, size_t size, size_t grid_planes, bool ntt_form, double scale,
-                                 uint64_t correction_factor, Ciphertext &dest, const char *what, Launch launch) const
+    void Evaluator::reduce_items(const Ciphertext &e, size_t rows, const ItemWalk &walk, size_t size, size_t grid_planes, bool ntt_form,
+                                 double scale, uint64_t correction_factor, Ciphertext &dest, const char *what, Launch launch) const
     {
         const Level &lvl = *e.level();
-        const size_t out_items = e.batch() / group;
         if (dest.ctx_ != e.ctx_)
         {
             dest.release();
@@ -1036,32 +1112,44 @@ namespace sealhip
         dest.is_ntt_form() = ntt_form;
         dest.scale() = scale;
         dest.correction_factor() = correction_factor;
-        const unsigned slices = batch_reduce_slices(grid_planes * dest.plane_words() / 2, group);
+        const unsigned slices = batch_reduce_slices(grid_planes * dest.plane_words() / 2, walk);
         std::unique_ptr<Scratch> scratch;
         if (slices > 1)
-            scratch.reset(new Scratch(batch_reduce_scratch_words(slices, (unsigned)size, out_items, (unsigned)context_.log_n(), lvl.K)));
-        ck(launch(out_items, slices, scratch ? scratch->p : nullptr), what);
+            scratch.reset(new Scratch(batch_reduce_scratch_words(slices, (unsigned)size, rows, (unsigned)context_.log_n(), lvl.K)));
+        ck(launch(slices, scratch ? scratch->p : nullptr), what);
         throw_if_transparent(dest);
+    }
+    void Evaluator::sum_items(const Ciphertext &e, size_t rows, const ItemWalk &walk, Ciphertext &dest) const
+    {
+        check_reduce_items(e, rows, dest);
+        e.settle(); // the operand's words are read by what follows
+        // one thread per output pair, the planes in the grid
+        reduce_items(e, rows, walk, e.size(), e.size(), e.is_ntt_form(), e.scale(), e.correction_factor(), dest, "sum (items)",
+                     [&](unsigned slices, uint64_t *scratch) {
+                         return k_sum_items(context_.dev_mods(), e.data_, e.plane_words(), dest.data_, dest.plane_words(), (unsigned)e.size(),
+                                            (unsigned)context_.log_n(), e.level()->K, rows, walk, slices, scratch, stream_);
+                     });
     }
     void Evaluator::sum_items(const Ciphertext &e, size_t group, Ciphertext &dest) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         check_valid(e, "encrypted");
-        check_reduce_items(e, group, dest);
-        e.settle(); // the operand's words are read by what follows
-        // one thread per output pair, the planes in the grid
-        reduce_items(e, group, e.size(), e.size(), e.is_ntt_form(), e.scale(), e.correction_factor(), dest, "sum (items)",
-                     [&](size_t out_items, unsigned slices, uint64_t *scratch) {
-                         return k_sum_items(context_.dev_mods(), e.data_, e.plane_words(), dest.data_, dest.plane_words(), (unsigned)e.size(),
-                                            (unsigned)context_.log_n(), e.level()->K, out_items, group, slices, scratch, stream_);
-                     });
+        size_t rows;
+        const ItemWalk walk = consecutive_walk(e, group, rows);
+        sum_items(e, rows, walk, dest);
     }
-    void Evaluator::dot_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, size_t group, double scale,
-                                     Ciphertext &dest) const
+    void Evaluator::sum_items_mapped(const Ciphertext &e, const ItemMap &map, Ciphertext &dest) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        check_plain_device(e, plain, batch, true, scale, dest);
-        check_reduce_items(e, group, dest);
+        check_valid(e, "encrypted");
+        size_t rows;
+        const ItemWalk walk = mapped_walk(e, map, rows);
+        sum_items(e, rows, walk, dest);
+    }
+    void Evaluator::dot_plain_items(const Ciphertext &e, const uint64_t *plain, size_t, size_t rows, const ItemWalk &walk, double scale,
+                                    Ciphertext &dest) const
+    {
+        check_reduce_items(e, rows, dest);
         // coefficient-form operands have no place in a reduction: the monomial branch of multiply_plain_normal is per item and data
         // dependent (include/sealhip.h)
         if (!e.is_ntt_form())
@@ -1072,48 +1160,91 @@ namespace sealhip
             throw std::invalid_argument("scale out of bounds");
         e.settle(); // the operand's words are read by what follows
         // one thread per output pair of one plane: the product loops over the planes
-        reduce_items(e, group, e.size(), 1, e.is_ntt_form(), new_scale, e.correction_factor(), dest, "dot_plain (items)",
-                     [&](size_t out_items, unsigned slices, uint64_t *scratch) {
+        reduce_items(e, rows, walk, e.size(), 1, e.is_ntt_form(), new_scale, e.correction_factor(), dest, "dot_plain (items)",
+                     [&](unsigned slices, uint64_t *scratch) {
                          return k_dot_plain_items(context_.dev_mods(), e.data_, e.plane_words(), plain, dest.data_, dest.plane_words(),
-                                                  (unsigned)e.size(), (unsigned)context_.log_n(), e.level()->K, out_items, group, slices, scratch,
+                                                  (unsigned)e.size(), (unsigned)context_.log_n(), e.level()->K, rows, walk, slices, scratch,
                                                   stream_);
                      });
     }
-
-    // sum over the items of a group of the 2 x 2 tensor products (include/sealhip.h: Evaluator_DotItems): the checks and metadata of
-    // multiply (ckks_multiply / bgv_multiply at 2 x 2) and of sum_items, one kernel and no stored product
-    void Evaluator::dot_items(const Ciphertext &e1, const Ciphertext &e2, size_t group, Ciphertext &dest) const
+    void Evaluator::dot_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, size_t group, double scale,
+                                     Ciphertext &dest) const
     {
         StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        check_valid(e1, "encrypted1");
-        check_valid(e2, "encrypted2");
-        const Scheme scheme = context_.scheme();
-        // BFV's product rounds per item (BEHZ): the sum of the rounded products is not the rounded sum
-        if (scheme != Scheme::ckks && scheme != Scheme::bgv)
-            throw std::invalid_argument("unsupported scheme");
+        check_plain_device(e, plain, batch, true, scale, dest);
+        size_t rows;
+        const ItemWalk walk = consecutive_walk(e, group, rows);
+        dot_plain_items(e, plain, batch, rows, walk, scale, dest);
+    }
+    void Evaluator::dot_plain_mapped(const Ciphertext &e, const uint64_t *plain, size_t plain_count, const ItemMap &map, double scale,
+                                     Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_plain_device(e, plain, plain_count, true, scale, dest, false);
+        if (plain_count != map.second_batch())
+            throw std::invalid_argument("plain_count does not equal the map's second_batch");
+        size_t rows;
+        const ItemWalk walk = mapped_walk(e, map, rows);
+        dot_plain_items(e, plain, plain_count, rows, walk, scale, dest);
+    }
+
+    // sum over the terms of an output item of the 2 x 2 tensor products (include/sealhip.h: Evaluator_DotItems): the checks and
+    // metadata of multiply (ckks_multiply / bgv_multiply at 2 x 2) and of sum_items, one kernel and no stored product.  The batches
+    // of the operands are the walk's business and checked by the callers
+    void Evaluator::dot_items(const Ciphertext &e1, const Ciphertext &e2, size_t rows, const ItemWalk &walk, Ciphertext &dest) const
+    {
         if (e1.level() != e2.level())
             throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
-        if (e1.batch() != e2.batch())
-            throw std::invalid_argument("batch mismatch");
         if (!(e1.is_ntt_form() && e2.is_ntt_form()))
             throw std::invalid_argument("encrypted1 or encrypted2 must be in NTT form");
         if (e1.size() != 2 || e2.size() != 2)
             throw std::invalid_argument("encrypted1 and encrypted2 must have size 2");
-        check_reduce_items(e1, group, dest);
+        check_reduce_items(e1, rows, dest);
         if (&dest == &e2)
             throw std::invalid_argument("destination must be different from encrypted");
         const Level &lvl = *e1.level();
-        const bool ckks = scheme == Scheme::ckks;
+        const bool ckks = context_.scheme() == Scheme::ckks;
         const double new_scale = ckks ? e1.scale() * e2.scale() : e1.scale();
         if (ckks && !scale_within_bounds(new_scale, lvl))
             throw std::invalid_argument("scale out of bounds");
         const uint64_t cf = ckks ? 1 : host::mulmod(e1.correction_factor(), e2.correction_factor(), context_.plain_modulus());
         // operands first: whatever is pending on them (a key-switch tail, a product of their own) is settled before their words are read
         const uint64_t *xw = e1.data(), *yw = &e1 == &e2 ? xw : e2.data();
-        reduce_items(e1, group, 3, 1, true, new_scale, cf, dest, "dot (items)", [&](size_t out_items, unsigned slices, uint64_t *scratch) {
+        reduce_items(e1, rows, walk, 3, 1, true, new_scale, cf, dest, "dot (items)", [&](unsigned slices, uint64_t *scratch) {
             return k_dot_items(context_.dev_mods(), xw, e1.plane_words(), yw, e2.plane_words(), dest.data_, dest.plane_words(),
-                               (unsigned)context_.log_n(), lvl.K, out_items, group, slices, scratch, stream_);
+                               (unsigned)context_.log_n(), lvl.K, rows, walk, slices, scratch, stream_);
         });
+    }
+    // what both forms check before they know their walk
+    static void check_dot_items_scheme(Scheme scheme)
+    {
+        // BFV's product rounds per item (BEHZ): the sum of the rounded products is not the rounded sum
+        if (scheme != Scheme::ckks && scheme != Scheme::bgv)
+            throw std::invalid_argument("unsupported scheme");
+    }
+    void Evaluator::dot_items(const Ciphertext &e1, const Ciphertext &e2, size_t group, Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_valid(e1, "encrypted1");
+        check_valid(e2, "encrypted2");
+        check_dot_items_scheme(context_.scheme());
+        if (e1.batch() != e2.batch())
+            throw std::invalid_argument("batch mismatch");
+        size_t rows;
+        const ItemWalk walk = consecutive_walk(e1, group, rows);
+        dot_items(e1, e2, rows, walk, dest);
+    }
+    void Evaluator::dot_items_mapped(const Ciphertext &e1, const Ciphertext &e2, const ItemMap &map, Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_valid(e1, "encrypted1");
+        check_valid(e2, "encrypted2");
+        check_dot_items_scheme(context_.scheme());
+        if (e2.batch() != map.second_batch())
+            throw std::invalid_argument("encrypted2's batch does not equal the map's second_batch");
+        size_t rows;
+        const ItemWalk walk = mapped_walk(e1, map, rows);
+        dot_items(e1, e2, rows, walk, dest);
     }
 
     void Evaluator::add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const

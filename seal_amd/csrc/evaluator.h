@@ -285,6 +285,37 @@ namespace sealhip
         size_t key_bytes(const Key &k) const;
     };
 
+    // A device-resident CSR list of item numbers (include/sealhip.h: ItemMap_Create): which items of a batch, or which pairs of
+    // items of two, the terms of each output item of a mapped reduction are.  Validated once, at construction (std::invalid_argument);
+    // uploaded once as 32-bit words, each list 16-byte aligned in one pool block, with a synchronous copy after a device drain.  The
+    // reductions read the lists from HBM, so one map serves many calls and recordings.  The destructor hands the block back to the
+    // stream-aware pool (pool.h) outside any stream scope, i.e. tagged "unknown": its next user first waits for every registered
+    // stream and the NULL stream, so a map may be destroyed while work that reads it is still queued - nothing is drained here.
+    struct ItemWalk;
+    class ItemMap
+    {
+    public:
+        ItemMap(const Context &context, uint64_t rows, const uint64_t *row_offsets, const uint64_t *first_items, const uint64_t *second_items,
+                uint64_t first_batch, uint64_t second_batch);
+        ~ItemMap();
+        ItemMap(const ItemMap &) = delete;
+        ItemMap &operator=(const ItemMap &) = delete;
+        const Context *context() const { return ctx_; }
+        size_t rows() const { return rows_; }
+        size_t terms() const { return terms_; }
+        size_t longest_row() const { return longest_; }
+        size_t first_batch() const { return first_batch_; }
+        size_t second_batch() const { return second_batch_; }
+        bool one_list() const { return first_ == second_; }
+        ItemWalk walk() const;
+
+    private:
+        const Context *ctx_;
+        size_t rows_, terms_ = 0, longest_ = 0, first_batch_, second_batch_;
+        uint64_t *block_ = nullptr;
+        const uint32_t *offsets_ = nullptr, *first_ = nullptr, *second_ = nullptr;
+    };
+
     class Evaluator
     {
     public:
@@ -351,6 +382,15 @@ namespace sealhip
         // on batches of one and add_many over the products, without storing a product.  CKKS and BGV, both operands of size 2 and in
         // NTT form; encrypted1 and encrypted2 may be the same object; destination is another object (size 3 afterwards).
         void dot_items(const Ciphertext &encrypted1, const Ciphertext &encrypted2, size_t group, Ciphertext &destination) const;
+        // The same three reductions over the items an ItemMap names (include/sealhip.h: Evaluator_SumItemsMapped ...): item o of
+        // destination, a batch of map.rows() items, is the sum over the terms t of row o of encrypted_first[t], of
+        // encrypted_first[t] (.) plain_second[t], or of encrypted1_first[t] (x) encrypted2_second[t].  Checks, metadata, settling and
+        // words are those of the forms above on the named items; encrypted's batch is the map's first_batch, the plaintexts' count /
+        // encrypted2's batch its second_batch.
+        void sum_items_mapped(const Ciphertext &encrypted, const ItemMap &map, Ciphertext &destination) const;
+        void dot_plain_mapped(const Ciphertext &encrypted, const uint64_t *plain, size_t plain_count, const ItemMap &map, double scale,
+                              Ciphertext &destination) const;
+        void dot_items_mapped(const Ciphertext &encrypted1, const Ciphertext &encrypted2, const ItemMap &map, Ciphertext &destination) const;
         void add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const;
         void multiply_many(const std::vector<const Ciphertext *> &encrypteds, const KSwitchKeys &relin_keys, Ciphertext &destination) const;
         void exponentiate_inplace(Ciphertext &encrypted, uint64_t exponent, const KSwitchKeys &relin_keys) const;
@@ -454,14 +494,23 @@ namespace sealhip
         void lift_chunks(const PlainOperand &plain, const Level &lvl, uint64_t scale_by, size_t batch, uint64_t *out, Use use) const;
         // what add_plain / sub_plain accept per scheme (shared by the per-object and the per-item forms)
         void check_addsub_plain_forms(const Ciphertext &encrypted, bool plain_is_ntt, const Level *plain_level, double plain_scale) const;
+        // per_item: one plaintext per item of encrypted (batch must be its batch); otherwise `batch` plaintexts that a map names
         void check_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
-                                const Ciphertext &destination) const;
+                                const Ciphertext &destination, bool per_item = true) const;
         uint64_t *begin_result(const Ciphertext &encrypted, Ciphertext &destination) const; // destination shaped like encrypted, words undefined
-        void check_reduce_items(const Ciphertext &encrypted, size_t group, const Ciphertext &destination) const;
-        // destination <- `size` planes of batch / group items with this metadata, filled by launch(out_items, slices, scratch)
+        // the walk of consecutive groups (group divides the batch) or of a map (whose first_batch is the batch); -> its output items
+        ItemWalk consecutive_walk(const Ciphertext &encrypted, size_t group, size_t &rows) const;
+        ItemWalk mapped_walk(const Ciphertext &encrypted, const ItemMap &map, size_t &rows) const;
+        void check_reduce_items(const Ciphertext &encrypted, size_t rows, const Ciphertext &destination) const;
+        // destination <- `size` planes of `rows` items with this metadata, filled by launch(slices, scratch)
         template <class Launch>
-        void reduce_items(const Ciphertext &encrypted, size_t group, size_t size, size_t grid_planes, bool ntt_form, double scale,
-                          uint64_t correction_factor, Ciphertext &destination, const char *what, Launch launch) const;
+        void reduce_items(const Ciphertext &encrypted, size_t rows, const ItemWalk &walk, size_t size, size_t grid_planes, bool ntt_form,
+                          double scale, uint64_t correction_factor, Ciphertext &destination, const char *what, Launch launch) const;
+        void sum_items(const Ciphertext &encrypted, size_t rows, const ItemWalk &walk, Ciphertext &destination) const;
+        void dot_plain_items(const Ciphertext &encrypted, const uint64_t *plain, size_t plain_count, size_t rows, const ItemWalk &walk,
+                             double scale, Ciphertext &destination) const;
+        void dot_items(const Ciphertext &encrypted1, const Ciphertext &encrypted2, size_t rows, const ItemWalk &walk,
+                       Ciphertext &destination) const;
         void bgv_correct_and_combine(
             Scratch &delta, const uint64_t *a, size_t a_stride, const ShoupOp *mul, unsigned ncomp, size_t items, uint64_t *out0,
             uint64_t *out1, size_t out_stride, int epi) const;

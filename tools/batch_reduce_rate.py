@@ -18,7 +18,18 @@ first; median and range per cell, the measured time ratio next to the byte ratio
 Sweep: the kernels on raw words (shl_reduce_items) at N = 8192, K = 3, size 2, groups of 64, for 1 .. 64 output items, in one
 launch and cut into 2 .. 64 slices: where the one-launch form catches up sets the threshold, the fastest cut the slice count.
 
-  python tools/batch_reduce_rate.py [--batch 256] [--reps 10] [--out FILE] [--small] [--lib PATH] [--no-headline] [--no-sweep]"""
+Item maps (--mapped): the kernels on raw words through the seams, by the library's rule, at the sweep's shapes (N = 8192, K = 3,
+groups of 64, 1 .. 64 output items) and at the headline level (N = 65536, K = 15, batch 256 in groups of 16), for the sum, the
+plaintext dot product and the ciphertext dot product, interleaved sample by sample:
+  (a) the contiguous form (shl_reduce_items / shl_dot_items) of this build - and, with --parent-lib, of the library built from the
+      parent commit, timed TWICE in every round (its A/A spread) next to this build's;
+  (b) shl_reduce_mapped with the identity map (rows of g consecutive items): (b) / (a) is the cost of the walk;
+  (c) a random permutation of the same items in the same rows;
+  (d) a ragged map with the same number of terms (row lengths drawn at random, every item once).
+A sample is the time of --inner calls between two HIP events; GB/s are the bytes the reduction needs over the median sample.
+
+  python tools/batch_reduce_rate.py [--batch 256] [--reps 10] [--out FILE] [--small] [--lib PATH] [--no-headline] [--no-sweep]
+                                    [--mapped [--parent-lib PATH] [--inner 20] [--mapped-out FILE]] [--no-composition]"""
 import argparse
 import ctypes as C
 import os
@@ -131,6 +142,127 @@ def sweep(a, lines):
     lines.append("")
 
 
+def parent_context(path, n, primes):
+    """the library built from the parent commit, with a CKKS context of its own (handles of one library never reach the other; the
+    context lives until the process ends)"""
+    lib = C.CDLL(os.path.abspath(path))
+    for name in ("EncParams_Create1", "EncParams_SetPolyModulusDegree", "EncParams_SetCoeffModulus", "SEALContext_Create", "shl_reduce_items",
+                 "shl_dot_items"):
+        getattr(lib, name).restype = C.c_long
+    parms, ctx = C.c_void_p(), C.c_void_p()
+    for hr in (lib.EncParams_Create1(C.c_uint8(2), C.byref(parms)), lib.EncParams_SetPolyModulusDegree(parms, C.c_uint64(n)),
+               lib.EncParams_SetCoeffModulus(parms, C.c_uint64(len(primes)), (C.c_uint64 * len(primes))(*primes)),
+               lib.SEALContext_Create(parms, C.c_bool(True), C.c_int(0), C.byref(ctx))):
+        if hr & 0xFFFFFFFF:
+            raise RuntimeError("parent library: HRESULT 0x%08X" % (hr & 0xFFFFFFFF))
+    return lib, ctx
+
+
+def ragged_lengths(rng, rows, terms):
+    """`rows` lengths >= 1 that add up to `terms`"""
+    if rows == 1:
+        return [terms]
+    cuts = np.sort(rng.choice(np.arange(1, terms), rows - 1, replace=False))
+    return [int(v) for v in np.diff(np.concatenate(([0], cuts, [terms])))]
+
+
+def mapped(a, lines, table):
+    size = 2
+    shapes = [(SWEEP_N, SWEEP_BITS, out_items * SWEEP_GROUP, SWEEP_GROUP) for out_items in (1, 2, 4, 8, 16, 32, 64)]
+    if not a.no_headline:
+        shapes.append((SHAPES[0][0], SHAPES[0][1], a.batch, 16 if a.batch % 16 == 0 and a.batch > 16 else a.batch))
+    rng = np.random.default_rng(3)
+    held = {}
+    for n, bits, batch, group in shapes:
+        primes = coeff_modulus_create(n, bits)
+        if (n, tuple(bits)) not in held:
+            d = DeviceSide("ckks", n, primes)
+            held[(n, tuple(bits))] = (d, parent_context(a.parent_lib, n, primes) if a.parent_lib else None)
+        d, parent = held[(n, tuple(bits))]
+        lib, ci = S._native.lib(), d.ctx.chain_index(d.ctx.first_parms_id())
+        K, rows = len(d.ctx.coeff_modulus_at(ci)), batch // group
+        words = K * n
+        P = batch * words * 8
+        # timing does not depend on the words: the operands are whatever the allocation holds (the tests own correctness)
+        x, y, pl = S.DeviceBuffer(size * batch * words), S.DeviceBuffer(size * batch * words), S.DeviceBuffer(batch * words)
+        r = S.DeviceBuffer(3 * rows * words)
+        identity = [list(range(o * group, (o + 1) * group)) for o in range(rows)]
+        perm = [int(v) for v in rng.permutation(batch)]
+        permuted = [perm[o * group:(o + 1) * group] for o in range(rows)]
+        lengths, at, ragged = ragged_lengths(rng, rows, batch), 0, []
+        for ln in lengths:
+            ragged.append(perm[at:at + ln])
+            at += ln
+        maps = {"identity map": S.ItemMap(d.ctx, identity, batch), "permuted map": S.ItemMap(d.ctx, permuted, batch),
+                "ragged map": S.ItemMap(d.ctx, ragged, batch)}
+        lines.append("N = %d, K = %d, size %d, batch %d in %d rows (contiguous: groups of %d; ragged rows: %d .. %d terms); median "
+                     "[min .. max] of %d interleaved samples of %d calls each (HIP events), ms per call"
+                     % (n, K, size, batch, rows, group, min(lengths), max(lengths), a.reps, a.inner))
+        used = C.c_uint64()
+        # scratch for the widest cut the rule makes of these maps (the contiguous forms cut like the identity map)
+        most = 1
+        for m in maps.values():
+            for kind in (0, 1, 2):
+                S._native.check(lib.shl_reduce_mapped(d.ctx._h, C.c_uint64(ci), C.c_int(kind), None, C.c_uint64(batch), None,
+                                                      C.c_uint64(batch if kind else 0), None, C.c_uint64(size), m._h, C.c_uint64(0), None,
+                                                      C.byref(used), None))
+                most = max(most, used.value)
+        scratch = S.DeviceBuffer(most * 3 * rows * words)
+        for kind, what, nbytes in ((0, "sum", size * P + size * P // group), (1, "dot plain", (size + 1) * P + size * P // group),
+                                   (2, "dot items", 4 * P + 3 * P // group)):
+            b = None if kind == 0 else (pl if kind == 1 else y)
+
+            def contiguous(l, ctx_h):
+                if kind == 2:
+                    hr = l.shl_dot_items(ctx_h, C.c_uint64(ci), C.c_void_p(x.ptr), C.c_void_p(y.ptr), C.c_void_p(r.ptr), C.c_uint64(batch),
+                                         C.c_uint64(group), C.c_uint64(0), C.c_void_p(scratch.ptr), C.byref(used), None)
+                else:
+                    hr = l.shl_reduce_items(ctx_h, C.c_uint64(ci), C.c_void_p(x.ptr), C.c_void_p(b.ptr if b else None), C.c_void_p(r.ptr),
+                                            C.c_uint64(size), C.c_uint64(batch), C.c_uint64(group), C.c_uint64(0), C.c_void_p(scratch.ptr),
+                                            C.byref(used), None)
+                S._native.check(hr)
+
+            def through_map(m):
+                S._native.check(lib.shl_reduce_mapped(d.ctx._h, C.c_uint64(ci), C.c_int(kind), C.c_void_p(x.ptr), C.c_uint64(batch),
+                                                      C.c_void_p(b.ptr if b else None), C.c_uint64(batch if b else 0), C.c_void_p(r.ptr),
+                                                      C.c_uint64(size), m._h, C.c_uint64(0), C.c_void_p(scratch.ptr), C.byref(used), None))
+
+            def many(fn):
+                def run():
+                    for _ in range(a.inner):
+                        fn()
+                return run
+
+            fns = [("contiguous", many(lambda: contiguous(lib, d.ctx._h)))]
+            if parent:
+                fns += [("parent A", many(lambda: contiguous(*parent))), ("parent B", many(lambda: contiguous(*parent)))]
+            fns += [(name, many(lambda m=m: through_map(m))) for name, m in maps.items()]
+            ms = {name: [v / a.inner for v in vals] for name, vals in interleaved(fns, a.reps).items()}
+            slices = {}
+            for name, m in maps.items():
+                through_map(m)
+                slices[name] = used.value
+            contiguous(lib, d.ctx._h)
+            slices["contiguous"] = used.value
+            S.device_synchronize()
+            med = {name: max(float(np.median(v)), 1e-9) for name, v in ms.items()}
+            for name, _ in fns:
+                lines.append("  %-10s %-13s %s%s" % (what, name, cell(ms[name], nbytes), "  slices %d" % slices[name] if name in slices else ""))
+            ratios = "identity / contiguous %.3f, permuted / contiguous %.3f, ragged / contiguous %.3f" % tuple(
+                med[k] / med["contiguous"] for k in ("identity map", "permuted map", "ragged map"))
+            if parent:
+                ratios += "; this build / parent %.3f, parent A / parent B %.3f" % (
+                    med["contiguous"] / (0.5 * (med["parent A"] + med["parent B"])), med["parent A"] / med["parent B"])
+            lines.append("  %-10s %s" % (what, ratios))
+            print("N = %d, %d rows: %s %s" % (n, rows, what, ratios), file=sys.stderr, flush=True)   # progress
+            gbs = lambda k: nbytes / max(med[k], 1e-9) / 1e6
+            table.append("| %d | %d | %d x %d | %s | %s | %.0f | %.0f | %.3f | %.0f | %.0f | %s |" % (
+                n, K, rows, group, what, "%.0f (A / B %.3f)" % (gbs("parent A"), med["parent A"] / med["parent B"]) if parent else "-",
+                gbs("contiguous"), gbs("identity map"), med["identity map"] / med["contiguous"], gbs("permuted map"), gbs("ragged map"),
+                "%.3f" % (med["contiguous"] / (0.5 * (med["parent A"] + med["parent B"]))) if parent else "-"))
+        lines.append("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
@@ -140,6 +272,11 @@ def main():
     ap.add_argument("--lib", help="library to load instead of the gfx950 build (the emulated one, for a dry run)")
     ap.add_argument("--no-headline", action="store_true", help="skip the N = 65536 shape")
     ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--no-composition", action="store_true", help="skip the fused forms against their composition")
+    ap.add_argument("--mapped", action="store_true", help="item maps next to the contiguous forms (see above)")
+    ap.add_argument("--parent-lib", help="libsealhip.so built from the parent commit: timed next to this build, twice per round")
+    ap.add_argument("--inner", type=int, default=20, help="calls per timed sample of --mapped")
+    ap.add_argument("--mapped-out", help="file for the --mapped section (default: --out)")
     a = ap.parse_args()
     global SHAPES, SWEEP_N, SWEEP_BITS, SWEEP_GROUP
     if a.small:
@@ -148,16 +285,27 @@ def main():
     S.load(a.lib)
     lines = []
     for n, bits in SHAPES:
-        if not (a.no_headline and n == 65536):
+        if not (a.no_headline and n == 65536) and not a.no_composition:
             composition(n, bits, a, lines)
     if not a.no_sweep:
         sweep(a, lines)
     text = "\n".join(lines) + "\n"
     print(text)
-    if a.out:
+    if a.out and lines:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(text)
+    if a.mapped:
+        lines, table = [], ["| N | K | rows x group | term | parent GB/s | this build GB/s | identity map GB/s | identity / contiguous | permuted GB/s | ragged GB/s | this build / parent |",
+                            "|---|---|---|---|---|---|---|---|---|---|---|"]
+        mapped(a, lines, table)
+        text = "\n".join(lines + table) + "\n"
+        print(text)
+        if a.mapped_out or a.out:
+            path = a.mapped_out or a.out
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                f.write(text)
 
 
 if __name__ == "__main__":
