@@ -511,6 +511,52 @@ SHL_FUNC Evaluator_SumItemsMapped(void *thisptr, void *encrypted, void *item_map
 SHL_FUNC Evaluator_DotPlainMapped(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t plain_count, void *item_map,
                                   double scale, void *destination);
 SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination);
+/* Scalar weights (library extensions): a dense plaintext matrix of SCALARS times a vector of ciphertexts,
+ * out_o = sum_b w[o][b] * ct_b - the encrypted linear layer with one ciphertext per feature and the samples in the slots, weighted
+ * averaging, any change of basis over the items.  A plaintext that holds one value in every slot is a constant polynomial, and in
+ * NTT form it is the same word at all N positions of a prime: a scalar at a level with K primes is K words, word k being the value
+ * every coefficient of prime k holds.  Scalars are [count][K] words in device memory; three host-side producers make them, each
+ * host array in, caller's device buffer out.  They are not hot-path calls: the words are computed on the host and uploaded with one
+ * synchronous copy after draining the device, as ItemMap_Create uploads its lists.
+ * CKKSEncoder_EncodeScalars: scalar i equals, word for word, what CKKSEncoder_Encode3(values[i], parms_id, scale) puts at every
+ *   coefficient, in all three branches of the reference (ckks.cpp:145-226: values of at most 64 bits, at most 128 bits, and the
+ *   multi-precision one).  Checks and messages are Encode3's - a scale out of bounds, a value that is not finite or too large - and
+ *   name the first failing index; a failed call writes nothing.  The values are host doubles on purpose: the reference's branch and
+ *   range checks go through log2 of the host libm.
+ * CKKSEncoder_EncodeIntegerScalars: the same against CKKSEncoder_Encode5 (scale 1.0).
+ * Evaluator_LiftScalars (BFV / BGV): scalar i equals what Evaluator_TransformPlainToNTTDevice leaves at every coefficient for the
+ *   polynomial values_mod_t[i] * X^0 - the centred lift of the reference's transform_to_ntt_inplace(Plaintext) in both its branches
+ *   (with and without the fast plain lift); the forward transform of a constant is that constant.  Values >= t are refused, CKKS is
+ *   refused as TransformPlainToNTTDevice refuses it.
+ * All three: SHL_E_INVALIDARG for an unknown parms_id, count == 0, NULL arrays and a device pointer that is not 16-byte aligned;
+ * SHL_E_POINTER for a NULL handle (LiftScalars: or a NULL parms_id).
+ * Evaluator_DotScalarsDevice: encrypted = a batch of B items, any size >= 2, any level, in NTT form (CKKS, BGV, or BFV after
+ *   Evaluator_TransformToNTT2); device_scalars = [rows][B][K] words at the ciphertext's level, 16-byte aligned, batch == B, NOT
+ *   validated like every *Device plaintext (out-of-range words give an unspecified result); destination = ANOTHER handle made with
+ *   Ciphertext_CreateBatch(rows), resized to the operand's size and level.  Output item o = sum_b ct_b (.) const(s[o][b]): word for
+ *   word Evaluator_DotPlainMapped with the dense map (row o names the items 0 .. B - 1, term (o, b) names plaintext o B + b) and
+ *   [rows B][K][N] plaintexts each filled with its scalar's K words, hence the reference's multiply_plain_inplace with the encoded
+ *   scalar per item and then add_many.  `scale` is the scalars' common scale (CKKS).  Metadata (scale product and its bound check,
+ *   correction factor, is_ntt_form, parms_id), the settle-before-read of an operand with a deferred tail or a pending product,
+ *   Evaluator_SetTransparentCheck on the result batch, "a failed check leaves the destination untouched" and the SHL_E_POINTER cases
+ *   are those of Evaluator_DotPlainDevice.  SHL_E_INVALIDARG in addition: rows == 0; rows B >= 2^32; batch != B; the destination's
+ *   batch != rows; destination == encrypted; scalars overlapping either ciphertext's words; a coefficient-form ciphertext.  A zero
+ *   scalar is an ordinary word: only the result batch is subject to the transparent check.  A sparse form is Evaluator_DotPlainMapped.
+ *   The call is enqueued on the evaluator's stream without a host round trip and records under Evaluator_BeginCapture.  One thread
+ *   holds one 16-byte coefficient pair of one plane and prime for a tile of 4 consecutive output rows and uses each loaded ciphertext
+ *   pair for all of them, so the operand is read once per tile of rows (ceil(rows / 4) size P bytes for an operand plane of P bytes,
+ *   against (size + 1) rows P through the dense map), and needs [rows][B][K] words of weights instead of [rows B][K][N].  From
+ *   N = 128 on a wavefront never leaves its row and reads the weights with scalar loads through the constant cache: THE SCALARS MUST
+ *   HAVE BEEN WRITTEN BY SOMETHING EARLIER ON THE STREAM (a copy, one of the producers above, a previous kernel), like the lists of
+ *   an item map.  Products are accumulated as plain 128-bit integers and reduced once per 256 items.  A small result is cut as for
+ *   Evaluator_DotPlainDevice, the rule being asked with size ceil(rows / 4) K N / 2 threads that each add B terms; slices of B are
+ *   computed by separate workgroups into pool scratch [slices][size][rows][K][N], which a second launch adds; the words do not
+ *   depend on it. */
+SHL_FUNC CKKSEncoder_EncodeScalars(void *thisptr, uint64_t count, const double *values, uint64_t *parms_id, double scale, uint64_t *device_words);
+SHL_FUNC CKKSEncoder_EncodeIntegerScalars(void *thisptr, uint64_t count, const int64_t *values, uint64_t *parms_id, uint64_t *device_words);
+SHL_FUNC Evaluator_LiftScalars(void *thisptr, uint64_t count, const uint64_t *values_mod_t, uint64_t *parms_id, uint64_t *device_words);
+SHL_FUNC Evaluator_DotScalarsDevice(void *thisptr, void *encrypted, const uint64_t *device_scalars, uint64_t rows, uint64_t batch, double scale,
+                                    void *destination);
 SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *pool);
 SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *pool);
@@ -627,6 +673,17 @@ SHL_FUNC shl_dot_items_flush_interval(uint64_t *items);
 SHL_FUNC shl_reduce_mapped(void *context, uint64_t chain_index, int kind, const uint64_t *a, uint64_t a_batch, const uint64_t *b,
                            uint64_t b_batch, uint64_t *r, uint64_t size, void *item_map, uint64_t slices, uint64_t *scratch,
                            uint64_t *slices_used, void *stream);
+/* The kernel of Evaluator_DotScalarsDevice on raw words at one level: a = [size][batch][K][N], scalars = [rows][batch][K],
+ * r = [size][rows][K][N], distinct from the operands.  slices: 0 = the library's rule, 1 = one launch, 2 .. min(batch, 64) = that cut
+ * of the batch; the scratch comes from the pool.  slices_used (may be NULL) receives the slices run; r == NULL only answers that.
+ * Nothing is validated beyond the shape.  shl_dot_scalars runs on the NULL stream and returns when the work is done;
+ * shl_dot_scalars_tile enqueues on `stream` with a row tile of 2, 4 or 8 output rows per thread (0: the library's) - the sweep of
+ * tools/dot_scalars_rate.py.  shl_dot_scalars_info: the library's row tile and the items between two reductions (256). */
+SHL_FUNC shl_dot_scalars(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *scalars, uint64_t *r, uint64_t size,
+                         uint64_t rows, uint64_t batch, uint64_t slices, uint64_t *slices_used);
+SHL_FUNC shl_dot_scalars_tile(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *scalars, uint64_t *r, uint64_t size,
+                              uint64_t rows, uint64_t batch, uint64_t slices, uint64_t *slices_used, uint64_t row_tile, void *stream);
+SHL_FUNC shl_dot_scalars_info(uint64_t *row_tile, uint64_t *flush);
 /* GaloisTool::apply_galois (ntt_form == 0, util/galois.cpp:148) / apply_galois_ntt (!= 0, galois.cpp:192) */
 SHL_FUNC shl_apply_galois(void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys, void *stream);
 /* RNSTool stages (util/rns.cpp) on one level, `polys` polynomials each [comps][N]:

@@ -890,6 +890,32 @@ class CKKSEncoder:
                                                  pid, C.c_double(scale), C.c_void_p(out.ptr)))
         return out
 
+    def _scalars_out(self, count, parms_id, out):
+        try:
+            K = len(self.context.coeff_modulus_at(self.context.chain_index(parms_id)))
+        except N.SealHipError:
+            K = 1   # an unknown parms_id: the call rejects it
+        return out if out is not None else DeviceBuffer(max(count * K, 1))
+
+    def encode_scalars(self, values, parms_id, scale, out=None):
+        """host doubles -> DeviceBuffer of [count][K] words: scalar i is what encode(values[i], parms_id, scale) holds at every
+        coefficient of each prime (sealhip.h: CKKSEncoder_EncodeScalars) - the weights of Evaluator.dot_scalars_device.  Not a
+        hot-path call: one synchronous copy after a drain.  `out` reuses a buffer; a refused value leaves it unchanged"""
+        a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        out = self._scalars_out(a.size, parms_id, out)
+        pid = (C.c_uint64 * 4)(*parms_id)
+        N.check(N.lib().CKKSEncoder_EncodeScalars(self._h, C.c_uint64(a.size), _p(a), pid, C.c_double(scale), C.c_void_p(out.ptr)))
+        return out
+
+    def encode_integer_scalars(self, values, parms_id, out=None):
+        """host int64 values -> DeviceBuffer of [count][K] words, scalar i as encode(int(values[i]), parms_id, None) (scale 1.0;
+        sealhip.h: CKKSEncoder_EncodeIntegerScalars)"""
+        a = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+        out = self._scalars_out(a.size, parms_id, out)
+        pid = (C.c_uint64 * 4)(*parms_id)
+        N.check(N.lib().CKKSEncoder_EncodeIntegerScalars(self._h, C.c_uint64(a.size), _p(a), pid, C.c_void_p(out.ptr)))
+        return out
+
     def decode_device(self, words, batch, parms_id, scale, complex_values=False, out=None):
         """words: DeviceBuffer of [batch][K][N] NTT-form words (e.g. Decryptor.decrypt_batch's) -> DeviceBuffer of [batch][N/2]
         doubles, or [batch][N/2][2] (re, im) with complex_values; read it with DeviceBuffer.to_array"""
@@ -1541,6 +1567,36 @@ class Evaluator:
         d = self._mapped_dest(item_map, destination)
         ptr = words.ptr if isinstance(words, DeviceBuffer) else words
         N.check(N.lib().Evaluator_DotPlainMapped(self._h, a._h, C.c_void_p(ptr), C.c_uint64(plain_count), item_map._h, C.c_double(scale), d._h))
+        return d
+
+    # ---- a dense matrix of scalar weights times a batch (sealhip.h: Evaluator_DotScalarsDevice)
+    def lift_scalars(self, values, parms_id, out=None):
+        """BFV / BGV: host values modulo t -> DeviceBuffer of [count][K] words, scalar i being what transform_plain_to_ntt_device
+        leaves at every coefficient for the constant polynomial values[i] (sealhip.h: Evaluator_LiftScalars).  Not a hot-path
+        call: one synchronous copy after a drain"""
+        a = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+        try:
+            K = len(self.context.coeff_modulus_at(self.context.chain_index(parms_id)))
+        except N.SealHipError:
+            K = 1   # an unknown parms_id: the call rejects it
+        out = out if out is not None else DeviceBuffer(max(a.size * K, 1))
+        pid = (C.c_uint64 * 4)(*parms_id)
+        N.check(N.lib().Evaluator_LiftScalars(self._h, C.c_uint64(a.size), _p(a), pid, C.c_void_p(out.ptr)))
+        return out
+
+    def dot_scalars_device(self, a, scalars, rows, scale=1.0, destination=None):
+        """item o of the result = the sum over the items b of `a` of item b * the constant plaintext scalars[o][b] (sealhip.h:
+        Evaluator_DotScalarsDevice).  scalars: DeviceBuffer of [rows][batch][K] words at the ciphertext's level
+        (CKKSEncoder.encode_scalars', encode_integer_scalars' or lift_scalars'), written before this call on the stream; `a` in
+        NTT form.  scale: the scalars' common scale (CKKS; the scales are multiplied).  destination None: a new Ciphertext of
+        `rows` items; otherwise a handle of that batch, distinct from `a`, which is only read.  -> the destination"""
+        batch = a.batch()
+        need = rows * batch * a.coeff_modulus_size()
+        if isinstance(scalars, DeviceBuffer) and scalars.words < need:
+            raise ValueError("%d scalar words for %d x %d scalars at this level: %d needed" % (scalars.words, rows, batch, need))
+        d = Ciphertext(self.context, batch=rows) if destination is None else destination
+        ptr = scalars.ptr if isinstance(scalars, DeviceBuffer) else scalars
+        N.check(N.lib().Evaluator_DotScalarsDevice(self._h, a._h, C.c_void_p(ptr), C.c_uint64(rows), C.c_uint64(batch), C.c_double(scale), d._h))
         return d
 
     def dot_items_mapped(self, a, b, item_map, destination=None):

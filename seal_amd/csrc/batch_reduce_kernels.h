@@ -78,4 +78,19 @@ namespace sealhip
     hipError_t k_dot_items(const ModDesc *mods, const uint64_t *x, size_t x_stride, const uint64_t *y, size_t y_stride, uint64_t *r,
                            size_t r_stride, unsigned n_log, unsigned K, size_t out_items, const ItemWalk &walk, unsigned slices,
                            uint64_t *scratch, hipStream_t s);
+
+    // Scalar weights: r[p][o][k][j] = sum_b a[p][b][k][j] * s[o][b][k] mod q_k for o < rows - a dense rows x batch matrix of scalar
+    // plaintexts times the items of a batch.  scalars = [rows][batch][K] words: word k is the value every coefficient of prime k
+    // holds in the NTT-form constant plaintext, so the words are those of k_dot_plain_items over the dense map with the scalars
+    // expanded to [rows * batch][K][N].  A thread holds a tile of dot_scalars_row_tile() consecutive rows of one coefficient pair
+    // and uses each loaded operand pair for all of them: the operand crosses HBM once per tile of rows.  From N = 128 on the
+    // weights are read with scalar loads through the constant cache: they must have been written by something earlier on the
+    // stream (a copy, a previous kernel).  rows * batch < 2^32.  slices, scratch: the cut of the batch as above, with scratch of
+    // batch_reduce_scratch_words(slices, size, rows, ...) words; the library's rule is asked with dot_scalars_threads() threads
+    // that each add `batch` terms.  row_tile: 0 = the library's, or one of the built ones (2, 4, 8: the rate tool's sweep).
+    unsigned dot_scalars_row_tile();
+    size_t dot_scalars_threads(unsigned size, size_t rows, unsigned n_log, unsigned K, unsigned row_tile = 0);
+    hipError_t k_dot_scalars(const ModDesc *mods, const uint64_t *a, size_t a_stride, const uint64_t *scalars, uint64_t *r, size_t r_stride,
+                             unsigned size, unsigned n_log, unsigned K, size_t rows, size_t batch, unsigned slices, uint64_t *scratch,
+                             unsigned row_tile, hipStream_t s);
 } // namespace sealhip

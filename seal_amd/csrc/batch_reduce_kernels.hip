@@ -2,6 +2,9 @@
 // flat in x (one thread per output pair) and, when the group is cut, the slices sit in y.  There is one kernel, reduce_items_kernel:
 // what a reduction adds per term is its Term (SumTerm, DotPlainTerm, DotItemsTerm), which items its terms are is its Walk
 // (ConsecutiveWalk, MappedWalk), everything else exists once.
+// The scalar weights have a kernel of their own, dot_scalars_kernel: its threads hold a TILE of output rows of one pair and use each
+// loaded operand pair for all of them, which a kernel of one output row per thread cannot do; it shares the accumulators, the flush
+// interval, the accesses, the grid, the cut and the sum of the slices.
 #include "batch_reduce_kernels.h"
 #include "stream_device.h"
 #include <algorithm>
@@ -315,6 +318,15 @@ namespace sealhip
             return launch_walk<Term>(mods, a, b, dst, g, slices, final, s, ConsecutiveWalk{});
         }
 
+        // the second launch of a cut: r [size][out_items][K][N] (planes r_stride words apart) = the sum of scratch [slices][size][out_items][K][N]
+        hipError_t sum_slices(const ModDesc *mods, const uint64_t *scratch, uint64_t *r, size_t r_stride, unsigned size, unsigned n_log, unsigned K,
+                              size_t out_items, unsigned slices, hipStream_t s)
+        {
+            const size_t words = (size_t)K << n_log, out_plane = out_items * words;
+            const ReduceGeom c{ out_plane, 0, words, size * out_plane, r_stride, 0, size * out_plane / 2, (unsigned)out_items, slices, slices, n_log, K };
+            return launch_reduce<SumTerm<false>>(mods, scratch, scratch, r, c, 1, true, s, ItemWalk(slices));
+        }
+
         // The host path of every reduction: r [size][out_items][K][N] (planes r_stride words apart) from operands whose planes are
         // a_plane / b_plane words apart and whose items are [K][N] blocks, the terms of an output item being what `walk` says.
         // launch(g, dst, slices, final) starts the reduction's own kernels over grid_planes planes per launch; with slices > 1 (a cut
@@ -336,8 +348,130 @@ namespace sealhip
             const hipError_t e = launch(g, final ? r : scratch, slices, final);
             if (e != hipSuccess || final)
                 return e;
-            const ReduceGeom c{ out_plane, 0, words, size * out_plane, r_stride, 0, size * out_plane / 2, (unsigned)out_items, slices, slices, n_log, K };
-            return launch_reduce<SumTerm<false>>(mods, scratch, scratch, r, c, 1, true, s, ItemWalk(slices));
+            return sum_slices(mods, scratch, r, r_stride, size, n_log, K, out_items, slices, s);
+        }
+
+        // ---- scalar weights (batch_reduce_kernels.h: k_dot_scalars): r[p][o] = sum_b a[p][b] * const(s[o][b]), the plaintext of term
+        // (o, b) being ONE word per prime.  One thread = one 16-byte pair of one plane and one prime for a TILE of R consecutive
+        // output rows: each loaded ciphertext pair is used for R x 2 products, so the operand crosses HBM once per tile of rows and
+        // not once per row.  The grid is flat over (plane, row tile, k, pair) - the weight is the same for every plane and its load
+        // is cheap, so the planes are in the grid -, slices of the batch in y.  Accumulators are the products' (U128, kDotFlush).
+        // UNIFORM (N >= 128): a wave covers 128 consecutive words and never leaves its (plane, tile, k) row: the row number is moved
+        // to an SGPR and the R weights of an item are scalar loads through the constant address space - SGPRs, not VGPRs, and
+        // uniform trip counts.  The scalars are therefore read through the constant cache: they must have been WRITTEN BY SOMETHING
+        // EARLIER ON THE STREAM (a copy, a previous kernel), as the lists of an item map.  Below N = 128 the lanes of a wave sit in
+        // different rows: per-lane loads.
+        // The last tile has rows mod R live rows; its dead rows are neither loaded nor stored (FULL = false).
+        struct ScalarGeom
+        {
+            size_t a_plane;              // words between two planes of the operand
+            size_t dst_plane, dst_slice; // result word of (slice s, plane p): s * dst_slice + p * dst_plane
+            size_t pairs;                // size * tiles * K * N / 2
+            unsigned rows, tiles, batch, per_slice; // slice s adds the items [s * per_slice, min(batch, (s + 1) * per_slice))
+            unsigned n_log, K;
+        };
+        // waves per SIMD the allocator is held to and the unroll factor of the loop over the items (profiles/dot_scalars.txt: no
+        // kernel uses scratch memory at these).  Two rows leave room for two items in flight; from four rows on the loop is left
+        // rolled - unrolled by two, R = 8 spills at 4 waves.  The per-lane kernels keep R weight addresses per lane.
+        template <unsigned R, bool UNIFORM>
+        constexpr unsigned scalar_waves()
+        {
+            return R == 2 ? (UNIFORM ? 8 : 5) : R == 4 ? 6 : 4;
+        }
+        template <unsigned R>
+        constexpr unsigned scalar_unroll()
+        {
+            return R == 2 ? 2 : 1;
+        }
+        template <unsigned R, bool UNIFORM, bool FINAL, bool FULL>
+        __device__ __forceinline__ void dot_scalars_rows(const ModDesc &md, const uint64_t *ap, const uint64_t *sp, uint64_t *d, const ScalarGeom &g,
+                                                         unsigned t0, unsigned t1, unsigned live)
+        {
+            const size_t words = (size_t)g.K << g.n_log, row_words = (size_t)g.batch * g.K; // between two items / two rows of weights
+            uint64_t tot[R][2] = {};
+            for (unsigned t = t0; t < t1;)
+            {
+                const unsigned end = t1 - t < kDotFlush ? t1 : t + kDotFlush;
+                U128 acc[R][2] = {};
+#pragma unroll scalar_unroll<R>()
+                for (; t < end; t++, ap += words, sp += g.K)
+                {
+                    uint64_t a0, a1;
+                    ld2<true>(ap, a0, a1);
+#pragma unroll
+                    for (unsigned r = 0; r < R; r++)
+                        if (FULL || r < live)
+                        {
+                            const uint64_t w = UNIFORM ? SHL_UCONST(sp)[r * row_words] : sp[r * row_words];
+                            mac128(acc[r][0], a0, w);
+                            mac128(acc[r][1], a1, w);
+                        }
+                }
+#pragma unroll
+                for (unsigned r = 0; r < R; r++)
+                    if (FULL || r < live)
+                        for (unsigned l = 0; l < 2; l++)
+                            tot[r][l] = add_mod(tot[r][l], barrett128(acc[r][l].lo, acc[r][l].hi, md), md.q);
+            }
+#pragma unroll
+            for (unsigned r = 0; r < R; r++)
+                if (FULL || r < live)
+                {
+                    if (FINAL)
+                        st2_nt(d + r * words, tot[r][0], tot[r][1]);
+                    else
+                        st2(d + r * words, tot[r][0], tot[r][1]);
+                }
+        }
+        template <unsigned R, bool UNIFORM, bool FINAL>
+        __global__ void __launch_bounds__(kBlock, (scalar_waves<R, UNIFORM>())) dot_scalars_kernel(const ModDesc *mods, const uint64_t *a, const uint64_t *scalars, uint64_t *dst, ScalarGeom g)
+        {
+            const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
+            if (w >= g.pairs)
+                return;
+            const size_t i = 2 * w, j = i & ((size_t(1) << g.n_log) - 1);
+            unsigned row = (unsigned)(i >> g.n_log); // (p * tiles + tile) * K + k
+            if (UNIFORM)
+                row = SHL_UNIFORM(row);
+            const unsigned k = row % g.K, pt = row / g.K, tile = pt % g.tiles, p = pt / g.tiles;
+            const unsigned o0 = tile * R, live = g.rows - o0 < R ? g.rows - o0 : R;
+            const ModDesc md = mods[k];
+            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.batch - t0 < g.per_slice ? g.batch : t0 + g.per_slice;
+            const size_t inner = ((size_t)k << g.n_log) + j; // component k, coefficient j
+            const uint64_t *ap = a + p * g.a_plane + (((size_t)t0 * g.K) << g.n_log) + inner; // item t0
+            const uint64_t *sp = scalars + ((size_t)o0 * g.batch + t0) * g.K + k;            // s[o0][t0][k]
+            uint64_t *d = dst + blockIdx.y * g.dst_slice + p * g.dst_plane + (((size_t)o0 * g.K) << g.n_log) + inner;
+            if (live == R)
+                dot_scalars_rows<R, UNIFORM, FINAL, true>(md, ap, sp, d, g, t0, t1, live);
+            else
+                dot_scalars_rows<R, UNIFORM, FINAL, false>(md, ap, sp, d, g, t0, t1, live);
+        }
+        template <unsigned R>
+        hipError_t launch_scalars(const ModDesc *mods, const uint64_t *a, const uint64_t *scalars, uint64_t *dst, const ScalarGeom &g, unsigned slices,
+                                  bool final, hipStream_t s)
+        {
+            unsigned blocks;
+            if (!flat_grid(g.pairs, g.n_log, blocks))
+                return hipErrorInvalidValue;
+            const dim3 grid(blocks, slices), block(kBlock);
+            if (g.n_log >= 7)
+            {
+                if (final)
+                    hipLaunchKernelGGL((dot_scalars_kernel<R, true, true>), grid, block, 0, s, mods, a, scalars, dst, g);
+                else
+                    hipLaunchKernelGGL((dot_scalars_kernel<R, true, false>), grid, block, 0, s, mods, a, scalars, dst, g);
+            }
+            else if (final)
+                hipLaunchKernelGGL((dot_scalars_kernel<R, false, true>), grid, block, 0, s, mods, a, scalars, dst, g);
+            else
+                hipLaunchKernelGGL((dot_scalars_kernel<R, false, false>), grid, block, 0, s, mods, a, scalars, dst, g);
+            return hipGetLastError();
+        }
+        // the row tile the library runs with (tools/dot_scalars_rate.py measures the three; DESIGN.md 8.6 has the table)
+        constexpr unsigned kRowTile = 4;
+        inline bool row_tile_built(unsigned r)
+        {
+            return r == 2 || r == 4 || r == 8;
         }
     } // namespace
 
@@ -412,5 +546,38 @@ namespace sealhip
                                 return square ? launch_reduce<DotItemsTerm<true>>(mods, x, y, dst, g, ns, final, s, walk)
                                               : launch_reduce<DotItemsTerm<false>>(mods, x, y, dst, g, ns, final, s, walk);
                             });
+    }
+
+    unsigned dot_scalars_row_tile()
+    {
+        return kRowTile;
+    }
+    size_t dot_scalars_threads(unsigned size, size_t rows, unsigned n_log, unsigned K, unsigned row_tile)
+    {
+        const unsigned R = row_tile ? row_tile : kRowTile;
+        return (((size_t)size * ((rows + R - 1) / R) * K) << n_log) / 2;
+    }
+    hipError_t k_dot_scalars(const ModDesc *mods, const uint64_t *a, size_t a_stride, const uint64_t *scalars, uint64_t *r, size_t r_stride,
+                             unsigned size, unsigned n_log, unsigned K, size_t rows, size_t batch, unsigned slices, uint64_t *scratch,
+                             unsigned row_tile, hipStream_t s)
+    {
+        const unsigned R = row_tile ? row_tile : kRowTile;
+        const size_t words = (size_t)K << n_log, out_plane = rows * words;
+        if (!size || !out_plane || !batch)
+            return hipSuccess;
+        unsigned per_slice;
+        if (!row_tile_built(R) || !cut(batch, slices, per_slice) || rows > 0xffffffffu || rows * batch > 0xffffffffu || (slices > 1 && !scratch))
+            return hipErrorInvalidValue;
+        const bool final = slices == 1;
+        const size_t tiles = (rows + R - 1) / R;
+        const ScalarGeom g{ a_stride, final ? r_stride : out_plane, final ? 0 : size * out_plane, size * tiles * words / 2,
+                            (unsigned)rows, (unsigned)tiles, (unsigned)batch, per_slice, n_log, K };
+        uint64_t *dst = final ? r : scratch;
+        const hipError_t e = R == 2   ? launch_scalars<2>(mods, a, scalars, dst, g, slices, final, s)
+                             : R == 4 ? launch_scalars<4>(mods, a, scalars, dst, g, slices, final, s)
+                                      : launch_scalars<8>(mods, a, scalars, dst, g, slices, final, s);
+        if (e != hipSuccess || final)
+            return e;
+        return sum_slices(mods, scratch, r, r_stride, size, n_log, K, rows, slices, s);
     }
 } // namespace sealhip

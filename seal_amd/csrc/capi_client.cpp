@@ -358,6 +358,20 @@ extern "C"
         as<CKKSEncoder>(thisptr)->encode_device(device_values, (size_t)value_count, (size_t)batch, is_complex, parms_id, scale, device_words);
         SHL_CATCH
     }
+    SHL_FUNC CKKSEncoder_EncodeScalars(void *thisptr, uint64_t count, const double *values, uint64_t *parms_id, double scale, uint64_t *device_words)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        SHL_TRY
+        as<CKKSEncoder>(thisptr)->encode_scalars((size_t)count, values, parms_id, scale, device_words);
+        SHL_CATCH
+    }
+    SHL_FUNC CKKSEncoder_EncodeIntegerScalars(void *thisptr, uint64_t count, const int64_t *values, uint64_t *parms_id, uint64_t *device_words)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        SHL_TRY
+        as<CKKSEncoder>(thisptr)->encode_integer_scalars((size_t)count, values, parms_id, device_words);
+        SHL_CATCH
+    }
     SHL_FUNC CKKSEncoder_DecodeDevice(void *thisptr, const uint64_t *device_words, uint64_t batch, uint64_t *parms_id, double scale,
                                       bool want_complex, double *device_values)
     {

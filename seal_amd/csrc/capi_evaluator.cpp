@@ -343,6 +343,28 @@ extern "C"
                                                  *as<Ciphertext>(destination));
         SHL_CATCH
     }
+    // scalar weights (library extensions): [count][K] words per scalar, and the dense matrix of them times a batch
+    SHL_FUNC Evaluator_LiftScalars(void *thisptr, uint64_t count, const uint64_t *values_mod_t, uint64_t *parms_id, uint64_t *device_words)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(parms_id, SHL_E_POINTER);
+        SHL_TRY
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->lift_scalars((size_t)count, values_mod_t, parms_id, device_words);
+        SHL_CATCH
+    }
+    SHL_FUNC Evaluator_DotScalarsDevice(void *thisptr, void *encrypted, const uint64_t *device_scalars, uint64_t rows, uint64_t batch, double scale,
+                                        void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->dot_scalars_device(*as<Ciphertext>(encrypted), device_scalars, (size_t)rows, (size_t)batch, scale,
+                                                   *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
     SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination)
     {
         IfNullRet(thisptr, SHL_E_POINTER);

@@ -1,6 +1,7 @@
 // extern "C" layer, part 4: the per-kernel seam (NTT, dyadic products, RNS stages on raw device buffers; include/sealhip.h)
 #include "capi_common.h"
 #include "batch_reduce_kernels.h"
+#include <memory>
 
 namespace
 {
@@ -169,6 +170,61 @@ extern "C"
                                                      cut, scratch, s),
                                          "dot (mapped)");
                           });
+    }
+    // k_dot_scalars on raw words: a [size][batch][K][N], scalars [rows][batch][K], r [size][rows][K][N]; slices == 0: the library's
+    // rule; r == NULL: the query.  Scratch comes from the pool; the NULL stream, and the call returns when the work is done.
+    // row_tile: 0 = the library's (what shl_dot_scalars runs); 2, 4, 8 are built for tools/dot_scalars_rate.py
+    SHL_FUNC shl_dot_scalars_tile(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *scalars, uint64_t *r, uint64_t size,
+                                  uint64_t rows, uint64_t batch, uint64_t slices, uint64_t *slices_used, uint64_t row_tile, void *stream)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        SHL_TRY
+        auto c = as<Context>(context);
+        auto l = c->level_by_chain_index(chain_index);
+        if (!l)
+            throw std::out_of_range("chain_index");
+        if (!size || size > 16 || !rows || !batch || (rows >> 32) || (batch >> 32) || ((rows * batch) >> 32) ||
+            (row_tile && row_tile != 2 && row_tile != 4 && row_tile != 8))
+            throw std::invalid_argument("1 <= size <= 16; 1 <= rows, batch; rows * batch < 2^32; row_tile 0, 2, 4 or 8");
+        const unsigned n_log = (unsigned)c->log_n();
+        if (!slices)
+            slices = batch_reduce_slices(dot_scalars_threads((unsigned)size, rows, n_log, l->K, (unsigned)row_tile), batch);
+        if (slices > batch || slices > 64)
+            throw std::invalid_argument("1 <= slices <= min(batch, 64)");
+        if (slices_used)
+            *slices_used = slices;
+        if (!r) // a query: the slices the library would use
+            return SHL_S_OK;
+        IfNullRet(a, SHL_E_POINTER);
+        IfNullRet(scalars, SHL_E_POINTER);
+        hipStream_t s = (hipStream_t)stream;
+        StreamScope scope(s);
+        const size_t words = (size_t)l->K * c->n();
+        std::unique_ptr<Scratch> scratch;
+        if (slices > 1)
+            scratch.reset(new Scratch(batch_reduce_scratch_words((unsigned)slices, (unsigned)size, rows, n_log, l->K)));
+        hip_ok(k_dot_scalars(c->dev_mods(), a, batch * words, scalars, r, rows * words, (unsigned)size, n_log, l->K, rows, batch, (unsigned)slices,
+                             scratch ? scratch->p : nullptr, (unsigned)row_tile, s),
+               "dot_scalars");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_dot_scalars(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *scalars, uint64_t *r, uint64_t size,
+                             uint64_t rows, uint64_t batch, uint64_t slices, uint64_t *slices_used)
+    {
+        const SHL_HRESULT hr = shl_dot_scalars_tile(context, chain_index, a, scalars, r, size, rows, batch, slices, slices_used, 0, nullptr);
+        if (hr != SHL_S_OK || !r)
+            return hr;
+        SHL_TRY
+        hip_ok(hipStreamSynchronize(nullptr), "dot_scalars sync");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_dot_scalars_info(uint64_t *row_tile, uint64_t *flush)
+    {
+        IfNullRet(row_tile, SHL_E_POINTER);
+        IfNullRet(flush, SHL_E_POINTER);
+        *row_tile = dot_scalars_row_tile();
+        *flush = batch_reduce_dot_flush();
+        return SHL_S_OK;
     }
     SHL_FUNC shl_apply_galois(
         void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys,

@@ -352,28 +352,33 @@ namespace sealhip
         dest.set_level(&lvl);
         dest.scale() = scale;
     }
-    void CKKSEncoder::encode_value(double value, const uint64_t *parms_id, double scale, Plaintext &dest) const
+    // the level and the scale check of encode(double) (ckks.cpp:72-90)
+    const Level &CKKSEncoder::value_level(const uint64_t *parms_id, double scale) const
     {
-        // ckks.cpp:72-205
         const Level *lvl = parms_id ? context_.level_by_parms_id(parms_id) : nullptr;
         if (!lvl)
             throw std::invalid_argument("parms_id is not valid for encryption parameters");
         if (!std::isfinite(scale) || scale <= 0 || (static_cast<int>(std::log2(scale)) >= lvl->total_coeff_modulus_bit_count))
             throw std::invalid_argument("scale out of bounds");
+        return *lvl;
+    }
+    // encode(double) without the fill (ckks.cpp:91-205): the value's checks, then the K words every coefficient of the constant
+    // plaintext holds.  Host doubles and the host libm on purpose: branch and range checks go through log2
+    void CKKSEncoder::value_residues(double value, const Level &lvl, double scale, uint64_t *residues) const
+    {
         if (!std::isfinite(value))
             throw std::invalid_argument("value must be finite");
         value *= scale;
         if (!std::isfinite(value))
             throw std::invalid_argument("encoded value is too large");
         const int coeff_bit_count = (std::fabs(value) < 1.0) ? 2 : (static_cast<int>(std::log2(std::fabs(value))) + 2);
-        if (coeff_bit_count >= lvl->total_coeff_modulus_bit_count)
+        if (coeff_bit_count >= lvl.total_coeff_modulus_bit_count)
             throw std::invalid_argument("encoded value is too large");
         const double two_pow_64 = std::pow(2.0, 64);
         double coeffd = std::round(value);
         const bool is_negative = std::signbit(coeffd);
         coeffd = std::fabs(coeffd);
-        std::vector<uint64_t> residues(lvl->K);
-        for (unsigned j = 0; j < lvl->K; j++)
+        for (unsigned j = 0; j < lvl.K; j++)
         {
             const uint64_t q = context_.coeff_modulus()[j];
             uint64_t r;
@@ -384,7 +389,7 @@ namespace sealhip
                 // ckks.cpp:165-196: the double cut into 64-bit words (fmod / division by 2^64, exact), reduced modulo q
                 // (RNSBase::decompose); Horner from the top word
                 std::vector<uint64_t> words;
-                for (double c = coeffd; c >= 1 && words.size() < lvl->K; c /= two_pow_64)
+                for (double c = coeffd; c >= 1 && words.size() < lvl.K; c /= two_pow_64)
                     words.push_back(static_cast<uint64_t>(std::fmod(c, two_pow_64)));
                 unsigned __int128 acc = 0;
                 for (size_t w = words.size(); w-- > 0;)
@@ -399,20 +404,15 @@ namespace sealhip
             }
             residues[j] = is_negative ? (r ? q - r : 0) : r;
         }
-        fill_constant(*lvl, residues, scale, dest);
     }
-    void CKKSEncoder::encode_integer(int64_t value, const uint64_t *parms_id, Plaintext &dest) const
+    // encode(int64_t) without the fill (ckks.cpp:207-250)
+    void CKKSEncoder::integer_residues(int64_t value, const Level &lvl, uint64_t *residues) const
     {
-        // ckks.cpp:207-250
-        const Level *lvl = parms_id ? context_.level_by_parms_id(parms_id) : nullptr;
-        if (!lvl)
-            throw std::invalid_argument("parms_id is not valid for encryption parameters");
         const uint64_t mag = value < 0 ? (uint64_t)0 - (uint64_t)value : (uint64_t)value;
         const int coeff_bit_count = (mag ? 64 - __builtin_clzll(mag) : 0) + 2;
-        if (coeff_bit_count >= lvl->total_coeff_modulus_bit_count)
+        if (coeff_bit_count >= lvl.total_coeff_modulus_bit_count)
             throw std::invalid_argument("encoded value is too large");
-        std::vector<uint64_t> residues(lvl->K);
-        for (unsigned j = 0; j < lvl->K; j++)
+        for (unsigned j = 0; j < lvl.K; j++)
         {
             const uint64_t q = context_.coeff_modulus()[j];
             uint64_t tmp = static_cast<uint64_t>(value);
@@ -420,7 +420,64 @@ namespace sealhip
                 tmp += q; // wraps modulo 2^64, as the reference's line does
             residues[j] = tmp % q;
         }
+    }
+    void CKKSEncoder::encode_value(double value, const uint64_t *parms_id, double scale, Plaintext &dest) const
+    {
+        // ckks.cpp:72-205
+        const Level &lvl = value_level(parms_id, scale);
+        std::vector<uint64_t> residues(lvl.K);
+        value_residues(value, lvl, scale, residues.data());
+        fill_constant(lvl, residues, scale, dest);
+    }
+    void CKKSEncoder::encode_integer(int64_t value, const uint64_t *parms_id, Plaintext &dest) const
+    {
+        // ckks.cpp:207-250
+        const Level *lvl = parms_id ? context_.level_by_parms_id(parms_id) : nullptr;
+        if (!lvl)
+            throw std::invalid_argument("parms_id is not valid for encryption parameters");
+        std::vector<uint64_t> residues(lvl->K);
+        integer_residues(value, *lvl, residues.data());
         fill_constant(*lvl, residues, 1.0, dest);
+    }
+
+    // `count` scalar plaintexts as [count][K] words in device memory (include/sealhip.h: CKKSEncoder_EncodeScalars): residues(i, out)
+    // gives scalar i's K words or throws the per-object form's refusal, which is passed on with the index.  Nothing is written
+    // unless every value passes; then one synchronous copy after a drain (not a hot-path call, like ItemMap_Create)
+    template <class Residues>
+    void CKKSEncoder::upload_scalars(size_t count, const void *values, const Level &lvl, uint64_t *words, Residues residues) const
+    {
+        if (!count)
+            throw std::invalid_argument("count cannot be zero");
+        if (!values || !words)
+            throw std::invalid_argument(values ? "device_words cannot be null" : "values cannot be null");
+        if ((uintptr_t)words % 16)
+            throw std::invalid_argument("device_words must be 16-byte aligned");
+        std::vector<uint64_t> host(count * lvl.K);
+        for (size_t i = 0; i < count; i++)
+        {
+            try
+            {
+                residues(i, host.data() + i * lvl.K);
+            }
+            catch (const std::invalid_argument &e)
+            {
+                throw std::invalid_argument(std::string(e.what()) + " (values[" + std::to_string(i) + "])");
+            }
+        }
+        ck(hipDeviceSynchronize(), "scalars upload"); // whatever read or wrote the buffer before is done
+        copy_h2d(words, host.data(), host.size() * 8);
+    }
+    void CKKSEncoder::encode_scalars(size_t count, const double *values, const uint64_t *parms_id, double scale, uint64_t *words) const
+    {
+        const Level &lvl = value_level(parms_id, scale);
+        upload_scalars(count, values, lvl, words, [&](size_t i, uint64_t *out) { value_residues(values[i], lvl, scale, out); });
+    }
+    void CKKSEncoder::encode_integer_scalars(size_t count, const int64_t *values, const uint64_t *parms_id, uint64_t *words) const
+    {
+        const Level *lvl = parms_id ? context_.level_by_parms_id(parms_id) : nullptr;
+        if (!lvl)
+            throw std::invalid_argument("parms_id is not valid for encryption parameters");
+        upload_scalars(count, values, *lvl, words, [&](size_t i, uint64_t *out) { integer_residues(values[i], *lvl, out); });
     }
 
     void CKKSEncoder::decode_batch(const uint64_t *words, size_t batch, const Level &lvl, double scale, bool want_complex, double *values) const

@@ -32,6 +32,11 @@ namespace sealhip
         // constant polynomial, whose NTT form is that constant in every position
         void encode_value(double value, const uint64_t *parms_id, double scale, Plaintext &destination) const;
         void encode_integer(int64_t value, const uint64_t *parms_id, Plaintext &destination) const;
+        // `count` such values as scalars (CKKSEncoder_EncodeScalars / _EncodeIntegerScalars, include/sealhip.h): host values in,
+        // [count][K] words in the caller's device buffer out - word k of scalar i is what encode_value / encode_integer put at every
+        // coefficient of prime k, and their refusals are passed on with the first failing index; a failed call writes nothing
+        void encode_scalars(size_t count, const double *values, const uint64_t *parms_id, double scale, uint64_t *device_words) const;
+        void encode_integer_scalars(size_t count, const int64_t *values, const uint64_t *parms_id, uint64_t *device_words) const;
         // CKKSEncoder::decode (ckks.h:683-789): N/2 complex numbers as (re, im) pairs, or their real parts
         void decode(const Plaintext &plain, double *values, bool want_complex) const;
         // whole batches in device memory (CKKSEncoder_EncodeDevice / _DecodeDevice, include/sealhip.h): encode writes [batch][K][N]
@@ -42,6 +47,11 @@ namespace sealhip
         void decode_device(const uint64_t *words, size_t batch, const uint64_t *parms_id, double scale, bool want_complex, double *values) const;
 
     private:
+        const Level &value_level(const uint64_t *parms_id, double scale) const;
+        void value_residues(double value, const Level &lvl, double scale, uint64_t *residues) const;
+        void integer_residues(int64_t value, const Level &lvl, uint64_t *residues) const;
+        template <class Residues>
+        void upload_scalars(size_t count, const void *values, const Level &lvl, uint64_t *device_words, Residues residues) const;
         void fill_constant(const Level &lvl, const std::vector<uint64_t> &residues, double scale, Plaintext &destination) const;
         struct LevelConst
         {

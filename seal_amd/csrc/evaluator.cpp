@@ -795,13 +795,14 @@ namespace sealhip
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
     }
     void Evaluator::check_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
-                                       const Ciphertext &dest, bool per_item) const
+                                       const Ciphertext &dest, bool per_item, size_t scalar_rows) const
     {
+        const std::string name = scalar_rows ? "device_scalars" : "device_plain";
         check_valid(e, "encrypted");
         if (!plain)
-            throw std::invalid_argument("device_plain is null");
+            throw std::invalid_argument(name + " is null");
         if ((uintptr_t)plain % 16)
-            throw std::invalid_argument("device_plain must be 16-byte aligned");
+            throw std::invalid_argument(name + " must be 16-byte aligned");
         if (!batch || (per_item && batch != e.batch()))
             throw std::invalid_argument("batch does not equal the ciphertext's batch");
         if (context_.scheme() == Scheme::ckks)
@@ -811,11 +812,13 @@ namespace sealhip
             if (!std::isnormal(scale) || scale <= 0) // is_metadata_valid_for(Plaintext)
                 throw std::invalid_argument("plain is not valid for encryption parameters");
         }
-        const size_t plain_bytes = batch * (plain_is_ntt ? (size_t)e.level()->K * context_.n() : context_.n()) * 8;
+        // a plaintext is [K][N] words or [N] coefficients; a scalar is [K] words, scalar_rows rows of `batch` of them
+        const size_t plain_bytes = scalar_rows ? scalar_rows * batch * e.level()->K * 8
+                                               : batch * (plain_is_ntt ? (size_t)e.level()->K * context_.n() : context_.n()) * 8;
         if (e.has_storage() && words_overlap(plain, plain_bytes, e.data(), e.capacity_words() * 8))
-            throw std::invalid_argument("device_plain and encrypted overlap");
+            throw std::invalid_argument(name + " and encrypted overlap");
         if (&dest != &e && dest.has_storage() && words_overlap(plain, plain_bytes, dest.data_, dest.capacity_words() * 8))
-            throw std::invalid_argument("device_plain and destination overlap");
+            throw std::invalid_argument(name + " and destination overlap");
     }
     uint64_t *Evaluator::begin_result(const Ciphertext &e, Ciphertext &dest) const
     {
@@ -1096,10 +1099,10 @@ namespace sealhip
             throw std::invalid_argument("destination's batch does not equal the number of output items");
     }
     // The one host path of the reductions, after their checks and with the operands settled: dest becomes `size` planes of `rows`
-    // items at e's level with the given metadata, the cut is the library's rule for grid_planes * (one result plane) / 2 threads and
-    // this walk, and launch(slices, scratch) starts the kernels
+    // items at e's level with the given metadata, the cut is the library's rule for `threads` threads (one per output pair:
+    // reduce_threads; a tile of rows per thread: dot_scalars_threads) and this walk, and launch(slices, scratch) starts the kernels
     template <class Launch>
-    void Evaluator::reduce_items(const Ciphertext &e, size_t rows, const ItemWalk &walk, size_t size, size_t grid_planes, bool ntt_form,
+    void Evaluator::reduce_items(const Ciphertext &e, size_t rows, const ItemWalk &walk, size_t size, size_t threads, bool ntt_form,
                                  double scale, uint64_t correction_factor, Ciphertext &dest, const char *what, Launch launch) const
     {
         const Level &lvl = *e.level();
@@ -1112,19 +1115,24 @@ namespace sealhip
         dest.is_ntt_form() = ntt_form;
         dest.scale() = scale;
         dest.correction_factor() = correction_factor;
-        const unsigned slices = batch_reduce_slices(grid_planes * dest.plane_words() / 2, walk);
+        const unsigned slices = batch_reduce_slices(threads, walk);
         std::unique_ptr<Scratch> scratch;
         if (slices > 1)
             scratch.reset(new Scratch(batch_reduce_scratch_words(slices, (unsigned)size, rows, (unsigned)context_.log_n(), lvl.K)));
         ck(launch(slices, scratch ? scratch->p : nullptr), what);
         throw_if_transparent(dest);
     }
+    // one thread per output pair of grid_planes planes of `rows` items at e's level
+    size_t Evaluator::reduce_threads(const Ciphertext &e, size_t rows, size_t grid_planes) const
+    {
+        return grid_planes * rows * e.level()->K * context_.n() / 2;
+    }
     void Evaluator::sum_items(const Ciphertext &e, size_t rows, const ItemWalk &walk, Ciphertext &dest) const
     {
         check_reduce_items(e, rows, dest);
         e.settle(); // the operand's words are read by what follows
         // one thread per output pair, the planes in the grid
-        reduce_items(e, rows, walk, e.size(), e.size(), e.is_ntt_form(), e.scale(), e.correction_factor(), dest, "sum (items)",
+        reduce_items(e, rows, walk, e.size(), reduce_threads(e, rows, e.size()), e.is_ntt_form(), e.scale(), e.correction_factor(), dest, "sum (items)",
                      [&](unsigned slices, uint64_t *scratch) {
                          return k_sum_items(context_.dev_mods(), e.data_, e.plane_words(), dest.data_, dest.plane_words(), (unsigned)e.size(),
                                             (unsigned)context_.log_n(), e.level()->K, rows, walk, slices, scratch, stream_);
@@ -1146,8 +1154,8 @@ namespace sealhip
         const ItemWalk walk = mapped_walk(e, map, rows);
         sum_items(e, rows, walk, dest);
     }
-    void Evaluator::dot_plain_items(const Ciphertext &e, const uint64_t *plain, size_t, size_t rows, const ItemWalk &walk, double scale,
-                                    Ciphertext &dest) const
+    // what the plaintext products over `rows` output items check once their operand is known: -> the result's scale
+    double Evaluator::check_dot_plain(const Ciphertext &e, size_t rows, double scale, const Ciphertext &dest) const
     {
         check_reduce_items(e, rows, dest);
         // coefficient-form operands have no place in a reduction: the monomial branch of multiply_plain_normal is per item and data
@@ -1158,9 +1166,15 @@ namespace sealhip
         const double new_scale = ckks ? e.scale() * scale : e.scale(); // as multiply_plain_device
         if (ckks && !scale_within_bounds(new_scale, *e.level()))
             throw std::invalid_argument("scale out of bounds");
+        return new_scale;
+    }
+    void Evaluator::dot_plain_items(const Ciphertext &e, const uint64_t *plain, size_t, size_t rows, const ItemWalk &walk, double scale,
+                                    Ciphertext &dest) const
+    {
+        const double new_scale = check_dot_plain(e, rows, scale, dest);
         e.settle(); // the operand's words are read by what follows
         // one thread per output pair of one plane: the product loops over the planes
-        reduce_items(e, rows, walk, e.size(), 1, e.is_ntt_form(), new_scale, e.correction_factor(), dest, "dot_plain (items)",
+        reduce_items(e, rows, walk, e.size(), reduce_threads(e, rows, 1), e.is_ntt_form(), new_scale, e.correction_factor(), dest, "dot_plain (items)",
                      [&](unsigned slices, uint64_t *scratch) {
                          return k_dot_plain_items(context_.dev_mods(), e.data_, e.plane_words(), plain, dest.data_, dest.plane_words(),
                                                   (unsigned)e.size(), (unsigned)context_.log_n(), e.level()->K, rows, walk, slices, scratch,
@@ -1188,6 +1202,58 @@ namespace sealhip
         dot_plain_items(e, plain, plain_count, rows, walk, scale, dest);
     }
 
+    // A dense rows x batch matrix of scalar plaintexts times the items of a batch (include/sealhip.h: Evaluator_DotScalarsDevice):
+    // dot_plain_mapped over the dense map with [K] words per plaintext instead of [K][N] - its checks, metadata and settling - and
+    // a kernel of its own, whose threads hold a tile of output rows (batch_reduce_kernels.h: k_dot_scalars)
+    void Evaluator::dot_scalars_device(const Ciphertext &e, const uint64_t *scalars, size_t rows, size_t batch, double scale,
+                                       Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        if (!rows || (rows >> 32) || (batch >> 32) || ((rows * batch) >> 32))
+            throw std::invalid_argument("1 <= rows and rows * batch < 2^32");
+        check_plain_device(e, scalars, batch, true, scale, dest, true, rows);
+        const double new_scale = check_dot_plain(e, rows, scale, dest);
+        e.settle(); // the operand's words are read by what follows
+        const unsigned n_log = (unsigned)context_.log_n(), K = e.level()->K;
+        reduce_items(e, rows, ItemWalk(batch), e.size(), dot_scalars_threads((unsigned)e.size(), rows, n_log, K), true, new_scale,
+                     e.correction_factor(), dest, "dot_scalars", [&](unsigned slices, uint64_t *scratch) {
+                         return k_dot_scalars(context_.dev_mods(), e.data_, e.plane_words(), scalars, dest.data_, dest.plane_words(),
+                                              (unsigned)e.size(), n_log, K, rows, batch, slices, scratch, 0, stream_);
+                     });
+    }
+    // BFV / BGV scalars (include/sealhip.h: Evaluator_LiftScalars): the centred lift of transform_to_ntt_inplace(Plaintext) for the
+    // constant polynomial m - m mod q_k, plus (Q - t) mod q_k from the upper-half threshold on, in both lift branches of the reference
+    // (evaluator.cpp:2243-2282) - and the forward transform of a constant is that constant at every position
+    void Evaluator::lift_scalars(size_t count, const uint64_t *values, const uint64_t *parms_id, uint64_t *words) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        if (!values || !words)
+            throw std::invalid_argument(values ? "device_words cannot be null" : "values cannot be null");
+        if ((uintptr_t)words % 16)
+            throw std::invalid_argument("device_words must be 16-byte aligned");
+        if (!count)
+            throw std::invalid_argument("count cannot be zero");
+        const Level *lvl = context_.level_by_parms_id(parms_id);
+        if (!lvl)
+            throw std::invalid_argument("parms_id is not valid for the current context");
+        if (context_.scheme() == Scheme::ckks)
+            throw std::invalid_argument("CKKS plain must be in NTT form");
+        const uint64_t t = context_.plain_modulus(), threshold = (t + 1) >> 1;
+        std::vector<uint64_t> host(count * lvl->K);
+        for (size_t i = 0; i < count; i++)
+        {
+            if (values[i] >= t)
+                throw std::invalid_argument("a value is not below the plain modulus (values[" + std::to_string(i) + "])");
+            for (unsigned k = 0; k < lvl->K; k++)
+            {
+                const uint64_t q = context_.coeff_modulus()[k], inc = (q - t % q) % q, v = values[i] % q;
+                host[i * lvl->K + k] = values[i] >= threshold ? (v + inc) % q : v;
+            }
+        }
+        ck(hipDeviceSynchronize(), "scalars upload"); // not a hot-path call: whatever read or wrote the buffer before is done
+        copy_h2d(words, host.data(), host.size() * 8);
+    }
+
     // sum over the terms of an output item of the 2 x 2 tensor products (include/sealhip.h: Evaluator_DotItems): the checks and
     // metadata of multiply (ckks_multiply / bgv_multiply at 2 x 2) and of sum_items, one kernel and no stored product.  The batches
     // of the operands are the walk's business and checked by the callers
@@ -1210,7 +1276,7 @@ namespace sealhip
         const uint64_t cf = ckks ? 1 : host::mulmod(e1.correction_factor(), e2.correction_factor(), context_.plain_modulus());
         // operands first: whatever is pending on them (a key-switch tail, a product of their own) is settled before their words are read
         const uint64_t *xw = e1.data(), *yw = &e1 == &e2 ? xw : e2.data();
-        reduce_items(e1, rows, walk, 3, 1, true, new_scale, cf, dest, "dot (items)", [&](unsigned slices, uint64_t *scratch) {
+        reduce_items(e1, rows, walk, 3, reduce_threads(e1, rows, 1), true, new_scale, cf, dest, "dot (items)", [&](unsigned slices, uint64_t *scratch) {
             return k_dot_items(context_.dev_mods(), xw, e1.plane_words(), yw, e2.plane_words(), dest.data_, dest.plane_words(),
                                (unsigned)context_.log_n(), lvl.K, rows, walk, slices, scratch, stream_);
         });

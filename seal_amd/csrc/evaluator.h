@@ -391,6 +391,15 @@ namespace sealhip
         void dot_plain_mapped(const Ciphertext &encrypted, const uint64_t *plain, size_t plain_count, const ItemMap &map, double scale,
                               Ciphertext &destination) const;
         void dot_items_mapped(const Ciphertext &encrypted1, const Ciphertext &encrypted2, const ItemMap &map, Ciphertext &destination) const;
+        // A dense rows x batch matrix of SCALAR plaintexts times the items of a batch (include/sealhip.h: Evaluator_DotScalarsDevice):
+        // item o of destination, a batch of `rows` items, becomes the sum over b of encrypted_b times the constant plaintext whose K
+        // words are scalars[o][b] - word for word dot_plain_mapped over the dense map with the scalars expanded to [K][N]; checks,
+        // metadata and settling are dot_plain_device's.  scalars: [rows][batch][K] device words, written earlier on the stream
+        void dot_scalars_device(const Ciphertext &encrypted, const uint64_t *scalars, size_t rows, size_t batch, double scale,
+                                Ciphertext &destination) const;
+        // BFV / BGV: host values modulo t -> [count][K] device words, scalar i = what transform_plain_to_ntt_device leaves at every
+        // coefficient for the constant polynomial values[i] (one synchronous copy after a drain; not a hot-path call)
+        void lift_scalars(size_t count, const uint64_t *values_mod_t, const uint64_t *parms_id, uint64_t *device_words) const;
         void add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const;
         void multiply_many(const std::vector<const Ciphertext *> &encrypteds, const KSwitchKeys &relin_keys, Ciphertext &destination) const;
         void exponentiate_inplace(Ciphertext &encrypted, uint64_t exponent, const KSwitchKeys &relin_keys) const;
@@ -494,9 +503,10 @@ namespace sealhip
         void lift_chunks(const PlainOperand &plain, const Level &lvl, uint64_t scale_by, size_t batch, uint64_t *out, Use use) const;
         // what add_plain / sub_plain accept per scheme (shared by the per-object and the per-item forms)
         void check_addsub_plain_forms(const Ciphertext &encrypted, bool plain_is_ntt, const Level *plain_level, double plain_scale) const;
-        // per_item: one plaintext per item of encrypted (batch must be its batch); otherwise `batch` plaintexts that a map names
+        // per_item: one plaintext per item of encrypted (batch must be its batch); otherwise `batch` plaintexts that a map names.
+        // scalar_rows: the operand is [scalar_rows][batch][K] words of scalars and not `batch` plaintexts
         void check_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
-                                const Ciphertext &destination, bool per_item = true) const;
+                                const Ciphertext &destination, bool per_item = true, size_t scalar_rows = 0) const;
         uint64_t *begin_result(const Ciphertext &encrypted, Ciphertext &destination) const; // destination shaped like encrypted, words undefined
         // the walk of consecutive groups (group divides the batch) or of a map (whose first_batch is the batch); -> its output items
         ItemWalk consecutive_walk(const Ciphertext &encrypted, size_t group, size_t &rows) const;
@@ -504,8 +514,10 @@ namespace sealhip
         void check_reduce_items(const Ciphertext &encrypted, size_t rows, const Ciphertext &destination) const;
         // destination <- `size` planes of `rows` items with this metadata, filled by launch(slices, scratch)
         template <class Launch>
-        void reduce_items(const Ciphertext &encrypted, size_t rows, const ItemWalk &walk, size_t size, size_t grid_planes, bool ntt_form,
+        void reduce_items(const Ciphertext &encrypted, size_t rows, const ItemWalk &walk, size_t size, size_t threads, bool ntt_form,
                           double scale, uint64_t correction_factor, Ciphertext &destination, const char *what, Launch launch) const;
+        size_t reduce_threads(const Ciphertext &encrypted, size_t rows, size_t grid_planes) const;
+        double check_dot_plain(const Ciphertext &encrypted, size_t rows, double scale, const Ciphertext &destination) const;
         void sum_items(const Ciphertext &encrypted, size_t rows, const ItemWalk &walk, Ciphertext &destination) const;
         void dot_plain_items(const Ciphertext &encrypted, const uint64_t *plain, size_t plain_count, size_t rows, const ItemWalk &walk,
                              double scale, Ciphertext &destination) const;
