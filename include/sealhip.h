@@ -557,6 +557,36 @@ SHL_FUNC CKKSEncoder_EncodeIntegerScalars(void *thisptr, uint64_t count, const i
 SHL_FUNC Evaluator_LiftScalars(void *thisptr, uint64_t count, const uint64_t *values_mod_t, uint64_t *parms_id, uint64_t *device_words);
 SHL_FUNC Evaluator_DotScalarsDevice(void *thisptr, void *encrypted, const uint64_t *device_scalars, uint64_t rows, uint64_t batch, double scale,
                                     void *destination);
+/* Ciphertext matrix times ciphertext matrix (library extension): out[i][j] = sum_k X[i][k] (x) Y[k][j] with one ciphertext per
+ * entry and the samples in the slots - Q K^T, a Gram or covariance matrix X X^T, all pairwise inner products or squared distances
+ * between two sets of encrypted vectors.  encrypted1 = a batch of rows * inner items, item (i, k) at i * inner + k; encrypted2 = a
+ * batch of inner * cols items, item (k, j) at k * cols + j, or - flags bit 0 - stored [cols][inner] with item (k, j) at j * inner + k;
+ * any other bit of flags is SHL_E_INVALIDARG.  CKKS or BGV, both operands of size 2, in NTT form and at the same level; BFV is
+ * refused with "unsupported scheme" as Evaluator_DotItems refuses it, and other sizes are refused.  The operands may be the same
+ * handle (X X^T with flags = 1 and rows == cols; no symmetric shortcut is taken).  destination = ANOTHER handle made with
+ * Ciphertext_CreateBatch(rows * cols), distinct from both operands, resized to size 3 at the operands' level; item (i, j) is at
+ * i * cols + j.  It is not relinearised and never a deferred product.
+ * Contract: output item (i, j) equals, word for word, Evaluator_DotItemsMapped over the map whose row i * cols + j names the pairs
+ * (i * inner + k, k * cols + j) for k < inner, hence the reference's multiply per pair and then add_many.  rows = cols = 1 gives
+ * Evaluator_DotItems' words with group = inner; inner = 1 gives Evaluator_Multiply's words for every pair.
+ * Metadata (the scale product with the reference's bound check, the correction-factor product mod t, is_ntt_form = true, the
+ * operands' parms_id), the settle-before-read of operands with a deferred tail or a pending product, Evaluator_SetTransparentCheck
+ * on the result batch and "a failed check leaves the destination untouched" are Evaluator_DotItems'.  SHL_E_POINTER for a NULL
+ * handle.  SHL_E_INVALIDARG: rows, inner or cols == 0; rows * inner, inner * cols or rows * cols >= 2^32; encrypted1's batch !=
+ * rows * inner or encrypted2's != inner * cols; the destination's batch != rows * cols; the destination is an operand; a
+ * coefficient-form operand; mismatched levels; a scale out of bounds; a result too large for one launch (the rows of the flat grid
+ * are numbered in 32 bits).  The call is enqueued on the evaluator's stream without a host round trip and records under
+ * Evaluator_BeginCapture.
+ * One thread holds a tile of 2 consecutive output rows x 4 consecutive output columns of one coefficient position of one prime: per
+ * k it loads the 2 x-items and 4 y-items once, both planes each, with the non-temporal hint, and uses them for all 8 outputs - 1.5
+ * plane-items read per term (i, j, k) where the mapped route reads 4.  Partial tiles at the right and bottom edges read and write
+ * nothing outside the batches.  Products are accumulated as plain 128-bit integers and reduced once per 128 values of k.  A small
+ * result is cut as for Evaluator_DotItems, the rule being asked with ceil(rows / 2) ceil(cols / 4) K N threads that each add `inner`
+ * terms: slices of the inner index are computed by separate workgroups into pool scratch [slices][3][rows cols][K][N], which a
+ * second launch adds; the words do not depend on it.  Measured on one MI355X (profiles/matmul_items.txt): 2.3 - 2.5 times the mapped
+ * route at N = 65536, K = 15 from 4 x 16 x 4 on; slower than it at rows = cols = 1 (use Evaluator_DotItems) and at N = 8192, 4 x 16 x 4. */
+SHL_FUNC Evaluator_MatMulItems(void *thisptr, void *encrypted1, void *encrypted2, uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags,
+                               void *destination);
 SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *pool);
 SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *pool);
@@ -684,6 +714,21 @@ SHL_FUNC shl_dot_scalars(void *context, uint64_t chain_index, const uint64_t *a,
 SHL_FUNC shl_dot_scalars_tile(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *scalars, uint64_t *r, uint64_t size,
                               uint64_t rows, uint64_t batch, uint64_t slices, uint64_t *slices_used, uint64_t row_tile, void *stream);
 SHL_FUNC shl_dot_scalars_info(uint64_t *row_tile, uint64_t *flush);
+/* The kernel of Evaluator_MatMulItems on raw words at one level: x = [2][rows * inner][K][N], y = [2][inner * cols][K][N] (items
+ * [cols][inner] when y_transposed != 0), r = [3][rows * cols][K][N], distinct from the operands; x == y is allowed.  slices: 0 = the
+ * library's rule, 1 = one launch, 2 .. min(inner, 64) = that cut of the inner index; the scratch comes from the pool.  slices_used
+ * (may be NULL) receives the slices run; r == NULL only answers that.  Nothing is validated beyond the shape.  shl_matmul_items runs
+ * on the NULL stream and returns when the work is done; shl_matmul_items_tile enqueues on `stream` with the tile
+ * tile_rows << 8 | tile_cols of output rows x columns per thread - 1 x 1 and 2 x 2 (a thread holds a 16-byte coefficient pair) and
+ * 2 x 4 (one coefficient) are built, 0 is the library's - to which
+ * 1 << 16 / 2 << 16 may be added for operand loads with / without the non-temporal hint (neither: the library's choice) - the sweep
+ * of tools/matmul_items_rate.py.  shl_matmul_items_info: the library's tile and the values of k between two reductions (128). */
+SHL_FUNC shl_matmul_items(void *context, uint64_t chain_index, const uint64_t *x, const uint64_t *y, uint64_t *r, uint64_t rows, uint64_t inner,
+                          uint64_t cols, int y_transposed, uint64_t slices, uint64_t *slices_used);
+SHL_FUNC shl_matmul_items_tile(void *context, uint64_t chain_index, const uint64_t *x, const uint64_t *y, uint64_t *r, uint64_t rows,
+                               uint64_t inner, uint64_t cols, int y_transposed, uint64_t slices, uint64_t *slices_used, uint64_t tile,
+                               void *stream);
+SHL_FUNC shl_matmul_items_info(uint64_t *tile_rows, uint64_t *tile_cols, uint64_t *flush);
 /* GaloisTool::apply_galois (ntt_form == 0, util/galois.cpp:148) / apply_galois_ntt (!= 0, galois.cpp:192) */
 SHL_FUNC shl_apply_galois(void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys, void *stream);
 /* RNSTool stages (util/rns.cpp) on one level, `polys` polynomials each [comps][N]:

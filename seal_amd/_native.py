@@ -87,6 +87,7 @@ Evaluator_DotItems shl_dot_items shl_dot_items_flush_interval
 ItemMap_Create ItemMap_Destroy ItemMap_Info Evaluator_SumItemsMapped Evaluator_DotPlainMapped Evaluator_DotItemsMapped shl_reduce_mapped
 CKKSEncoder_EncodeScalars CKKSEncoder_EncodeIntegerScalars Evaluator_LiftScalars Evaluator_DotScalarsDevice
 shl_dot_scalars shl_dot_scalars_tile shl_dot_scalars_info
+Evaluator_MatMulItems shl_matmul_items shl_matmul_items_tile shl_matmul_items_info
 KSwitchKeys_Create1 KSwitchKeys_Destroy KSwitchKeys_Size KSwitchKeys_SetKey KSwitchKeys_SetKeyFromDevice
 KSwitchKeys_SetKeyDigits KSwitchKeys_HasKey KSwitchKeys_DeviceBytes RelinKeys_GetIndex GaloisKeys_GetIndex GaloisTool_GetEltFromStep
 Evaluator_Create Evaluator_Destroy Evaluator_SetStream Evaluator_Synchronize Evaluator_CopyTo Evaluator_SetTransparentCheck

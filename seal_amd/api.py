@@ -1541,6 +1541,17 @@ class Evaluator:
         N.check(N.lib().Evaluator_DotItems(self._h, a._h, b._h, C.c_uint64(group), d._h))
         return d
 
+    def matmul_items(self, a, b, rows, inner, cols, second_transposed=False, destination=None):
+        """item i * cols + j of the result = the sum over k < inner of a[i * inner + k] (x) b[k * cols + j] - b[j * inner + k] with
+        second_transposed -, size 3, not relinearised: a matrix of ciphertexts times a matrix of ciphertexts (sealhip.h:
+        Evaluator_MatMulItems).  a: a batch of rows * inner, b: a batch of inner * cols size-2 ciphertexts in NTT form at one level
+        (CKKS, BGV); `b is a` is allowed.  destination None: a new Ciphertext of rows * cols items; otherwise a handle of that
+        batch, distinct from both operands.  -> the destination"""
+        d = Ciphertext(self.context, batch=rows * cols) if destination is None else destination
+        N.check(N.lib().Evaluator_MatMulItems(self._h, a._h, b._h, C.c_uint64(rows), C.c_uint64(inner), C.c_uint64(cols),
+                                              C.c_uint64(1 if second_transposed else 0), d._h))
+        return d
+
     # ---- the same reductions over the items an ItemMap names (sealhip.h: Evaluator_SumItemsMapped ...)
     def _mapped_dest(self, item_map, destination):
         return Ciphertext(self.context, batch=item_map.rows()) if destination is None else destination

@@ -93,4 +93,30 @@ namespace sealhip
     hipError_t k_dot_scalars(const ModDesc *mods, const uint64_t *a, size_t a_stride, const uint64_t *scalars, uint64_t *r, size_t r_stride,
                              unsigned size, unsigned n_log, unsigned K, size_t rows, size_t batch, unsigned slices, uint64_t *scratch,
                              unsigned row_tile, hipStream_t s);
+
+    // Ciphertext matrix x ciphertext matrix over the items of two batches: x = [2][rows * inner][K][N] with item (i, k) at
+    // i * inner + k, y = [2][inner * cols][K][N] with item (k, j) at k * cols + j - or at j * inner + k when y_transposed -, both of
+    // size 2 and in NTT form (planes x_stride / y_stride words apart), r = [3][rows * cols][K][N] with item (i, j) at i * cols + j:
+    //   r[.][i][j] = sum_k x[i][k] (x) y[k][j],  the term being k_dot_items' (c0 += x0 y0, c1 += x0 y1 + x1 y0, c2 += x1 y1)
+    // - word for word k_dot_items over the map whose row i * cols + j names the pairs (i * inner + k, k * cols + j).  A thread holds
+    // a tile of TR consecutive output rows x TC consecutive output columns of one coefficient position of one prime, loads the TR
+    // x-items and TC y-items of a k once and uses them for all TR TC outputs: 2 (TR + TC) plane-items read per TR TC terms, where
+    // the map reads 4 per term.  Sums are plain 128-bit integers, reduced once per batch_reduce_dot_items_flush() values of k.
+    // x == y (same pointer) is allowed; r must not be an operand.  Each of rows * inner, inner * cols and rows * cols < 2^32.
+    // slices, scratch: the cut of the inner index as above, with scratch of batch_reduce_scratch_words(slices, 3, rows * cols, ...)
+    // words; the library's rule is asked with matmul_items_threads() threads that each add `inner` terms.
+    // tile: 0 = the library's, or matmul_items_tile_id(TR, TC) of a built one (1 x 1, 2 x 2, 2 x 4: the rate tool's sweep), to
+    // which kMatmulItemsNonTemporal / kMatmulItemsCached may be added to give the operand loads the non-temporal hint or not (neither:
+    // the library's choice).  matmul_items_threads is 0 for a tile that is not built and for a launch the flat grid refuses (rows of
+    // the grid are numbered in 32 bits): k_matmul_items fails on both.
+    constexpr unsigned matmul_items_tile_id(unsigned tile_rows, unsigned tile_cols)
+    {
+        return tile_rows << 8 | tile_cols;
+    }
+    constexpr unsigned kMatmulItemsNonTemporal = 1u << 16, kMatmulItemsCached = 2u << 16, kMatmulItemsHintMask = 3u << 16;
+    void matmul_items_tile(unsigned &tile_rows, unsigned &tile_cols); // the library's
+    size_t matmul_items_threads(size_t rows, size_t cols, unsigned n_log, unsigned K, unsigned tile = 0);
+    hipError_t k_matmul_items(const ModDesc *mods, const uint64_t *x, size_t x_stride, const uint64_t *y, size_t y_stride, uint64_t *r,
+                              size_t r_stride, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols, bool y_transposed,
+                              unsigned slices, uint64_t *scratch, unsigned tile, hipStream_t s);
 } // namespace sealhip

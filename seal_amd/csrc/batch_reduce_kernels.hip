@@ -473,6 +473,200 @@ namespace sealhip
         {
             return r == 2 || r == 4 || r == 8;
         }
+
+        // ---- ciphertext matrix x ciphertext matrix (batch_reduce_kernels.h: k_matmul_items): r[i][j] = sum_k x[i][k] (x) y[k][j],
+        // the term being DotItemsTerm<false>'s.  One thread = W adjacent words of one prime for a TILE of TR consecutive output rows
+        // x TC consecutive output columns: per k it loads the TR x-items and the TC y-items once, both planes each, and uses them for
+        // all TR x TC outputs - 2 (TR + TC) plane-items per TR TC terms where one output per thread reads 4 per term.  The grid is
+        // flat over (row tile, column tile, prime, word), slices of the inner index in y.  Items are numbered arithmetically: there
+        // are no lists to read, so the kernel has one form at every N.
+        // The accumulators are U128 and carry the running total themselves: a flush replaces the sum by its canonical residue, and
+        // the next run of kDotItemsFlush items is added on top of that residue - which fits, see the static_assert - so no second
+        // set of TR x TC x 3 totals is kept in registers.
+        // Partial tiles at the right and bottom edges: dead rows and columns are neither loaded nor stored (FULL = false).
+        // NT: the operand loads carry the non-temporal hint.  Unlike in the other reductions an operand word is used by several
+        // tiles (a row of x by every column tile, a column of y by every row tile), so both forms are built and were measured
+        // (profiles/matmul_items.txt): the hint wins where the operands come from HBM.
+        static_assert((unsigned __int128)kDotFlush * ((uint64_t(1) << kPrimeBits) - 1) * ((uint64_t(1) << kPrimeBits) - 1) <=
+                          ~(unsigned __int128)0 - ((uint64_t(1) << kPrimeBits) - 1),
+                      "a canonical residue plus kDotFlush products of words below 2^60 must fit 128 bits");
+        struct MatmulGeom
+        {
+            size_t x_plane, y_plane;     // words between the two planes of x / of y
+            size_t y_term, y_col;        // words from y item (k, j) to (k + 1, j) / to (k, j + 1): the layout of y
+            size_t dst_plane, dst_slice; // result word of (slice s, plane p): s * dst_slice + p * dst_plane
+            size_t threads;              // row tiles * col tiles * K * N / W
+            unsigned rows, inner, cols, col_tiles, per_slice; // slice s adds the k in [s * per_slice, min(inner, (s + 1) * per_slice))
+            unsigned n_log, K;
+        };
+        template <unsigned W, bool NT>
+        __device__ __forceinline__ void ldw(const uint64_t *p, uint64_t (&v)[W])
+        {
+            if constexpr (W == 2)
+                ld2<NT>(p, v[0], v[1]);
+            else
+            {
+#if defined(__HIP_DEVICE_COMPILE__)
+                v[0] = NT ? __builtin_nontemporal_load(p) : *p;
+#else
+                v[0] = *p;
+#endif
+            }
+        }
+        template <unsigned W, bool FINAL>
+        __device__ __forceinline__ void stw(uint64_t *p, const U128 (&v)[W])
+        {
+            if constexpr (W == 2)
+            {
+                if (FINAL)
+                    st2_nt(p, v[0].lo, v[1].lo);
+                else
+                    st2(p, v[0].lo, v[1].lo);
+            }
+            else
+            {
+#if defined(__HIP_DEVICE_COMPILE__)
+                if (FINAL)
+                    __builtin_nontemporal_store(v[0].lo, p);
+                else
+#endif
+                    *p = v[0].lo;
+            }
+        }
+        // the built tiles: words per thread and the waves per SIMD the allocator is held to (profiles/matmul_items.txt has the
+        // registers; no tile uses scratch memory at these).  A thread holds a 16-byte pair, as in the other kernels, while its
+        // 3 TR TC W sums of four registers and the operands of a term fit the 168 registers of three waves: 2 x 2 with pairs is 96
+        // + 32 (162 allocated; one word per thread takes 144, and spills at the 128 of four waves).  2 x 4 holds one word.
+        template <unsigned TR, unsigned TC>
+        struct MatmulTile;
+        template <>
+        struct MatmulTile<1, 1>
+        {
+            static constexpr unsigned kWords = 2, kWaves = 5;
+        };
+        template <>
+        struct MatmulTile<2, 2>
+        {
+            static constexpr unsigned kWords = 2, kWaves = 3;
+        };
+        template <>
+        struct MatmulTile<2, 4>
+        {
+            static constexpr unsigned kWords = 1, kWaves = 3;
+        };
+        template <unsigned TR, unsigned TC, bool NT, bool FINAL, bool FULL>
+        __device__ __forceinline__ void matmul_items_body(const ModDesc &md, const uint64_t *xp, const uint64_t *yp, uint64_t *d, const MatmulGeom &g,
+                                                          unsigned t0, unsigned t1, unsigned live_r, unsigned live_c)
+        {
+            constexpr unsigned W = MatmulTile<TR, TC>::kWords;
+            const size_t words = (size_t)g.K << g.n_log, x_row = (size_t)g.inner * words; // between two items / two rows of x
+            U128 acc[TR][TC][3][W] = {};
+            for (unsigned t = t0; t < t1;)
+            {
+                const unsigned end = t1 - t < kDotItemsFlush ? t1 : t + kDotItemsFlush;
+                for (; t < end; t++, xp += words, yp += g.y_term)
+                {
+                    uint64_t x[TR][2][W], y[TC][2][W];
+#pragma unroll
+                    for (unsigned r = 0; r < TR; r++)
+                        if (FULL || r < live_r)
+                        {
+                            ldw<W, NT>(xp + r * x_row, x[r][0]);
+                            ldw<W, NT>(xp + r * x_row + g.x_plane, x[r][1]);
+                        }
+#pragma unroll
+                    for (unsigned c = 0; c < TC; c++)
+                        if (FULL || c < live_c)
+                        {
+                            ldw<W, NT>(yp + c * g.y_col, y[c][0]);
+                            ldw<W, NT>(yp + c * g.y_col + g.y_plane, y[c][1]);
+                        }
+#pragma unroll
+                    for (unsigned r = 0; r < TR; r++)
+#pragma unroll
+                        for (unsigned c = 0; c < TC; c++)
+                            if (FULL || (r < live_r && c < live_c))
+                                for (unsigned l = 0; l < W; l++)
+                                {
+                                    mac128(acc[r][c][0][l], x[r][0][l], y[c][0][l]);
+                                    mac128(acc[r][c][1][l], x[r][0][l], y[c][1][l]);
+                                    mac128(acc[r][c][1][l], x[r][1][l], y[c][0][l]);
+                                    mac128(acc[r][c][2][l], x[r][1][l], y[c][1][l]);
+                                }
+                }
+#pragma unroll
+                for (unsigned r = 0; r < TR; r++)
+#pragma unroll
+                    for (unsigned c = 0; c < TC; c++)
+                        if (FULL || (r < live_r && c < live_c))
+                            for (unsigned q = 0; q < 3; q++)
+                                for (unsigned l = 0; l < W; l++)
+                                    acc[r][c][q][l] = U128{ barrett128(acc[r][c][q][l].lo, acc[r][c][q][l].hi, md), 0 };
+            }
+#pragma unroll
+            for (unsigned r = 0; r < TR; r++)
+#pragma unroll
+                for (unsigned c = 0; c < TC; c++)
+                    if (FULL || (r < live_r && c < live_c))
+                        for (unsigned q = 0; q < 3; q++)
+                            stw<W, FINAL>(d + ((size_t)r * g.cols + c) * words + q * g.dst_plane, acc[r][c][q]);
+        }
+        template <unsigned TR, unsigned TC, bool NT, bool FINAL>
+        __global__ void __launch_bounds__(kBlock, (MatmulTile<TR, TC>::kWaves)) matmul_items_kernel(const ModDesc *mods, const uint64_t *x, const uint64_t *y, uint64_t *dst, MatmulGeom g)
+        {
+            constexpr unsigned W = MatmulTile<TR, TC>::kWords;
+            const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
+            if (w >= g.threads)
+                return;
+            const size_t i = W * w, j = i & ((size_t(1) << g.n_log) - 1);
+            const unsigned row = (unsigned)(i >> g.n_log); // (row tile * col_tiles + col tile) * K + k
+            const unsigned k = row % g.K, tile = row / g.K, i0 = tile / g.col_tiles * TR, j0 = tile % g.col_tiles * TC;
+            const unsigned live_r = g.rows - i0 < TR ? g.rows - i0 : TR, live_c = g.cols - j0 < TC ? g.cols - j0 : TC;
+            const ModDesc md = mods[k];
+            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.inner - t0 < g.per_slice ? g.inner : t0 + g.per_slice;
+            const size_t words = (size_t)g.K << g.n_log, inner = ((size_t)k << g.n_log) + j; // component k, coefficient j
+            const uint64_t *xp = x + ((size_t)i0 * g.inner + t0) * words + inner;           // item (i0, t0)
+            const uint64_t *yp = y + t0 * g.y_term + j0 * g.y_col + inner;                  // item (t0, j0)
+            uint64_t *d = dst + blockIdx.y * g.dst_slice + ((size_t)i0 * g.cols + j0) * words + inner;
+            if (live_r == TR && live_c == TC)
+                matmul_items_body<TR, TC, NT, FINAL, true>(md, xp, yp, d, g, t0, t1, live_r, live_c);
+            else
+                matmul_items_body<TR, TC, NT, FINAL, false>(md, xp, yp, d, g, t0, t1, live_r, live_c);
+        }
+        template <unsigned TR, unsigned TC>
+        hipError_t launch_matmul(const ModDesc *mods, const uint64_t *x, const uint64_t *y, uint64_t *dst, const MatmulGeom &g, unsigned slices,
+                                 bool nt, bool final, hipStream_t s)
+        {
+            if (!g.threads) // matmul_items_threads: a launch that flat_grid refuses
+                return hipErrorInvalidValue;
+            const dim3 grid((unsigned)((g.threads + kBlock - 1) / kBlock), slices), block(kBlock);
+            if (nt)
+            {
+                if (final)
+                    hipLaunchKernelGGL((matmul_items_kernel<TR, TC, true, true>), grid, block, 0, s, mods, x, y, dst, g);
+                else
+                    hipLaunchKernelGGL((matmul_items_kernel<TR, TC, true, false>), grid, block, 0, s, mods, x, y, dst, g);
+            }
+            else if (final)
+                hipLaunchKernelGGL((matmul_items_kernel<TR, TC, false, true>), grid, block, 0, s, mods, x, y, dst, g);
+            else
+                hipLaunchKernelGGL((matmul_items_kernel<TR, TC, false, false>), grid, block, 0, s, mods, x, y, dst, g);
+            return hipGetLastError();
+        }
+        // the tile the library runs with and whether its operand loads are non-temporal: the fastest of the built ones at N = 65536,
+        // 8 x 16 x 8 (tools/matmul_items_rate.py measures every tile both ways; DESIGN.md 8.7 has the table).  The hint wins by 4 - 8 %
+        // where the operands come from HBM and loses as much where they fit the caches (N = 8192)
+        constexpr unsigned kMatmulTile = matmul_items_tile_id(2, 4);
+        constexpr bool kMatmulNonTemporal = true;
+        inline bool matmul_tile(unsigned tile, unsigned &tr, unsigned &tc, bool &nt)
+        {
+            const unsigned hint = tile & kMatmulItemsHintMask, shape = tile & ~kMatmulItemsHintMask ? tile & ~kMatmulItemsHintMask : kMatmulTile;
+            tr = shape >> 8;
+            tc = shape & 0xff;
+            nt = hint ? hint == kMatmulItemsNonTemporal : kMatmulNonTemporal;
+            return hint != kMatmulItemsHintMask &&
+                   (shape == matmul_items_tile_id(1, 1) || shape == matmul_items_tile_id(2, 2) || shape == matmul_items_tile_id(2, 4));
+        }
     } // namespace
 
     unsigned batch_reduce_sum_flush()
@@ -579,5 +773,49 @@ namespace sealhip
         if (e != hipSuccess || final)
             return e;
         return sum_slices(mods, scratch, r, r_stride, size, n_log, K, rows, slices, s);
+    }
+
+    void matmul_items_tile(unsigned &tile_rows, unsigned &tile_cols)
+    {
+        bool nt;
+        matmul_tile(0, tile_rows, tile_cols, nt);
+    }
+    size_t matmul_items_threads(size_t rows, size_t cols, unsigned n_log, unsigned K, unsigned tile)
+    {
+        unsigned tr, tc;
+        bool nt;
+        if (!matmul_tile(tile, tr, tc, nt))
+            return 0;
+        const unsigned words = tr == 1 ? MatmulTile<1, 1>::kWords : tc == 2 ? MatmulTile<2, 2>::kWords : MatmulTile<2, 4>::kWords;
+        const size_t grid_rows = ((rows + tr - 1) / tr) * ((cols + tc - 1) / tc) * K, threads = (grid_rows << n_log) / words;
+        // flat_grid's refusal, which counts pairs; a thread of one word makes twice the workgroups
+        unsigned blocks;
+        if (rows > 0xffffffffu || cols > 0xffffffffu || !flat_grid(threads * words / 2, n_log, blocks) || (threads + kBlock - 1) / kBlock > 0x7fffffffu)
+            return 0;
+        return threads;
+    }
+    hipError_t k_matmul_items(const ModDesc *mods, const uint64_t *x, size_t x_stride, const uint64_t *y, size_t y_stride, uint64_t *r,
+                              size_t r_stride, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols, bool y_transposed,
+                              unsigned slices, uint64_t *scratch, unsigned tile, hipStream_t s)
+    {
+        unsigned tr, tc, per_slice;
+        bool nt;
+        const size_t words = (size_t)K << n_log;
+        if (!matmul_tile(tile, tr, tc, nt) || !rows || !inner || !cols || !words || rows > 0xffffffffu || inner > 0xffffffffu || cols > 0xffffffffu ||
+            rows * inner > 0xffffffffu || inner * cols > 0xffffffffu || rows * cols > 0xffffffffu || !cut(inner, slices, per_slice) ||
+            (slices > 1 && !scratch))
+            return hipErrorInvalidValue;
+        const bool final = slices == 1;
+        const size_t out_plane = rows * cols * words, col_tiles = (cols + tc - 1) / tc;
+        const MatmulGeom g{ x_stride, y_stride, y_transposed ? words : cols * words, y_transposed ? inner * words : words,
+                            final ? r_stride : out_plane, final ? 0 : 3 * out_plane, matmul_items_threads(rows, cols, n_log, K, tile),
+                            (unsigned)rows, (unsigned)inner, (unsigned)cols, (unsigned)col_tiles, per_slice, n_log, K };
+        uint64_t *dst = final ? r : scratch;
+        const hipError_t e = tr == 1   ? launch_matmul<1, 1>(mods, x, y, dst, g, slices, nt, final, s)
+                             : tc == 2 ? launch_matmul<2, 2>(mods, x, y, dst, g, slices, nt, final, s)
+                                       : launch_matmul<2, 4>(mods, x, y, dst, g, slices, nt, final, s);
+        if (e != hipSuccess || final)
+            return e;
+        return sum_slices(mods, scratch, r, r_stride, 3, n_log, K, rows * cols, slices, s);
     }
 } // namespace sealhip

@@ -365,6 +365,22 @@ extern "C"
                                                    *as<Ciphertext>(destination));
         SHL_CATCH
     }
+    // ciphertext matrix x ciphertext matrix (library extension); flags bit 0: encrypted2 is stored [cols][inner]
+    SHL_FUNC Evaluator_MatMulItems(void *thisptr, void *encrypted1, void *encrypted2, uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags,
+                                   void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted1, SHL_E_POINTER);
+        IfNullRet(encrypted2, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        if (flags & ~uint64_t(1))
+            throw std::invalid_argument("unknown flags");
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->matmul_items(*as<Ciphertext>(encrypted1), *as<Ciphertext>(encrypted2), (size_t)rows, (size_t)inner, (size_t)cols,
+                                             (flags & 1) != 0, *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
     SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination)
     {
         IfNullRet(thisptr, SHL_E_POINTER);

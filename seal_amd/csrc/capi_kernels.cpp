@@ -226,6 +226,68 @@ extern "C"
         *flush = batch_reduce_dot_flush();
         return SHL_S_OK;
     }
+    // k_matmul_items on raw words: x [2][rows * inner][K][N], y [2][inner * cols][K][N] ([cols][inner] items with y_transposed),
+    // r [3][rows * cols][K][N]; slices == 0: the library's rule; r == NULL: the query.  Scratch comes from the pool.
+    // tile: 0 = the library's (what shl_matmul_items runs); otherwise tile_rows << 8 | tile_cols of a built tile, plus 1 << 16 /
+    // 2 << 16 for operand loads with / without the non-temporal hint - the sweep of tools/matmul_items_rate.py
+    SHL_FUNC shl_matmul_items_tile(void *context, uint64_t chain_index, const uint64_t *x, const uint64_t *y, uint64_t *r, uint64_t rows,
+                                   uint64_t inner, uint64_t cols, int y_transposed, uint64_t slices, uint64_t *slices_used, uint64_t tile,
+                                   void *stream)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        SHL_TRY
+        auto c = as<Context>(context);
+        auto l = c->level_by_chain_index(chain_index);
+        if (!l)
+            throw std::out_of_range("chain_index");
+        const unsigned n_log = (unsigned)c->log_n();
+        const size_t threads = (tile >> 32) ? 0 : matmul_items_threads(rows, cols, n_log, l->K, (unsigned)tile);
+        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
+            ((rows * cols) >> 32) || !threads)
+            throw std::invalid_argument("1 <= rows, inner, cols; rows * inner, inner * cols, rows * cols < 2^32; a built tile");
+        if (!slices)
+            slices = batch_reduce_slices(threads, inner);
+        if (slices > inner || slices > 64)
+            throw std::invalid_argument("1 <= slices <= min(inner, 64)");
+        if (slices_used)
+            *slices_used = slices;
+        if (!r) // a query: the slices the library would use
+            return SHL_S_OK;
+        IfNullRet(x, SHL_E_POINTER);
+        IfNullRet(y, SHL_E_POINTER);
+        hipStream_t s = (hipStream_t)stream;
+        StreamScope scope(s);
+        const size_t words = (size_t)l->K * c->n();
+        std::unique_ptr<Scratch> scratch;
+        if (slices > 1)
+            scratch.reset(new Scratch(batch_reduce_scratch_words((unsigned)slices, 3, rows * cols, n_log, l->K)));
+        hip_ok(k_matmul_items(c->dev_mods(), x, rows * inner * words, y, inner * cols * words, r, rows * cols * words, n_log, l->K, rows, inner, cols,
+                              y_transposed != 0, (unsigned)slices, scratch ? scratch->p : nullptr, (unsigned)tile, s),
+               "matmul_items");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_matmul_items(void *context, uint64_t chain_index, const uint64_t *x, const uint64_t *y, uint64_t *r, uint64_t rows, uint64_t inner,
+                              uint64_t cols, int y_transposed, uint64_t slices, uint64_t *slices_used)
+    {
+        const SHL_HRESULT hr = shl_matmul_items_tile(context, chain_index, x, y, r, rows, inner, cols, y_transposed, slices, slices_used, 0, nullptr);
+        if (hr != SHL_S_OK || !r)
+            return hr;
+        SHL_TRY
+        hip_ok(hipStreamSynchronize(nullptr), "matmul_items sync");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_matmul_items_info(uint64_t *tile_rows, uint64_t *tile_cols, uint64_t *flush)
+    {
+        IfNullRet(tile_rows, SHL_E_POINTER);
+        IfNullRet(tile_cols, SHL_E_POINTER);
+        IfNullRet(flush, SHL_E_POINTER);
+        unsigned tr, tc;
+        matmul_items_tile(tr, tc);
+        *tile_rows = tr;
+        *tile_cols = tc;
+        *flush = batch_reduce_dot_items_flush();
+        return SHL_S_OK;
+    }
     SHL_FUNC shl_apply_galois(
         void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys,
         void *stream)

@@ -1257,7 +1257,8 @@ namespace sealhip
     // sum over the terms of an output item of the 2 x 2 tensor products (include/sealhip.h: Evaluator_DotItems): the checks and
     // metadata of multiply (ckks_multiply / bgv_multiply at 2 x 2) and of sum_items, one kernel and no stored product.  The batches
     // of the operands are the walk's business and checked by the callers
-    void Evaluator::dot_items(const Ciphertext &e1, const Ciphertext &e2, size_t rows, const ItemWalk &walk, Ciphertext &dest) const
+    void Evaluator::check_dot_items(const Ciphertext &e1, const Ciphertext &e2, size_t rows, const Ciphertext &dest, double &new_scale,
+                                    uint64_t &cf) const
     {
         if (e1.level() != e2.level())
             throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
@@ -1268,12 +1269,18 @@ namespace sealhip
         check_reduce_items(e1, rows, dest);
         if (&dest == &e2)
             throw std::invalid_argument("destination must be different from encrypted");
-        const Level &lvl = *e1.level();
         const bool ckks = context_.scheme() == Scheme::ckks;
-        const double new_scale = ckks ? e1.scale() * e2.scale() : e1.scale();
-        if (ckks && !scale_within_bounds(new_scale, lvl))
+        new_scale = ckks ? e1.scale() * e2.scale() : e1.scale();
+        if (ckks && !scale_within_bounds(new_scale, *e1.level()))
             throw std::invalid_argument("scale out of bounds");
-        const uint64_t cf = ckks ? 1 : host::mulmod(e1.correction_factor(), e2.correction_factor(), context_.plain_modulus());
+        cf = ckks ? 1 : host::mulmod(e1.correction_factor(), e2.correction_factor(), context_.plain_modulus());
+    }
+    void Evaluator::dot_items(const Ciphertext &e1, const Ciphertext &e2, size_t rows, const ItemWalk &walk, Ciphertext &dest) const
+    {
+        double new_scale;
+        uint64_t cf;
+        check_dot_items(e1, e2, rows, dest, new_scale, cf);
+        const Level &lvl = *e1.level();
         // operands first: whatever is pending on them (a key-switch tail, a product of their own) is settled before their words are read
         const uint64_t *xw = e1.data(), *yw = &e1 == &e2 ? xw : e2.data();
         reduce_items(e1, rows, walk, 3, reduce_threads(e1, rows, 1), true, new_scale, cf, dest, "dot (items)", [&](unsigned slices, uint64_t *scratch) {
@@ -1311,6 +1318,36 @@ namespace sealhip
         size_t rows;
         const ItemWalk walk = mapped_walk(e1, map, rows);
         dot_items(e1, e2, rows, walk, dest);
+    }
+
+    // ciphertext matrix x ciphertext matrix (include/sealhip.h: Evaluator_MatMulItems): dot_items' checks, metadata and settling over
+    // rows * cols output items that each add `inner` terms, and a kernel of its own, whose threads hold a tile of outputs
+    void Evaluator::matmul_items(const Ciphertext &e1, const Ciphertext &e2, size_t rows, size_t inner, size_t cols, bool second_transposed,
+                                 Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_valid(e1, "encrypted1");
+        check_valid(e2, "encrypted2");
+        check_dot_items_scheme(context_.scheme());
+        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
+            ((rows * cols) >> 32))
+            throw std::invalid_argument("1 <= rows, inner, cols and rows * inner, inner * cols, rows * cols < 2^32");
+        if (e1.batch() != rows * inner || e2.batch() != inner * cols)
+            throw std::invalid_argument("batch mismatch");
+        double new_scale;
+        uint64_t cf;
+        check_dot_items(e1, e2, rows * cols, dest, new_scale, cf);
+        const unsigned n_log = (unsigned)context_.log_n(), K = e1.level()->K;
+        const size_t threads = matmul_items_threads(rows, cols, n_log, K);
+        if (!threads)
+            throw std::invalid_argument("the result is too large for one launch");
+        // operands first: whatever is pending on them (a key-switch tail, a product of their own) is settled before their words are read
+        const uint64_t *xw = e1.data(), *yw = &e1 == &e2 ? xw : e2.data();
+        reduce_items(e1, rows * cols, ItemWalk(inner), 3, threads, true, new_scale, cf, dest, "matmul (items)",
+                     [&](unsigned slices, uint64_t *scratch) {
+                         return k_matmul_items(context_.dev_mods(), xw, e1.plane_words(), yw, e2.plane_words(), dest.data_, dest.plane_words(),
+                                               n_log, K, rows, inner, cols, second_transposed, slices, scratch, 0, stream_);
+                     });
     }
 
     void Evaluator::add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const

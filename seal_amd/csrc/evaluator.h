@@ -391,6 +391,13 @@ namespace sealhip
         void dot_plain_mapped(const Ciphertext &encrypted, const uint64_t *plain, size_t plain_count, const ItemMap &map, double scale,
                               Ciphertext &destination) const;
         void dot_items_mapped(const Ciphertext &encrypted1, const Ciphertext &encrypted2, const ItemMap &map, Ciphertext &destination) const;
+        // Ciphertext matrix x ciphertext matrix (include/sealhip.h: Evaluator_MatMulItems): item i * cols + j of destination, a batch
+        // of rows * cols items, becomes the sum over k < inner of encrypted1_(i * inner + k) (x) encrypted2_(k * cols + j) - item
+        // j * inner + k of encrypted2 when second_transposed - word for word dot_items_mapped over the dense pair map; checks,
+        // metadata and settling are dot_items'.  A kernel of its own, whose threads hold a tile of output rows x columns
+        // (batch_reduce_kernels.h: k_matmul_items)
+        void matmul_items(const Ciphertext &encrypted1, const Ciphertext &encrypted2, size_t rows, size_t inner, size_t cols,
+                          bool second_transposed, Ciphertext &destination) const;
         // A dense rows x batch matrix of SCALAR plaintexts times the items of a batch (include/sealhip.h: Evaluator_DotScalarsDevice):
         // item o of destination, a batch of `rows` items, becomes the sum over b of encrypted_b times the constant plaintext whose K
         // words are scalars[o][b] - word for word dot_plain_mapped over the dense map with the scalars expanded to [K][N]; checks,
@@ -521,6 +528,10 @@ namespace sealhip
         void sum_items(const Ciphertext &encrypted, size_t rows, const ItemWalk &walk, Ciphertext &destination) const;
         void dot_plain_items(const Ciphertext &encrypted, const uint64_t *plain, size_t plain_count, size_t rows, const ItemWalk &walk,
                              double scale, Ciphertext &destination) const;
+        // what the ciphertext x ciphertext sums over `rows` output items check once their operands are known: -> the result's
+        // scale and correction factor
+        void check_dot_items(const Ciphertext &encrypted1, const Ciphertext &encrypted2, size_t rows, const Ciphertext &destination,
+                             double &scale, uint64_t &correction_factor) const;
         void dot_items(const Ciphertext &encrypted1, const Ciphertext &encrypted2, size_t rows, const ItemWalk &walk,
                        Ciphertext &destination) const;
         void bgv_correct_and_combine(
