@@ -587,6 +587,46 @@ SHL_FUNC Evaluator_DotScalarsDevice(void *thisptr, void *encrypted, const uint64
  * route at N = 65536, K = 15 from 4 x 16 x 4 on; slower than it at rows = cols = 1 (use Evaluator_DotItems) and at N = 8192, 4 x 16 x 4. */
 SHL_FUNC Evaluator_MatMulItems(void *thisptr, void *encrypted1, void *encrypted2, uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags,
                                void *destination);
+/* Plaintext matrix times ciphertext matrix (library extension): out[i][j] = sum_k P[i][k] (.) X[k][j] with one full plaintext and
+ * one ciphertext per entry and the samples in the slots - packed (per-slot) weights applied to encrypted activations, the giant
+ * step sum_k diag_k (.) rot_k(x) of a diagonal-method product for many right-hand sides, a block-sparse layer one dense block at a
+ * time.  device_plain = [rows * inner][K][N] NTT-form words at the ciphertext's level, plaintext (i, k) at i * inner + k - what
+ * CKKSEncoder_EncodeDevice and Evaluator_TransformPlainToNTTDevice write -, 16-byte aligned and NOT validated, as for
+ * Evaluator_DotPlainDevice; coefficient-form plaintexts are not taken.  encrypted = a batch of inner * cols items, item (k, j) at
+ * k * cols + j, of any size >= 2 at any level in NTT form: CKKS, BGV, or BFV after Evaluator_TransformToNTT2 (a plaintext product
+ * does not round).  destination = ANOTHER handle made with Ciphertext_CreateBatch(rows * cols), resized to the operand's size and
+ * level; item (i, j) is at i * cols + j.  `scale` is the plaintexts' (CKKS; ignored otherwise).
+ * flags bit 0: the ciphertext matrix is stored [cols][inner], item (k, j) at j * inner + k.  Bit 1: the RESULT is stored
+ * [cols][rows], item (i, j) at j * rows + i.  Any other bit is SHL_E_INVALIDARG.  The plaintexts need no flag: the caller encodes
+ * them in whatever order it likes.  With both bits set, X W with the ciphertexts on the left is this call on the transposes with no
+ * data movement: (X W)[a][b] = sum_k W^T[b][k] X^T[k][a], so rows = W's columns, cols = X's rows, X as it is stored is X^T stored
+ * [cols][inner], and the result comes out as X W stored [X's rows][W's columns].
+ * Contract: output item (i, j) equals, word for word and in its metadata, Evaluator_DotPlainMapped over the dense map whose row
+ * i * cols + j names, for k < inner, ciphertext item k * cols + j and plaintext i * inner + k - hence the reference's
+ * multiply_plain_inplace per pair and then add_many.  rows = cols = 1 gives Evaluator_DotPlainDevice's words with group = inner;
+ * inner = 1 gives Evaluator_MultiplyPlainDevice's words (plain_is_ntt = true) on the corresponding pairs.  Bit 1 permutes items
+ * and nothing else.
+ * Metadata (the scale product with the reference's bound check, the correction factor, is_ntt_form and parms_id), the
+ * settle-before-read of an operand with a deferred key-switch tail or a pending product, Evaluator_SetTransparentCheck on the
+ * result batch and "a failed check leaves the destination untouched" are Evaluator_DotPlainDevice's.  SHL_E_POINTER for a NULL
+ * handle.  SHL_E_INVALIDARG: rows, inner or cols == 0; rows * inner, inner * cols or rows * cols >= 2^32; the ciphertext's batch
+ * != inner * cols; the destination's batch != rows * cols; destination == encrypted; a NULL or misaligned device_plain;
+ * device_plain overlapping the words of either ciphertext; a coefficient-form ciphertext; an invalid or foreign ciphertext; a
+ * scale out of bounds; a result too large for one launch (the rows of the flat grid are numbered in 32 bits).  The call is
+ * enqueued on the evaluator's stream without a host round trip and records under Evaluator_BeginCapture.
+ * One thread holds a tile of 4 consecutive output rows x 4 consecutive output columns of one coefficient position of one prime
+ * and one plane (the planes are in the grid): per k it loads the 4 plaintext words and the 4 ciphertext words once and uses them
+ * for all 16 products - 0.5 plane-items read per term and plane where the mapped route reads (size + 1) / size.  Partial tiles
+ * at the right and bottom edges read and write nothing outside the operands.  Products are accumulated as plain 128-bit integers
+ * and reduced once per 256 values of k.  A small result is cut as for Evaluator_DotPlainDevice, the rule being asked with
+ * size ceil(rows / 4) ceil(cols / 4) K N threads that each add `inner` terms: slices of the inner index are computed by separate
+ * workgroups into pool scratch [slices][size][rows cols][K][N], which a second launch adds; the words do not depend on it.
+ * Measured on one MI355X at size 2 (profiles/matmul_plain_items.txt): 2.35 - 2.45 times the mapped route at N = 65536, K = 15 from
+ * 4 x 16 x 4 on, with either flag or both, and 1.49 - 1.92 times at N = 8192, K = 3 from 8 x 16 x 8 on; slower than it at rows =
+ * cols = 1 (0.86 of it at N = 8192, 0.45 at N = 65536: use Evaluator_DotPlainDevice) and at N = 8192, 4 x 16 x 4 (0.57: the rule
+ * cuts the 2 K N threads of the one tile into 4 slices and a second launch).  Sizes other than 2 and the rings below N = 128: not measured. */
+SHL_FUNC Evaluator_MatMulPlainItems(void *thisptr, const uint64_t *device_plain, void *encrypted, uint64_t rows, uint64_t inner, uint64_t cols,
+                                    uint64_t flags, double scale, void *destination);
 SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *pool);
 SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *pool);
@@ -729,6 +769,22 @@ SHL_FUNC shl_matmul_items_tile(void *context, uint64_t chain_index, const uint64
                                uint64_t inner, uint64_t cols, int y_transposed, uint64_t slices, uint64_t *slices_used, uint64_t tile,
                                void *stream);
 SHL_FUNC shl_matmul_items_info(uint64_t *tile_rows, uint64_t *tile_cols, uint64_t *flush);
+/* The kernel of Evaluator_MatMulPlainItems on raw words at one level: pl = [rows * inner][K][N], a = [size][inner * cols][K][N]
+ * (items [cols][inner] with flags bit 0), r = [size][rows * cols][K][N] (items [cols][rows] with flags bit 1), distinct from the
+ * operands; 1 <= size <= 16, any other bit of flags is refused.  slices: 0 = the library's rule, 1 = one launch, 2 .. min(inner, 64)
+ * = that cut of the inner index; the scratch comes from the pool.  slices_used (may be NULL) receives the slices run; r == NULL only
+ * answers that.  Nothing is validated beyond the shape.  shl_matmul_plain_items runs on the NULL stream and returns when the work
+ * is done; shl_matmul_plain_items_tile enqueues on `stream` with the tile tile_rows << 8 | tile_cols of output rows x columns per
+ * thread - 1 x 1 (a thread holds a 16-byte coefficient pair) and 2 x 4, 4 x 4, 4 x 8 (one coefficient) are built, 0 is the
+ * library's, anything else is SHL_E_INVALIDARG - to which 1 << 16 / 2 << 16 may be added for operand loads with / without the
+ * non-temporal hint (neither: the library's choice) - the sweep of tools/matmul_plain_items_rate.py.
+ * shl_matmul_plain_items_info: the library's tile and the values of k between two reductions (256). */
+SHL_FUNC shl_matmul_plain_items(void *context, uint64_t chain_index, const uint64_t *pl, const uint64_t *a, uint64_t *r, uint64_t size,
+                                uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used);
+SHL_FUNC shl_matmul_plain_items_tile(void *context, uint64_t chain_index, const uint64_t *pl, const uint64_t *a, uint64_t *r, uint64_t size,
+                                     uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used,
+                                     uint64_t tile, void *stream);
+SHL_FUNC shl_matmul_plain_items_info(uint64_t *tile_rows, uint64_t *tile_cols, uint64_t *flush);
 /* GaloisTool::apply_galois (ntt_form == 0, util/galois.cpp:148) / apply_galois_ntt (!= 0, galois.cpp:192) */
 SHL_FUNC shl_apply_galois(void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys, void *stream);
 /* RNSTool stages (util/rns.cpp) on one level, `polys` polynomials each [comps][N]:

@@ -88,6 +88,7 @@ ItemMap_Create ItemMap_Destroy ItemMap_Info Evaluator_SumItemsMapped Evaluator_D
 CKKSEncoder_EncodeScalars CKKSEncoder_EncodeIntegerScalars Evaluator_LiftScalars Evaluator_DotScalarsDevice
 shl_dot_scalars shl_dot_scalars_tile shl_dot_scalars_info
 Evaluator_MatMulItems shl_matmul_items shl_matmul_items_tile shl_matmul_items_info
+Evaluator_MatMulPlainItems shl_matmul_plain_items shl_matmul_plain_items_tile shl_matmul_plain_items_info
 KSwitchKeys_Create1 KSwitchKeys_Destroy KSwitchKeys_Size KSwitchKeys_SetKey KSwitchKeys_SetKeyFromDevice
 KSwitchKeys_SetKeyDigits KSwitchKeys_HasKey KSwitchKeys_DeviceBytes RelinKeys_GetIndex GaloisKeys_GetIndex GaloisTool_GetEltFromStep
 Evaluator_Create Evaluator_Destroy Evaluator_SetStream Evaluator_Synchronize Evaluator_CopyTo Evaluator_SetTransparentCheck

@@ -1552,6 +1552,23 @@ class Evaluator:
                                               C.c_uint64(1 if second_transposed else 0), d._h))
         return d
 
+    def matmul_plain_items(self, words, a, rows, inner, cols, scale=1.0, second_transposed=False, result_transposed=False, destination=None):
+        """item i * cols + j of the result - j * rows + i with result_transposed - = the sum over k < inner of plaintext i * inner + k
+        times a[k * cols + j] - a[j * inner + k] with second_transposed: a matrix of plaintexts times a matrix of ciphertexts
+        (sealhip.h: Evaluator_MatMulPlainItems).  words: DeviceBuffer of [rows * inner][K][N] NTT-form words at the ciphertext's
+        level (CKKSEncoder.encode_device's or transform_plain_to_ntt_device's); a: a batch of inner * cols ciphertexts in NTT form.
+        scale: the plaintexts' common scale (CKKS; the scales are multiplied).  destination None: a new Ciphertext of rows * cols
+        items; otherwise a handle of that batch, distinct from `a`.  -> the destination"""
+        need = rows * inner * a.poly_modulus_degree() * a.coeff_modulus_size()
+        if isinstance(words, DeviceBuffer) and words.words < need:
+            raise ValueError("%d plaintext words for %d x %d plaintexts at this level: %d needed" % (words.words, rows, inner, need))
+        d = Ciphertext(self.context, batch=rows * cols) if destination is None else destination
+        ptr = words.ptr if isinstance(words, DeviceBuffer) else words
+        flags = (1 if second_transposed else 0) | (2 if result_transposed else 0)
+        N.check(N.lib().Evaluator_MatMulPlainItems(self._h, C.c_void_p(ptr), a._h, C.c_uint64(rows), C.c_uint64(inner), C.c_uint64(cols),
+                                                   C.c_uint64(flags), C.c_double(scale), d._h))
+        return d
+
     # ---- the same reductions over the items an ItemMap names (sealhip.h: Evaluator_SumItemsMapped ...)
     def _mapped_dest(self, item_map, destination):
         return Ciphertext(self.context, batch=item_map.rows()) if destination is None else destination

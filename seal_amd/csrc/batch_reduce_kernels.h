@@ -119,4 +119,26 @@ namespace sealhip
     hipError_t k_matmul_items(const ModDesc *mods, const uint64_t *x, size_t x_stride, const uint64_t *y, size_t y_stride, uint64_t *r,
                               size_t r_stride, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols, bool y_transposed,
                               unsigned slices, uint64_t *scratch, unsigned tile, hipStream_t s);
+
+    // Plaintext matrix x ciphertext matrix over the items of a batch: pl = [rows * inner][K][N] NTT-form plaintexts with (i, k) at
+    // i * inner + k, a = [size][inner * cols][K][N] in NTT form (planes a_stride words apart) with item (k, j) at k * cols + j - or at
+    // j * inner + k when a_transposed -, r = [size][rows * cols][K][N] with item (i, j) at i * cols + j - or at j * rows + i when
+    // r_transposed:
+    //   r[p][i][j] = sum_k pl[i][k] a[p][k][j] mod q_k
+    // - word for word k_dot_plain_items over the map whose row i * cols + j names item k * cols + j and plaintext i * inner + k.  A
+    // thread holds a tile of TP consecutive output rows x TC consecutive output columns of one coefficient position of one prime and
+    // one plane (the planes are in the grid, so any size is one launch), loads the TP plaintext words and TC ciphertext words of a
+    // k once and uses them for all TP TC products: (TP + TC) / (TP TC) plane-items read per term and plane, where the map reads
+    // (size + 1) / size.  Both layouts of a and of r are strides of the one kernel.  Sums are plain 128-bit integers, reduced once
+    // per batch_reduce_dot_flush() values of k.  r must not be an operand.  Each of rows * inner, inner * cols, rows * cols < 2^32.
+    // slices, scratch: the cut of the inner index as above, with scratch of batch_reduce_scratch_words(slices, size, rows * cols,
+    // ...) words; the library's rule is asked with matmul_plain_items_threads() threads that each add `inner` terms.
+    // tile: 0 = the library's, or matmul_items_tile_id(TP, TC) of a built one (1 x 1, 2 x 4, 4 x 4, 4 x 8: the rate tool's sweep),
+    // to which kMatmulItemsNonTemporal / kMatmulItemsCached may be added as for k_matmul_items.  matmul_plain_items_threads is 0 for
+    // a tile that is not built and for a launch the flat grid refuses: k_matmul_plain_items fails on both.
+    void matmul_plain_items_tile(unsigned &tile_rows, unsigned &tile_cols); // the library's
+    size_t matmul_plain_items_threads(unsigned size, size_t rows, size_t cols, unsigned n_log, unsigned K, unsigned tile = 0);
+    hipError_t k_matmul_plain_items(const ModDesc *mods, const uint64_t *pl, const uint64_t *a, size_t a_stride, uint64_t *r, size_t r_stride,
+                                    unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols, bool a_transposed,
+                                    bool r_transposed, unsigned slices, uint64_t *scratch, unsigned tile, hipStream_t s);
 } // namespace sealhip

@@ -8,6 +8,7 @@
 #include "batch_reduce_kernels.h"
 #include "stream_device.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace sealhip
 {
@@ -667,6 +668,182 @@ namespace sealhip
             return hint != kMatmulItemsHintMask &&
                    (shape == matmul_items_tile_id(1, 1) || shape == matmul_items_tile_id(2, 2) || shape == matmul_items_tile_id(2, 4));
         }
+
+        // ---- plaintext matrix x ciphertext matrix (batch_reduce_kernels.h: k_matmul_plain_items): r[p][i][j] = sum_k pl[i][k] a[p][k][j],
+        // the term being DotPlainTerm's.  One thread = W adjacent words of one prime and ONE plane for a TILE of TP consecutive output
+        // rows (the plaintext side) x TC consecutive output columns (the ciphertext side): per k it loads the TP plaintext words and
+        // the TC ciphertext words once and uses them for all TP x TC products - (TP + TC) plane-items per TP TC terms where one
+        // output per thread reads (size + 1) / size per term.  The planes are in the grid, as in dot_scalars_kernel: the grid is flat
+        // over (plane, row tile, column tile, prime, word), slices of the inner index in y.  The layouts of the ciphertext matrix and
+        // of the result are two strides each, so [inner][cols] / [cols][inner] and [rows][cols] / [cols][rows] are one kernel.  Items
+        // are numbered arithmetically: no lists, one form at every N.
+        // The accumulators carry the running total as matmul_items_kernel's do: a flush replaces the sum by its canonical residue
+        // and the next kDotFlush products are added on top of it.
+        // Partial tiles at the bottom and right edges: dead rows and columns are neither loaded nor stored (FULL = false).
+        // NT: the operand loads carry the non-temporal hint.  A plaintext word is used by the `size` plane-threads and by every
+        // column tile, a ciphertext word by every row tile: both forms are built and were measured (profiles/matmul_plain_items.txt).
+        static_assert((unsigned __int128)kDotFlush * ((uint64_t(1) << kPrimeBits) - 1) * ((uint64_t(1) << kPrimeBits) - 1) <=
+                          ~(unsigned __int128)0 - ((uint64_t(1) << kPrimeBits) - 1),
+                      "a canonical residue plus kDotFlush products of words below 2^60 must fit 128 bits");
+        struct MatmulPlainGeom
+        {
+            size_t a_plane;              // words between two planes of the ciphertexts
+            size_t a_term, a_col;        // words from ciphertext item (k, j) to (k + 1, j) / to (k, j + 1): the layout of the matrix
+            size_t r_row, r_col;         // words from result item (i, j) to (i + 1, j) / to (i, j + 1): the layout of the result
+            size_t dst_plane, dst_slice; // result word of (slice s, plane p): s * dst_slice + p * dst_plane
+            size_t threads;              // size * row tiles * col tiles * K * N / W
+            unsigned rows, inner, cols, row_tiles, col_tiles, per_slice; // slice s adds the k in [s * per_slice, min(inner, (s + 1) * per_slice))
+            unsigned n_log, K;
+        };
+        // the built tiles: words per thread and the waves per SIMD the allocator is held to (profiles/matmul_plain_items.txt has
+        // the registers; no tile uses scratch memory at these).  A sum is four registers and a 64 x 64 multiply-accumulate takes
+        // about ten more, so from 2 x 4 on a thread holds one word: 2 x 4 takes 90 registers (with a pair, or at six waves, it
+        // spills), 4 x 4 134 (it spills at the 128 of four waves) and 4 x 8 needs 287 - the 32 past 255 are accumulation
+        // registers, which only one wave per SIMD can have; at two waves it spills 124 bytes per lane
+        template <unsigned TP, unsigned TC>
+        struct MatmulPlainTile;
+        template <>
+        struct MatmulPlainTile<1, 1>
+        {
+            static constexpr unsigned kWords = 2, kWaves = 8;
+        };
+        template <>
+        struct MatmulPlainTile<2, 4>
+        {
+            static constexpr unsigned kWords = 1, kWaves = 5;
+        };
+        template <>
+        struct MatmulPlainTile<4, 4>
+        {
+            static constexpr unsigned kWords = 1, kWaves = 3;
+        };
+        template <>
+        struct MatmulPlainTile<4, 8>
+        {
+            static constexpr unsigned kWords = 1, kWaves = 1;
+        };
+        template <unsigned TP, unsigned TC, bool NT, bool FINAL, bool FULL>
+        __device__ __forceinline__ void matmul_plain_body(const ModDesc &md, const uint64_t *pp, const uint64_t *ap, uint64_t *d, const MatmulPlainGeom &g,
+                                                          unsigned t0, unsigned t1, unsigned live_r, unsigned live_c)
+        {
+            constexpr unsigned W = MatmulPlainTile<TP, TC>::kWords;
+            const size_t words = (size_t)g.K << g.n_log, p_row = (size_t)g.inner * words; // between two plaintexts / two rows of them
+            U128 acc[TP][TC][W] = {};
+            for (unsigned t = t0; t < t1;)
+            {
+                const unsigned end = t1 - t < kDotFlush ? t1 : t + kDotFlush;
+                for (; t < end; t++, pp += words, ap += g.a_term)
+                {
+                    uint64_t p[TP][W], a[TC][W];
+#pragma unroll
+                    for (unsigned r = 0; r < TP; r++)
+                        if (FULL || r < live_r)
+                            ldw<W, NT>(pp + r * p_row, p[r]);
+#pragma unroll
+                    for (unsigned c = 0; c < TC; c++)
+                        if (FULL || c < live_c)
+                            ldw<W, NT>(ap + c * g.a_col, a[c]);
+#pragma unroll
+                    for (unsigned r = 0; r < TP; r++)
+#pragma unroll
+                        for (unsigned c = 0; c < TC; c++)
+                            if (FULL || (r < live_r && c < live_c))
+                                for (unsigned l = 0; l < W; l++)
+                                    mac128(acc[r][c][l], p[r][l], a[c][l]);
+                }
+#pragma unroll
+                for (unsigned r = 0; r < TP; r++)
+#pragma unroll
+                    for (unsigned c = 0; c < TC; c++)
+                        if (FULL || (r < live_r && c < live_c))
+                            for (unsigned l = 0; l < W; l++)
+                                acc[r][c][l] = U128{ barrett128(acc[r][c][l].lo, acc[r][c][l].hi, md), 0 };
+            }
+#pragma unroll
+            for (unsigned r = 0; r < TP; r++)
+#pragma unroll
+                for (unsigned c = 0; c < TC; c++)
+                    if (FULL || (r < live_r && c < live_c))
+                        stw<W, FINAL>(d + r * g.r_row + c * g.r_col, acc[r][c]);
+        }
+        template <unsigned TP, unsigned TC, bool NT, bool FINAL>
+        __global__ void __launch_bounds__(kBlock, (MatmulPlainTile<TP, TC>::kWaves)) matmul_plain_items_kernel(const ModDesc *mods, const uint64_t *pl, const uint64_t *a, uint64_t *dst, MatmulPlainGeom g)
+        {
+            constexpr unsigned W = MatmulPlainTile<TP, TC>::kWords;
+            const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
+            if (w >= g.threads)
+                return;
+            const size_t i = W * w, j = i & ((size_t(1) << g.n_log) - 1);
+            const unsigned row = (unsigned)(i >> g.n_log); // ((p * row_tiles + row tile) * col_tiles + col tile) * K + k
+            const unsigned k = row % g.K, tile = row / g.K, ct = tile % g.col_tiles, pr = tile / g.col_tiles, rt = pr % g.row_tiles, p = pr / g.row_tiles;
+            const unsigned i0 = rt * TP, j0 = ct * TC;
+            const unsigned live_r = g.rows - i0 < TP ? g.rows - i0 : TP, live_c = g.cols - j0 < TC ? g.cols - j0 : TC;
+            const ModDesc md = mods[k];
+            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.inner - t0 < g.per_slice ? g.inner : t0 + g.per_slice;
+            const size_t words = (size_t)g.K << g.n_log, inner = ((size_t)k << g.n_log) + j; // component k, coefficient j
+            const uint64_t *pp = pl + ((size_t)i0 * g.inner + t0) * words + inner;         // plaintext (i0, t0)
+            const uint64_t *ap = a + p * g.a_plane + t0 * g.a_term + j0 * g.a_col + inner; // plane p of item (t0, j0)
+            uint64_t *d = dst + blockIdx.y * g.dst_slice + p * g.dst_plane + i0 * g.r_row + j0 * g.r_col + inner;
+            if (live_r == TP && live_c == TC)
+                matmul_plain_body<TP, TC, NT, FINAL, true>(md, pp, ap, d, g, t0, t1, live_r, live_c);
+            else
+                matmul_plain_body<TP, TC, NT, FINAL, false>(md, pp, ap, d, g, t0, t1, live_r, live_c);
+        }
+        template <unsigned TP, unsigned TC>
+        hipError_t launch_matmul_plain(const ModDesc *mods, const uint64_t *pl, const uint64_t *a, uint64_t *dst, const MatmulPlainGeom &g,
+                                       unsigned slices, bool nt, bool final, hipStream_t s)
+        {
+            if (!g.threads) // matmul_plain_items_threads: a launch that flat_grid refuses
+                return hipErrorInvalidValue;
+            const dim3 grid((unsigned)((g.threads + kBlock - 1) / kBlock), slices), block(kBlock);
+            if (nt)
+            {
+                if (final)
+                    hipLaunchKernelGGL((matmul_plain_items_kernel<TP, TC, true, true>), grid, block, 0, s, mods, pl, a, dst, g);
+                else
+                    hipLaunchKernelGGL((matmul_plain_items_kernel<TP, TC, true, false>), grid, block, 0, s, mods, pl, a, dst, g);
+            }
+            else if (final)
+                hipLaunchKernelGGL((matmul_plain_items_kernel<TP, TC, false, true>), grid, block, 0, s, mods, pl, a, dst, g);
+            else
+                hipLaunchKernelGGL((matmul_plain_items_kernel<TP, TC, false, false>), grid, block, 0, s, mods, pl, a, dst, g);
+            return hipGetLastError();
+        }
+        // the tile the library runs with and whether its operand loads are non-temporal: the fastest of the built ones at N = 65536,
+        // 8 x 16 x 8 (tools/matmul_plain_items_rate.py measures every tile both ways; DESIGN.md 8.8 has the table).  The hint wins by
+        // 1 - 2 % where the operands come from HBM and loses 8 - 15 % where they fit the caches (N = 8192); 4 x 8 at its one wave per
+        // SIMD is 15 - 17 % behind 4 x 4 there
+        constexpr unsigned kMatmulPlainTile = matmul_items_tile_id(4, 4);
+        constexpr bool kMatmulPlainNonTemporal = true;
+        // f(MatmulPlainTile<TP, TC>{}, TP, TC) for the built tile `shape` names; false = not built
+        template <class F>
+        inline bool with_plain_tile(unsigned shape, F f)
+        {
+            switch (shape)
+            {
+            case matmul_items_tile_id(1, 1):
+                f(std::integral_constant<unsigned, 1>{}, std::integral_constant<unsigned, 1>{});
+                return true;
+            case matmul_items_tile_id(2, 4):
+                f(std::integral_constant<unsigned, 2>{}, std::integral_constant<unsigned, 4>{});
+                return true;
+            case matmul_items_tile_id(4, 4):
+                f(std::integral_constant<unsigned, 4>{}, std::integral_constant<unsigned, 4>{});
+                return true;
+            case matmul_items_tile_id(4, 8):
+                f(std::integral_constant<unsigned, 4>{}, std::integral_constant<unsigned, 8>{});
+                return true;
+            }
+            return false;
+        }
+        // tile: a tile id with the hint bits (batch_reduce_kernels.h) -> its shape (0: the library's) and hint (neither: the library's)
+        inline bool matmul_plain_tile(unsigned tile, unsigned &shape, bool &nt)
+        {
+            const unsigned hint = tile & kMatmulItemsHintMask;
+            shape = tile & ~kMatmulItemsHintMask ? tile & ~kMatmulItemsHintMask : kMatmulPlainTile;
+            nt = hint ? hint == kMatmulItemsNonTemporal : kMatmulPlainNonTemporal;
+            return hint != kMatmulItemsHintMask && with_plain_tile(shape, [](auto, auto) {});
+        }
     } // namespace
 
     unsigned batch_reduce_sum_flush()
@@ -817,5 +994,63 @@ namespace sealhip
         if (e != hipSuccess || final)
             return e;
         return sum_slices(mods, scratch, r, r_stride, 3, n_log, K, rows * cols, slices, s);
+    }
+
+    void matmul_plain_items_tile(unsigned &tile_rows, unsigned &tile_cols)
+    {
+        tile_rows = kMatmulPlainTile >> 8;
+        tile_cols = kMatmulPlainTile & 0xff;
+    }
+    size_t matmul_plain_items_threads(unsigned size, size_t rows, size_t cols, unsigned n_log, unsigned K, unsigned tile)
+    {
+        unsigned shape, words = 0;
+        bool nt;
+        if (!matmul_plain_tile(tile, shape, nt) || rows > 0xffffffffu || cols > 0xffffffffu)
+            return 0;
+        with_plain_tile(shape, [&](auto tp, auto tc) { words = MatmulPlainTile<decltype(tp)::value, decltype(tc)::value>::kWords; });
+        const unsigned tp = shape >> 8, tc = shape & 0xff;
+        const size_t grid_rows = size * ((rows + tp - 1) / tp) * ((cols + tc - 1) / tc) * K, threads = (grid_rows << n_log) / words;
+        // flat_grid's refusal, which counts pairs; a thread of one word makes twice the workgroups
+        unsigned blocks;
+        if (!flat_grid(threads * words / 2, n_log, blocks) || (threads + kBlock - 1) / kBlock > 0x7fffffffu)
+            return 0;
+        return threads;
+    }
+    hipError_t k_matmul_plain_items(const ModDesc *mods, const uint64_t *pl, const uint64_t *a, size_t a_stride, uint64_t *r, size_t r_stride,
+                                    unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols, bool a_transposed,
+                                    bool r_transposed, unsigned slices, uint64_t *scratch, unsigned tile, hipStream_t s)
+    {
+        unsigned shape, per_slice;
+        bool nt;
+        const size_t words = (size_t)K << n_log;
+        if (!matmul_plain_tile(tile, shape, nt) || !size || !rows || !inner || !cols || !words || rows > 0xffffffffu || inner > 0xffffffffu ||
+            cols > 0xffffffffu || rows * inner > 0xffffffffu || inner * cols > 0xffffffffu || rows * cols > 0xffffffffu ||
+            !cut(inner, slices, per_slice) || (slices > 1 && !scratch))
+            return hipErrorInvalidValue;
+        const bool final = slices == 1;
+        const unsigned tp = shape >> 8, tc = shape & 0xff;
+        const size_t out_plane = rows * cols * words;
+        const MatmulPlainGeom g{ a_stride,
+                                 a_transposed ? words : cols * words,
+                                 a_transposed ? inner * words : words,
+                                 r_transposed ? words : cols * words,
+                                 r_transposed ? rows * words : words,
+                                 final ? r_stride : out_plane,
+                                 final ? 0 : size * out_plane,
+                                 matmul_plain_items_threads(size, rows, cols, n_log, K, tile),
+                                 (unsigned)rows,
+                                 (unsigned)inner,
+                                 (unsigned)cols,
+                                 (unsigned)((rows + tp - 1) / tp),
+                                 (unsigned)((cols + tc - 1) / tc),
+                                 per_slice,
+                                 n_log,
+                                 K };
+        uint64_t *dst = final ? r : scratch;
+        hipError_t e = hipErrorInvalidValue;
+        with_plain_tile(shape, [&](auto p, auto c) { e = launch_matmul_plain<decltype(p)::value, decltype(c)::value>(mods, pl, a, dst, g, slices, nt, final, s); });
+        if (e != hipSuccess || final)
+            return e;
+        return sum_slices(mods, scratch, r, r_stride, size, n_log, K, rows * cols, slices, s);
     }
 } // namespace sealhip

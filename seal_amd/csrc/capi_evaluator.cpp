@@ -381,6 +381,22 @@ extern "C"
                                              (flags & 1) != 0, *as<Ciphertext>(destination));
         SHL_CATCH
     }
+    // plaintext matrix x ciphertext matrix (library extension); flags bit 0: encrypted is stored [cols][inner], bit 1: the result
+    // is stored [cols][rows]
+    SHL_FUNC Evaluator_MatMulPlainItems(void *thisptr, const uint64_t *device_plain, void *encrypted, uint64_t rows, uint64_t inner, uint64_t cols,
+                                        uint64_t flags, double scale, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        if (flags & ~uint64_t(3))
+            throw std::invalid_argument("unknown flags");
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->matmul_plain_items(device_plain, *as<Ciphertext>(encrypted), (size_t)rows, (size_t)inner, (size_t)cols,
+                                                   (flags & 1) != 0, (flags & 2) != 0, scale, *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
     SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination)
     {
         IfNullRet(thisptr, SHL_E_POINTER);

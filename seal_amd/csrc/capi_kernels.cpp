@@ -288,6 +288,71 @@ extern "C"
         *flush = batch_reduce_dot_items_flush();
         return SHL_S_OK;
     }
+    // k_matmul_plain_items on raw words: pl [rows * inner][K][N], a [size][inner * cols][K][N] ([cols][inner] items with flags bit 0),
+    // r [size][rows * cols][K][N] ([cols][rows] items with flags bit 1); slices == 0: the library's rule; r == NULL: the query.
+    // Scratch comes from the pool.  tile: 0 = the library's (what shl_matmul_plain_items runs); otherwise tile_rows << 8 | tile_cols
+    // of a built tile, plus 1 << 16 / 2 << 16 for operand loads with / without the non-temporal hint - the sweep of
+    // tools/matmul_plain_items_rate.py
+    SHL_FUNC shl_matmul_plain_items_tile(void *context, uint64_t chain_index, const uint64_t *pl, const uint64_t *a, uint64_t *r, uint64_t size,
+                                         uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used,
+                                         uint64_t tile, void *stream)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        SHL_TRY
+        auto c = as<Context>(context);
+        auto l = c->level_by_chain_index(chain_index);
+        if (!l)
+            throw std::out_of_range("chain_index");
+        const unsigned n_log = (unsigned)c->log_n();
+        if (!size || size > 16 || (flags & ~uint64_t(3)))
+            throw std::invalid_argument("1 <= size <= 16; flags 0 .. 3");
+        const size_t threads = (tile >> 32) ? 0 : matmul_plain_items_threads((unsigned)size, rows, cols, n_log, l->K, (unsigned)tile);
+        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
+            ((rows * cols) >> 32) || !threads)
+            throw std::invalid_argument("1 <= rows, inner, cols; rows * inner, inner * cols, rows * cols < 2^32; a built tile");
+        if (!slices)
+            slices = batch_reduce_slices(threads, inner);
+        if (slices > inner || slices > 64)
+            throw std::invalid_argument("1 <= slices <= min(inner, 64)");
+        if (slices_used)
+            *slices_used = slices;
+        if (!r) // a query: the slices the library would use
+            return SHL_S_OK;
+        IfNullRet(pl, SHL_E_POINTER);
+        IfNullRet(a, SHL_E_POINTER);
+        hipStream_t s = (hipStream_t)stream;
+        StreamScope scope(s);
+        const size_t words = (size_t)l->K * c->n();
+        std::unique_ptr<Scratch> scratch;
+        if (slices > 1)
+            scratch.reset(new Scratch(batch_reduce_scratch_words((unsigned)slices, (unsigned)size, rows * cols, n_log, l->K)));
+        hip_ok(k_matmul_plain_items(c->dev_mods(), pl, a, inner * cols * words, r, rows * cols * words, (unsigned)size, n_log, l->K, rows, inner,
+                                    cols, (flags & 1) != 0, (flags & 2) != 0, (unsigned)slices, scratch ? scratch->p : nullptr, (unsigned)tile, s),
+               "matmul_plain_items");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_matmul_plain_items(void *context, uint64_t chain_index, const uint64_t *pl, const uint64_t *a, uint64_t *r, uint64_t size,
+                                    uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used)
+    {
+        const SHL_HRESULT hr = shl_matmul_plain_items_tile(context, chain_index, pl, a, r, size, rows, inner, cols, flags, slices, slices_used, 0, nullptr);
+        if (hr != SHL_S_OK || !r)
+            return hr;
+        SHL_TRY
+        hip_ok(hipStreamSynchronize(nullptr), "matmul_plain_items sync");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_matmul_plain_items_info(uint64_t *tile_rows, uint64_t *tile_cols, uint64_t *flush)
+    {
+        IfNullRet(tile_rows, SHL_E_POINTER);
+        IfNullRet(tile_cols, SHL_E_POINTER);
+        IfNullRet(flush, SHL_E_POINTER);
+        unsigned tp, tc;
+        matmul_plain_items_tile(tp, tc);
+        *tile_rows = tp;
+        *tile_cols = tc;
+        *flush = batch_reduce_dot_flush();
+        return SHL_S_OK;
+    }
     SHL_FUNC shl_apply_galois(
         void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys,
         void *stream)

@@ -1221,6 +1221,31 @@ namespace sealhip
                                               (unsigned)e.size(), n_log, K, rows, batch, slices, scratch, 0, stream_);
                      });
     }
+    // plaintext matrix x ciphertext matrix (include/sealhip.h: Evaluator_MatMulPlainItems): dot_plain_mapped's checks, metadata and
+    // settling over rows * cols output items that each add `inner` terms, and a kernel of its own, whose threads hold a tile of outputs
+    void Evaluator::matmul_plain_items(const uint64_t *plain, const Ciphertext &e, size_t rows, size_t inner, size_t cols, bool second_transposed,
+                                       bool result_transposed, double scale, Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
+            ((rows * cols) >> 32))
+            throw std::invalid_argument("1 <= rows, inner, cols and rows * inner, inner * cols, rows * cols < 2^32");
+        check_plain_device(e, plain, rows * inner, true, scale, dest, false);
+        if (e.batch() != inner * cols)
+            throw std::invalid_argument("the ciphertext's batch does not equal inner * cols");
+        const double new_scale = check_dot_plain(e, rows * cols, scale, dest);
+        const unsigned n_log = (unsigned)context_.log_n(), K = e.level()->K;
+        const size_t threads = matmul_plain_items_threads((unsigned)e.size(), rows, cols, n_log, K);
+        if (!threads)
+            throw std::invalid_argument("the result is too large for one launch");
+        e.settle(); // the operand's words are read by what follows
+        reduce_items(e, rows * cols, ItemWalk(inner), e.size(), threads, true, new_scale, e.correction_factor(), dest, "matmul_plain (items)",
+                     [&](unsigned slices, uint64_t *scratch) {
+                         return k_matmul_plain_items(context_.dev_mods(), plain, e.data_, e.plane_words(), dest.data_, dest.plane_words(),
+                                                     (unsigned)e.size(), n_log, K, rows, inner, cols, second_transposed, result_transposed,
+                                                     slices, scratch, 0, stream_);
+                     });
+    }
     // BFV / BGV scalars (include/sealhip.h: Evaluator_LiftScalars): the centred lift of transform_to_ntt_inplace(Plaintext) for the
     // constant polynomial m - m mod q_k, plus (Q - t) mod q_k from the upper-half threshold on, in both lift branches of the reference
     // (evaluator.cpp:2243-2282) - and the forward transform of a constant is that constant at every position

@@ -398,6 +398,14 @@ namespace sealhip
         // (batch_reduce_kernels.h: k_matmul_items)
         void matmul_items(const Ciphertext &encrypted1, const Ciphertext &encrypted2, size_t rows, size_t inner, size_t cols,
                           bool second_transposed, Ciphertext &destination) const;
+        // Plaintext matrix x ciphertext matrix (include/sealhip.h: Evaluator_MatMulPlainItems): item i * cols + j of destination, a
+        // batch of rows * cols items - item j * rows + i when result_transposed -, becomes the sum over k < inner of plaintext
+        // i * inner + k times encrypted_(k * cols + j) - item j * inner + k when second_transposed - word for word dot_plain_mapped
+        // over the dense map; checks, metadata and settling are dot_plain_device's.  plain: [rows * inner][K][N] NTT-form device
+        // words at encrypted's level.  A kernel of its own, whose threads hold a tile of output rows x columns
+        // (batch_reduce_kernels.h: k_matmul_plain_items)
+        void matmul_plain_items(const uint64_t *plain, const Ciphertext &encrypted, size_t rows, size_t inner, size_t cols,
+                                bool second_transposed, bool result_transposed, double scale, Ciphertext &destination) const;
         // A dense rows x batch matrix of SCALAR plaintexts times the items of a batch (include/sealhip.h: Evaluator_DotScalarsDevice):
         // item o of destination, a batch of `rows` items, becomes the sum over b of encrypted_b times the constant plaintext whose K
         // words are scalars[o][b] - word for word dot_plain_mapped over the dense map with the scalars expanded to [K][N]; checks,
