@@ -627,6 +627,49 @@ SHL_FUNC Evaluator_MatMulItems(void *thisptr, void *encrypted1, void *encrypted2
  * cuts the 2 K N threads of the one tile into 4 slices and a second launch).  Sizes other than 2 and the rings below N = 128: not measured. */
 SHL_FUNC Evaluator_MatMulPlainItems(void *thisptr, const uint64_t *device_plain, void *encrypted, uint64_t rows, uint64_t inner, uint64_t cols,
                                     uint64_t flags, double scale, void *destination);
+/* Library extension: a matrix of SCALAR weights times a matrix of ciphertexts, out[i][j] = sum_k W[i][k] X[k][j] for i < rows,
+ * j < cols, k < inner - the dense layer applied to many blocks at once, one ciphertext per (feature, block).  It is
+ * Evaluator_MatMulPlainItems with one value in every slot of a plaintext, held as that value and not as [K][N] words, and
+ * Evaluator_DotScalarsDevice with a column index.  encrypted, destination, flags bits 0 and 1 (with the transposed-use note) and
+ * `scale` are Evaluator_MatMulPlainItems'.
+ * flags bit 2 clear - WIDE weights: device_weights = [rows * inner][K] 64-bit words at the ciphertext's level, weight (i, k) at
+ * i * inner + k: what CKKSEncoder_EncodeScalars / CKKSEncoder_EncodeIntegerScalars / Evaluator_LiftScalars write.  `scale` (CKKS) is
+ * the scale the scalars were encoded at.
+ * flags bit 2 set - NARROW weights: device_weights = [rows * inner] signed 32-bit integers; the weight is the constant polynomial
+ * with that integer value, one 4-byte word for all K primes: it stands for the K words w mod q_k.  For CKKS these are the words
+ * CKKSEncoder_EncodeIntegerScalars(w) gives - the words of scale 1.0 - whenever w >= -q_k, that is for every weight when no prime
+ * of the level is below 2^31 (for a smaller prime and w < -q_k that producer follows the reference's Encode5, whose 64-bit sum
+ * q_k + w wraps) - and `scale` is metadata only: the 2^s the caller quantised with, which becomes part of the result's scale
+ * (ct.scale * scale, with the reference's bound check).  For BFV / BGV it stands for
+ * Evaluator_LiftScalars(w mod t) for w inside the centred range of the lift, -(t - ceil(t / 2)) <= w < ceil(t / 2); outside it the
+ * result is unspecified, as for any unvalidated device plaintext.
+ * Any other bit is SHL_E_INVALIDARG.  Both forms must be 16-byte aligned, are not validated, and from N = 128 on are read through
+ * the constant cache: they must have been WRITTEN BY SOMETHING EARLIER ON THE STREAM, as Evaluator_DotScalarsDevice's scalars.
+ * Contract: output item (i, j) equals, word for word and in its metadata, Evaluator_MatMulPlainItems with the same bits 0 and 1 on
+ * [rows * inner][K][N] plaintexts each filled with its weight's K words - hence the reference's multiply_plain_inplace per pair and
+ * then add_many.  With cols = 1 and flags = 0 the words are Evaluator_DotScalarsDevice's.  The narrow form's words are the wide
+ * form's on the words its weights stand for: the arithmetic is exact modulo each prime.
+ * Metadata, the settle-before-read of an operand, Evaluator_SetTransparentCheck on the result batch and "a failed check leaves the
+ * destination untouched" are Evaluator_MatMulPlainItems'.  SHL_E_POINTER for a NULL handle.  SHL_E_INVALIDARG: rows, inner or
+ * cols == 0; rows * inner, inner * cols or rows * cols >= 2^32; the ciphertext's batch != inner * cols; the destination's batch !=
+ * rows * cols; destination == encrypted; NULL or misaligned device_weights; device_weights overlapping the words of either
+ * ciphertext; a coefficient-form ciphertext; an invalid or foreign ciphertext; a scale out of bounds; a result too large for one
+ * launch.  The call is enqueued on the evaluator's stream without a host round trip and records under Evaluator_BeginCapture.
+ * One thread holds a 16-byte coefficient pair of one plane, one prime and one output column for a tile of R consecutive output rows
+ * - 4 for wide, 8 for narrow weights - and uses each loaded ciphertext pair for all of them.  Wide products are accumulated as plain 128-bit integers and reduced once
+ * per 256 values of k.  A narrow weight is used as u = w + 2^31, unsigned: sum a u and sum a are accumulated exactly as 128-bit
+ * integers - a product is two 32 x 32 multiplies where the wide form's compiles to six multiply instructions - and sum a w = sum a u - 2^31 sum a is reduced to
+ * canonical words once per 1024 values of k.  A small result is cut as for Evaluator_DotPlainDevice, the rule being asked with
+ * size ceil(rows / R) cols K N / 2 threads that each add `inner` terms; the words do not depend on it.
+ * Measured on one MI355X at size 2 (profiles/matmul_scalars.txt), cols in {1, 4, 16}: at N = 65536, K = 15 the wide form is 1.7 - 6.6
+ * times Evaluator_MatMulPlainItems' kernel on the expanded plaintexts and runs at 2.0 Tmac/s from 8 rows on, bound by its 64 x 64
+ * multiplies; the narrow form is 1.27 - 1.30 times the wide form there (2.3 - 2.6 Tmac/s) and up to 1.58 times at N = 8192, K = 3.
+ * At cols = 1 the wide form is not slower than Evaluator_DotScalarsDevice's kernel at any measured shape beyond the spread of the
+ * samples.  The narrow form is slower than the wide one with a single row (0.67 - 0.99 at eight of nine shapes: seven of its eight
+ * rows are dead) and at N = 8192, 8 x 16 x 1 and 8 x 16 x 4 (0.86 and 0.55: its fewer threads; at the second they are cut into
+ * slices and a second launch).  Sizes other than 2 and the rings below N = 128: not measured. */
+SHL_FUNC Evaluator_MatMulScalarsItems(void *thisptr, const void *device_weights, void *encrypted, uint64_t rows, uint64_t inner, uint64_t cols,
+                                      uint64_t flags, double scale, void *destination);
 SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *pool);
 SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *pool);
@@ -785,6 +828,20 @@ SHL_FUNC shl_matmul_plain_items_tile(void *context, uint64_t chain_index, const 
                                      uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used,
                                      uint64_t tile, void *stream);
 SHL_FUNC shl_matmul_plain_items_info(uint64_t *tile_rows, uint64_t *tile_cols, uint64_t *flush);
+/* The kernel of Evaluator_MatMulScalarsItems on raw words at one level: weights = [rows * inner][K] 64-bit words or, with flags bit
+ * 2, [rows * inner] signed 32-bit integers; a, r, size, flags bits 0 and 1, slices and slices_used as for shl_matmul_plain_items.
+ * slices_used receives the slices run: of a forced cut those that ceil(inner / slices) values of k each leave non-empty.
+ * Nothing is validated beyond the shape.  shl_matmul_scalars runs on the NULL stream and returns when the work is done;
+ * shl_matmul_scalars_tile enqueues on `stream` with row_tile output rows per thread - 4 and 8 are built, 0 is the library's for the
+ * form, anything else is SHL_E_INVALIDARG - the sweep of tools/matmul_scalars_rate.py.
+ * shl_matmul_scalars_info: the library's row tile for wide and for narrow weights and the values of k between two reductions of
+ * each form (256 and 1024). */
+SHL_FUNC shl_matmul_scalars(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
+                            uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used);
+SHL_FUNC shl_matmul_scalars_tile(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
+                                 uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used,
+                                 uint64_t row_tile, void *stream);
+SHL_FUNC shl_matmul_scalars_info(uint64_t *row_tile, uint64_t *narrow_row_tile, uint64_t *flush, uint64_t *narrow_flush);
 /* GaloisTool::apply_galois (ntt_form == 0, util/galois.cpp:148) / apply_galois_ntt (!= 0, galois.cpp:192) */
 SHL_FUNC shl_apply_galois(void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys, void *stream);
 /* RNSTool stages (util/rns.cpp) on one level, `polys` polynomials each [comps][N]:

@@ -1569,6 +1569,26 @@ class Evaluator:
                                                    C.c_uint64(flags), C.c_double(scale), d._h))
         return d
 
+    def matmul_scalars_items(self, weights, a, rows, inner, cols, flags=0, scale=1.0, narrow=False, destination=None):
+        """item i * cols + j of the result - j * rows + i with flags bit 1 - = the sum over k < inner of the scalar weight
+        i * inner + k times a[k * cols + j] - a[j * inner + k] with flags bit 0: a matrix of scalar weights times a matrix of
+        ciphertexts (sealhip.h: Evaluator_MatMulScalarsItems).  weights: DeviceBuffer of [rows * inner][K] words at the ciphertext's
+        level (CKKSEncoder.encode_scalars' / encode_integer_scalars' or lift_scalars') or, narrow, of [rows * inner] signed 32-bit
+        integers (DeviceBuffer.from_int32), written before this call on the stream; a: a batch of inner * cols
+        ciphertexts in NTT form.  scale: the weights' scale (CKKS; narrow: the 2^s they were quantised with).  destination None: a
+        new Ciphertext of rows * cols items; otherwise a handle of that batch, distinct from `a`.  -> the destination"""
+        if flags & ~3:
+            raise ValueError("flags: bits 0 and 1; narrow weights are the `narrow` argument")
+        need = -(-rows * inner // 2) if narrow else rows * inner * a.coeff_modulus_size()
+        if isinstance(weights, DeviceBuffer) and weights.words < need:
+            raise ValueError("%d words of weights for %d x %d %s weights at this level: %d needed"
+                             % (weights.words, rows, inner, "narrow" if narrow else "wide", need))
+        d = Ciphertext(self.context, batch=rows * cols) if destination is None else destination
+        ptr = weights.ptr if isinstance(weights, DeviceBuffer) else weights
+        N.check(N.lib().Evaluator_MatMulScalarsItems(self._h, C.c_void_p(ptr), a._h, C.c_uint64(rows), C.c_uint64(inner), C.c_uint64(cols),
+                                                     C.c_uint64(flags | (4 if narrow else 0)), C.c_double(scale), d._h))
+        return d
+
     # ---- the same reductions over the items an ItemMap names (sealhip.h: Evaluator_SumItemsMapped ...)
     def _mapped_dest(self, item_map, destination):
         return Ciphertext(self.context, batch=item_map.rows()) if destination is None else destination
@@ -1794,6 +1814,14 @@ class DeviceBuffer:
         if a.dtype.itemsize not in (8, 16):
             raise TypeError("from_array takes 8-byte or complex128 elements, not %s" % a.dtype)
         b = DeviceBuffer(max(a.nbytes // 8, 1))
+        N.check(N.lib().shl_memcpy_h2d(b._ptr, _p(a), C.c_uint64(a.nbytes)))
+        return b
+
+    @staticmethod
+    def from_int32(a):
+        """signed 32-bit integers, two to a word: the narrow weights of Evaluator.matmul_scalars_items"""
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        b = DeviceBuffer(max((a.size + 1) // 2, 1))
         N.check(N.lib().shl_memcpy_h2d(b._ptr, _p(a), C.c_uint64(a.nbytes)))
         return b
 

@@ -141,4 +141,25 @@ namespace sealhip
     hipError_t k_matmul_plain_items(const ModDesc *mods, const uint64_t *pl, const uint64_t *a, size_t a_stride, uint64_t *r, size_t r_stride,
                                     unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols, bool a_transposed,
                                     bool r_transposed, unsigned slices, uint64_t *scratch, unsigned tile, hipStream_t s);
+
+    // Scalar weight matrix x ciphertext matrix over the items of a batch: k_matmul_plain_items with ONE value per prime (or one for
+    // all primes) instead of [K][N] words per plaintext, and k_dot_scalars with a column index.  a, r, a_transposed, r_transposed,
+    // slices and scratch are k_matmul_plain_items':
+    //   r[p][i][j] = sum_k const(w[i][k]) a[p][k][j] mod q
+    // weights, wide (narrow false): [rows * inner][K] 64-bit words, weight (i, k) at i * inner + k - k_dot_scalars' scalars, and with
+    // cols = 1 and no flag its words.  Narrow: [rows * inner] signed 32-bit integers; weight w stands for the K words w mod q, so
+    // the result words are the wide form's on those.  Its products are 32 x 64 bits - two multiplies each - and its sums are
+    // reduced once per matmul_scalars_narrow_flush() values of k (the wide form's: batch_reduce_dot_flush()).  A thread holds a tile
+    // of R consecutive output rows of one coefficient pair of one output column: the operand crosses HBM once per tile of rows.
+    // From N = 128 on the weights are read with scalar loads through the constant cache: they must have been written by something
+    // earlier on the stream.  Each of rows * inner, inner * cols, rows * cols < 2^32; r must not be an operand.
+    // The library's rule is asked with matmul_scalars_threads() threads that each add `inner` terms; it is 0 for a tile that is not
+    // built and for a launch the flat grid refuses: k_matmul_scalars fails on both.  row_tile: 0 = the library's for the form, or
+    // one of the built ones (4, 8: the rate tool's sweep).
+    unsigned matmul_scalars_row_tile(bool narrow);
+    unsigned matmul_scalars_narrow_flush();
+    size_t matmul_scalars_threads(unsigned size, size_t rows, size_t cols, unsigned n_log, unsigned K, bool narrow, unsigned row_tile = 0);
+    hipError_t k_matmul_scalars(const ModDesc *mods, const void *weights, bool narrow, const uint64_t *a, size_t a_stride, uint64_t *r,
+                                size_t r_stride, unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols,
+                                bool a_transposed, bool r_transposed, unsigned slices, uint64_t *scratch, unsigned row_tile, hipStream_t s);
 } // namespace sealhip

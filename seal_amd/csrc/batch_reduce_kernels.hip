@@ -844,6 +844,175 @@ namespace sealhip
             nt = hint ? hint == kMatmulItemsNonTemporal : kMatmulPlainNonTemporal;
             return hint != kMatmulItemsHintMask && with_plain_tile(shape, [](auto, auto) {});
         }
+
+        // ---- scalar weight matrix x ciphertext matrix (batch_reduce_kernels.h: k_matmul_scalars): r[p][i][j] = sum_k w[i][k] a[p][k][j],
+        // the plaintext of term (i, k) being ONE value per prime as in dot_scalars_kernel.  One thread = one 16-byte pair of one plane,
+        // one prime and one output COLUMN for a TILE of R consecutive output rows: the operand pair of (k, j) is loaded once and used
+        // for R x 2 products.  The grid is flat over (plane, row tile, column, prime, pair), slices of the inner index in y; the
+        // layouts of the ciphertext matrix and of the result are two strides each, as in matmul_plain_items_kernel.
+        // UNIFORM (N >= 128): as in dot_scalars_kernel the row number is moved to an SGPR and the R weights of a term are scalar loads
+        // through the constant address space, so the weights must have been WRITTEN BY SOMETHING EARLIER ON THE STREAM.  Below
+        // N = 128 the loads are per lane.  The last tile's dead rows are neither loaded nor stored (FULL = false).
+        // The accumulators are U128 and carry the running total, as matmul_plain_items_kernel's do.
+        // Two forms of the weights:
+        //   wide    [rows * inner][K] 64-bit words, weight (i, k) of prime q at (i * inner + k) * K + q: dot_scalars_kernel's products
+        //           (a 64 x 64 -> 128 multiply each) and its flush interval, kDotFlush.
+        //   narrow  [rows * inner] signed 32-bit integers, one for all primes.  The weight w is used BIASED, u = w + 2^31 in
+        //           [0, 2^32) (the sign bit flipped): sum_k a_k w_k = sum_k a_k u_k - 2^31 sum_k a_k.  Both sums are unsigned and
+        //           exact; the second does not depend on the output row, so a thread keeps one per word of its pair and not one per
+        //           row.  A product a u is two 32 x 32 -> 64 multiplies (the halves of a) where the wide form's compiles to six multiply
+        //           instructions (four v_mad_u64_u32, two v_mul).  At a flush
+        //           the total becomes  (P mod q) - (2^31 mod q) (S mod q)  mod q, the canonical residue of sum_k a_k w_k.
+        // kNarrowFlush terms between two reductions.  Bound (the widest prime the library admits is below 2^60, so a canonical
+        // word is at most 2^60 - 1; w = -2^31 gives u = 0 and w = 2^31 - 1 the largest u = 2^32 - 1, so every u is covered):
+        //   P <= (q - 1) + T (2^60 - 1)(2^32 - 1) < 2^60 + T 2^92,   S <= T (2^60 - 1) < T 2^60
+        // both below 2^128 for T <= 2^35.  The inner index is below 2^32, so the sums could not overflow at all; the interval is
+        // kept far below the bound so that the loop is the wide form's and its boundary is met by tests of ordinary size - one
+        // reduction of R + 1 sums per 1024 terms costs nothing measurable.
+        constexpr unsigned kNarrowFlush = 1u << 10;
+        static_assert((unsigned __int128)kNarrowFlush * ((uint64_t(1) << kPrimeBits) - 1) * 0xffffffffu <=
+                          ~(unsigned __int128)0 - ((uint64_t(1) << kPrimeBits) - 1),
+                      "a canonical residue plus kNarrowFlush products of a word below 2^60 and a biased 32-bit weight must fit 128 bits");
+        struct MatmulScalarsGeom
+        {
+            size_t a_plane;              // words between two planes of the ciphertexts
+            size_t a_term, a_col;        // words from ciphertext item (k, j) to (k + 1, j) / to (k, j + 1): the layout of the matrix
+            size_t r_row, r_col;         // words from result item (i, j) to (i + 1, j) / to (i, j + 1): the layout of the result
+            size_t dst_plane, dst_slice; // result word of (slice s, plane p): s * dst_slice + p * dst_plane
+            size_t pairs;                // size * tiles * cols * K * N / 2
+            unsigned rows, inner, cols, tiles, per_slice; // slice s adds the k in [s * per_slice, min(inner, (s + 1) * per_slice))
+            unsigned n_log, K;
+        };
+        // acc += a u for a canonical word a and a 32-bit u.  Written on the 128-bit integer type: the product becomes the two
+        // 32 x 32 -> 64 multiply-adds of the halves of a and the sum one chain of four adds with carry, 7 vector instructions per
+        // product where the same sum through add128's comparison takes 11
+        __device__ __forceinline__ void mac_narrow(U128 &acc, uint64_t a, uint32_t u)
+        {
+            const unsigned __int128 sum = ((unsigned __int128)acc.hi << 64 | acc.lo) + (unsigned __int128)a * u;
+            acc.lo = (uint64_t)sum;
+            acc.hi = (uint64_t)(sum >> 64);
+        }
+        // waves per SIMD the allocator is held to (profiles/matmul_scalars.txt has the registers: no kernel uses scratch memory at
+        // these, and the allocator stays below them: 62 - 72 registers at four rows, 80 - 106 at eight).  The per-lane kernels keep
+        // a weight address per lane and the narrow form two more sums
+        template <unsigned R>
+        constexpr unsigned matmul_scalars_waves()
+        {
+            return R == 4 ? 6 : 4;
+        }
+        template <unsigned R, bool NARROW, bool UNIFORM, bool FINAL, bool FULL>
+        __device__ __forceinline__ void matmul_scalars_rows(const ModDesc &md, const uint64_t *ap, const void *weights, size_t first, uint64_t *d,
+                                                            const MatmulScalarsGeom &g, unsigned k, unsigned t0, unsigned t1, unsigned live)
+        {
+            using Word = std::conditional_t<NARROW, uint32_t, uint64_t>;
+            constexpr unsigned kFlush = NARROW ? kNarrowFlush : kDotFlush;
+            // weight (o0, t0) [of prime k]; words from a term to the next and from a row to the next
+            const size_t step = NARROW ? 1 : g.K, row_words = (size_t)g.inner * step;
+            const Word *wp = static_cast<const Word *>(weights) + (NARROW ? first : first * g.K + k);
+            const uint64_t bias = NARROW ? barrett64(uint64_t(1) << 31, md) : 0; // 2^31 mod q
+            U128 acc[R][2] = {};
+            for (unsigned t = t0; t < t1;)
+            {
+                const unsigned end = t1 - t < kFlush ? t1 : t + kFlush;
+                U128 plain[2] = {}; // narrow: the sum of the operand words themselves
+                for (; t < end; t++, ap += g.a_term, wp += step)
+                {
+                    uint64_t a0, a1;
+                    ld2<true>(ap, a0, a1);
+                    if (NARROW)
+                    {
+                        add128(plain[0], a0, 0);
+                        add128(plain[1], a1, 0);
+                    }
+#pragma unroll
+                    for (unsigned r = 0; r < R; r++)
+                        if (FULL || r < live)
+                        {
+                            if constexpr (NARROW)
+                            {
+                                const uint32_t u = (UNIFORM ? SHL_UCONST32(wp)[r * row_words] : wp[r * row_words]) ^ 0x80000000u;
+                                mac_narrow(acc[r][0], a0, u);
+                                mac_narrow(acc[r][1], a1, u);
+                            }
+                            else
+                            {
+                                const uint64_t w = UNIFORM ? SHL_UCONST(wp)[r * row_words] : wp[r * row_words];
+                                mac128(acc[r][0], a0, w);
+                                mac128(acc[r][1], a1, w);
+                            }
+                        }
+                }
+                uint64_t less[2] = {}; // narrow: 2^31 times that sum
+                if (NARROW)
+                    for (unsigned l = 0; l < 2; l++)
+                        less[l] = mul_mod(barrett128(plain[l].lo, plain[l].hi, md), bias, md);
+#pragma unroll
+                for (unsigned r = 0; r < R; r++)
+                    if (FULL || r < live)
+                        for (unsigned l = 0; l < 2; l++)
+                            acc[r][l] = U128{ sub_mod(barrett128(acc[r][l].lo, acc[r][l].hi, md), less[l], md.q), 0 };
+            }
+#pragma unroll
+            for (unsigned r = 0; r < R; r++)
+                if (FULL || r < live)
+                {
+                    if (FINAL)
+                        st2_nt(d + r * g.r_row, acc[r][0].lo, acc[r][1].lo);
+                    else
+                        st2(d + r * g.r_row, acc[r][0].lo, acc[r][1].lo);
+                }
+        }
+        template <unsigned R, bool NARROW, bool UNIFORM, bool FINAL>
+        __global__ void __launch_bounds__(kBlock, matmul_scalars_waves<R>()) matmul_scalars_kernel(const ModDesc *mods, const void *weights, const uint64_t *a, uint64_t *dst, MatmulScalarsGeom g)
+        {
+            const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
+            if (w >= g.pairs)
+                return;
+            const size_t i = 2 * w, j = i & ((size_t(1) << g.n_log) - 1);
+            unsigned row = (unsigned)(i >> g.n_log); // ((p * tiles + tile) * cols + c) * K + k
+            if (UNIFORM)
+                row = SHL_UNIFORM(row);
+            const unsigned k = row % g.K, pc = row / g.K, c = pc % g.cols, pt = pc / g.cols, tile = pt % g.tiles, p = pt / g.tiles;
+            const unsigned o0 = tile * R, live = g.rows - o0 < R ? g.rows - o0 : R;
+            const ModDesc md = mods[k];
+            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.inner - t0 < g.per_slice ? g.inner : t0 + g.per_slice;
+            const size_t inner = ((size_t)k << g.n_log) + j; // component k, coefficient j
+            const uint64_t *ap = a + p * g.a_plane + t0 * g.a_term + c * g.a_col + inner; // plane p of item (t0, c)
+            uint64_t *d = dst + blockIdx.y * g.dst_slice + p * g.dst_plane + o0 * g.r_row + c * g.r_col + inner;
+            const size_t first = (size_t)o0 * g.inner + t0; // weight (o0, t0)
+            if (live == R)
+                matmul_scalars_rows<R, NARROW, UNIFORM, FINAL, true>(md, ap, weights, first, d, g, k, t0, t1, live);
+            else
+                matmul_scalars_rows<R, NARROW, UNIFORM, FINAL, false>(md, ap, weights, first, d, g, k, t0, t1, live);
+        }
+        template <unsigned R, bool NARROW>
+        hipError_t launch_matmul_scalars(const ModDesc *mods, const void *weights, const uint64_t *a, uint64_t *dst, const MatmulScalarsGeom &g,
+                                         unsigned slices, bool final, hipStream_t s)
+        {
+            if (!g.pairs) // matmul_scalars_threads: a launch that flat_grid refuses
+                return hipErrorInvalidValue;
+            const dim3 grid((unsigned)((g.pairs + kBlock - 1) / kBlock), slices), block(kBlock);
+            if (g.n_log >= 7)
+            {
+                if (final)
+                    hipLaunchKernelGGL((matmul_scalars_kernel<R, NARROW, true, true>), grid, block, 0, s, mods, weights, a, dst, g);
+                else
+                    hipLaunchKernelGGL((matmul_scalars_kernel<R, NARROW, true, false>), grid, block, 0, s, mods, weights, a, dst, g);
+            }
+            else if (final)
+                hipLaunchKernelGGL((matmul_scalars_kernel<R, NARROW, false, true>), grid, block, 0, s, mods, weights, a, dst, g);
+            else
+                hipLaunchKernelGGL((matmul_scalars_kernel<R, NARROW, false, false>), grid, block, 0, s, mods, weights, a, dst, g);
+            return hipGetLastError();
+        }
+        // the row tile the library runs each form with (tools/matmul_scalars_rate.py measures both; DESIGN.md 8.9 has the table).
+        // Wide: both tiles are bound by the 64 x 64 multiplies (2.0 - 2.1 Tmac/s at N = 65536) and R = 4 cuts small results less
+        // often.  Narrow: R = 4 is bound by the operand stream there, R = 8 is 8 - 10 % faster from 8 rows on
+        constexpr unsigned kMatmulScalarsTile = 4, kMatmulScalarsNarrowTile = 8;
+        inline bool matmul_scalars_tile_built(unsigned r)
+        {
+            return r == 4 || r == 8;
+        }
     } // namespace
 
     unsigned batch_reduce_sum_flush()
@@ -1049,6 +1218,61 @@ namespace sealhip
         uint64_t *dst = final ? r : scratch;
         hipError_t e = hipErrorInvalidValue;
         with_plain_tile(shape, [&](auto p, auto c) { e = launch_matmul_plain<decltype(p)::value, decltype(c)::value>(mods, pl, a, dst, g, slices, nt, final, s); });
+        if (e != hipSuccess || final)
+            return e;
+        return sum_slices(mods, scratch, r, r_stride, size, n_log, K, rows * cols, slices, s);
+    }
+
+    unsigned matmul_scalars_row_tile(bool narrow)
+    {
+        return narrow ? kMatmulScalarsNarrowTile : kMatmulScalarsTile;
+    }
+    unsigned matmul_scalars_narrow_flush()
+    {
+        return kNarrowFlush;
+    }
+    size_t matmul_scalars_threads(unsigned size, size_t rows, size_t cols, unsigned n_log, unsigned K, bool narrow, unsigned row_tile)
+    {
+        const unsigned R = row_tile ? row_tile : matmul_scalars_row_tile(narrow);
+        if (!matmul_scalars_tile_built(R) || rows > 0xffffffffu || cols > 0xffffffffu || rows * cols > 0xffffffffu)
+            return 0;
+        const size_t pairs = ((size * ((rows + R - 1) / R) * cols * K) << n_log) / 2;
+        unsigned blocks;
+        return flat_grid(pairs, n_log, blocks) ? pairs : 0;
+    }
+    hipError_t k_matmul_scalars(const ModDesc *mods, const void *weights, bool narrow, const uint64_t *a, size_t a_stride, uint64_t *r,
+                                size_t r_stride, unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols,
+                                bool a_transposed, bool r_transposed, unsigned slices, uint64_t *scratch, unsigned row_tile, hipStream_t s)
+    {
+        const unsigned R = row_tile ? row_tile : matmul_scalars_row_tile(narrow);
+        unsigned per_slice;
+        const size_t words = (size_t)K << n_log;
+        if (!matmul_scalars_tile_built(R) || !size || !rows || !inner || !cols || !words || rows > 0xffffffffu || inner > 0xffffffffu ||
+            cols > 0xffffffffu || rows * inner > 0xffffffffu || inner * cols > 0xffffffffu || rows * cols > 0xffffffffu ||
+            !cut(inner, slices, per_slice) || (slices > 1 && !scratch))
+            return hipErrorInvalidValue;
+        const bool final = slices == 1;
+        const size_t out_plane = rows * cols * words;
+        const MatmulScalarsGeom g{ a_stride,
+                                   a_transposed ? words : cols * words,
+                                   a_transposed ? inner * words : words,
+                                   r_transposed ? words : cols * words,
+                                   r_transposed ? rows * words : words,
+                                   final ? r_stride : out_plane,
+                                   final ? 0 : size * out_plane,
+                                   matmul_scalars_threads(size, rows, cols, n_log, K, narrow, R),
+                                   (unsigned)rows,
+                                   (unsigned)inner,
+                                   (unsigned)cols,
+                                   (unsigned)((rows + R - 1) / R),
+                                   per_slice,
+                                   n_log,
+                                   K };
+        uint64_t *dst = final ? r : scratch;
+        const hipError_t e = narrow ? (R == 4 ? launch_matmul_scalars<4, true>(mods, weights, a, dst, g, slices, final, s)
+                                              : launch_matmul_scalars<8, true>(mods, weights, a, dst, g, slices, final, s))
+                                    : (R == 4 ? launch_matmul_scalars<4, false>(mods, weights, a, dst, g, slices, final, s)
+                                              : launch_matmul_scalars<8, false>(mods, weights, a, dst, g, slices, final, s));
         if (e != hipSuccess || final)
             return e;
         return sum_slices(mods, scratch, r, r_stride, size, n_log, K, rows * cols, slices, s);

@@ -397,6 +397,22 @@ extern "C"
                                                    (flags & 1) != 0, (flags & 2) != 0, scale, *as<Ciphertext>(destination));
         SHL_CATCH
     }
+    // scalar weight matrix x ciphertext matrix (library extension); flags bits 0 and 1 as above, bit 2: the weights are signed 32-bit
+    // integers and not [K] words each
+    SHL_FUNC Evaluator_MatMulScalarsItems(void *thisptr, const void *device_weights, void *encrypted, uint64_t rows, uint64_t inner, uint64_t cols,
+                                          uint64_t flags, double scale, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        if (flags & ~uint64_t(7))
+            throw std::invalid_argument("unknown flags");
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->matmul_scalars_items(device_weights, (flags & 4) != 0, *as<Ciphertext>(encrypted), (size_t)rows, (size_t)inner,
+                                                     (size_t)cols, (flags & 1) != 0, (flags & 2) != 0, scale, *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
     SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination)
     {
         IfNullRet(thisptr, SHL_E_POINTER);

@@ -353,6 +353,73 @@ extern "C"
         *flush = batch_reduce_dot_flush();
         return SHL_S_OK;
     }
+    // k_matmul_scalars on raw words: weights [rows * inner][K] 64-bit words or, flags bit 2, [rows * inner] signed 32-bit integers,
+    // a [size][inner * cols][K][N] ([cols][inner] items with flags bit 0), r [size][rows * cols][K][N] ([cols][rows] items with flags
+    // bit 1); slices == 0: the library's rule; r == NULL: the query.  Scratch comes from the pool.  row_tile: 0 = the library's for
+    // the form (what shl_matmul_scalars runs); 4 and 8 are built - the sweep of tools/matmul_scalars_rate.py
+    SHL_FUNC shl_matmul_scalars_tile(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
+                                     uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used,
+                                     uint64_t row_tile, void *stream)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        SHL_TRY
+        auto c = as<Context>(context);
+        auto l = c->level_by_chain_index(chain_index);
+        if (!l)
+            throw std::out_of_range("chain_index");
+        const unsigned n_log = (unsigned)c->log_n();
+        if (!size || size > 16 || (flags & ~uint64_t(7)))
+            throw std::invalid_argument("1 <= size <= 16; flags 0 .. 7");
+        const bool narrow = (flags & 4) != 0;
+        const size_t threads = (row_tile >> 32) ? 0 : matmul_scalars_threads((unsigned)size, rows, cols, n_log, l->K, narrow, (unsigned)row_tile);
+        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
+            ((rows * cols) >> 32) || !threads)
+            throw std::invalid_argument("1 <= rows, inner, cols; rows * inner, inner * cols, rows * cols < 2^32; a built row tile");
+        if (!slices)
+            slices = batch_reduce_slices(threads, inner);
+        if (slices > inner || slices > 64)
+            throw std::invalid_argument("1 <= slices <= min(inner, 64)");
+        slices = (inner + (inner + slices - 1) / slices - 1) / ((inner + slices - 1) / slices); // those the cut leaves non-empty
+        if (slices_used)
+            *slices_used = slices;
+        if (!r) // a query: the slices the library would use
+            return SHL_S_OK;
+        IfNullRet(weights, SHL_E_POINTER);
+        IfNullRet(a, SHL_E_POINTER);
+        hipStream_t s = (hipStream_t)stream;
+        StreamScope scope(s);
+        const size_t words = (size_t)l->K * c->n();
+        std::unique_ptr<Scratch> scratch;
+        if (slices > 1)
+            scratch.reset(new Scratch(batch_reduce_scratch_words((unsigned)slices, (unsigned)size, rows * cols, n_log, l->K)));
+        hip_ok(k_matmul_scalars(c->dev_mods(), weights, narrow, a, inner * cols * words, r, rows * cols * words, (unsigned)size, n_log, l->K, rows,
+                                inner, cols, (flags & 1) != 0, (flags & 2) != 0, (unsigned)slices, scratch ? scratch->p : nullptr,
+                                (unsigned)row_tile, s),
+               "matmul_scalars");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_matmul_scalars(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
+                                uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used)
+    {
+        const SHL_HRESULT hr = shl_matmul_scalars_tile(context, chain_index, weights, a, r, size, rows, inner, cols, flags, slices, slices_used, 0, nullptr);
+        if (hr != SHL_S_OK || !r)
+            return hr;
+        SHL_TRY
+        hip_ok(hipStreamSynchronize(nullptr), "matmul_scalars sync");
+        SHL_CATCH
+    }
+    SHL_FUNC shl_matmul_scalars_info(uint64_t *row_tile, uint64_t *narrow_row_tile, uint64_t *flush, uint64_t *narrow_flush)
+    {
+        IfNullRet(row_tile, SHL_E_POINTER);
+        IfNullRet(narrow_row_tile, SHL_E_POINTER);
+        IfNullRet(flush, SHL_E_POINTER);
+        IfNullRet(narrow_flush, SHL_E_POINTER);
+        *row_tile = matmul_scalars_row_tile(false);
+        *narrow_row_tile = matmul_scalars_row_tile(true);
+        *flush = batch_reduce_dot_flush();
+        *narrow_flush = matmul_scalars_narrow_flush();
+        return SHL_S_OK;
+    }
     SHL_FUNC shl_apply_galois(
         void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys,
         void *stream)

@@ -795,7 +795,7 @@ namespace sealhip
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
     }
     void Evaluator::check_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
-                                       const Ciphertext &dest, bool per_item, size_t scalar_rows) const
+                                       const Ciphertext &dest, bool per_item, size_t scalar_rows, bool narrow_scalars) const
     {
         const std::string name = scalar_rows ? "device_scalars" : "device_plain";
         check_valid(e, "encrypted");
@@ -812,8 +812,8 @@ namespace sealhip
             if (!std::isnormal(scale) || scale <= 0) // is_metadata_valid_for(Plaintext)
                 throw std::invalid_argument("plain is not valid for encryption parameters");
         }
-        // a plaintext is [K][N] words or [N] coefficients; a scalar is [K] words, scalar_rows rows of `batch` of them
-        const size_t plain_bytes = scalar_rows ? scalar_rows * batch * e.level()->K * 8
+        // a plaintext is [K][N] words or [N] coefficients; a scalar is [K] words or one 32-bit integer, scalar_rows rows of `batch` of them
+        const size_t plain_bytes = scalar_rows ? scalar_rows * batch * (narrow_scalars ? 4 : e.level()->K * 8)
                                                : batch * (plain_is_ntt ? (size_t)e.level()->K * context_.n() : context_.n()) * 8;
         if (e.has_storage() && words_overlap(plain, plain_bytes, e.data(), e.capacity_words() * 8))
             throw std::invalid_argument(name + " and encrypted overlap");
@@ -1244,6 +1244,31 @@ namespace sealhip
                          return k_matmul_plain_items(context_.dev_mods(), plain, e.data_, e.plane_words(), dest.data_, dest.plane_words(),
                                                      (unsigned)e.size(), n_log, K, rows, inner, cols, second_transposed, result_transposed,
                                                      slices, scratch, 0, stream_);
+                     });
+    }
+    // scalar weight matrix x ciphertext matrix (include/sealhip.h: Evaluator_MatMulScalarsItems): matmul_plain_items with [K] words or
+    // one 32-bit integer per plaintext instead of [K][N] - its checks, metadata and settling - and dot_scalars_device's kind of kernel
+    void Evaluator::matmul_scalars_items(const void *weights, bool narrow, const Ciphertext &e, size_t rows, size_t inner, size_t cols,
+                                         bool second_transposed, bool result_transposed, double scale, Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
+            ((rows * cols) >> 32))
+            throw std::invalid_argument("1 <= rows, inner, cols and rows * inner, inner * cols, rows * cols < 2^32");
+        check_plain_device(e, static_cast<const uint64_t *>(weights), inner, true, scale, dest, false, rows, narrow);
+        if (e.batch() != inner * cols)
+            throw std::invalid_argument("the ciphertext's batch does not equal inner * cols");
+        const double new_scale = check_dot_plain(e, rows * cols, scale, dest);
+        const unsigned n_log = (unsigned)context_.log_n(), K = e.level()->K;
+        const size_t threads = matmul_scalars_threads((unsigned)e.size(), rows, cols, n_log, K, narrow);
+        if (!threads)
+            throw std::invalid_argument("the result is too large for one launch");
+        e.settle(); // the operand's words are read by what follows
+        reduce_items(e, rows * cols, ItemWalk(inner), e.size(), threads, true, new_scale, e.correction_factor(), dest, "matmul_scalars (items)",
+                     [&](unsigned slices, uint64_t *scratch) {
+                         return k_matmul_scalars(context_.dev_mods(), weights, narrow, e.data_, e.plane_words(), dest.data_, dest.plane_words(),
+                                                 (unsigned)e.size(), n_log, K, rows, inner, cols, second_transposed, result_transposed, slices,
+                                                 scratch, 0, stream_);
                      });
     }
     // BFV / BGV scalars (include/sealhip.h: Evaluator_LiftScalars): the centred lift of transform_to_ntt_inplace(Plaintext) for the

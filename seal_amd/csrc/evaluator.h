@@ -406,6 +406,13 @@ namespace sealhip
         // (batch_reduce_kernels.h: k_matmul_plain_items)
         void matmul_plain_items(const uint64_t *plain, const Ciphertext &encrypted, size_t rows, size_t inner, size_t cols,
                                 bool second_transposed, bool result_transposed, double scale, Ciphertext &destination) const;
+        // Scalar weight matrix x ciphertext matrix (include/sealhip.h: Evaluator_MatMulScalarsItems): matmul_plain_items with the
+        // plaintext i * inner + k being the constant whose K words are weights[i * inner + k] ([rows * inner][K] device words) or,
+        // narrow, the constant polynomial with the signed 32-bit integer value weights[i * inner + k] ([rows * inner] of them) - word
+        // for word matmul_plain_items with the weights expanded to [K][N]; checks, metadata and settling are dot_plain_device's.
+        // weights: written earlier on the stream.  A kernel of its own (batch_reduce_kernels.h: k_matmul_scalars)
+        void matmul_scalars_items(const void *weights, bool narrow, const Ciphertext &encrypted, size_t rows, size_t inner, size_t cols,
+                                  bool second_transposed, bool result_transposed, double scale, Ciphertext &destination) const;
         // A dense rows x batch matrix of SCALAR plaintexts times the items of a batch (include/sealhip.h: Evaluator_DotScalarsDevice):
         // item o of destination, a batch of `rows` items, becomes the sum over b of encrypted_b times the constant plaintext whose K
         // words are scalars[o][b] - word for word dot_plain_mapped over the dense map with the scalars expanded to [K][N]; checks,
@@ -519,9 +526,10 @@ namespace sealhip
         // what add_plain / sub_plain accept per scheme (shared by the per-object and the per-item forms)
         void check_addsub_plain_forms(const Ciphertext &encrypted, bool plain_is_ntt, const Level *plain_level, double plain_scale) const;
         // per_item: one plaintext per item of encrypted (batch must be its batch); otherwise `batch` plaintexts that a map names.
-        // scalar_rows: the operand is [scalar_rows][batch][K] words of scalars and not `batch` plaintexts
+        // scalar_rows: the operand is [scalar_rows][batch][K] words of scalars and not `batch` plaintexts - or, narrow_scalars,
+        // [scalar_rows][batch] 32-bit integers
         void check_plain_device(const Ciphertext &encrypted, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
-                                const Ciphertext &destination, bool per_item = true, size_t scalar_rows = 0) const;
+                                const Ciphertext &destination, bool per_item = true, size_t scalar_rows = 0, bool narrow_scalars = false) const;
         uint64_t *begin_result(const Ciphertext &encrypted, Ciphertext &destination) const; // destination shaped like encrypted, words undefined
         // the walk of consecutive groups (group divides the batch) or of a map (whose first_batch is the batch); -> its output items
         ItemWalk consecutive_walk(const Ciphertext &encrypted, size_t group, size_t &rows) const;
