@@ -88,6 +88,8 @@ namespace sealhip
     // stream (a copy, a previous kernel).  rows * batch < 2^32.  slices, scratch: the cut of the batch as above, with scratch of
     // batch_reduce_scratch_words(slices, size, rows, ...) words; the library's rule is asked with dot_scalars_threads() threads
     // that each add `batch` terms.  row_tile: 0 = the library's, or one of the built ones (2, 4, 8: the rate tool's sweep).
+    // It is k_matmul_scalars (below) at one column: the wide form with cols = 1, inner = batch and neither layout flag, run by the
+    // same kernel.
     unsigned dot_scalars_row_tile();
     size_t dot_scalars_threads(unsigned size, size_t rows, unsigned n_log, unsigned K, unsigned row_tile = 0);
     hipError_t k_dot_scalars(const ModDesc *mods, const uint64_t *a, size_t a_stride, const uint64_t *scalars, uint64_t *r, size_t r_stride,

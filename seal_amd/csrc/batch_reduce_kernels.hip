@@ -1,10 +1,13 @@
-// See batch_reduce_kernels.h.  One thread = two adjacent words of one output row (N is even, rows are 16-byte aligned); the grid is
-// flat in x (one thread per output pair) and, when the group is cut, the slices sit in y.  There is one kernel, reduce_items_kernel:
-// what a reduction adds per term is its Term (SumTerm, DotPlainTerm, DotItemsTerm), which items its terms are is its Walk
-// (ConsecutiveWalk, MappedWalk), everything else exists once.
-// The scalar weights have a kernel of their own, dot_scalars_kernel: its threads hold a TILE of output rows of one pair and use each
-// loaded operand pair for all of them, which a kernel of one output row per thread cannot do; it shares the accumulators, the flush
-// interval, the accesses, the grid, the cut and the sum of the slices.
+// See batch_reduce_kernels.h.  Two skeletons, each with one launch path and one host path:
+// - reduce_items_kernel, one output item per thread: one thread = two adjacent words of one output row (N is even, rows are 16-byte
+//   aligned); the grid is flat in x (one thread per output pair).  What a reduction adds per term is its Term (SumTerm,
+//   DotPlainTerm, DotItemsTerm), which items its terms are is its Walk (ConsecutiveWalk, MappedWalk); launch_reduce and
+//   reduce_items are the launch and the host path.
+// - the tiled products (the matrix products and the scalar weights), a TILE of output items per thread, so that each loaded operand
+//   word is used for all of them: one geometry (TileGeom), one prologue (TileThread), two bodies - matmul_words_kernel with its term
+//   (MatmulItemsTerm, MatmulPlainTerm) and matmul_scalars_kernel, whose weights are scalar loads -, launch_tiled and tiled_reduce.
+// Both share the accumulators and flush intervals, the accesses, the flat grid with the slices of a cut in y, the cut and the sum of
+// the slices.
 #include "batch_reduce_kernels.h"
 #include "stream_device.h"
 #include <algorithm>
@@ -352,154 +355,72 @@ namespace sealhip
             return sum_slices(mods, scratch, r, r_stride, size, n_log, K, out_items, slices, s);
         }
 
-        // ---- scalar weights (batch_reduce_kernels.h: k_dot_scalars): r[p][o] = sum_b a[p][b] * const(s[o][b]), the plaintext of term
-        // (o, b) being ONE word per prime.  One thread = one 16-byte pair of one plane and one prime for a TILE of R consecutive
-        // output rows: each loaded ciphertext pair is used for R x 2 products, so the operand crosses HBM once per tile of rows and
-        // not once per row.  The grid is flat over (plane, row tile, k, pair) - the weight is the same for every plane and its load
-        // is cheap, so the planes are in the grid -, slices of the batch in y.  Accumulators are the products' (U128, kDotFlush).
-        // UNIFORM (N >= 128): a wave covers 128 consecutive words and never leaves its (plane, tile, k) row: the row number is moved
-        // to an SGPR and the R weights of an item are scalar loads through the constant address space - SGPRs, not VGPRs, and
-        // uniform trip counts.  The scalars are therefore read through the constant cache: they must have been WRITTEN BY SOMETHING
-        // EARLIER ON THE STREAM (a copy, a previous kernel), as the lists of an item map.  Below N = 128 the lanes of a wave sit in
-        // different rows: per-lane loads.
-        // The last tile has rows mod R live rows; its dead rows are neither loaded nor stored (FULL = false).
-        struct ScalarGeom
-        {
-            size_t a_plane;              // words between two planes of the operand
-            size_t dst_plane, dst_slice; // result word of (slice s, plane p): s * dst_slice + p * dst_plane
-            size_t pairs;                // size * tiles * K * N / 2
-            unsigned rows, tiles, batch, per_slice; // slice s adds the items [s * per_slice, min(batch, (s + 1) * per_slice))
-            unsigned n_log, K;
-        };
-        // waves per SIMD the allocator is held to and the unroll factor of the loop over the items (profiles/dot_scalars.txt: no
-        // kernel uses scratch memory at these).  Two rows leave room for two items in flight; from four rows on the loop is left
-        // rolled - unrolled by two, R = 8 spills at 4 waves.  The per-lane kernels keep R weight addresses per lane.
-        template <unsigned R, bool UNIFORM>
-        constexpr unsigned scalar_waves()
-        {
-            return R == 2 ? (UNIFORM ? 8 : 5) : R == 4 ? 6 : 4;
-        }
-        template <unsigned R>
-        constexpr unsigned scalar_unroll()
-        {
-            return R == 2 ? 2 : 1;
-        }
-        template <unsigned R, bool UNIFORM, bool FINAL, bool FULL>
-        __device__ __forceinline__ void dot_scalars_rows(const ModDesc &md, const uint64_t *ap, const uint64_t *sp, uint64_t *d, const ScalarGeom &g,
-                                                         unsigned t0, unsigned t1, unsigned live)
-        {
-            const size_t words = (size_t)g.K << g.n_log, row_words = (size_t)g.batch * g.K; // between two items / two rows of weights
-            uint64_t tot[R][2] = {};
-            for (unsigned t = t0; t < t1;)
-            {
-                const unsigned end = t1 - t < kDotFlush ? t1 : t + kDotFlush;
-                U128 acc[R][2] = {};
-#pragma unroll scalar_unroll<R>()
-                for (; t < end; t++, ap += words, sp += g.K)
-                {
-                    uint64_t a0, a1;
-                    ld2<true>(ap, a0, a1);
-#pragma unroll
-                    for (unsigned r = 0; r < R; r++)
-                        if (FULL || r < live)
-                        {
-                            const uint64_t w = UNIFORM ? SHL_UCONST(sp)[r * row_words] : sp[r * row_words];
-                            mac128(acc[r][0], a0, w);
-                            mac128(acc[r][1], a1, w);
-                        }
-                }
-#pragma unroll
-                for (unsigned r = 0; r < R; r++)
-                    if (FULL || r < live)
-                        for (unsigned l = 0; l < 2; l++)
-                            tot[r][l] = add_mod(tot[r][l], barrett128(acc[r][l].lo, acc[r][l].hi, md), md.q);
-            }
-#pragma unroll
-            for (unsigned r = 0; r < R; r++)
-                if (FULL || r < live)
-                {
-                    if (FINAL)
-                        st2_nt(d + r * words, tot[r][0], tot[r][1]);
-                    else
-                        st2(d + r * words, tot[r][0], tot[r][1]);
-                }
-        }
-        template <unsigned R, bool UNIFORM, bool FINAL>
-        __global__ void __launch_bounds__(kBlock, (scalar_waves<R, UNIFORM>())) dot_scalars_kernel(const ModDesc *mods, const uint64_t *a, const uint64_t *scalars, uint64_t *dst, ScalarGeom g)
-        {
-            const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
-            if (w >= g.pairs)
-                return;
-            const size_t i = 2 * w, j = i & ((size_t(1) << g.n_log) - 1);
-            unsigned row = (unsigned)(i >> g.n_log); // (p * tiles + tile) * K + k
-            if (UNIFORM)
-                row = SHL_UNIFORM(row);
-            const unsigned k = row % g.K, pt = row / g.K, tile = pt % g.tiles, p = pt / g.tiles;
-            const unsigned o0 = tile * R, live = g.rows - o0 < R ? g.rows - o0 : R;
-            const ModDesc md = mods[k];
-            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.batch - t0 < g.per_slice ? g.batch : t0 + g.per_slice;
-            const size_t inner = ((size_t)k << g.n_log) + j; // component k, coefficient j
-            const uint64_t *ap = a + p * g.a_plane + (((size_t)t0 * g.K) << g.n_log) + inner; // item t0
-            const uint64_t *sp = scalars + ((size_t)o0 * g.batch + t0) * g.K + k;            // s[o0][t0][k]
-            uint64_t *d = dst + blockIdx.y * g.dst_slice + p * g.dst_plane + (((size_t)o0 * g.K) << g.n_log) + inner;
-            if (live == R)
-                dot_scalars_rows<R, UNIFORM, FINAL, true>(md, ap, sp, d, g, t0, t1, live);
-            else
-                dot_scalars_rows<R, UNIFORM, FINAL, false>(md, ap, sp, d, g, t0, t1, live);
-        }
-        template <unsigned R>
-        hipError_t launch_scalars(const ModDesc *mods, const uint64_t *a, const uint64_t *scalars, uint64_t *dst, const ScalarGeom &g, unsigned slices,
-                                  bool final, hipStream_t s)
-        {
-            unsigned blocks;
-            if (!flat_grid(g.pairs, g.n_log, blocks))
-                return hipErrorInvalidValue;
-            const dim3 grid(blocks, slices), block(kBlock);
-            if (g.n_log >= 7)
-            {
-                if (final)
-                    hipLaunchKernelGGL((dot_scalars_kernel<R, true, true>), grid, block, 0, s, mods, a, scalars, dst, g);
-                else
-                    hipLaunchKernelGGL((dot_scalars_kernel<R, true, false>), grid, block, 0, s, mods, a, scalars, dst, g);
-            }
-            else if (final)
-                hipLaunchKernelGGL((dot_scalars_kernel<R, false, true>), grid, block, 0, s, mods, a, scalars, dst, g);
-            else
-                hipLaunchKernelGGL((dot_scalars_kernel<R, false, false>), grid, block, 0, s, mods, a, scalars, dst, g);
-            return hipGetLastError();
-        }
-        // the row tile the library runs with (tools/dot_scalars_rate.py measures the three; DESIGN.md 8.6 has the table)
-        constexpr unsigned kRowTile = 4;
-        inline bool row_tile_built(unsigned r)
-        {
-            return r == 2 || r == 4 || r == 8;
-        }
-
-        // ---- ciphertext matrix x ciphertext matrix (batch_reduce_kernels.h: k_matmul_items): r[i][j] = sum_k x[i][k] (x) y[k][j],
-        // the term being DotItemsTerm<false>'s.  One thread = W adjacent words of one prime for a TILE of TR consecutive output rows
-        // x TC consecutive output columns: per k it loads the TR x-items and the TC y-items once, both planes each, and uses them for
-        // all TR x TC outputs - 2 (TR + TC) plane-items per TR TC terms where one output per thread reads 4 per term.  The grid is
-        // flat over (row tile, column tile, prime, word), slices of the inner index in y.  Items are numbered arithmetically: there
-        // are no lists to read, so the kernel has one form at every N.
+        // ---- the tiled products: r[p][i][j] = sum_t x[i][t] * y[p][t][j] over a rows x inner matrix x (ciphertexts, plaintexts or
+        // scalar weights; item (i, t) at i * inner + t) and an inner x cols matrix y of ciphertext items.  One thread = W adjacent
+        // words of one prime for a TILE of TR consecutive output rows x TC consecutive output columns: per t it loads the TR items
+        // of x and the TC items of y once and uses them for all TR x TC outputs, which a kernel of one output per thread cannot do.
+        // The grid is flat over (plane, row tile, column tile, prime, word), slices of the inner index in y.  The layouts of y and
+        // of the result are two strides each, so [inner][cols] / [cols][inner] and [rows][cols] / [cols][rows] are one kernel.
+        // Items are numbered arithmetically: there are no lists to read.
         // The accumulators are U128 and carry the running total themselves: a flush replaces the sum by its canonical residue, and
-        // the next run of kDotItemsFlush items is added on top of that residue - which fits, see the static_assert - so no second
-        // set of TR x TC x 3 totals is kept in registers.
+        // the next run of terms is added on top of that residue - which fits, see the static_assert - so no second set of totals
+        // is kept in registers.
         // Partial tiles at the right and bottom edges: dead rows and columns are neither loaded nor stored (FULL = false).
-        // NT: the operand loads carry the non-temporal hint.  Unlike in the other reductions an operand word is used by several
-        // tiles (a row of x by every column tile, a column of y by every row tile), so both forms are built and were measured
-        // (profiles/matmul_items.txt): the hint wins where the operands come from HBM.
+        // What differs between the products is the BODY (matmul_words_body with its term, matmul_scalars_rows); the geometry, the
+        // prologue (TileThread), the launch (launch_tiled), the thread count (tiled_threads), the tile ids (decode_tile) and the
+        // host path (tiled_reduce) exist once.
         static_assert((unsigned __int128)kDotFlush * ((uint64_t(1) << kPrimeBits) - 1) * ((uint64_t(1) << kPrimeBits) - 1) <=
                           ~(unsigned __int128)0 - ((uint64_t(1) << kPrimeBits) - 1),
                       "a canonical residue plus kDotFlush products of words below 2^60 must fit 128 bits");
-        struct MatmulGeom
+        // strides in words.  A row of the grid is ((p * row_tiles + row tile) * col_tiles + col tile) * K + k
+        struct TileGeom
         {
-            size_t x_plane, y_plane;     // words between the two planes of x / of y
-            size_t y_term, y_col;        // words from y item (k, j) to (k + 1, j) / to (k, j + 1): the layout of y
+            size_t x_plane;              // words between the two planes of an x item (ciphertext x ciphertext; otherwise 0)
+            size_t y_plane;              // words between two planes of y
+            size_t y_term, y_col;        // words from y item (t, j) to (t + 1, j) / to (t, j + 1): the layout of y
+            size_t r_row, r_col;         // words from result item (i, j) to (i + 1, j) / to (i, j + 1): the layout of the result
             size_t dst_plane, dst_slice; // result word of (slice s, plane p): s * dst_slice + p * dst_plane
-            size_t threads;              // row tiles * col tiles * K * N / W
-            unsigned rows, inner, cols, col_tiles, per_slice; // slice s adds the k in [s * per_slice, min(inner, (s + 1) * per_slice))
+            size_t threads;              // grid planes * row_tiles * col_tiles * K * N / W; 0: a launch that tiled_threads refuses
+            unsigned rows, inner, cols;  // of the product
+            unsigned row_tiles, col_tiles; // ceil(rows / TR), ceil(cols / TC)
+            unsigned per_slice;          // slice s adds the t in [s * per_slice, min(inner, (s + 1) * per_slice))
             unsigned n_log, K;
         };
+        // where a thread is: its prime k, grid plane p, the tile's first row i0 and column j0 with the live rows and columns from
+        // there, the slice's terms [t0, t1) and the word of (component k, coefficient j) inside an item.
+        // UNIFORM (valid from N = 128 on): a wave covers 128 consecutive words and never leaves its grid row, so the row number is
+        // moved to an SGPR and everything derived from it is uniform.  Below N = 128 the lanes of a wave sit in different rows.
+        struct TileThread
+        {
+            unsigned k, p, i0, j0, live_r, live_c, t0, t1;
+            size_t word;
+            // of thread w < g.threads of the flat grid
+            template <unsigned TR, unsigned TC, unsigned W, bool UNIFORM>
+            static __device__ __forceinline__ TileThread at(const TileGeom &g, size_t w)
+            {
+                const size_t i = W * w, j = i & ((size_t(1) << g.n_log) - 1);
+                unsigned row = (unsigned)(i >> g.n_log);
+                if (UNIFORM)
+                    row = SHL_UNIFORM(row);
+                const unsigned tile = row / g.K, pr = tile / g.col_tiles;
+                TileThread th;
+                th.k = row % g.K;
+                th.p = pr / g.row_tiles;
+                th.i0 = pr % g.row_tiles * TR;
+                th.j0 = tile % g.col_tiles * TC;
+                th.live_r = g.rows - th.i0 < TR ? g.rows - th.i0 : TR;
+                th.live_c = g.cols - th.j0 < TC ? g.cols - th.j0 : TC;
+                th.t0 = blockIdx.y * g.per_slice;
+                th.t1 = g.inner - th.t0 < g.per_slice ? g.inner : th.t0 + g.per_slice;
+                th.word = ((size_t)th.k << g.n_log) + j;
+                return th;
+            }
+        };
+
+        // ---- word plaintexts: x items are [K][N] words like y's.  NT: the operand loads carry the non-temporal hint.  Unlike in
+        // the other reductions an operand word is used by several tiles (a row of x by every column tile and, for plaintexts, by
+        // every plane; a column of y by every row tile), so both forms are built and were measured (profiles/matmul_items.txt,
+        // profiles/matmul_plain_items.txt): the hint wins where the operands come from HBM.
         template <unsigned W, bool NT>
         __device__ __forceinline__ void ldw(const uint64_t *p, uint64_t (&v)[W])
         {
@@ -534,73 +455,98 @@ namespace sealhip
                     *p = v[0].lo;
             }
         }
-        // the built tiles: words per thread and the waves per SIMD the allocator is held to (profiles/matmul_items.txt has the
-        // registers; no tile uses scratch memory at these).  A thread holds a 16-byte pair, as in the other kernels, while its
-        // 3 TR TC W sums of four registers and the operands of a term fit the 168 registers of three waves: 2 x 2 with pairs is 96
-        // + 32 (162 allocated; one word per thread takes 144, and spills at the 128 of four waves).  2 x 4 holds one word.
-        template <unsigned TR, unsigned TC>
-        struct MatmulTile;
-        template <>
-        struct MatmulTile<1, 1>
+        // The terms of the word-plaintext products.  A term has kPlanesX / kPlanesY planes loaded per x / y item, kOut sums per
+        // tile cell, kFlush terms between two reductions and mac(): add word l of the term of one cell to the cell's sums.
+        // ciphertext matrix x ciphertext matrix (batch_reduce_kernels.h: k_matmul_items), DotItemsTerm<false>'s term: per t a tile
+        // loads both planes of its TR x-items and TC y-items - 2 (TR + TC) plane-items per TR TC terms where one output per thread
+        // reads 4 per term
+        struct MatmulItemsTerm
         {
-            static constexpr unsigned kWords = 2, kWaves = 5;
-        };
-        template <>
-        struct MatmulTile<2, 2>
-        {
-            static constexpr unsigned kWords = 2, kWaves = 3;
-        };
-        template <>
-        struct MatmulTile<2, 4>
-        {
-            static constexpr unsigned kWords = 1, kWaves = 3;
-        };
-        template <unsigned TR, unsigned TC, bool NT, bool FINAL, bool FULL>
-        __device__ __forceinline__ void matmul_items_body(const ModDesc &md, const uint64_t *xp, const uint64_t *yp, uint64_t *d, const MatmulGeom &g,
-                                                          unsigned t0, unsigned t1, unsigned live_r, unsigned live_c)
-        {
-            constexpr unsigned W = MatmulTile<TR, TC>::kWords;
-            const size_t words = (size_t)g.K << g.n_log, x_row = (size_t)g.inner * words; // between two items / two rows of x
-            U128 acc[TR][TC][3][W] = {};
-            for (unsigned t = t0; t < t1;)
+            static constexpr unsigned kPlanesX = 2, kPlanesY = 2, kOut = 3, kFlush = kDotItemsFlush;
+            template <unsigned W>
+            static __device__ __forceinline__ void mac(U128 (&acc)[kOut][W], const uint64_t (&x)[kPlanesX][W], const uint64_t (&y)[kPlanesY][W], unsigned l)
             {
-                const unsigned end = t1 - t < kDotItemsFlush ? t1 : t + kDotItemsFlush;
+                mac128(acc[0][l], x[0][l], y[0][l]);
+                mac128(acc[1][l], x[0][l], y[1][l]);
+                mac128(acc[1][l], x[1][l], y[0][l]);
+                mac128(acc[2][l], x[1][l], y[1][l]);
+            }
+        };
+        // plaintext matrix x ciphertext matrix (batch_reduce_kernels.h: k_matmul_plain_items), DotPlainTerm's term for ONE plane:
+        // the planes are in the grid, so any size is one launch.  (TP + TC) plane-items per TP TC terms where one output per
+        // thread reads (size + 1) / size per term
+        struct MatmulPlainTerm
+        {
+            static constexpr unsigned kPlanesX = 1, kPlanesY = 1, kOut = 1, kFlush = kDotFlush;
+            template <unsigned W>
+            static __device__ __forceinline__ void mac(U128 (&acc)[kOut][W], const uint64_t (&x)[kPlanesX][W], const uint64_t (&y)[kPlanesY][W], unsigned l)
+            {
+                mac128(acc[0][l], x[0][l], y[0][l]);
+            }
+        };
+        // The built tiles: words per thread and the waves per SIMD the allocator is held to (profiles/matmul_items.txt and
+        // profiles/matmul_plain_items.txt have the registers; no tile uses scratch memory at these).
+        // Ciphertext x ciphertext: a thread holds a 16-byte pair, as in the other kernels, while its 3 TR TC W sums of four
+        // registers and the operands of a term fit the 168 registers of three waves: 2 x 2 with pairs is 96 + 32 (162 allocated;
+        // one word per thread takes 144, and spills at the 128 of four waves).  2 x 4 holds one word.
+        // Plaintext x ciphertext: a sum is four registers and a 64 x 64 multiply-accumulate takes about ten more, so from 2 x 4 on
+        // a thread holds one word: 2 x 4 takes 90 registers (with a pair, or at six waves, it spills), 4 x 4 134 (it spills at the
+        // 128 of four waves) and 4 x 8 needs 287 - the 32 past 255 are accumulation registers, which only one wave per SIMD can
+        // have; at two waves it spills 124 bytes per lane
+        template <class Term, unsigned TR, unsigned TC>
+        struct Tile;
+        template <unsigned WORDS, unsigned WAVES>
+        struct TileOf
+        {
+            static constexpr unsigned kWords = WORDS, kWaves = WAVES;
+        };
+        // clang-format off
+        template <> struct Tile<MatmulItemsTerm, 1, 1> : TileOf<2, 5> {};
+        template <> struct Tile<MatmulItemsTerm, 2, 2> : TileOf<2, 3> {};
+        template <> struct Tile<MatmulItemsTerm, 2, 4> : TileOf<1, 3> {};
+        template <> struct Tile<MatmulPlainTerm, 1, 1> : TileOf<2, 8> {};
+        template <> struct Tile<MatmulPlainTerm, 2, 4> : TileOf<1, 5> {};
+        template <> struct Tile<MatmulPlainTerm, 4, 4> : TileOf<1, 3> {};
+        template <> struct Tile<MatmulPlainTerm, 4, 8> : TileOf<1, 1> {};
+        // clang-format on
+        template <class Term, unsigned TR, unsigned TC, bool NT, bool FINAL, bool FULL>
+        __device__ __forceinline__ void matmul_words_body(const ModDesc &md, const uint64_t *xp, const uint64_t *yp, uint64_t *d, const TileGeom &g,
+                                                          const TileThread &th)
+        {
+            constexpr unsigned W = Tile<Term, TR, TC>::kWords;
+            const size_t words = (size_t)g.K << g.n_log, x_row = (size_t)g.inner * words; // between two items / two rows of x
+            const unsigned t1 = th.t1, live_r = th.live_r, live_c = th.live_c;
+            U128 acc[TR][TC][Term::kOut][W] = {};
+            for (unsigned t = th.t0; t < t1;)
+            {
+                const unsigned end = t1 - t < Term::kFlush ? t1 : t + Term::kFlush;
                 for (; t < end; t++, xp += words, yp += g.y_term)
                 {
-                    uint64_t x[TR][2][W], y[TC][2][W];
+                    uint64_t x[TR][Term::kPlanesX][W], y[TC][Term::kPlanesY][W];
 #pragma unroll
                     for (unsigned r = 0; r < TR; r++)
                         if (FULL || r < live_r)
-                        {
-                            ldw<W, NT>(xp + r * x_row, x[r][0]);
-                            ldw<W, NT>(xp + r * x_row + g.x_plane, x[r][1]);
-                        }
+                            for (unsigned q = 0; q < Term::kPlanesX; q++)
+                                ldw<W, NT>(xp + r * x_row + q * g.x_plane, x[r][q]);
 #pragma unroll
                     for (unsigned c = 0; c < TC; c++)
                         if (FULL || c < live_c)
-                        {
-                            ldw<W, NT>(yp + c * g.y_col, y[c][0]);
-                            ldw<W, NT>(yp + c * g.y_col + g.y_plane, y[c][1]);
-                        }
+                            for (unsigned q = 0; q < Term::kPlanesY; q++)
+                                ldw<W, NT>(yp + c * g.y_col + q * g.y_plane, y[c][q]);
 #pragma unroll
                     for (unsigned r = 0; r < TR; r++)
 #pragma unroll
                         for (unsigned c = 0; c < TC; c++)
                             if (FULL || (r < live_r && c < live_c))
                                 for (unsigned l = 0; l < W; l++)
-                                {
-                                    mac128(acc[r][c][0][l], x[r][0][l], y[c][0][l]);
-                                    mac128(acc[r][c][1][l], x[r][0][l], y[c][1][l]);
-                                    mac128(acc[r][c][1][l], x[r][1][l], y[c][0][l]);
-                                    mac128(acc[r][c][2][l], x[r][1][l], y[c][1][l]);
-                                }
+                                    Term::mac(acc[r][c], x[r], y[c], l);
                 }
 #pragma unroll
                 for (unsigned r = 0; r < TR; r++)
 #pragma unroll
                     for (unsigned c = 0; c < TC; c++)
                         if (FULL || (r < live_r && c < live_c))
-                            for (unsigned q = 0; q < 3; q++)
+                            for (unsigned q = 0; q < Term::kOut; q++)
                                 for (unsigned l = 0; l < W; l++)
                                     acc[r][c][q][l] = U128{ barrett128(acc[r][c][q][l].lo, acc[r][c][q][l].hi, md), 0 };
             }
@@ -609,260 +555,58 @@ namespace sealhip
 #pragma unroll
                 for (unsigned c = 0; c < TC; c++)
                     if (FULL || (r < live_r && c < live_c))
-                        for (unsigned q = 0; q < 3; q++)
-                            stw<W, FINAL>(d + ((size_t)r * g.cols + c) * words + q * g.dst_plane, acc[r][c][q]);
+                        for (unsigned q = 0; q < Term::kOut; q++)
+                            stw<W, FINAL>(d + r * g.r_row + c * g.r_col + q * g.dst_plane, acc[r][c][q]);
         }
-        template <unsigned TR, unsigned TC, bool NT, bool FINAL>
-        __global__ void __launch_bounds__(kBlock, (MatmulTile<TR, TC>::kWaves)) matmul_items_kernel(const ModDesc *mods, const uint64_t *x, const uint64_t *y, uint64_t *dst, MatmulGeom g)
+        template <class Term, unsigned TR, unsigned TC, bool NT, bool FINAL>
+        __global__ void __launch_bounds__(kBlock, (Tile<Term, TR, TC>::kWaves)) matmul_words_kernel(const ModDesc *mods, const uint64_t *x, const uint64_t *y, uint64_t *dst, TileGeom g)
         {
-            constexpr unsigned W = MatmulTile<TR, TC>::kWords;
             const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
             if (w >= g.threads)
                 return;
-            const size_t i = W * w, j = i & ((size_t(1) << g.n_log) - 1);
-            const unsigned row = (unsigned)(i >> g.n_log); // (row tile * col_tiles + col tile) * K + k
-            const unsigned k = row % g.K, tile = row / g.K, i0 = tile / g.col_tiles * TR, j0 = tile % g.col_tiles * TC;
-            const unsigned live_r = g.rows - i0 < TR ? g.rows - i0 : TR, live_c = g.cols - j0 < TC ? g.cols - j0 : TC;
-            const ModDesc md = mods[k];
-            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.inner - t0 < g.per_slice ? g.inner : t0 + g.per_slice;
-            const size_t words = (size_t)g.K << g.n_log, inner = ((size_t)k << g.n_log) + j; // component k, coefficient j
-            const uint64_t *xp = x + ((size_t)i0 * g.inner + t0) * words + inner;           // item (i0, t0)
-            const uint64_t *yp = y + t0 * g.y_term + j0 * g.y_col + inner;                  // item (t0, j0)
-            uint64_t *d = dst + blockIdx.y * g.dst_slice + ((size_t)i0 * g.cols + j0) * words + inner;
-            if (live_r == TR && live_c == TC)
-                matmul_items_body<TR, TC, NT, FINAL, true>(md, xp, yp, d, g, t0, t1, live_r, live_c);
+            const TileThread th = TileThread::at<TR, TC, Tile<Term, TR, TC>::kWords, false>(g, w);
+            const ModDesc md = mods[th.k];
+            const size_t words = (size_t)g.K << g.n_log;
+            const uint64_t *xp = x + ((size_t)th.i0 * g.inner + th.t0) * words + th.word;            // item (i0, t0)
+            const uint64_t *yp = y + th.p * g.y_plane + th.t0 * g.y_term + th.j0 * g.y_col + th.word; // plane p of item (t0, j0)
+            uint64_t *d = dst + blockIdx.y * g.dst_slice + th.p * g.dst_plane + th.i0 * g.r_row + th.j0 * g.r_col + th.word;
+            if (th.live_r == TR && th.live_c == TC)
+                matmul_words_body<Term, TR, TC, NT, FINAL, true>(md, xp, yp, d, g, th);
             else
-                matmul_items_body<TR, TC, NT, FINAL, false>(md, xp, yp, d, g, t0, t1, live_r, live_c);
+                matmul_words_body<Term, TR, TC, NT, FINAL, false>(md, xp, yp, d, g, th);
         }
-        template <unsigned TR, unsigned TC>
-        hipError_t launch_matmul(const ModDesc *mods, const uint64_t *x, const uint64_t *y, uint64_t *dst, const MatmulGeom &g, unsigned slices,
-                                 bool nt, bool final, hipStream_t s)
+        // the kernels of a tile by (NT, FINAL): what launch_tiled starts
+        template <class Term, unsigned TR, unsigned TC>
+        struct WordsFamily
         {
-            if (!g.threads) // matmul_items_threads: a launch that flat_grid refuses
-                return hipErrorInvalidValue;
-            const dim3 grid((unsigned)((g.threads + kBlock - 1) / kBlock), slices), block(kBlock);
-            if (nt)
-            {
-                if (final)
-                    hipLaunchKernelGGL((matmul_items_kernel<TR, TC, true, true>), grid, block, 0, s, mods, x, y, dst, g);
-                else
-                    hipLaunchKernelGGL((matmul_items_kernel<TR, TC, true, false>), grid, block, 0, s, mods, x, y, dst, g);
-            }
-            else if (final)
-                hipLaunchKernelGGL((matmul_items_kernel<TR, TC, false, true>), grid, block, 0, s, mods, x, y, dst, g);
-            else
-                hipLaunchKernelGGL((matmul_items_kernel<TR, TC, false, false>), grid, block, 0, s, mods, x, y, dst, g);
-            return hipGetLastError();
-        }
-        // the tile the library runs with and whether its operand loads are non-temporal: the fastest of the built ones at N = 65536,
-        // 8 x 16 x 8 (tools/matmul_items_rate.py measures every tile both ways; DESIGN.md 8.7 has the table).  The hint wins by 4 - 8 %
-        // where the operands come from HBM and loses as much where they fit the caches (N = 8192)
-        constexpr unsigned kMatmulTile = matmul_items_tile_id(2, 4);
-        constexpr bool kMatmulNonTemporal = true;
-        inline bool matmul_tile(unsigned tile, unsigned &tr, unsigned &tc, bool &nt)
-        {
-            const unsigned hint = tile & kMatmulItemsHintMask, shape = tile & ~kMatmulItemsHintMask ? tile & ~kMatmulItemsHintMask : kMatmulTile;
-            tr = shape >> 8;
-            tc = shape & 0xff;
-            nt = hint ? hint == kMatmulItemsNonTemporal : kMatmulNonTemporal;
-            return hint != kMatmulItemsHintMask &&
-                   (shape == matmul_items_tile_id(1, 1) || shape == matmul_items_tile_id(2, 2) || shape == matmul_items_tile_id(2, 4));
-        }
-
-        // ---- plaintext matrix x ciphertext matrix (batch_reduce_kernels.h: k_matmul_plain_items): r[p][i][j] = sum_k pl[i][k] a[p][k][j],
-        // the term being DotPlainTerm's.  One thread = W adjacent words of one prime and ONE plane for a TILE of TP consecutive output
-        // rows (the plaintext side) x TC consecutive output columns (the ciphertext side): per k it loads the TP plaintext words and
-        // the TC ciphertext words once and uses them for all TP x TC products - (TP + TC) plane-items per TP TC terms where one
-        // output per thread reads (size + 1) / size per term.  The planes are in the grid, as in dot_scalars_kernel: the grid is flat
-        // over (plane, row tile, column tile, prime, word), slices of the inner index in y.  The layouts of the ciphertext matrix and
-        // of the result are two strides each, so [inner][cols] / [cols][inner] and [rows][cols] / [cols][rows] are one kernel.  Items
-        // are numbered arithmetically: no lists, one form at every N.
-        // The accumulators carry the running total as matmul_items_kernel's do: a flush replaces the sum by its canonical residue
-        // and the next kDotFlush products are added on top of it.
-        // Partial tiles at the bottom and right edges: dead rows and columns are neither loaded nor stored (FULL = false).
-        // NT: the operand loads carry the non-temporal hint.  A plaintext word is used by the `size` plane-threads and by every
-        // column tile, a ciphertext word by every row tile: both forms are built and were measured (profiles/matmul_plain_items.txt).
-        static_assert((unsigned __int128)kDotFlush * ((uint64_t(1) << kPrimeBits) - 1) * ((uint64_t(1) << kPrimeBits) - 1) <=
-                          ~(unsigned __int128)0 - ((uint64_t(1) << kPrimeBits) - 1),
-                      "a canonical residue plus kDotFlush products of words below 2^60 must fit 128 bits");
-        struct MatmulPlainGeom
-        {
-            size_t a_plane;              // words between two planes of the ciphertexts
-            size_t a_term, a_col;        // words from ciphertext item (k, j) to (k + 1, j) / to (k, j + 1): the layout of the matrix
-            size_t r_row, r_col;         // words from result item (i, j) to (i + 1, j) / to (i, j + 1): the layout of the result
-            size_t dst_plane, dst_slice; // result word of (slice s, plane p): s * dst_slice + p * dst_plane
-            size_t threads;              // size * row tiles * col tiles * K * N / W
-            unsigned rows, inner, cols, row_tiles, col_tiles, per_slice; // slice s adds the k in [s * per_slice, min(inner, (s + 1) * per_slice))
-            unsigned n_log, K;
+            template <bool NT, bool FINAL>
+            static constexpr auto kernel = &matmul_words_kernel<Term, TR, TC, NT, FINAL>;
         };
-        // the built tiles: words per thread and the waves per SIMD the allocator is held to (profiles/matmul_plain_items.txt has
-        // the registers; no tile uses scratch memory at these).  A sum is four registers and a 64 x 64 multiply-accumulate takes
-        // about ten more, so from 2 x 4 on a thread holds one word: 2 x 4 takes 90 registers (with a pair, or at six waves, it
-        // spills), 4 x 4 134 (it spills at the 128 of four waves) and 4 x 8 needs 287 - the 32 past 255 are accumulation
-        // registers, which only one wave per SIMD can have; at two waves it spills 124 bytes per lane
-        template <unsigned TP, unsigned TC>
-        struct MatmulPlainTile;
-        template <>
-        struct MatmulPlainTile<1, 1>
-        {
-            static constexpr unsigned kWords = 2, kWaves = 8;
-        };
-        template <>
-        struct MatmulPlainTile<2, 4>
-        {
-            static constexpr unsigned kWords = 1, kWaves = 5;
-        };
-        template <>
-        struct MatmulPlainTile<4, 4>
-        {
-            static constexpr unsigned kWords = 1, kWaves = 3;
-        };
-        template <>
-        struct MatmulPlainTile<4, 8>
-        {
-            static constexpr unsigned kWords = 1, kWaves = 1;
-        };
-        template <unsigned TP, unsigned TC, bool NT, bool FINAL, bool FULL>
-        __device__ __forceinline__ void matmul_plain_body(const ModDesc &md, const uint64_t *pp, const uint64_t *ap, uint64_t *d, const MatmulPlainGeom &g,
-                                                          unsigned t0, unsigned t1, unsigned live_r, unsigned live_c)
-        {
-            constexpr unsigned W = MatmulPlainTile<TP, TC>::kWords;
-            const size_t words = (size_t)g.K << g.n_log, p_row = (size_t)g.inner * words; // between two plaintexts / two rows of them
-            U128 acc[TP][TC][W] = {};
-            for (unsigned t = t0; t < t1;)
-            {
-                const unsigned end = t1 - t < kDotFlush ? t1 : t + kDotFlush;
-                for (; t < end; t++, pp += words, ap += g.a_term)
-                {
-                    uint64_t p[TP][W], a[TC][W];
-#pragma unroll
-                    for (unsigned r = 0; r < TP; r++)
-                        if (FULL || r < live_r)
-                            ldw<W, NT>(pp + r * p_row, p[r]);
-#pragma unroll
-                    for (unsigned c = 0; c < TC; c++)
-                        if (FULL || c < live_c)
-                            ldw<W, NT>(ap + c * g.a_col, a[c]);
-#pragma unroll
-                    for (unsigned r = 0; r < TP; r++)
-#pragma unroll
-                        for (unsigned c = 0; c < TC; c++)
-                            if (FULL || (r < live_r && c < live_c))
-                                for (unsigned l = 0; l < W; l++)
-                                    mac128(acc[r][c][l], p[r][l], a[c][l]);
-                }
-#pragma unroll
-                for (unsigned r = 0; r < TP; r++)
-#pragma unroll
-                    for (unsigned c = 0; c < TC; c++)
-                        if (FULL || (r < live_r && c < live_c))
-                            for (unsigned l = 0; l < W; l++)
-                                acc[r][c][l] = U128{ barrett128(acc[r][c][l].lo, acc[r][c][l].hi, md), 0 };
-            }
-#pragma unroll
-            for (unsigned r = 0; r < TP; r++)
-#pragma unroll
-                for (unsigned c = 0; c < TC; c++)
-                    if (FULL || (r < live_r && c < live_c))
-                        stw<W, FINAL>(d + r * g.r_row + c * g.r_col, acc[r][c]);
-        }
-        template <unsigned TP, unsigned TC, bool NT, bool FINAL>
-        __global__ void __launch_bounds__(kBlock, (MatmulPlainTile<TP, TC>::kWaves)) matmul_plain_items_kernel(const ModDesc *mods, const uint64_t *pl, const uint64_t *a, uint64_t *dst, MatmulPlainGeom g)
-        {
-            constexpr unsigned W = MatmulPlainTile<TP, TC>::kWords;
-            const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
-            if (w >= g.threads)
-                return;
-            const size_t i = W * w, j = i & ((size_t(1) << g.n_log) - 1);
-            const unsigned row = (unsigned)(i >> g.n_log); // ((p * row_tiles + row tile) * col_tiles + col tile) * K + k
-            const unsigned k = row % g.K, tile = row / g.K, ct = tile % g.col_tiles, pr = tile / g.col_tiles, rt = pr % g.row_tiles, p = pr / g.row_tiles;
-            const unsigned i0 = rt * TP, j0 = ct * TC;
-            const unsigned live_r = g.rows - i0 < TP ? g.rows - i0 : TP, live_c = g.cols - j0 < TC ? g.cols - j0 : TC;
-            const ModDesc md = mods[k];
-            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.inner - t0 < g.per_slice ? g.inner : t0 + g.per_slice;
-            const size_t words = (size_t)g.K << g.n_log, inner = ((size_t)k << g.n_log) + j; // component k, coefficient j
-            const uint64_t *pp = pl + ((size_t)i0 * g.inner + t0) * words + inner;         // plaintext (i0, t0)
-            const uint64_t *ap = a + p * g.a_plane + t0 * g.a_term + j0 * g.a_col + inner; // plane p of item (t0, j0)
-            uint64_t *d = dst + blockIdx.y * g.dst_slice + p * g.dst_plane + i0 * g.r_row + j0 * g.r_col + inner;
-            if (live_r == TP && live_c == TC)
-                matmul_plain_body<TP, TC, NT, FINAL, true>(md, pp, ap, d, g, t0, t1, live_r, live_c);
-            else
-                matmul_plain_body<TP, TC, NT, FINAL, false>(md, pp, ap, d, g, t0, t1, live_r, live_c);
-        }
-        template <unsigned TP, unsigned TC>
-        hipError_t launch_matmul_plain(const ModDesc *mods, const uint64_t *pl, const uint64_t *a, uint64_t *dst, const MatmulPlainGeom &g,
-                                       unsigned slices, bool nt, bool final, hipStream_t s)
-        {
-            if (!g.threads) // matmul_plain_items_threads: a launch that flat_grid refuses
-                return hipErrorInvalidValue;
-            const dim3 grid((unsigned)((g.threads + kBlock - 1) / kBlock), slices), block(kBlock);
-            if (nt)
-            {
-                if (final)
-                    hipLaunchKernelGGL((matmul_plain_items_kernel<TP, TC, true, true>), grid, block, 0, s, mods, pl, a, dst, g);
-                else
-                    hipLaunchKernelGGL((matmul_plain_items_kernel<TP, TC, true, false>), grid, block, 0, s, mods, pl, a, dst, g);
-            }
-            else if (final)
-                hipLaunchKernelGGL((matmul_plain_items_kernel<TP, TC, false, true>), grid, block, 0, s, mods, pl, a, dst, g);
-            else
-                hipLaunchKernelGGL((matmul_plain_items_kernel<TP, TC, false, false>), grid, block, 0, s, mods, pl, a, dst, g);
-            return hipGetLastError();
-        }
-        // the tile the library runs with and whether its operand loads are non-temporal: the fastest of the built ones at N = 65536,
-        // 8 x 16 x 8 (tools/matmul_plain_items_rate.py measures every tile both ways; DESIGN.md 8.8 has the table).  The hint wins by
-        // 1 - 2 % where the operands come from HBM and loses 8 - 15 % where they fit the caches (N = 8192); 4 x 8 at its one wave per
+        // the tiles the library runs with and whether their operand loads are non-temporal: the fastest of the built ones at
+        // N = 65536, 8 x 16 x 8 (tools/matmul_items_rate.py and tools/matmul_plain_items_rate.py measure every tile both ways;
+        // DESIGN.md 8.7 and 8.8 have the tables).  Where the operands come from HBM the hint wins by 4 - 8 % (ciphertexts) and
+        // 1 - 2 % (plaintexts), and loses 8 - 15 % where they fit the caches (N = 8192); the plaintexts' 4 x 8 at its one wave per
         // SIMD is 15 - 17 % behind 4 x 4 there
-        constexpr unsigned kMatmulPlainTile = matmul_items_tile_id(4, 4);
-        constexpr bool kMatmulPlainNonTemporal = true;
-        // f(MatmulPlainTile<TP, TC>{}, TP, TC) for the built tile `shape` names; false = not built
-        template <class F>
-        inline bool with_plain_tile(unsigned shape, F f)
-        {
-            switch (shape)
-            {
-            case matmul_items_tile_id(1, 1):
-                f(std::integral_constant<unsigned, 1>{}, std::integral_constant<unsigned, 1>{});
-                return true;
-            case matmul_items_tile_id(2, 4):
-                f(std::integral_constant<unsigned, 2>{}, std::integral_constant<unsigned, 4>{});
-                return true;
-            case matmul_items_tile_id(4, 4):
-                f(std::integral_constant<unsigned, 4>{}, std::integral_constant<unsigned, 4>{});
-                return true;
-            case matmul_items_tile_id(4, 8):
-                f(std::integral_constant<unsigned, 4>{}, std::integral_constant<unsigned, 8>{});
-                return true;
-            }
-            return false;
-        }
-        // tile: a tile id with the hint bits (batch_reduce_kernels.h) -> its shape (0: the library's) and hint (neither: the library's)
-        inline bool matmul_plain_tile(unsigned tile, unsigned &shape, bool &nt)
-        {
-            const unsigned hint = tile & kMatmulItemsHintMask;
-            shape = tile & ~kMatmulItemsHintMask ? tile & ~kMatmulItemsHintMask : kMatmulPlainTile;
-            nt = hint ? hint == kMatmulItemsNonTemporal : kMatmulPlainNonTemporal;
-            return hint != kMatmulItemsHintMask && with_plain_tile(shape, [](auto, auto) {});
-        }
+        constexpr unsigned kMatmulTile = matmul_items_tile_id(2, 4), kMatmulPlainTile = matmul_items_tile_id(4, 4);
+        constexpr bool kMatmulNonTemporal = true, kMatmulPlainNonTemporal = true;
 
-        // ---- scalar weight matrix x ciphertext matrix (batch_reduce_kernels.h: k_matmul_scalars): r[p][i][j] = sum_k w[i][k] a[p][k][j],
-        // the plaintext of term (i, k) being ONE value per prime as in dot_scalars_kernel.  One thread = one 16-byte pair of one plane,
-        // one prime and one output COLUMN for a TILE of R consecutive output rows: the operand pair of (k, j) is loaded once and used
-        // for R x 2 products.  The grid is flat over (plane, row tile, column, prime, pair), slices of the inner index in y; the
-        // layouts of the ciphertext matrix and of the result are two strides each, as in matmul_plain_items_kernel.
-        // UNIFORM (N >= 128): as in dot_scalars_kernel the row number is moved to an SGPR and the R weights of a term are scalar loads
-        // through the constant address space, so the weights must have been WRITTEN BY SOMETHING EARLIER ON THE STREAM.  Below
-        // N = 128 the loads are per lane.  The last tile's dead rows are neither loaded nor stored (FULL = false).
-        // The accumulators are U128 and carry the running total, as matmul_plain_items_kernel's do.
+        // ---- scalar weights (batch_reduce_kernels.h: k_matmul_scalars, and k_dot_scalars, which is its one column): the x item of
+        // term (i, t) is ONE value per prime.  One thread = one 16-byte pair of one plane, one prime and one output COLUMN for a
+        // tile of R consecutive output rows: the operand pair of (t, j) is loaded once and used for R x 2 products, so the operand
+        // crosses HBM once per tile of rows and not once per row.
+        // UNIFORM (N >= 128): the R weights of a term are scalar loads through the constant address space - SGPRs, not VGPRs, and
+        // uniform trip counts.  The weights are therefore read through the constant cache: they must have been WRITTEN BY
+        // SOMETHING EARLIER ON THE STREAM (a copy, a previous kernel), as the lists of an item map.  Below N = 128 the loads are
+        // per lane.
         // Two forms of the weights:
-        //   wide    [rows * inner][K] 64-bit words, weight (i, k) of prime q at (i * inner + k) * K + q: dot_scalars_kernel's products
-        //           (a 64 x 64 -> 128 multiply each) and its flush interval, kDotFlush.
+        //   wide    [rows * inner][K] 64-bit words, weight (i, t) of prime q at (i * inner + t) * K + q: a 64 x 64 -> 128 multiply
+        //           per product and the products' flush interval, kDotFlush.
         //   narrow  [rows * inner] signed 32-bit integers, one for all primes.  The weight w is used BIASED, u = w + 2^31 in
-        //           [0, 2^32) (the sign bit flipped): sum_k a_k w_k = sum_k a_k u_k - 2^31 sum_k a_k.  Both sums are unsigned and
+        //           [0, 2^32) (the sign bit flipped): sum_t a_t w_t = sum_t a_t u_t - 2^31 sum_t a_t.  Both sums are unsigned and
         //           exact; the second does not depend on the output row, so a thread keeps one per word of its pair and not one per
         //           row.  A product a u is two 32 x 32 -> 64 multiplies (the halves of a) where the wide form's compiles to six multiply
         //           instructions (four v_mad_u64_u32, two v_mul).  At a flush
-        //           the total becomes  (P mod q) - (2^31 mod q) (S mod q)  mod q, the canonical residue of sum_k a_k w_k.
+        //           the total becomes  (P mod q) - (2^31 mod q) (S mod q)  mod q, the canonical residue of sum_t a_t w_t.
         // kNarrowFlush terms between two reductions.  Bound (the widest prime the library admits is below 2^60, so a canonical
         // word is at most 2^60 - 1; w = -2^31 gives u = 0 and w = 2^31 - 1 the largest u = 2^32 - 1, so every u is covered):
         //   P <= (q - 1) + T (2^60 - 1)(2^32 - 1) < 2^60 + T 2^92,   S <= T (2^60 - 1) < T 2^60
@@ -873,16 +617,6 @@ namespace sealhip
         static_assert((unsigned __int128)kNarrowFlush * ((uint64_t(1) << kPrimeBits) - 1) * 0xffffffffu <=
                           ~(unsigned __int128)0 - ((uint64_t(1) << kPrimeBits) - 1),
                       "a canonical residue plus kNarrowFlush products of a word below 2^60 and a biased 32-bit weight must fit 128 bits");
-        struct MatmulScalarsGeom
-        {
-            size_t a_plane;              // words between two planes of the ciphertexts
-            size_t a_term, a_col;        // words from ciphertext item (k, j) to (k + 1, j) / to (k, j + 1): the layout of the matrix
-            size_t r_row, r_col;         // words from result item (i, j) to (i + 1, j) / to (i, j + 1): the layout of the result
-            size_t dst_plane, dst_slice; // result word of (slice s, plane p): s * dst_slice + p * dst_plane
-            size_t pairs;                // size * tiles * cols * K * N / 2
-            unsigned rows, inner, cols, tiles, per_slice; // slice s adds the k in [s * per_slice, min(inner, (s + 1) * per_slice))
-            unsigned n_log, K;
-        };
         // acc += a u for a canonical word a and a 32-bit u.  Written on the 128-bit integer type: the product becomes the two
         // 32 x 32 -> 64 multiply-adds of the halves of a and the sum one chain of four adds with carry, 7 vector instructions per
         // product where the same sum through add128's comparison takes 11
@@ -892,30 +626,32 @@ namespace sealhip
             acc.lo = (uint64_t)sum;
             acc.hi = (uint64_t)(sum >> 64);
         }
-        // waves per SIMD the allocator is held to (profiles/matmul_scalars.txt has the registers: no kernel uses scratch memory at
-        // these, and the allocator stays below them: 62 - 72 registers at four rows, 80 - 106 at eight).  The per-lane kernels keep
-        // a weight address per lane and the narrow form two more sums
-        template <unsigned R>
+        // waves per SIMD the allocator is held to (profiles/matmul_scalars.txt and profiles/dot_scalars.txt have the registers: no
+        // kernel uses scratch memory at these, and the allocator stays below them: 62 - 72 registers at four rows, 80 - 106 at
+        // eight).  The per-lane kernels keep a weight address per lane and the narrow form two more sums.  Two rows are built for
+        // the one-column product only (the sweep of tools/dot_scalars_rate.py)
+        template <unsigned R, bool UNIFORM>
         constexpr unsigned matmul_scalars_waves()
         {
-            return R == 4 ? 6 : 4;
+            return R == 2 ? (UNIFORM ? 8 : 5) : R == 4 ? 6 : 4;
         }
         template <unsigned R, bool NARROW, bool UNIFORM, bool FINAL, bool FULL>
-        __device__ __forceinline__ void matmul_scalars_rows(const ModDesc &md, const uint64_t *ap, const void *weights, size_t first, uint64_t *d,
-                                                            const MatmulScalarsGeom &g, unsigned k, unsigned t0, unsigned t1, unsigned live)
+        __device__ __forceinline__ void matmul_scalars_rows(const ModDesc &md, const uint64_t *ap, const void *weights, uint64_t *d, const TileGeom &g,
+                                                            const TileThread &th)
         {
             using Word = std::conditional_t<NARROW, uint32_t, uint64_t>;
             constexpr unsigned kFlush = NARROW ? kNarrowFlush : kDotFlush;
-            // weight (o0, t0) [of prime k]; words from a term to the next and from a row to the next
-            const size_t step = NARROW ? 1 : g.K, row_words = (size_t)g.inner * step;
-            const Word *wp = static_cast<const Word *>(weights) + (NARROW ? first : first * g.K + k);
+            // weight (i0, t0) [of prime k]; words from a term to the next and from a row to the next
+            const size_t first = (size_t)th.i0 * g.inner + th.t0, step = NARROW ? 1 : g.K, row_words = (size_t)g.inner * step;
+            const Word *wp = static_cast<const Word *>(weights) + (NARROW ? first : first * g.K + th.k);
             const uint64_t bias = NARROW ? barrett64(uint64_t(1) << 31, md) : 0; // 2^31 mod q
+            const unsigned t1 = th.t1, live = th.live_r;
             U128 acc[R][2] = {};
-            for (unsigned t = t0; t < t1;)
+            for (unsigned t = th.t0; t < t1;)
             {
                 const unsigned end = t1 - t < kFlush ? t1 : t + kFlush;
                 U128 plain[2] = {}; // narrow: the sum of the operand words themselves
-                for (; t < end; t++, ap += g.a_term, wp += step)
+                for (; t < end; t++, ap += g.y_term, wp += step)
                 {
                     uint64_t a0, a1;
                     ld2<true>(ap, a0, a1);
@@ -963,55 +699,175 @@ namespace sealhip
                 }
         }
         template <unsigned R, bool NARROW, bool UNIFORM, bool FINAL>
-        __global__ void __launch_bounds__(kBlock, matmul_scalars_waves<R>()) matmul_scalars_kernel(const ModDesc *mods, const void *weights, const uint64_t *a, uint64_t *dst, MatmulScalarsGeom g)
+        __global__ void __launch_bounds__(kBlock, (matmul_scalars_waves<R, UNIFORM>())) matmul_scalars_kernel(const ModDesc *mods, const void *weights, const uint64_t *a, uint64_t *dst, TileGeom g)
         {
             const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
-            if (w >= g.pairs)
+            if (w >= g.threads)
                 return;
-            const size_t i = 2 * w, j = i & ((size_t(1) << g.n_log) - 1);
-            unsigned row = (unsigned)(i >> g.n_log); // ((p * tiles + tile) * cols + c) * K + k
-            if (UNIFORM)
-                row = SHL_UNIFORM(row);
-            const unsigned k = row % g.K, pc = row / g.K, c = pc % g.cols, pt = pc / g.cols, tile = pt % g.tiles, p = pt / g.tiles;
-            const unsigned o0 = tile * R, live = g.rows - o0 < R ? g.rows - o0 : R;
-            const ModDesc md = mods[k];
-            const unsigned t0 = blockIdx.y * g.per_slice, t1 = g.inner - t0 < g.per_slice ? g.inner : t0 + g.per_slice;
-            const size_t inner = ((size_t)k << g.n_log) + j; // component k, coefficient j
-            const uint64_t *ap = a + p * g.a_plane + t0 * g.a_term + c * g.a_col + inner; // plane p of item (t0, c)
-            uint64_t *d = dst + blockIdx.y * g.dst_slice + p * g.dst_plane + o0 * g.r_row + c * g.r_col + inner;
-            const size_t first = (size_t)o0 * g.inner + t0; // weight (o0, t0)
-            if (live == R)
-                matmul_scalars_rows<R, NARROW, UNIFORM, FINAL, true>(md, ap, weights, first, d, g, k, t0, t1, live);
+            const TileThread th = TileThread::at<R, 1, 2, UNIFORM>(g, w);
+            const ModDesc md = mods[th.k];
+            const uint64_t *ap = a + th.p * g.y_plane + th.t0 * g.y_term + th.j0 * g.y_col + th.word; // plane p of item (t0, j0)
+            uint64_t *d = dst + blockIdx.y * g.dst_slice + th.p * g.dst_plane + th.i0 * g.r_row + th.j0 * g.r_col + th.word;
+            if (th.live_r == R)
+                matmul_scalars_rows<R, NARROW, UNIFORM, FINAL, true>(md, ap, weights, d, g, th);
             else
-                matmul_scalars_rows<R, NARROW, UNIFORM, FINAL, false>(md, ap, weights, first, d, g, k, t0, t1, live);
+                matmul_scalars_rows<R, NARROW, UNIFORM, FINAL, false>(md, ap, weights, d, g, th);
         }
+        // the kernels of a row tile by (UNIFORM, FINAL)
         template <unsigned R, bool NARROW>
-        hipError_t launch_matmul_scalars(const ModDesc *mods, const void *weights, const uint64_t *a, uint64_t *dst, const MatmulScalarsGeom &g,
-                                         unsigned slices, bool final, hipStream_t s)
+        struct ScalarsFamily
         {
-            if (!g.pairs) // matmul_scalars_threads: a launch that flat_grid refuses
-                return hipErrorInvalidValue;
-            const dim3 grid((unsigned)((g.pairs + kBlock - 1) / kBlock), slices), block(kBlock);
-            if (g.n_log >= 7)
+            template <bool UNIFORM, bool FINAL>
+            static constexpr auto kernel = &matmul_scalars_kernel<R, NARROW, UNIFORM, FINAL>;
+        };
+        // the row tiles the library runs with (tools/dot_scalars_rate.py and tools/matmul_scalars_rate.py measure them; DESIGN.md
+        // 8.6 and 8.9 have the tables).  Wide: the tiles are bound by the 64 x 64 multiplies (2.0 - 2.1 Tmac/s at N = 65536) and
+        // R = 4 cuts small results less often.  Narrow: R = 4 is bound by the operand stream there, R = 8 is 8 - 10 % faster from
+        // 8 rows on
+        constexpr unsigned kRowTile = 4, kMatmulScalarsTile = 4, kMatmulScalarsNarrowTile = 8;
+
+        // ---- the built tiles of a product as a list, and the one dispatch on it: f(BuiltTile<TR, TC>{}) for the tile that is
+        // TR x TC; false = not built
+        template <unsigned TR, unsigned TC>
+        struct BuiltTile
+        {
+            static constexpr unsigned kRows = TR, kCols = TC;
+        };
+        template <class... Tiles>
+        struct BuiltTiles
+        {
+            template <class F>
+            static bool with(unsigned tr, unsigned tc, F f)
             {
-                if (final)
-                    hipLaunchKernelGGL((matmul_scalars_kernel<R, NARROW, true, true>), grid, block, 0, s, mods, weights, a, dst, g);
-                else
-                    hipLaunchKernelGGL((matmul_scalars_kernel<R, NARROW, true, false>), grid, block, 0, s, mods, weights, a, dst, g);
+                return ((tr == Tiles::kRows && tc == Tiles::kCols && (f(Tiles{}), true)) || ...);
             }
-            else if (final)
-                hipLaunchKernelGGL((matmul_scalars_kernel<R, NARROW, false, true>), grid, block, 0, s, mods, weights, a, dst, g);
+        };
+        using MatmulItemsTiles = BuiltTiles<BuiltTile<1, 1>, BuiltTile<2, 2>, BuiltTile<2, 4>>;
+        using MatmulPlainTiles = BuiltTiles<BuiltTile<1, 1>, BuiltTile<2, 4>, BuiltTile<4, 4>, BuiltTile<4, 8>>;
+        using MatmulScalarsTiles = BuiltTiles<BuiltTile<4, 1>, BuiltTile<8, 1>>;
+        using DotScalarsTiles = BuiltTiles<BuiltTile<2, 1>, BuiltTile<4, 1>, BuiltTile<8, 1>>; // wide only
+        // a tile id with the hint bits (batch_reduce_kernels.h) -> its shape (0: the library's), words per thread and hint
+        // (neither bit: the library's); false = both hint bits, or a tile that is not built
+        struct TileChoice
+        {
+            unsigned tr, tc, words;
+            bool nt;
+        };
+        template <class Term, class Built>
+        inline bool decode_tile(unsigned tile, unsigned library, bool library_nt, TileChoice &c)
+        {
+            const unsigned hint = tile & kMatmulItemsHintMask, shape = tile & ~kMatmulItemsHintMask ? tile & ~kMatmulItemsHintMask : library;
+            c.tr = shape >> 8;
+            c.tc = shape & 0xff;
+            c.nt = hint ? hint == kMatmulItemsNonTemporal : library_nt;
+            return hint != kMatmulItemsHintMask &&
+                   Built::with(c.tr, c.tc, [&](auto t) { c.words = Tile<Term, decltype(t)::kRows, decltype(t)::kCols>::kWords; });
+        }
+
+        // threads of a tiled launch: one per W words of (grid plane, row tile, column tile, prime); 0 = a launch that is refused -
+        // flat_grid's refusal, which counts pairs (rows of the grid are numbered in 32 bits); a thread of one word makes twice the
+        // workgroups
+        inline size_t tiled_threads(unsigned planes, size_t rows, size_t cols, unsigned n_log, unsigned K, unsigned tr, unsigned tc, unsigned words)
+        {
+            if (rows > 0xffffffffu || cols > 0xffffffffu)
+                return 0;
+            const size_t grid_rows = planes * ((rows + tr - 1) / tr) * ((cols + tc - 1) / tc) * K, threads = (grid_rows << n_log) / words;
+            unsigned blocks;
+            if (!flat_grid(threads * words / 2, n_log, blocks) || (threads + kBlock - 1) / kBlock > 0x7fffffffu)
+                return 0;
+            return threads;
+        }
+        // the one launch of the tiled kernels: Family::kernel<first, FINAL>, `first` being the family's own switch (NT, UNIFORM)
+        template <class Family, class X>
+        hipError_t launch_tiled(const ModDesc *mods, const X *x, const uint64_t *y, uint64_t *dst, const TileGeom &g, unsigned slices, bool first,
+                                bool final, hipStream_t s)
+        {
+            if (!g.threads)
+                return hipErrorInvalidValue;
+            const dim3 grid((unsigned)((g.threads + kBlock - 1) / kBlock), slices), block(kBlock);
+            const auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, mods, x, y, dst, g); };
+            if (first)
+                final ? go(Family::template kernel<true, true>) : go(Family::template kernel<true, false>);
             else
-                hipLaunchKernelGGL((matmul_scalars_kernel<R, NARROW, false, false>), grid, block, 0, s, mods, weights, a, dst, g);
+                final ? go(Family::template kernel<false, true>) : go(Family::template kernel<false, false>);
             return hipGetLastError();
         }
-        // the row tile the library runs each form with (tools/matmul_scalars_rate.py measures both; DESIGN.md 8.9 has the table).
-        // Wide: both tiles are bound by the 64 x 64 multiplies (2.0 - 2.1 Tmac/s at N = 65536) and R = 4 cuts small results less
-        // often.  Narrow: R = 4 is bound by the operand stream there, R = 8 is 8 - 10 % faster from 8 rows on
-        constexpr unsigned kMatmulScalarsTile = 4, kMatmulScalarsNarrowTile = 8;
-        inline bool matmul_scalars_tile_built(unsigned r)
+        // The host path of every tiled product: r [size][rows * cols][K][N] (planes r_stride words apart) from x, whose items have
+        // planes x_plane words apart, and y, whose planes are y_plane words apart, in the layouts the flags name.  `threads` is
+        // tiled_threads' count for the tile tr x tc.  launch(g, dst, slices, final) starts the product's kernel; with slices > 1 (a
+        // cut of the inner index) it fills scratch [slices][size][rows * cols][K][N] and the sum of the slices follows.
+        template <class Launch>
+        hipError_t tiled_reduce(const ModDesc *mods, size_t x_plane, size_t y_plane, bool y_transposed, uint64_t *r, size_t r_stride, bool r_transposed,
+                                unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols, unsigned tr, unsigned tc,
+                                size_t threads, unsigned slices, uint64_t *scratch, hipStream_t s, Launch launch)
         {
-            return r == 4 || r == 8;
+            unsigned per_slice;
+            const size_t words = (size_t)K << n_log;
+            if (!size || !rows || !inner || !cols || !words || rows > 0xffffffffu || inner > 0xffffffffu || cols > 0xffffffffu ||
+                rows * inner > 0xffffffffu || inner * cols > 0xffffffffu || rows * cols > 0xffffffffu || !cut(inner, slices, per_slice) ||
+                (slices > 1 && !scratch))
+                return hipErrorInvalidValue;
+            const bool final = slices == 1;
+            const size_t out_plane = rows * cols * words;
+            const TileGeom g{ x_plane,
+                              y_plane,
+                              y_transposed ? words : cols * words,
+                              y_transposed ? inner * words : words,
+                              r_transposed ? words : cols * words,
+                              r_transposed ? rows * words : words,
+                              final ? r_stride : out_plane,
+                              final ? 0 : size * out_plane,
+                              threads,
+                              (unsigned)rows,
+                              (unsigned)inner,
+                              (unsigned)cols,
+                              (unsigned)((rows + tr - 1) / tr),
+                              (unsigned)((cols + tc - 1) / tc),
+                              per_slice,
+                              n_log,
+                              K };
+            const hipError_t e = launch(g, final ? r : scratch, slices, final);
+            if (e != hipSuccess || final)
+                return e;
+            return sum_slices(mods, scratch, r, r_stride, size, n_log, K, rows * cols, slices, s);
+        }
+        // the launch of a word-plaintext product with the tile decode_tile chose
+        template <class Term, class Built>
+        hipError_t launch_words(const ModDesc *mods, const uint64_t *x, const uint64_t *y, uint64_t *dst, const TileGeom &g, unsigned slices,
+                                const TileChoice &c, bool final, hipStream_t s)
+        {
+            hipError_t e = hipErrorInvalidValue;
+            Built::with(c.tr, c.tc, [&](auto t) {
+                e = launch_tiled<WordsFamily<Term, decltype(t)::kRows, decltype(t)::kCols>>(mods, x, y, dst, g, slices, c.nt, final, s);
+            });
+            return e;
+        }
+        // k_matmul_scalars and k_dot_scalars: the tiled host path with the scalar-weights kernel of row tile R, one of Built's
+        template <class Built>
+        hipError_t scalars_reduce(const ModDesc *mods, const void *weights, bool narrow, const uint64_t *a, size_t a_stride, uint64_t *r,
+                                  size_t r_stride, unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols,
+                                  bool a_transposed, bool r_transposed, unsigned slices, uint64_t *scratch, unsigned R, hipStream_t s)
+        {
+            if (!Built::with(R, 1, [](auto) {}))
+                return hipErrorInvalidValue;
+            return tiled_reduce(mods, 0, a_stride, a_transposed, r, r_stride, r_transposed, size, n_log, K, rows, inner, cols, R, 1,
+                                tiled_threads(size, rows, cols, n_log, K, R, 1, 2), slices, scratch, s,
+                                [=](const TileGeom &g, uint64_t *dst, unsigned ns, bool final) {
+                                    hipError_t e = hipErrorInvalidValue;
+                                    Built::with(R, 1, [&](auto t) {
+                                        constexpr unsigned kR = decltype(t)::kRows;
+                                        if constexpr (kR != 2) // two rows: the wide form only
+                                        {
+                                            if (narrow)
+                                            {
+                                                e = launch_tiled<ScalarsFamily<kR, true>>(mods, weights, a, dst, g, ns, n_log >= 7, final, s);
+                                                return;
+                                            }
+                                        }
+                                        e = launch_tiled<ScalarsFamily<kR, false>>(mods, weights, a, dst, g, ns, n_log >= 7, final, s);
+                                    });
+                                    return e;
+                                });
         }
     } // namespace
 
@@ -1094,75 +950,44 @@ namespace sealhip
     }
     size_t dot_scalars_threads(unsigned size, size_t rows, unsigned n_log, unsigned K, unsigned row_tile)
     {
-        const unsigned R = row_tile ? row_tile : kRowTile;
-        return (((size_t)size * ((rows + R - 1) / R) * K) << n_log) / 2;
+        return tiled_threads(size, rows, 1, n_log, K, row_tile ? row_tile : kRowTile, 1, 2);
     }
+    // k_matmul_scalars' wide form at one column: inner = batch, neither layout flag, weights = scalars
     hipError_t k_dot_scalars(const ModDesc *mods, const uint64_t *a, size_t a_stride, const uint64_t *scalars, uint64_t *r, size_t r_stride,
                              unsigned size, unsigned n_log, unsigned K, size_t rows, size_t batch, unsigned slices, uint64_t *scratch,
                              unsigned row_tile, hipStream_t s)
     {
-        const unsigned R = row_tile ? row_tile : kRowTile;
-        const size_t words = (size_t)K << n_log, out_plane = rows * words;
-        if (!size || !out_plane || !batch)
+        if (!size || !rows || !K || !batch)
             return hipSuccess;
-        unsigned per_slice;
-        if (!row_tile_built(R) || !cut(batch, slices, per_slice) || rows > 0xffffffffu || rows * batch > 0xffffffffu || (slices > 1 && !scratch))
-            return hipErrorInvalidValue;
-        const bool final = slices == 1;
-        const size_t tiles = (rows + R - 1) / R;
-        const ScalarGeom g{ a_stride, final ? r_stride : out_plane, final ? 0 : size * out_plane, size * tiles * words / 2,
-                            (unsigned)rows, (unsigned)tiles, (unsigned)batch, per_slice, n_log, K };
-        uint64_t *dst = final ? r : scratch;
-        const hipError_t e = R == 2   ? launch_scalars<2>(mods, a, scalars, dst, g, slices, final, s)
-                             : R == 4 ? launch_scalars<4>(mods, a, scalars, dst, g, slices, final, s)
-                                      : launch_scalars<8>(mods, a, scalars, dst, g, slices, final, s);
-        if (e != hipSuccess || final)
-            return e;
-        return sum_slices(mods, scratch, r, r_stride, size, n_log, K, rows, slices, s);
+        return scalars_reduce<DotScalarsTiles>(mods, scalars, false, a, a_stride, r, r_stride, size, n_log, K, rows, batch, 1, false, false, slices,
+                                               scratch, row_tile ? row_tile : kRowTile, s);
     }
 
     void matmul_items_tile(unsigned &tile_rows, unsigned &tile_cols)
     {
-        bool nt;
-        matmul_tile(0, tile_rows, tile_cols, nt);
+        tile_rows = kMatmulTile >> 8;
+        tile_cols = kMatmulTile & 0xff;
     }
     size_t matmul_items_threads(size_t rows, size_t cols, unsigned n_log, unsigned K, unsigned tile)
     {
-        unsigned tr, tc;
-        bool nt;
-        if (!matmul_tile(tile, tr, tc, nt))
+        TileChoice c;
+        if (!decode_tile<MatmulItemsTerm, MatmulItemsTiles>(tile, kMatmulTile, kMatmulNonTemporal, c))
             return 0;
-        const unsigned words = tr == 1 ? MatmulTile<1, 1>::kWords : tc == 2 ? MatmulTile<2, 2>::kWords : MatmulTile<2, 4>::kWords;
-        const size_t grid_rows = ((rows + tr - 1) / tr) * ((cols + tc - 1) / tc) * K, threads = (grid_rows << n_log) / words;
-        // flat_grid's refusal, which counts pairs; a thread of one word makes twice the workgroups
-        unsigned blocks;
-        if (rows > 0xffffffffu || cols > 0xffffffffu || !flat_grid(threads * words / 2, n_log, blocks) || (threads + kBlock - 1) / kBlock > 0x7fffffffu)
-            return 0;
-        return threads;
+        return tiled_threads(1, rows, cols, n_log, K, c.tr, c.tc, c.words);
     }
     hipError_t k_matmul_items(const ModDesc *mods, const uint64_t *x, size_t x_stride, const uint64_t *y, size_t y_stride, uint64_t *r,
                               size_t r_stride, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols, bool y_transposed,
                               unsigned slices, uint64_t *scratch, unsigned tile, hipStream_t s)
     {
-        unsigned tr, tc, per_slice;
-        bool nt;
-        const size_t words = (size_t)K << n_log;
-        if (!matmul_tile(tile, tr, tc, nt) || !rows || !inner || !cols || !words || rows > 0xffffffffu || inner > 0xffffffffu || cols > 0xffffffffu ||
-            rows * inner > 0xffffffffu || inner * cols > 0xffffffffu || rows * cols > 0xffffffffu || !cut(inner, slices, per_slice) ||
-            (slices > 1 && !scratch))
+        TileChoice c;
+        if (!decode_tile<MatmulItemsTerm, MatmulItemsTiles>(tile, kMatmulTile, kMatmulNonTemporal, c))
             return hipErrorInvalidValue;
-        const bool final = slices == 1;
-        const size_t out_plane = rows * cols * words, col_tiles = (cols + tc - 1) / tc;
-        const MatmulGeom g{ x_stride, y_stride, y_transposed ? words : cols * words, y_transposed ? inner * words : words,
-                            final ? r_stride : out_plane, final ? 0 : 3 * out_plane, matmul_items_threads(rows, cols, n_log, K, tile),
-                            (unsigned)rows, (unsigned)inner, (unsigned)cols, (unsigned)col_tiles, per_slice, n_log, K };
-        uint64_t *dst = final ? r : scratch;
-        const hipError_t e = tr == 1   ? launch_matmul<1, 1>(mods, x, y, dst, g, slices, nt, final, s)
-                             : tc == 2 ? launch_matmul<2, 2>(mods, x, y, dst, g, slices, nt, final, s)
-                                       : launch_matmul<2, 4>(mods, x, y, dst, g, slices, nt, final, s);
-        if (e != hipSuccess || final)
-            return e;
-        return sum_slices(mods, scratch, r, r_stride, 3, n_log, K, rows * cols, slices, s);
+        // one grid plane: a thread forms the three result planes, dst_plane words apart
+        return tiled_reduce(mods, x_stride, y_stride, y_transposed, r, r_stride, false, 3, n_log, K, rows, inner, cols, c.tr, c.tc,
+                            tiled_threads(1, rows, cols, n_log, K, c.tr, c.tc, c.words), slices, scratch, s,
+                            [=](const TileGeom &g, uint64_t *dst, unsigned ns, bool final) {
+                                return launch_words<MatmulItemsTerm, MatmulItemsTiles>(mods, x, y, dst, g, ns, c, final, s);
+                            });
     }
 
     void matmul_plain_items_tile(unsigned &tile_rows, unsigned &tile_cols)
@@ -1172,55 +997,23 @@ namespace sealhip
     }
     size_t matmul_plain_items_threads(unsigned size, size_t rows, size_t cols, unsigned n_log, unsigned K, unsigned tile)
     {
-        unsigned shape, words = 0;
-        bool nt;
-        if (!matmul_plain_tile(tile, shape, nt) || rows > 0xffffffffu || cols > 0xffffffffu)
+        TileChoice c;
+        if (!decode_tile<MatmulPlainTerm, MatmulPlainTiles>(tile, kMatmulPlainTile, kMatmulPlainNonTemporal, c))
             return 0;
-        with_plain_tile(shape, [&](auto tp, auto tc) { words = MatmulPlainTile<decltype(tp)::value, decltype(tc)::value>::kWords; });
-        const unsigned tp = shape >> 8, tc = shape & 0xff;
-        const size_t grid_rows = size * ((rows + tp - 1) / tp) * ((cols + tc - 1) / tc) * K, threads = (grid_rows << n_log) / words;
-        // flat_grid's refusal, which counts pairs; a thread of one word makes twice the workgroups
-        unsigned blocks;
-        if (!flat_grid(threads * words / 2, n_log, blocks) || (threads + kBlock - 1) / kBlock > 0x7fffffffu)
-            return 0;
-        return threads;
+        return tiled_threads(size, rows, cols, n_log, K, c.tr, c.tc, c.words);
     }
     hipError_t k_matmul_plain_items(const ModDesc *mods, const uint64_t *pl, const uint64_t *a, size_t a_stride, uint64_t *r, size_t r_stride,
                                     unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols, bool a_transposed,
                                     bool r_transposed, unsigned slices, uint64_t *scratch, unsigned tile, hipStream_t s)
     {
-        unsigned shape, per_slice;
-        bool nt;
-        const size_t words = (size_t)K << n_log;
-        if (!matmul_plain_tile(tile, shape, nt) || !size || !rows || !inner || !cols || !words || rows > 0xffffffffu || inner > 0xffffffffu ||
-            cols > 0xffffffffu || rows * inner > 0xffffffffu || inner * cols > 0xffffffffu || rows * cols > 0xffffffffu ||
-            !cut(inner, slices, per_slice) || (slices > 1 && !scratch))
+        TileChoice c;
+        if (!decode_tile<MatmulPlainTerm, MatmulPlainTiles>(tile, kMatmulPlainTile, kMatmulPlainNonTemporal, c))
             return hipErrorInvalidValue;
-        const bool final = slices == 1;
-        const unsigned tp = shape >> 8, tc = shape & 0xff;
-        const size_t out_plane = rows * cols * words;
-        const MatmulPlainGeom g{ a_stride,
-                                 a_transposed ? words : cols * words,
-                                 a_transposed ? inner * words : words,
-                                 r_transposed ? words : cols * words,
-                                 r_transposed ? rows * words : words,
-                                 final ? r_stride : out_plane,
-                                 final ? 0 : size * out_plane,
-                                 matmul_plain_items_threads(size, rows, cols, n_log, K, tile),
-                                 (unsigned)rows,
-                                 (unsigned)inner,
-                                 (unsigned)cols,
-                                 (unsigned)((rows + tp - 1) / tp),
-                                 (unsigned)((cols + tc - 1) / tc),
-                                 per_slice,
-                                 n_log,
-                                 K };
-        uint64_t *dst = final ? r : scratch;
-        hipError_t e = hipErrorInvalidValue;
-        with_plain_tile(shape, [&](auto p, auto c) { e = launch_matmul_plain<decltype(p)::value, decltype(c)::value>(mods, pl, a, dst, g, slices, nt, final, s); });
-        if (e != hipSuccess || final)
-            return e;
-        return sum_slices(mods, scratch, r, r_stride, size, n_log, K, rows * cols, slices, s);
+        return tiled_reduce(mods, 0, a_stride, a_transposed, r, r_stride, r_transposed, size, n_log, K, rows, inner, cols, c.tr, c.tc,
+                            tiled_threads(size, rows, cols, n_log, K, c.tr, c.tc, c.words), slices, scratch, s,
+                            [=](const TileGeom &g, uint64_t *dst, unsigned ns, bool final) {
+                                return launch_words<MatmulPlainTerm, MatmulPlainTiles>(mods, pl, a, dst, g, ns, c, final, s);
+                            });
     }
 
     unsigned matmul_scalars_row_tile(bool narrow)
@@ -1234,47 +1027,15 @@ namespace sealhip
     size_t matmul_scalars_threads(unsigned size, size_t rows, size_t cols, unsigned n_log, unsigned K, bool narrow, unsigned row_tile)
     {
         const unsigned R = row_tile ? row_tile : matmul_scalars_row_tile(narrow);
-        if (!matmul_scalars_tile_built(R) || rows > 0xffffffffu || cols > 0xffffffffu || rows * cols > 0xffffffffu)
+        if (!MatmulScalarsTiles::with(R, 1, [](auto) {}) || rows * cols > 0xffffffffu)
             return 0;
-        const size_t pairs = ((size * ((rows + R - 1) / R) * cols * K) << n_log) / 2;
-        unsigned blocks;
-        return flat_grid(pairs, n_log, blocks) ? pairs : 0;
+        return tiled_threads(size, rows, cols, n_log, K, R, 1, 2);
     }
     hipError_t k_matmul_scalars(const ModDesc *mods, const void *weights, bool narrow, const uint64_t *a, size_t a_stride, uint64_t *r,
                                 size_t r_stride, unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols,
                                 bool a_transposed, bool r_transposed, unsigned slices, uint64_t *scratch, unsigned row_tile, hipStream_t s)
     {
-        const unsigned R = row_tile ? row_tile : matmul_scalars_row_tile(narrow);
-        unsigned per_slice;
-        const size_t words = (size_t)K << n_log;
-        if (!matmul_scalars_tile_built(R) || !size || !rows || !inner || !cols || !words || rows > 0xffffffffu || inner > 0xffffffffu ||
-            cols > 0xffffffffu || rows * inner > 0xffffffffu || inner * cols > 0xffffffffu || rows * cols > 0xffffffffu ||
-            !cut(inner, slices, per_slice) || (slices > 1 && !scratch))
-            return hipErrorInvalidValue;
-        const bool final = slices == 1;
-        const size_t out_plane = rows * cols * words;
-        const MatmulScalarsGeom g{ a_stride,
-                                   a_transposed ? words : cols * words,
-                                   a_transposed ? inner * words : words,
-                                   r_transposed ? words : cols * words,
-                                   r_transposed ? rows * words : words,
-                                   final ? r_stride : out_plane,
-                                   final ? 0 : size * out_plane,
-                                   matmul_scalars_threads(size, rows, cols, n_log, K, narrow, R),
-                                   (unsigned)rows,
-                                   (unsigned)inner,
-                                   (unsigned)cols,
-                                   (unsigned)((rows + R - 1) / R),
-                                   per_slice,
-                                   n_log,
-                                   K };
-        uint64_t *dst = final ? r : scratch;
-        const hipError_t e = narrow ? (R == 4 ? launch_matmul_scalars<4, true>(mods, weights, a, dst, g, slices, final, s)
-                                              : launch_matmul_scalars<8, true>(mods, weights, a, dst, g, slices, final, s))
-                                    : (R == 4 ? launch_matmul_scalars<4, false>(mods, weights, a, dst, g, slices, final, s)
-                                              : launch_matmul_scalars<8, false>(mods, weights, a, dst, g, slices, final, s));
-        if (e != hipSuccess || final)
-            return e;
-        return sum_slices(mods, scratch, r, r_stride, size, n_log, K, rows * cols, slices, s);
+        return scalars_reduce<MatmulScalarsTiles>(mods, weights, narrow, a, a_stride, r, r_stride, size, n_log, K, rows, inner, cols, a_transposed,
+                                                  r_transposed, slices, scratch, row_tile ? row_tile : matmul_scalars_row_tile(narrow), s);
     }
 } // namespace sealhip

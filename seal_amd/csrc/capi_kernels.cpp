@@ -48,6 +48,55 @@ namespace
         return raw_reduce(context, chain_index, bad ? shape : nullptr, grid_planes, out_items, walk, slices, slices_used, r, operands, scratch,
                           [&](Context *c, const Level *l, size_t words, unsigned cut) { launch(c, l, out_items, words, walk, cut); });
     }
+    // The prologue of the raw seams of the tiled products (shl_dot_scalars_tile, shl_matmul_items_tile, shl_matmul_plain_items_tile,
+    // shl_matmul_scalars_tile), rows x inner times inner x cols with `planes` result planes: the level, then `error` (the entry's
+    // own checks, NULL = passed), then the shape - shape_error when a dimension is 0 or beyond 32 bits, a product of two is, or
+    // threads(n_log, K) is 0: a tile that is not built or a launch the flat grid refuses.  slices == 0 asks for the library's rule
+    // over those threads; *slices_used is set, a call without a result is the query and ends there; otherwise the pool gives the
+    // scratch and launch(context, level, n_log, words per item, slices, scratch, stream) runs inside a StreamScope.
+    // Two differences between the entries are kept as they were.  shl_dot_scalars_tile checks its shape and tile itself, under its
+    // own message (shape_error NULL), and leaves a grid that does not fit to the launch.  Only shl_matmul_scalars_tile reports
+    // (and allocates for) the slices the cut leaves non-empty (normalise); the others report the slices asked for.
+    template <class Threads, class Launch>
+    SHL_HRESULT raw_tiled(void *context, uint64_t chain_index, const char *error, const char *shape_error, const char *slices_error,
+                          uint64_t planes, uint64_t rows, uint64_t inner, uint64_t cols, uint64_t slices, bool normalise, uint64_t *slices_used,
+                          const uint64_t *r, const void *x, const void *y, void *stream, Threads threads, Launch launch)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        SHL_TRY
+        auto c = as<Context>(context);
+        auto l = c->level_by_chain_index(chain_index);
+        if (!l)
+            throw std::out_of_range("chain_index");
+        if (error)
+            throw std::invalid_argument(error);
+        const unsigned n_log = (unsigned)c->log_n();
+        const size_t count = threads(n_log, l->K);
+        if (shape_error && (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) ||
+                            ((inner * cols) >> 32) || ((rows * cols) >> 32) || !count))
+            throw std::invalid_argument(shape_error);
+        if (!slices)
+            slices = batch_reduce_slices(count, inner);
+        if (slices > inner || slices > 64)
+            throw std::invalid_argument(slices_error);
+        if (normalise)
+            slices = (inner + (inner + slices - 1) / slices - 1) / ((inner + slices - 1) / slices); // those the cut leaves non-empty
+        if (slices_used)
+            *slices_used = slices;
+        if (!r) // a query: the slices the library would use
+            return SHL_S_OK;
+        IfNullRet(x, SHL_E_POINTER);
+        IfNullRet(y, SHL_E_POINTER);
+        hipStream_t s = (hipStream_t)stream;
+        StreamScope scope(s);
+        std::unique_ptr<Scratch> scratch;
+        if (slices > 1)
+            scratch.reset(new Scratch(batch_reduce_scratch_words((unsigned)slices, (unsigned)planes, rows * cols, n_log, l->K)));
+        launch(c, l, n_log, (size_t)l->K * c->n(), (unsigned)slices, scratch ? scratch->p : nullptr, s);
+        SHL_CATCH
+    }
+    constexpr const char *kMatmulShape = "1 <= rows, inner, cols; rows * inner, inner * cols, rows * cols < 2^32; a built tile";
+    constexpr const char *kMatmulSlices = "1 <= slices <= min(inner, 64)";
 } // namespace
 
 extern "C"
@@ -177,36 +226,17 @@ extern "C"
     SHL_FUNC shl_dot_scalars_tile(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *scalars, uint64_t *r, uint64_t size,
                                   uint64_t rows, uint64_t batch, uint64_t slices, uint64_t *slices_used, uint64_t row_tile, void *stream)
     {
-        IfNullRet(context, SHL_E_POINTER);
-        SHL_TRY
-        auto c = as<Context>(context);
-        auto l = c->level_by_chain_index(chain_index);
-        if (!l)
-            throw std::out_of_range("chain_index");
-        if (!size || size > 16 || !rows || !batch || (rows >> 32) || (batch >> 32) || ((rows * batch) >> 32) ||
-            (row_tile && row_tile != 2 && row_tile != 4 && row_tile != 8))
-            throw std::invalid_argument("1 <= size <= 16; 1 <= rows, batch; rows * batch < 2^32; row_tile 0, 2, 4 or 8");
-        const unsigned n_log = (unsigned)c->log_n();
-        if (!slices)
-            slices = batch_reduce_slices(dot_scalars_threads((unsigned)size, rows, n_log, l->K, (unsigned)row_tile), batch);
-        if (slices > batch || slices > 64)
-            throw std::invalid_argument("1 <= slices <= min(batch, 64)");
-        if (slices_used)
-            *slices_used = slices;
-        if (!r) // a query: the slices the library would use
-            return SHL_S_OK;
-        IfNullRet(a, SHL_E_POINTER);
-        IfNullRet(scalars, SHL_E_POINTER);
-        hipStream_t s = (hipStream_t)stream;
-        StreamScope scope(s);
-        const size_t words = (size_t)l->K * c->n();
-        std::unique_ptr<Scratch> scratch;
-        if (slices > 1)
-            scratch.reset(new Scratch(batch_reduce_scratch_words((unsigned)slices, (unsigned)size, rows, n_log, l->K)));
-        hip_ok(k_dot_scalars(c->dev_mods(), a, batch * words, scalars, r, rows * words, (unsigned)size, n_log, l->K, rows, batch, (unsigned)slices,
-                             scratch ? scratch->p : nullptr, (unsigned)row_tile, s),
-               "dot_scalars");
-        SHL_CATCH
+        const bool bad = !size || size > 16 || !rows || !batch || (rows >> 32) || (batch >> 32) || ((rows * batch) >> 32) ||
+                         (row_tile && row_tile != 2 && row_tile != 4 && row_tile != 8);
+        return raw_tiled(
+            context, chain_index, bad ? "1 <= size <= 16; 1 <= rows, batch; rows * batch < 2^32; row_tile 0, 2, 4 or 8" : nullptr, nullptr,
+            "1 <= slices <= min(batch, 64)", size, rows, batch, 1, slices, false, slices_used, r, a, scalars, stream,
+            [&](unsigned n_log, unsigned K) { return dot_scalars_threads((unsigned)size, rows, n_log, K, (unsigned)row_tile); },
+            [&](Context *c, const Level *l, unsigned n_log, size_t words, unsigned cut, uint64_t *scratch, hipStream_t s) {
+                hip_ok(k_dot_scalars(c->dev_mods(), a, batch * words, scalars, r, rows * words, (unsigned)size, n_log, l->K, rows, batch, cut, scratch,
+                                     (unsigned)row_tile, s),
+                       "dot_scalars");
+            });
     }
     SHL_FUNC shl_dot_scalars(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *scalars, uint64_t *r, uint64_t size,
                              uint64_t rows, uint64_t batch, uint64_t slices, uint64_t *slices_used)
@@ -234,37 +264,14 @@ extern "C"
                                    uint64_t inner, uint64_t cols, int y_transposed, uint64_t slices, uint64_t *slices_used, uint64_t tile,
                                    void *stream)
     {
-        IfNullRet(context, SHL_E_POINTER);
-        SHL_TRY
-        auto c = as<Context>(context);
-        auto l = c->level_by_chain_index(chain_index);
-        if (!l)
-            throw std::out_of_range("chain_index");
-        const unsigned n_log = (unsigned)c->log_n();
-        const size_t threads = (tile >> 32) ? 0 : matmul_items_threads(rows, cols, n_log, l->K, (unsigned)tile);
-        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
-            ((rows * cols) >> 32) || !threads)
-            throw std::invalid_argument("1 <= rows, inner, cols; rows * inner, inner * cols, rows * cols < 2^32; a built tile");
-        if (!slices)
-            slices = batch_reduce_slices(threads, inner);
-        if (slices > inner || slices > 64)
-            throw std::invalid_argument("1 <= slices <= min(inner, 64)");
-        if (slices_used)
-            *slices_used = slices;
-        if (!r) // a query: the slices the library would use
-            return SHL_S_OK;
-        IfNullRet(x, SHL_E_POINTER);
-        IfNullRet(y, SHL_E_POINTER);
-        hipStream_t s = (hipStream_t)stream;
-        StreamScope scope(s);
-        const size_t words = (size_t)l->K * c->n();
-        std::unique_ptr<Scratch> scratch;
-        if (slices > 1)
-            scratch.reset(new Scratch(batch_reduce_scratch_words((unsigned)slices, 3, rows * cols, n_log, l->K)));
-        hip_ok(k_matmul_items(c->dev_mods(), x, rows * inner * words, y, inner * cols * words, r, rows * cols * words, n_log, l->K, rows, inner, cols,
-                              y_transposed != 0, (unsigned)slices, scratch ? scratch->p : nullptr, (unsigned)tile, s),
-               "matmul_items");
-        SHL_CATCH
+        return raw_tiled(
+            context, chain_index, nullptr, kMatmulShape, kMatmulSlices, 3, rows, inner, cols, slices, false, slices_used, r, x, y, stream,
+            [&](unsigned n_log, unsigned K) { return (tile >> 32) ? 0 : matmul_items_threads(rows, cols, n_log, K, (unsigned)tile); },
+            [&](Context *c, const Level *l, unsigned n_log, size_t words, unsigned cut, uint64_t *scratch, hipStream_t s) {
+                hip_ok(k_matmul_items(c->dev_mods(), x, rows * inner * words, y, inner * cols * words, r, rows * cols * words, n_log, l->K, rows,
+                                      inner, cols, y_transposed != 0, cut, scratch, (unsigned)tile, s),
+                       "matmul_items");
+            });
     }
     SHL_FUNC shl_matmul_items(void *context, uint64_t chain_index, const uint64_t *x, const uint64_t *y, uint64_t *r, uint64_t rows, uint64_t inner,
                               uint64_t cols, int y_transposed, uint64_t slices, uint64_t *slices_used)
@@ -297,39 +304,18 @@ extern "C"
                                          uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used,
                                          uint64_t tile, void *stream)
     {
-        IfNullRet(context, SHL_E_POINTER);
-        SHL_TRY
-        auto c = as<Context>(context);
-        auto l = c->level_by_chain_index(chain_index);
-        if (!l)
-            throw std::out_of_range("chain_index");
-        const unsigned n_log = (unsigned)c->log_n();
-        if (!size || size > 16 || (flags & ~uint64_t(3)))
-            throw std::invalid_argument("1 <= size <= 16; flags 0 .. 3");
-        const size_t threads = (tile >> 32) ? 0 : matmul_plain_items_threads((unsigned)size, rows, cols, n_log, l->K, (unsigned)tile);
-        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
-            ((rows * cols) >> 32) || !threads)
-            throw std::invalid_argument("1 <= rows, inner, cols; rows * inner, inner * cols, rows * cols < 2^32; a built tile");
-        if (!slices)
-            slices = batch_reduce_slices(threads, inner);
-        if (slices > inner || slices > 64)
-            throw std::invalid_argument("1 <= slices <= min(inner, 64)");
-        if (slices_used)
-            *slices_used = slices;
-        if (!r) // a query: the slices the library would use
-            return SHL_S_OK;
-        IfNullRet(pl, SHL_E_POINTER);
-        IfNullRet(a, SHL_E_POINTER);
-        hipStream_t s = (hipStream_t)stream;
-        StreamScope scope(s);
-        const size_t words = (size_t)l->K * c->n();
-        std::unique_ptr<Scratch> scratch;
-        if (slices > 1)
-            scratch.reset(new Scratch(batch_reduce_scratch_words((unsigned)slices, (unsigned)size, rows * cols, n_log, l->K)));
-        hip_ok(k_matmul_plain_items(c->dev_mods(), pl, a, inner * cols * words, r, rows * cols * words, (unsigned)size, n_log, l->K, rows, inner,
-                                    cols, (flags & 1) != 0, (flags & 2) != 0, (unsigned)slices, scratch ? scratch->p : nullptr, (unsigned)tile, s),
-               "matmul_plain_items");
-        SHL_CATCH
+        const bool bad = !size || size > 16 || (flags & ~uint64_t(3));
+        return raw_tiled(
+            context, chain_index, bad ? "1 <= size <= 16; flags 0 .. 3" : nullptr, kMatmulShape, kMatmulSlices, size, rows, inner, cols, slices,
+            false, slices_used, r, pl, a, stream,
+            [&](unsigned n_log, unsigned K) {
+                return (tile >> 32) ? 0 : matmul_plain_items_threads((unsigned)size, rows, cols, n_log, K, (unsigned)tile);
+            },
+            [&](Context *c, const Level *l, unsigned n_log, size_t words, unsigned cut, uint64_t *scratch, hipStream_t s) {
+                hip_ok(k_matmul_plain_items(c->dev_mods(), pl, a, inner * cols * words, r, rows * cols * words, (unsigned)size, n_log, l->K, rows,
+                                            inner, cols, (flags & 1) != 0, (flags & 2) != 0, cut, scratch, (unsigned)tile, s),
+                       "matmul_plain_items");
+            });
     }
     SHL_FUNC shl_matmul_plain_items(void *context, uint64_t chain_index, const uint64_t *pl, const uint64_t *a, uint64_t *r, uint64_t size,
                                     uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used)
@@ -361,42 +347,19 @@ extern "C"
                                      uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used,
                                      uint64_t row_tile, void *stream)
     {
-        IfNullRet(context, SHL_E_POINTER);
-        SHL_TRY
-        auto c = as<Context>(context);
-        auto l = c->level_by_chain_index(chain_index);
-        if (!l)
-            throw std::out_of_range("chain_index");
-        const unsigned n_log = (unsigned)c->log_n();
-        if (!size || size > 16 || (flags & ~uint64_t(7)))
-            throw std::invalid_argument("1 <= size <= 16; flags 0 .. 7");
-        const bool narrow = (flags & 4) != 0;
-        const size_t threads = (row_tile >> 32) ? 0 : matmul_scalars_threads((unsigned)size, rows, cols, n_log, l->K, narrow, (unsigned)row_tile);
-        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
-            ((rows * cols) >> 32) || !threads)
-            throw std::invalid_argument("1 <= rows, inner, cols; rows * inner, inner * cols, rows * cols < 2^32; a built row tile");
-        if (!slices)
-            slices = batch_reduce_slices(threads, inner);
-        if (slices > inner || slices > 64)
-            throw std::invalid_argument("1 <= slices <= min(inner, 64)");
-        slices = (inner + (inner + slices - 1) / slices - 1) / ((inner + slices - 1) / slices); // those the cut leaves non-empty
-        if (slices_used)
-            *slices_used = slices;
-        if (!r) // a query: the slices the library would use
-            return SHL_S_OK;
-        IfNullRet(weights, SHL_E_POINTER);
-        IfNullRet(a, SHL_E_POINTER);
-        hipStream_t s = (hipStream_t)stream;
-        StreamScope scope(s);
-        const size_t words = (size_t)l->K * c->n();
-        std::unique_ptr<Scratch> scratch;
-        if (slices > 1)
-            scratch.reset(new Scratch(batch_reduce_scratch_words((unsigned)slices, (unsigned)size, rows * cols, n_log, l->K)));
-        hip_ok(k_matmul_scalars(c->dev_mods(), weights, narrow, a, inner * cols * words, r, rows * cols * words, (unsigned)size, n_log, l->K, rows,
-                                inner, cols, (flags & 1) != 0, (flags & 2) != 0, (unsigned)slices, scratch ? scratch->p : nullptr,
-                                (unsigned)row_tile, s),
-               "matmul_scalars");
-        SHL_CATCH
+        const bool bad = !size || size > 16 || (flags & ~uint64_t(7)), narrow = (flags & 4) != 0;
+        return raw_tiled(
+            context, chain_index, bad ? "1 <= size <= 16; flags 0 .. 7" : nullptr,
+            "1 <= rows, inner, cols; rows * inner, inner * cols, rows * cols < 2^32; a built row tile", kMatmulSlices, size, rows, inner, cols,
+            slices, true, slices_used, r, weights, a, stream,
+            [&](unsigned n_log, unsigned K) {
+                return (row_tile >> 32) ? 0 : matmul_scalars_threads((unsigned)size, rows, cols, n_log, K, narrow, (unsigned)row_tile);
+            },
+            [&](Context *c, const Level *l, unsigned n_log, size_t words, unsigned cut, uint64_t *scratch, hipStream_t s) {
+                hip_ok(k_matmul_scalars(c->dev_mods(), weights, narrow, a, inner * cols * words, r, rows * cols * words, (unsigned)size, n_log, l->K,
+                                        rows, inner, cols, (flags & 1) != 0, (flags & 2) != 0, cut, scratch, (unsigned)row_tile, s),
+                       "matmul_scalars");
+            });
     }
     SHL_FUNC shl_matmul_scalars(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
                                 uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used)

@@ -325,10 +325,12 @@ def integers(xc, s, q):
     return out
 
 
-def case_flush(n, bits, batches=None, patterns=("max", "alternating", "half", "random"), size=2, seed=61):
+def case_flush(n, bits, batches=None, patterns=("max", "alternating", "half", "random"), size=2, seed=61, row_tile=None):
     """B around the flush interval, R + 1 rows (a full tile and a short one), one launch: every word equals the sum formed with
-    Python integers.  With "max" every ciphertext word and every scalar is q - 1: the largest run the accumulators must hold"""
+    Python integers.  With "max" every ciphertext word and every scalar is q - 1: the largest run the accumulators must hold.
+    row_tile: that built tile through shl_dot_scalars_tile instead of the library's"""
     R, flush = info()
+    R = R if row_tile is None else row_tile
     assert flush == DOT_FLUSH == 256 and FLUSH_BATCHES == [1, 255, 256, 257, 515]
     side = Side("ckks", n, bits)
     rng = np.random.default_rng(seed)
@@ -339,8 +341,8 @@ def case_flush(n, bits, batches=None, patterns=("max", "alternating", "half", "r
             xc = _columns(side, ci, pattern if pattern != "alternating" else "max", rng, (size, batch))
             s = scalar_pattern(side, ci, pattern, rng, R + 1, batch)
             x = np.ascontiguousarray(np.tile(xc, n // 2))
-            got, used = raw(side, ci, x, s, 1)
-            assert used == 1 and np.array_equal(got, np.tile(integers(xc, s, q), n // 2)), ("flush", n, batch, pattern)
+            got, used = raw(side, ci, x, s, 1) if row_tile is None else raw_tile(side, ci, x, s, row_tile, 1)
+            assert used == 1 and np.array_equal(got, np.tile(integers(xc, s, q), n // 2)), ("flush", n, batch, pattern, row_tile)
 
 
 def case_cuts(n, bits, slice_counts=(1, 2, 3, 5, 23), sizes=(1, 2, 4), patterns=("max", "random"), batch=23, seed=67):

@@ -65,6 +65,15 @@ def test_flush_boundaries(gpu, n, bits):
     DS.case_flush(n, bits)
 
 
+@pytest.mark.parametrize("row_tile", [2, 4, 8])
+@pytest.mark.parametrize("n,bits", [(8, [30, 30, 30]), (128, [60, 40, 40, 60])])
+def test_flush_boundaries_every_tile(gpu, n, bits, row_tile):
+    """every built row tile, per lane (N = 8) and per wave (N = 128): the accumulators carry the running residue across the flush"""
+    import dot_scalars_cases as DS
+    DS.case_flush(n, bits, batches=[DS.DOT_FLUSH - 1, DS.DOT_FLUSH, DS.DOT_FLUSH + 1, 2 * DS.DOT_FLUSH + 3], patterns=("max", "random"),
+                  row_tile=row_tile)
+
+
 @pytest.mark.parametrize("n,bits", [(8, [30, 30, 30]), MID])
 def test_cuts(gpu, n, bits):
     import dot_scalars_cases as DS
