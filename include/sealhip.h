@@ -670,6 +670,55 @@ SHL_FUNC Evaluator_MatMulPlainItems(void *thisptr, const uint64_t *device_plain,
  * slices and a second launch).  Sizes other than 2 and the rings below N = 128: not measured. */
 SHL_FUNC Evaluator_MatMulScalarsItems(void *thisptr, const void *device_weights, void *encrypted, uint64_t rows, uint64_t inner, uint64_t cols,
                                       uint64_t flags, double scale, void *destination);
+/* Library extension: a 2-D convolution of SCALAR weights over a grid of ciphertexts, one ciphertext per (channel, pixel) with the
+ * samples in the slots - the convolutional layer as one call and one pass, with no gathered (im2col) batch and with zero padding.
+ * With OH = (height + 2 pad_h - kernel_h) / stride_h + 1, OW likewise and inner = in_channels * kernel_h * kernel_w:
+ *   out(o, y', x') = sum_{c, dy, dx} W[o][(c * kernel_h + dy) * kernel_w + dx] * X(c, y' stride_h + dy - pad_h, x' stride_w + dx - pad_w)
+ * over the taps that fall inside the image.  encrypted: a batch of in_channels * height * width items, item (c, y, x) at
+ * (c * height + y) * width + x, of any size >= 2, at any level, in NTT form (CKKS, BGV, or BFV after Evaluator_TransformToNTT2).
+ * destination: another handle of out_channels * OH * OW items, item (o, y', x') at (o * OH + y') * OW + x'.  `shape` is host memory.
+ * flags bit 0: the input is stored channel-last, item (c, y, x) at (y * width + x) * in_channels + c; bit 1: the result is stored
+ * channel-last, item (o, y', x') at (y' * OW + x') * out_channels + o; the layouts are strides of the one kernel, no data is moved.
+ * Bit 2: NARROW weights, [out_channels * inner] signed 32-bit integers; otherwise WIDE, [out_channels * inner][K] 64-bit words.
+ * Both forms, `scale`, their producers, their 16-byte alignment and "WRITTEN BY SOMETHING EARLIER ON THE STREAM" are exactly
+ * Evaluator_MatMulScalarsItems'.  Any other bit is SHL_E_INVALIDARG.
+ * Contract: output item (o, y', x') equals, word for word and in its metadata, Evaluator_DotPlainMapped over the map whose row for
+ * that item names, for every tap inside the image, the input item and plaintext o * inner + (c * kernel_h + dy) * kernel_w + dx of
+ * [out_channels * inner][K][N] plaintexts each filled with its weight's K words - hence the reference's multiply_plain_inplace per
+ * tap and then add_many.  With a 1 x 1 kernel, stride 1 and no padding the words are Evaluator_MatMulScalarsItems' at rows =
+ * out_channels, inner = in_channels, cols = height * width (flags as given); with kernel = the whole image, no padding and a
+ * channel-first input they are its words at cols = 1.
+ * Metadata, the settle-before-read of an operand, Evaluator_SetTransparentCheck on the result batch and "a failed check leaves the
+ * destination untouched" are Evaluator_MatMulScalarsItems'.  SHL_E_POINTER for a NULL handle.  SHL_E_INVALIDARG: a NULL shape; an
+ * extent or stride of 0; pad_h >= kernel_h or pad_w >= kernel_w (so every output has a tap inside the image and no transparent
+ * item is made by construction); height + 2 pad_h < kernel_h, and likewise the width; one of C H W, OC OH OW, OC inner >= 2^32,
+ * or inner OH OW >= 2^32 (the terms of one launch are numbered in 32 bits); the ciphertext's batch != C H W; the destination's
+ * batch != OC OH OW; destination == encrypted; NULL or misaligned device_weights; device_weights overlapping the words of either
+ * ciphertext; a coefficient-form ciphertext; an invalid or foreign ciphertext; a scale out of bounds; a result too large for one
+ * launch.  Dilation and groups: not provided.  The call is enqueued on the evaluator's stream without a host round trip and
+ * records under Evaluator_BeginCapture.
+ * One thread holds a 16-byte coefficient pair of one plane, one prime and one output position for a tile of R consecutive output
+ * channels - 4 for wide, 8 for narrow weights - with Evaluator_MatMulScalarsItems' sums and reductions, once per 256 / 1024 EXECUTED
+ * taps.  The taps of an output position inside the image are a rectangle of the kernel, found once per thread; taps outside it are
+ * neither read nor multiplied.  A small result is cut as for Evaluator_DotPlainDevice, the rule being asked with
+ * size ceil(OC / R) OH OW K N / 2 threads that each add `inner` terms; a slice is a range of the term index (c * kernel_h + dy) *
+ * kernel_w + dx, and the words do not depend on the cut.
+ * Measured on one MI355X at size 2 (profiles/conv2d_scalars.txt) against the route without this call - the Evaluator_SumItemsMapped
+ * gather into an im2col batch, then Evaluator_MatMulScalarsItems - on raw words: at N = 65536, K = 15, 3 x 3 over 8 channels of
+ * 8 x 8 with 8 and 16 output channels and 5 x 5, stride 2, over one channel of 28 x 28 with 5, the wide form is 1.27 - 1.83 times and
+ * the narrow form 1.31 - 1.84 times the two calls, in 12.6 - 23.7 GB of operands where the two calls hold 53.4 - 80.3 GB; at N = 8192,
+ * K = 3, 1.34 - 2.04 times.  Slower than Evaluator_MatMulScalarsItems ALONE on an already gathered batch at N = 65536: the wide form
+ * runs at 0.94 - 0.95 of its rate at the 3 x 3 shapes (2.25 - 2.30 against 2.40 - 2.42 Tmac/s), the narrow form at 0.84 - 0.86 (3.12
+ * against 3.72) - the same bytes come from HBM, since the caches do not catch the re-reads of an item by neighbouring outputs, and
+ * the walk from tap to tap costs 2.7 times the scalar instructions (wide) or 14 % more vector instructions and a wave (narrow).  The
+ * operand loads carry no non-temporal hint: with it 1 % is gained at the 3 x 3 shapes at N = 65536 and 4 - 10 % lost at 28 x 28 and at
+ * N = 8192.  Sizes other than 2 and the rings below N = 128: not measured. */
+typedef struct
+{
+    uint64_t in_channels, height, width, out_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w;
+} SHL_CONV2D;
+SHL_FUNC Evaluator_Conv2dScalarsItems(void *thisptr, const void *device_weights, void *encrypted, const SHL_CONV2D *shape, uint64_t flags,
+                                      double scale, void *destination);
 SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *pool);
 SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool);
 SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *pool);
@@ -842,6 +891,20 @@ SHL_FUNC shl_matmul_scalars_tile(void *context, uint64_t chain_index, const void
                                  uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used,
                                  uint64_t row_tile, void *stream);
 SHL_FUNC shl_matmul_scalars_info(uint64_t *row_tile, uint64_t *narrow_row_tile, uint64_t *flush, uint64_t *narrow_flush);
+/* The kernel of Evaluator_Conv2dScalarsItems on raw words at one level: weights = [OC * inner][K] 64-bit words or, with flags bit 2,
+ * [OC * inner] signed 32-bit integers, inner = C * kernel_h * kernel_w; a = [size][C * H * W][K][N] (channel-last items with flags
+ * bit 0), r = [size][OC * OH * OW][K][N] (channel-last items with bit 1); shape is host memory.  slices == 0: the library's rule;
+ * otherwise 1 <= slices <= min(inner, 64) ranges of the term index, anything else is SHL_E_INVALIDARG; slices_used receives the
+ * slices run: of a forced cut those that ceil(inner / slices) terms each leave non-empty.  r == NULL: the query.  Nothing is
+ * validated beyond the shape.  shl_conv2d_scalars runs on the NULL stream and returns when the work is done;
+ * shl_conv2d_scalars_tile enqueues on `stream` with row_tile output channels per thread (0, 4, 8 as shl_matmul_scalars_tile) and
+ * operand loads with (hint 1) or without (hint 2) the non-temporal hint, 0 = the library's choice - the sweep of
+ * tools/conv2d_scalars_rate.py.  The row tiles and flush intervals are those shl_matmul_scalars_info reports. */
+SHL_FUNC shl_conv2d_scalars(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
+                            const SHL_CONV2D *shape, uint64_t flags, uint64_t slices, uint64_t *slices_used);
+SHL_FUNC shl_conv2d_scalars_tile(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
+                                 const SHL_CONV2D *shape, uint64_t flags, uint64_t slices, uint64_t *slices_used, uint64_t row_tile,
+                                 uint64_t hint, void *stream);
 /* GaloisTool::apply_galois (ntt_form == 0, util/galois.cpp:148) / apply_galois_ntt (!= 0, galois.cpp:192) */
 SHL_FUNC shl_apply_galois(void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys, void *stream);
 /* RNSTool stages (util/rns.cpp) on one level, `polys` polynomials each [comps][N]:

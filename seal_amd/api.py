@@ -1264,6 +1264,23 @@ class ItemMap:
     __del__ = destroy
 
 
+class Conv2dShape(C.Structure):
+    """sealhip.h: SHL_CONV2D, the shape of Evaluator.conv2d_scalars_items"""
+    _fields_ = [(name, C.c_uint64) for name in ("in_channels", "height", "width", "out_channels", "kernel_h", "kernel_w",
+                                                 "stride_h", "stride_w", "pad_h", "pad_w")]
+
+    def out_size(self):
+        """(OH, OW); (0, 0) for a shape the library refuses before it divides"""
+        if not self.stride_h or not self.stride_w or self.height + 2 * self.pad_h < self.kernel_h or self.width + 2 * self.pad_w < self.kernel_w:
+            return 0, 0
+        return ((self.height + 2 * self.pad_h - self.kernel_h) // self.stride_h + 1,
+                (self.width + 2 * self.pad_w - self.kernel_w) // self.stride_w + 1)
+
+    def out_items(self):
+        oh, ow = self.out_size()
+        return self.out_channels * oh * ow
+
+
 class Evaluator:
     """seal::Evaluator's hot-path surface (evaluator.h:79-1387), in-place and destination forms."""
 
@@ -1587,6 +1604,31 @@ class Evaluator:
         ptr = weights.ptr if isinstance(weights, DeviceBuffer) else weights
         N.check(N.lib().Evaluator_MatMulScalarsItems(self._h, C.c_void_p(ptr), a._h, C.c_uint64(rows), C.c_uint64(inner), C.c_uint64(cols),
                                                      C.c_uint64(flags | (4 if narrow else 0)), C.c_double(scale), d._h))
+        return d
+
+    def conv2d_scalars_items(self, weights, a, shape, flags=0, scale=1.0, narrow=False, destination=None, *, input_channel_last=False,
+                             result_channel_last=False):
+        """a 2-D convolution of scalar weights over a grid of ciphertexts, one per (channel, pixel) (sealhip.h:
+        Evaluator_Conv2dScalarsItems): item (o * OH + y') * OW + x' of the result = the sum over the taps (c, dy, dx) inside the
+        image of weight o * inner + (c * kh + dy) * kw + dx times a[(c * H + y' sh + dy - ph) * W + x' sw + dx - pw], inner =
+        C * kh * kw.  shape: a Conv2dShape, or its fields in order (in_channels, height, width, out_channels, kernel_h, kernel_w,
+        stride_h, stride_w, pad_h, pad_w) as a sequence or dict.  flags bit 0 / input_channel_last: item (c, y, x) of `a` is at
+        (y * W + x) * C + c; bit 1 / result_channel_last: the same for the result.  weights, scale, narrow: those of
+        matmul_scalars_items with rows = out_channels.  destination None: a new Ciphertext of OC * OH * OW items; otherwise a
+        handle of that batch, distinct from `a`.  -> the destination"""
+        if flags & ~3:
+            raise ValueError("flags: bits 0 and 1; narrow weights are the `narrow` argument")
+        flags |= (1 if input_channel_last else 0) | (2 if result_channel_last else 0)
+        s = shape if isinstance(shape, Conv2dShape) else Conv2dShape(**shape) if isinstance(shape, dict) else Conv2dShape(*shape)
+        count = s.out_channels * s.in_channels * s.kernel_h * s.kernel_w
+        need = -(-count // 2) if narrow else count * a.coeff_modulus_size()
+        if isinstance(weights, DeviceBuffer) and weights.words < need:
+            raise ValueError("%d words of weights for %d %s weights at this level: %d needed"
+                             % (weights.words, count, "narrow" if narrow else "wide", need))
+        d = Ciphertext(self.context, batch=s.out_items()) if destination is None else destination
+        ptr = weights.ptr if isinstance(weights, DeviceBuffer) else weights
+        N.check(N.lib().Evaluator_Conv2dScalarsItems(self._h, C.c_void_p(ptr), a._h, C.byref(s), C.c_uint64(flags | (4 if narrow else 0)),
+                                                     C.c_double(scale), d._h))
         return d
 
     # ---- the same reductions over the items an ItemMap names (sealhip.h: Evaluator_SumItemsMapped ...)

@@ -164,4 +164,33 @@ namespace sealhip
     hipError_t k_matmul_scalars(const ModDesc *mods, const void *weights, bool narrow, const uint64_t *a, size_t a_stride, uint64_t *r,
                                 size_t r_stride, unsigned size, unsigned n_log, unsigned K, size_t rows, size_t inner, size_t cols,
                                 bool a_transposed, bool r_transposed, unsigned slices, uint64_t *scratch, unsigned row_tile, hipStream_t s);
+
+    // 2-D convolution of scalar weights over a grid of items: k_matmul_scalars with rows = the output channels, cols = the output
+    // positions OH * OW and inner = C * kh * kw, whose operand of term t = (c * kh + dy) * kw + dx at output position (y', x') is
+    // not item (t, j) of a dense matrix but input item (c, y' sh + dy - ph, x' sw + dx - pw) - no gathered batch exists:
+    //   r[p][o][y'][x'] = sum_{c, dy, dx} const(w[o][(c * kh + dy) * kw + dx]) a[p][c][y' sh + dy - ph][x' sw + dx - pw] mod q
+    // over the taps inside the image; the others are skipped, not read.  OH = (H + 2 ph - kh) / sh + 1, OW likewise.
+    // a = [size][C * H * W][K][N], item (c, y, x) at (c * H + y) * W + x - or at (y * W + x) * C + c when in_last -, r = [size][OC *
+    // OH * OW][K][N], item (o, y', x') at (o * OH + y') * OW + x' - or at (y' * OW + x') * OC + o when out_last: strides, as the
+    // layouts of k_matmul_scalars.  weights, narrow, the tile of R output channels per thread, the flush intervals (which count
+    // executed taps) and "written by something earlier on the stream" are k_matmul_scalars'.  From N = 128 on the output position
+    // is wave-uniform like the column there, and with it the in-image range of dy and dx.
+    // conv2d_shape_error: nullptr, or what is wrong with a shape - an extent or stride of 0, pad >= kernel (so every output has a
+    // tap), H + 2 ph < kh (or the width), or one of C H W, OC OH OW, OC inner, inner OH OW >= 2^32 (the last is the skeleton's bound
+    // on the terms of a launch); oh and ow are set when it is nullptr.
+    // slices, scratch: a cut of the flat term index t as above, with scratch of batch_reduce_scratch_words(slices, size, OC * OH *
+    // OW, ...) words; a slice without a live term for some output stores zeros there.  The library's rule is asked with
+    // conv2d_scalars_threads() threads that each add `inner` terms; it is 0 for a tile that is not built, a shape that is refused
+    // and a launch the flat grid refuses: k_conv2d_scalars fails on all three.  row_tile: 0 or 4, 8 as k_matmul_scalars.
+    // hint: the operand loads carry the non-temporal hint (1) or not (2), 0 = the library's choice: unlike the product's operand an
+    // input item is read by up to ceil(kh / sh) ceil(kw / sw) neighbouring outputs, times ceil(OC / R) channel tiles.
+    struct Conv2dShape
+    {
+        uint64_t in_channels, height, width, out_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w;
+    };
+    const char *conv2d_shape_error(const Conv2dShape &shape, size_t &oh, size_t &ow);
+    size_t conv2d_scalars_threads(unsigned size, const Conv2dShape &shape, unsigned n_log, unsigned K, bool narrow, unsigned row_tile = 0);
+    hipError_t k_conv2d_scalars(const ModDesc *mods, const void *weights, bool narrow, const uint64_t *a, size_t a_stride, uint64_t *r,
+                                size_t r_stride, unsigned size, unsigned n_log, unsigned K, const Conv2dShape &shape, bool in_last,
+                                bool out_last, unsigned slices, uint64_t *scratch, unsigned row_tile, unsigned hint, hipStream_t s);
 } // namespace sealhip

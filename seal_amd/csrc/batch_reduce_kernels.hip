@@ -5,7 +5,8 @@
 //   reduce_items are the launch and the host path.
 // - the tiled products (the matrix products and the scalar weights), a TILE of output items per thread, so that each loaded operand
 //   word is used for all of them: one geometry (TileGeom), one prologue (TileThread), two bodies - matmul_words_kernel with its term
-//   (MatmulItemsTerm, MatmulPlainTerm) and matmul_scalars_kernel, whose weights are scalar loads -, launch_tiled and tiled_reduce.
+//   (MatmulItemsTerm, MatmulPlainTerm) and matmul_scalars_kernel, whose weights are scalar loads -, launch_tiled and tiled_reduce;
+//   conv2d_scalars_kernel is the second body with another walk: its operand is found in an image, not in a dense matrix.
 // Both share the accumulators and flush intervals, the accesses, the flat grid with the slices of a cut in y, the cut and the sum of
 // the slices.
 #include "batch_reduce_kernels.h"
@@ -726,6 +727,160 @@ namespace sealhip
         // 8 rows on
         constexpr unsigned kRowTile = 4, kMatmulScalarsTile = 4, kMatmulScalarsNarrowTile = 8;
 
+        // ---- 2-D convolution of scalar weights (batch_reduce_kernels.h: k_conv2d_scalars): the scalar-weights product with rows =
+        // the output channels, cols = the output positions and inner = C * kh * kw, in the same grid, with the same prologue,
+        // weights, accumulators and flushes.  What differs is where the operand of a term is: term t = (c * kh + dy) * kw + dx of
+        // output position (y', x') is input item (c, y' sh + dy - ph, x' sw + dx - pw), three strides from the item of channel 0 at
+        // the top left of the image, and a term outside the image is no term.  The result's layout is TileGeom's r_row (from a
+        // channel to the next) and r_col (from a position to the next: a position is one index in both layouts).
+        struct ConvGeom : TileGeom
+        {
+            size_t in_c, in_y, in_x; // words from input item (c, y, x) to (c + 1, y, x) / (c, y + 1, x) / (c, y, x + 1)
+            size_t sh, sw;           // strides (1 where there is one output row / column: then no product with them matters)
+            unsigned H, W, OW, kh, kw, ph, pw;
+        };
+        // one reduction of the tile's sums, which then carry their canonical residues; narrow: and of the plain sum, which restarts
+        template <unsigned R, bool NARROW, bool FULL>
+        __device__ __forceinline__ void scalars_flush(U128 (&acc)[R][2], U128 (&plain)[2], const ModDesc &md, uint64_t bias, unsigned live)
+        {
+            uint64_t less[2] = {}; // narrow: 2^31 times the sum of the operand words
+            if (NARROW)
+#pragma unroll
+                for (unsigned l = 0; l < 2; l++)
+                {
+                    less[l] = mul_mod(barrett128(plain[l].lo, plain[l].hi, md), bias, md);
+                    plain[l] = U128{ 0, 0 };
+                }
+#pragma unroll
+            for (unsigned r = 0; r < R; r++)
+                if (FULL || r < live)
+#pragma unroll
+                    for (unsigned l = 0; l < 2; l++)
+                        acc[r][l] = U128{ sub_mod(barrett128(acc[r][l].lo, acc[r][l].hi, md), less[l], md.q), 0 };
+        }
+        // The in-image taps of an output position are a rectangle [dy0, dy1) x [dx0, dx1) of the kernel, the same for every channel
+        // and computed once per thread (per wave when UNIFORM); the loop runs over the channels the slice [t0, t1) touches, the
+        // live dy and, clipped to the slice, the live dx, whose operands are in_x words apart and whose weights are consecutive.
+        // Nothing outside the batch is addressed: an operand pointer is formed for a live tap only.  `run` counts the executed
+        // taps since the last reduction, so a run of taps ends where the sums could no longer take another one.
+        // a: component k of plane p of input item (0, 0, 0); lane: the thread's words from there.  When UNIFORM the first is the
+        // wave's and the walk from tap to tap is scalar arithmetic: a lane keeps one 32-bit offset, not the two pointers of the
+        // per-lane walk.
+        template <unsigned R, bool NARROW, bool NT, bool UNIFORM, bool FINAL, bool FULL>
+        __device__ __forceinline__ void conv2d_scalars_rows(const ModDesc &md, const uint64_t *a, unsigned lane, const void *weights, uint64_t *d,
+                                                            const ConvGeom &g, const TileThread &th)
+        {
+            using Word = std::conditional_t<NARROW, uint32_t, uint64_t>;
+            constexpr unsigned kFlush = NARROW ? kNarrowFlush : kDotFlush;
+            // weight (i0, term 0) [of prime k]; words from a term to the next and from a channel to the next
+            const size_t step = NARROW ? 1 : g.K, row_words = (size_t)g.inner * step;
+            const Word *wp = static_cast<const Word *>(weights) + (size_t)th.i0 * row_words + (NARROW ? 0 : th.k);
+            const uint64_t bias = NARROW ? barrett64(uint64_t(1) << 31, md) : 0; // 2^31 mod q
+            const unsigned live = th.live_r;
+            // tap (dy, dx) of this position is input row y0 + dy - ph, column x0 + dx - pw (64 bits: H + ph may pass 2^32)
+            const uint64_t y0 = th.j0 / g.OW * g.sh, x0 = th.j0 % g.OW * g.sw;
+            const unsigned dy0 = y0 < g.ph ? (unsigned)(g.ph - y0) : 0, dy1 = (uint64_t)g.H + g.ph - y0 < g.kh ? (unsigned)((uint64_t)g.H + g.ph - y0) : g.kh;
+            const unsigned dx0 = x0 < g.pw ? (unsigned)(g.pw - x0) : 0, dx1 = (uint64_t)g.W + g.pw - x0 < g.kw ? (unsigned)((uint64_t)g.W + g.pw - x0) : g.kw;
+            const unsigned taps = g.kh * g.kw, c0 = th.t0 / taps, c1 = (th.t1 - 1) / taps; // (a slice is not empty)
+            U128 acc[R][2] = {};
+            U128 plain[2] = {}; // narrow: the sum of the operand words themselves
+            unsigned run = 0;
+            for (unsigned c = c0; c <= c1; c++)
+                for (unsigned dy = dy0; dy < dy1; dy++)
+                {
+                    const unsigned base = (c * g.kh + dy) * g.kw; // term (c, dy, 0)
+                    unsigned t = base + dx0 > th.t0 ? base + dx0 : th.t0;
+                    const unsigned last = base + dx1 < th.t1 ? base + dx1 : th.t1;
+                    if (t >= last)
+                        continue;
+                    const uint64_t *ap = a + c * g.in_c + (size_t)(y0 + dy - g.ph) * g.in_y + (size_t)(x0 + (t - base) - g.pw) * g.in_x;
+                    const Word *w = wp + t * step;
+                    while (t < last)
+                    {
+                        const unsigned end = last - t < kFlush - run ? last : t + (kFlush - run);
+                        run += end - t;
+                        for (; t < end; t++, ap += g.in_x, w += step)
+                        {
+                            uint64_t a0, a1;
+                            ld2<NT>(ap + lane, a0, a1);
+                            if (NARROW)
+                            {
+                                add128(plain[0], a0, 0);
+                                add128(plain[1], a1, 0);
+                            }
+#pragma unroll
+                            for (unsigned r = 0; r < R; r++)
+                                if (FULL || r < live)
+                                {
+                                    if constexpr (NARROW)
+                                    {
+                                        const uint32_t u = (UNIFORM ? SHL_UCONST32(w)[r * row_words] : w[r * row_words]) ^ 0x80000000u;
+                                        mac_narrow(acc[r][0], a0, u);
+                                        mac_narrow(acc[r][1], a1, u);
+                                    }
+                                    else
+                                    {
+                                        const uint64_t v = UNIFORM ? SHL_UCONST(w)[r * row_words] : w[r * row_words];
+                                        mac128(acc[r][0], a0, v);
+                                        mac128(acc[r][1], a1, v);
+                                    }
+                                }
+                        }
+                        if (run == kFlush)
+                        {
+                            scalars_flush<R, NARROW, FULL>(acc, plain, md, bias, live);
+                            run = 0;
+                        }
+                    }
+                }
+            scalars_flush<R, NARROW, FULL>(acc, plain, md, bias, live); // (of nothing but residues when the last run was full)
+#pragma unroll
+            for (unsigned r = 0; r < R; r++)
+                if (FULL || r < live)
+                {
+                    if (FINAL)
+                        st2_nt(d + r * g.r_row, acc[r][0].lo, acc[r][1].lo);
+                    else
+                        st2(d + r * g.r_row, acc[r][0].lo, acc[r][1].lo);
+                }
+        }
+        // waves per SIMD the allocator is held to (profiles/conv2d_scalars.txt has the registers of every instantiation: none uses
+        // scratch memory at these).  The wave-uniform kernels: the product's.  The per-lane kernels, which exist for the rings
+        // below N = 128, keep the tap range, the term and two more addresses per lane and spill at the product's bounds
+        template <unsigned R, bool NARROW, bool UNIFORM>
+        constexpr unsigned conv2d_scalars_waves()
+        {
+            return !UNIFORM ? (R == 4 ? 4 : 3) : R == 4 ? matmul_scalars_waves<4, true>() : NARROW ? 4 : 5;
+        }
+        template <unsigned R, bool NARROW, bool NT, bool UNIFORM, bool FINAL>
+        __global__ void __launch_bounds__(kBlock, (conv2d_scalars_waves<R, NARROW, UNIFORM>())) conv2d_scalars_kernel(const ModDesc *mods, const void *weights, const uint64_t *a, uint64_t *dst, ConvGeom g)
+        {
+            const size_t w = blockIdx.x * (size_t)kBlock + threadIdx.x;
+            if (w >= g.threads)
+                return;
+            const TileThread th = TileThread::at<R, 1, 2, UNIFORM>(g, w); // i0: the tile's first output channel, j0: the output position
+            const ModDesc md = mods[th.k];
+            const unsigned lane = (unsigned)(th.word & ((size_t(1) << g.n_log) - 1)); // the coefficient
+            const uint64_t *ap = a + th.p * g.y_plane + ((size_t)th.k << g.n_log); // component k of plane p of input item (0, 0, 0)
+            uint64_t *d = dst + blockIdx.y * g.dst_slice + th.p * g.dst_plane + th.i0 * g.r_row + th.j0 * g.r_col + th.word;
+            if (th.live_r == R)
+                conv2d_scalars_rows<R, NARROW, NT, UNIFORM, FINAL, true>(md, ap, lane, weights, d, g, th);
+            else
+                conv2d_scalars_rows<R, NARROW, NT, UNIFORM, FINAL, false>(md, ap, lane, weights, d, g, th);
+        }
+        // the kernels of a row tile, a form and a hint by (UNIFORM, FINAL)
+        template <unsigned R, bool NARROW, bool NT>
+        struct ConvFamily
+        {
+            template <bool UNIFORM, bool FINAL>
+            static constexpr auto kernel = &conv2d_scalars_kernel<R, NARROW, NT, UNIFORM, FINAL>;
+        };
+        // whether the library's operand loads carry the non-temporal hint (tools/conv2d_scalars_rate.py measures both; DESIGN.md
+        // 8.11 has the table): not.  At N = 65536 the hint wins 1 % where 3 x 3 windows overlap over 8 channels and loses 5 - 11 % on
+        // the 28 x 28 image under a 5 x 5 kernel, whose neighbouring outputs re-read an item while it is still cached; at
+        // N = 8192, where the whole input fits the caches, it loses 4 - 9 % everywhere
+        constexpr bool kConvNonTemporal = false;
+
         // ---- the built tiles of a product as a list, and the one dispatch on it: f(BuiltTile<TR, TC>{}) for the tile that is
         // TR x TC; false = not built
         template <unsigned TR, unsigned TC>
@@ -777,9 +932,10 @@ namespace sealhip
                 return 0;
             return threads;
         }
-        // the one launch of the tiled kernels: Family::kernel<first, FINAL>, `first` being the family's own switch (NT, UNIFORM)
-        template <class Family, class X>
-        hipError_t launch_tiled(const ModDesc *mods, const X *x, const uint64_t *y, uint64_t *dst, const TileGeom &g, unsigned slices, bool first,
+        // the one launch of the tiled kernels: Family::kernel<first, FINAL>, `first` being the family's own switch (NT, UNIFORM);
+        // Geom: TileGeom, or what a family's kernels take in its place (ConvGeom)
+        template <class Family, class X, class Geom>
+        hipError_t launch_tiled(const ModDesc *mods, const X *x, const uint64_t *y, uint64_t *dst, const Geom &g, unsigned slices, bool first,
                                 bool final, hipStream_t s)
         {
             if (!g.threads)
@@ -1037,5 +1193,77 @@ namespace sealhip
     {
         return scalars_reduce<MatmulScalarsTiles>(mods, weights, narrow, a, a_stride, r, r_stride, size, n_log, K, rows, inner, cols, a_transposed,
                                                   r_transposed, slices, scratch, row_tile ? row_tile : matmul_scalars_row_tile(narrow), s);
+    }
+
+    const char *conv2d_shape_error(const Conv2dShape &c, size_t &oh, size_t &ow)
+    {
+        const uint64_t lim = uint64_t(1) << 32;
+        if (!c.in_channels || !c.height || !c.width || !c.out_channels || !c.kernel_h || !c.kernel_w || !c.stride_h || !c.stride_w)
+            return "an extent or stride of the convolution is 0";
+        if (c.pad_h >= c.kernel_h || c.pad_w >= c.kernel_w)
+            return "pad must be below the kernel: every output has a tap inside the image";
+        // (from here on pad < kernel; every factor is checked before it is multiplied, so no product wraps)
+        if (c.in_channels >= lim || c.height >= lim || c.width >= lim || c.out_channels >= lim || c.kernel_h >= lim || c.kernel_w >= lim)
+            return "C * H * W, OC * OH * OW and OC * C * kh * kw must be below 2^32";
+        if (c.height + 2 * c.pad_h < c.kernel_h || c.width + 2 * c.pad_w < c.kernel_w)
+            return "the kernel is larger than the padded image";
+        const uint64_t h = (c.height + 2 * c.pad_h - c.kernel_h) / c.stride_h + 1, w = (c.width + 2 * c.pad_w - c.kernel_w) / c.stride_w + 1;
+        const uint64_t taps = c.kernel_h * c.kernel_w, image = c.height * c.width; // both below 2^64
+        if (h >= lim || w >= lim || h * w >= lim || taps >= lim || image >= lim || c.in_channels * image >= lim || c.out_channels * h * w >= lim ||
+            c.in_channels * taps >= lim || c.out_channels * c.in_channels * taps >= lim)
+            return "C * H * W, OC * OH * OW and OC * C * kh * kw must be below 2^32";
+        if (c.in_channels * taps * h * w >= lim)
+            return "the result is too large for one launch: C * kh * kw * OH * OW must be below 2^32";
+        oh = (size_t)h;
+        ow = (size_t)w;
+        return nullptr;
+    }
+    size_t conv2d_scalars_threads(unsigned size, const Conv2dShape &shape, unsigned n_log, unsigned K, bool narrow, unsigned row_tile)
+    {
+        size_t oh, ow;
+        if (conv2d_shape_error(shape, oh, ow))
+            return 0;
+        return matmul_scalars_threads(size, shape.out_channels, oh * ow, n_log, K, narrow, row_tile);
+    }
+    // the tiled host path with rows = OC, inner = C * kh * kw, cols = OH * OW (a channel-last result is the transposed one), whose
+    // launch completes the geometry with the input's strides and the shape
+    hipError_t k_conv2d_scalars(const ModDesc *mods, const void *weights, bool narrow, const uint64_t *a, size_t a_stride, uint64_t *r,
+                                size_t r_stride, unsigned size, unsigned n_log, unsigned K, const Conv2dShape &c, bool in_last, bool out_last,
+                                unsigned slices, uint64_t *scratch, unsigned row_tile, unsigned hint, hipStream_t s)
+    {
+        size_t oh, ow;
+        const unsigned R = row_tile ? row_tile : matmul_scalars_row_tile(narrow);
+        if (conv2d_shape_error(c, oh, ow) || !MatmulScalarsTiles::with(R, 1, [](auto) {}) || hint > 2)
+            return hipErrorInvalidValue;
+        const bool nt = hint ? hint == 1 : kConvNonTemporal, uniform = n_log >= 7;
+        const size_t words = (size_t)K << n_log, C = c.in_channels, H = c.height, W = c.width, inner = C * c.kernel_h * c.kernel_w, cols = oh * ow;
+        return tiled_reduce(mods, 0, a_stride, false, r, r_stride, out_last, size, n_log, K, c.out_channels, inner, cols, R, 1,
+                            tiled_threads(size, c.out_channels, cols, n_log, K, R, 1, 2), slices, scratch, s,
+                            [=](const TileGeom &t, uint64_t *dst, unsigned ns, bool final) {
+                                const ConvGeom g{ t,
+                                                  in_last ? words : H * W * words,
+                                                  in_last ? W * C * words : W * words,
+                                                  in_last ? C * words : words,
+                                                  oh > 1 ? (size_t)c.stride_h : 1,
+                                                  ow > 1 ? (size_t)c.stride_w : 1,
+                                                  (unsigned)H,
+                                                  (unsigned)W,
+                                                  (unsigned)ow,
+                                                  (unsigned)c.kernel_h,
+                                                  (unsigned)c.kernel_w,
+                                                  (unsigned)c.pad_h,
+                                                  (unsigned)c.pad_w };
+                                hipError_t e = hipErrorInvalidValue;
+                                MatmulScalarsTiles::with(R, 1, [&](auto tile) {
+                                    constexpr unsigned kR = decltype(tile)::kRows;
+                                    if (narrow)
+                                        e = nt ? launch_tiled<ConvFamily<kR, true, true>>(mods, weights, a, dst, g, ns, uniform, final, s)
+                                               : launch_tiled<ConvFamily<kR, true, false>>(mods, weights, a, dst, g, ns, uniform, final, s);
+                                    else
+                                        e = nt ? launch_tiled<ConvFamily<kR, false, true>>(mods, weights, a, dst, g, ns, uniform, final, s)
+                                               : launch_tiled<ConvFamily<kR, false, false>>(mods, weights, a, dst, g, ns, uniform, final, s);
+                                });
+                                return e;
+                            });
     }
 } // namespace sealhip

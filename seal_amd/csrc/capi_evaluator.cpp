@@ -1,5 +1,6 @@
 // extern "C" layer, part 3: KSwitchKeys, Evaluator (ciphertext, plaintext-operand and many-operand forms), communicator and digit-parallel forms (include/sealhip.h)
 #include "capi_common.h"
+#include "batch_reduce_kernels.h"
 
 extern "C"
 {
@@ -411,6 +412,26 @@ extern "C"
         StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
         as<Evaluator>(thisptr)->matmul_scalars_items(device_weights, (flags & 4) != 0, *as<Ciphertext>(encrypted), (size_t)rows, (size_t)inner,
                                                      (size_t)cols, (flags & 1) != 0, (flags & 2) != 0, scale, *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
+    // 2-D convolution of scalar weights over a grid of items (library extension); flags bit 0: the input is stored channel-last,
+    // bit 1: the result is, bit 2: narrow weights
+    SHL_FUNC Evaluator_Conv2dScalarsItems(void *thisptr, const void *device_weights, void *encrypted, const SHL_CONV2D *shape, uint64_t flags,
+                                          double scale, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        if (!shape)
+            throw std::invalid_argument("shape is null");
+        if (flags & ~uint64_t(7))
+            throw std::invalid_argument("unknown flags");
+        const Conv2dShape c{ shape->in_channels, shape->height,   shape->width,    shape->out_channels, shape->kernel_h,
+                             shape->kernel_w,    shape->stride_h, shape->stride_w, shape->pad_h,        shape->pad_w };
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->conv2d_scalars_items(device_weights, (flags & 4) != 0, *as<Ciphertext>(encrypted), c, (flags & 1) != 0,
+                                                     (flags & 2) != 0, scale, *as<Ciphertext>(destination));
         SHL_CATCH
     }
     SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination)

@@ -383,6 +383,48 @@ extern "C"
         *narrow_flush = matmul_scalars_narrow_flush();
         return SHL_S_OK;
     }
+    // k_conv2d_scalars on raw words: weights [OC * inner][K] 64-bit words or, flags bit 2, [OC * inner] signed 32-bit integers with
+    // inner = C * kh * kw, a [size][C * H * W][K][N] (channel-last items with flags bit 0), r [size][OC * OH * OW][K][N] (channel-last
+    // items with flags bit 1); slices == 0: the library's rule; r == NULL: the query.  Scratch comes from the pool.  row_tile: as
+    // shl_matmul_scalars_tile; hint: 0 = the library's choice, 1 / 2 = operand loads with / without the non-temporal hint - the
+    // sweep of tools/conv2d_scalars_rate.py
+    SHL_FUNC shl_conv2d_scalars_tile(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
+                                     const SHL_CONV2D *shape, uint64_t flags, uint64_t slices, uint64_t *slices_used, uint64_t row_tile,
+                                     uint64_t hint, void *stream)
+    {
+        const bool narrow = (flags & 4) != 0;
+        Conv2dShape c{};
+        if (shape)
+            c = Conv2dShape{ shape->in_channels, shape->height,   shape->width,    shape->out_channels, shape->kernel_h,
+                             shape->kernel_w,    shape->stride_h, shape->stride_w, shape->pad_h,        shape->pad_w };
+        size_t oh = 0, ow = 0;
+        const char *error = !size || size > 16 || (flags & ~uint64_t(7)) || hint > 2 ? "1 <= size <= 16; flags 0 .. 7; hint 0 .. 2"
+                            : !shape                                                ? "shape is null"
+                                                                                    : conv2d_shape_error(c, oh, ow);
+        const uint64_t inner = error ? 0 : c.in_channels * c.kernel_h * c.kernel_w;
+        return raw_tiled(
+            context, chain_index, error, "a result too large for one launch; a built row tile", "1 <= slices <= min(C * kh * kw, 64)", size,
+            c.out_channels, inner, oh * ow, slices, true, slices_used, r, weights, a, stream,
+            [&](unsigned n_log, unsigned K) {
+                return (row_tile >> 32) ? 0 : conv2d_scalars_threads((unsigned)size, c, n_log, K, narrow, (unsigned)row_tile);
+            },
+            [&](Context *ctx, const Level *l, unsigned n_log, size_t words, unsigned cut, uint64_t *scratch, hipStream_t s) {
+                hip_ok(k_conv2d_scalars(ctx->dev_mods(), weights, narrow, a, c.in_channels * c.height * c.width * words, r,
+                                        c.out_channels * oh * ow * words, (unsigned)size, n_log, l->K, c, (flags & 1) != 0, (flags & 2) != 0, cut,
+                                        scratch, (unsigned)row_tile, (unsigned)hint, s),
+                       "conv2d_scalars");
+            });
+    }
+    SHL_FUNC shl_conv2d_scalars(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
+                                const SHL_CONV2D *shape, uint64_t flags, uint64_t slices, uint64_t *slices_used)
+    {
+        const SHL_HRESULT hr = shl_conv2d_scalars_tile(context, chain_index, weights, a, r, size, shape, flags, slices, slices_used, 0, 0, nullptr);
+        if (hr != SHL_S_OK || !r)
+            return hr;
+        SHL_TRY
+        hip_ok(hipStreamSynchronize(nullptr), "conv2d_scalars sync");
+        SHL_CATCH
+    }
     SHL_FUNC shl_apply_galois(
         void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys,
         void *stream)

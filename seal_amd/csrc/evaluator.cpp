@@ -1271,6 +1271,32 @@ namespace sealhip
                                                  scratch, 0, stream_);
                      });
     }
+    // 2-D convolution of scalar weights over a grid of items (include/sealhip.h: Evaluator_Conv2dScalarsItems): matmul_scalars_items
+    // with rows = OC, inner = C * kh * kw and cols = OH * OW - its checks, metadata, settling and cut - and a kernel that finds the
+    // operand of a term in the image instead of in a gathered batch
+    void Evaluator::conv2d_scalars_items(const void *weights, bool narrow, const Ciphertext &e, const Conv2dShape &shape, bool in_last,
+                                         bool out_last, double scale, Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        size_t oh, ow;
+        if (const char *wrong = conv2d_shape_error(shape, oh, ow))
+            throw std::invalid_argument(wrong);
+        const size_t rows = shape.out_channels, inner = shape.in_channels * shape.kernel_h * shape.kernel_w, cols = oh * ow;
+        check_plain_device(e, static_cast<const uint64_t *>(weights), inner, true, scale, dest, false, rows, narrow);
+        if (e.batch() != shape.in_channels * shape.height * shape.width)
+            throw std::invalid_argument("the ciphertext's batch does not equal in_channels * height * width");
+        const double new_scale = check_dot_plain(e, rows * cols, scale, dest);
+        const unsigned n_log = (unsigned)context_.log_n(), K = e.level()->K;
+        const size_t threads = conv2d_scalars_threads((unsigned)e.size(), shape, n_log, K, narrow);
+        if (!threads)
+            throw std::invalid_argument("the result is too large for one launch");
+        e.settle(); // the operand's words are read by what follows
+        reduce_items(e, rows * cols, ItemWalk(inner), e.size(), threads, true, new_scale, e.correction_factor(), dest, "conv2d_scalars (items)",
+                     [&](unsigned slices, uint64_t *scratch) {
+                         return k_conv2d_scalars(context_.dev_mods(), weights, narrow, e.data_, e.plane_words(), dest.data_, dest.plane_words(),
+                                                 (unsigned)e.size(), n_log, K, shape, in_last, out_last, slices, scratch, 0, 0, stream_);
+                     });
+    }
     // BFV / BGV scalars (include/sealhip.h: Evaluator_LiftScalars): the centred lift of transform_to_ntt_inplace(Plaintext) for the
     // constant polynomial m - m mod q_k, plus (Q - t) mod q_k from the upper-half threshold on, in both lift branches of the reference
     // (evaluator.cpp:2243-2282) - and the forward transform of a constant is that constant at every position

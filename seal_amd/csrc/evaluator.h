@@ -292,6 +292,7 @@ namespace sealhip
     // stream-aware pool (pool.h) outside any stream scope, i.e. tagged "unknown": its next user first waits for every registered
     // stream and the NULL stream, so a map may be destroyed while work that reads it is still queued - nothing is drained here.
     struct ItemWalk;
+    struct Conv2dShape;
     class ItemMap
     {
     public:
@@ -413,6 +414,14 @@ namespace sealhip
         // weights: written earlier on the stream.  A kernel of its own (batch_reduce_kernels.h: k_matmul_scalars)
         void matmul_scalars_items(const void *weights, bool narrow, const Ciphertext &encrypted, size_t rows, size_t inner, size_t cols,
                                   bool second_transposed, bool result_transposed, double scale, Ciphertext &destination) const;
+        // 2-D convolution of scalar weights over a grid of items (include/sealhip.h: Evaluator_Conv2dScalarsItems): encrypted is a
+        // batch of C * H * W items, destination one of OC * OH * OW, weights [OC][C * kh * kw] in either form of
+        // matmul_scalars_items; output item (o, y', x') is the sum over the taps inside the image - word for word dot_plain_mapped
+        // over the map of those taps with the weights expanded to [K][N]; checks, metadata and settling are matmul_scalars_items'.
+        // in_last / out_last: the channel is the fastest index of the input / result.  No gathered batch is made
+        // (batch_reduce_kernels.h: k_conv2d_scalars)
+        void conv2d_scalars_items(const void *weights, bool narrow, const Ciphertext &encrypted, const Conv2dShape &shape, bool in_last,
+                                  bool out_last, double scale, Ciphertext &destination) const;
         // A dense rows x batch matrix of SCALAR plaintexts times the items of a batch (include/sealhip.h: Evaluator_DotScalarsDevice):
         // item o of destination, a batch of `rows` items, becomes the sum over b of encrypted_b times the constant plaintext whose K
         // words are scalars[o][b] - word for word dot_plain_mapped over the dense map with the scalars expanded to [K][N]; checks,
