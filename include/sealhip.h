@@ -511,6 +511,52 @@ SHL_FUNC Evaluator_SumItemsMapped(void *thisptr, void *encrypted, void *item_map
 SHL_FUNC Evaluator_DotPlainMapped(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t plain_count, void *item_map,
                                   double scale, void *destination);
 SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination);
+/* A sparse matrix of SCALAR weights over an item map (library extension): Evaluator_DotPlainMapped whose plaintexts are constants,
+ *   out_o = sum_{t in row o} const(w[second[t]]) (.) ct[first[t]],   row_offsets[o] <= t < row_offsets[o + 1],  o < rows
+ * - with one ciphertext per feature and the samples in the slots: a pruned dense layer, grouped, depthwise and dilated convolutions,
+ * average pooling with any window, transposed and 1-D convolution, graph aggregation with edge weights, banded operators.  A weight
+ * is [K] words or one integer where Evaluator_DotPlainMapped needs [K][N] words (N = 65536, K = 15: 7.9 MB per weight).
+ * encrypted = a batch of first_batch items, any size >= 2, any level, in NTT form (CKKS, BGV, or BFV after
+ *   Evaluator_TransformToNTT2); destination = ANOTHER handle made with Ciphertext_CreateBatch(rows), resized to the operand's size
+ *   and level; weight_count must equal the map's second_batch, so a map made without a second list means one weight per input
+ *   item.  An item or a weight named twice is used twice.  One map and one weight buffer serve many calls.
+ * flags: bit 2 clear = WIDE weights, [weight_count][K] 64-bit words at the ciphertext's level, as the three scalar producers write
+ *   them; bit 2 set = NARROW weights, [weight_count] signed 32-bit integers.  The meaning of each form, of `scale`, the 16-byte
+ *   alignment, "not validated" and THE WEIGHTS MUST HAVE BEEN WRITTEN BY SOMETHING EARLIER ON THE STREAM are exactly
+ *   Evaluator_MatMulScalarsItems' (below), whose bit this is.  Every other bit, bits 0 and 1 included, is SHL_E_INVALIDARG.
+ * Contract: output item o equals, word for word and in its metadata, Evaluator_DotPlainMapped with the same map on
+ *   [weight_count][K][N] plaintexts each filled with its weight's K words, hence the reference's multiply_plain_inplace per term
+ *   followed by add_many.  The narrow form's words are the wide form's on the words its weights stand for.  Over the dense map (row
+ *   o names the items 0 .. B - 1, term (o, b) names weight o B + b) the words are Evaluator_DotScalarsDevice's; over the map of the
+ *   in-image taps with weight o * inner + tap they are Evaluator_Conv2dScalarsItems'.  Metadata (scale product and its bound check,
+ *   correction factor, is_ntt_form, parms_id), the settle-before-read of an operand with a deferred tail or a pending product,
+ *   Evaluator_SetTransparentCheck on the result batch and "a failed check leaves the destination untouched" are
+ *   Evaluator_DotPlainMapped's.  SHL_E_POINTER for NULL handles.  SHL_E_INVALIDARG: an unknown flag bit; weight_count !=
+ *   second_batch; the ciphertext's batch != first_batch; the destination's batch != rows; destination == encrypted; NULL or
+ *   misaligned device_weights; weights overlapping the words of either ciphertext; a coefficient-form ciphertext; an invalid or
+ *   foreign ciphertext, or a map of another context; a scale out of bounds.  The kernel indexes the weights in 64 bits, so
+ *   weight_count * K has no bound of its own (weight_count is a second_batch, below 2^32).
+ * The call is enqueued on the evaluator's stream without a host round trip and records under Evaluator_BeginCapture.
+ * Kernel: the mapped reductions' with one more term.  One thread holds one 16-byte coefficient pair of one prime, one plane and
+ *   one output item (the planes are in the grid: the weight is a scalar, so nothing is gained by holding it over the planes).  From
+ *   N = 128 on a wavefront never leaves its row and a term is a chain of scalar loads through the constant cache - the two list
+ *   entries, then the weight - and one vector load; four terms are in flight per wavefront (the list entries of four consecutive
+ *   terms are one 16-byte scalar load each).  On smaller rings every lane reads its own.  Wide products are accumulated as 128-bit
+ *   integers and reduced once per 256 terms; narrow ones use the biased weight and the two exact sums of
+ *   Evaluator_MatMulScalarsItems, reduced once per 1024 terms.
+ * Cut: the mapped family's (above), the rule being asked with size rows K N / 2 threads: WHETHER to cut, and into how many slices,
+ *   follows from the mean row; the slices are sized from the longest row, slices past the end of a short row store zeros, and a
+ *   second launch adds the slices from pool scratch [slices][size][rows][K][N].  The words do not depend on the cut.
+ * Bytes: at size 2 a term and coefficient pair reads two ciphertext pairs (32 B) where Evaluator_DotPlainMapped reads those and a
+ *   plaintext pair (48 B): 1.5 x fewer.  Measured on one MI355X (CKKS, size 2, both forms alike, against the DotPlainMapped kernel
+ *   over the same map on expanded plaintexts; DESIGN.md 8.12 has the table): at N = 65536, K = 15, 1.59 x for a pruned layer of 64
+ *   rows x 8 terms (1.51 ms), 1.57 x for a depthwise 3 x 3 over 8 channels of 8 x 8 (11.3 ms), 1.48 x for the dense 16 x 64 map
+ *   (2.72 ms) and 1.24 x for 2 x 2 pooling, whose rows have 4 terms; 6.0 - 6.3 TB/s by this model and 0.63 - 0.74 Tmac/s: bound by
+ *   HBM, not by the scalar-load chain.  At N = 8192, K = 3, where the operands come from the caches: 1.09 x (pooling) to 2.1 x
+ *   (dense).  Where the map IS dense, Evaluator_DotScalarsDevice reads the operand once per four rows and is 3.1 x faster than this
+ *   call at N = 65536.  Not measured: other sizes, rings below N = 8192 (so none of the per-lane kernels), BGV / BFV. */
+SHL_FUNC Evaluator_DotScalarsMapped(void *thisptr, void *encrypted, const void *device_weights, uint64_t weight_count, void *item_map,
+                                    uint64_t flags, double scale, void *destination);
 /* Scalar weights (library extensions): a dense plaintext matrix of SCALARS times a vector of ciphertexts,
  * out_o = sum_b w[o][b] * ct_b - the encrypted linear layer with one ciphertext per feature and the samples in the slots, weighted
  * averaging, any change of basis over the items.  A plaintext that holds one value in every slot is a constant polynomial, and in
@@ -541,7 +587,7 @@ SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypt
  *   Evaluator_SetTransparentCheck on the result batch, "a failed check leaves the destination untouched" and the SHL_E_POINTER cases
  *   are those of Evaluator_DotPlainDevice.  SHL_E_INVALIDARG in addition: rows == 0; rows B >= 2^32; batch != B; the destination's
  *   batch != rows; destination == encrypted; scalars overlapping either ciphertext's words; a coefficient-form ciphertext.  A zero
- *   scalar is an ordinary word: only the result batch is subject to the transparent check.  A sparse form is Evaluator_DotPlainMapped.
+ *   scalar is an ordinary word: only the result batch is subject to the transparent check.  The sparse form is Evaluator_DotScalarsMapped.
  *   The call is enqueued on the evaluator's stream without a host round trip and records under Evaluator_BeginCapture.  One thread
  *   holds one 16-byte coefficient pair of one plane and prime for a tile of 4 consecutive output rows and uses each loaded ciphertext
  *   pair for all of them, so the operand is read once per tile of rows (ceil(rows / 4) size P bytes for an operand plane of P bytes,
@@ -835,6 +881,16 @@ SHL_FUNC shl_dot_items_flush_interval(uint64_t *items);
 SHL_FUNC shl_reduce_mapped(void *context, uint64_t chain_index, int kind, const uint64_t *a, uint64_t a_batch, const uint64_t *b,
                            uint64_t b_batch, uint64_t *r, uint64_t size, void *item_map, uint64_t slices, uint64_t *scratch,
                            uint64_t *slices_used, void *stream);
+/* The kernel of Evaluator_DotScalarsMapped on raw words at one level, with shl_reduce_mapped's conventions: weights =
+ * [weight_count][K] 64-bit words or, narrow != 0, [weight_count] signed 32-bit integers; a = [size][a_batch][K][N]; r =
+ * [size][rows][K][N], distinct from the operands.  a_batch / weight_count must be the map's first_batch / second_batch.  slices: 0 =
+ * the library's rule (size * rows * K * N / 2 threads), 1 = one launch, 2 .. min(longest_row, 64) = that cut of the longest row, with
+ * scratch of slices * size * rows * K * N words; slices_used (may be NULL) receives the slices run; r == NULL only answers that.
+ * Nothing is validated beyond the shape.  shl_dot_scalars_mapped_info: the terms between two reductions (wide 256, narrow 1024). */
+SHL_FUNC shl_dot_scalars_mapped(void *context, uint64_t chain_index, const void *weights, uint64_t weight_count, int narrow, const uint64_t *a,
+                                uint64_t a_batch, uint64_t *r, uint64_t size, void *item_map, uint64_t slices, uint64_t *scratch,
+                                uint64_t *slices_used, void *stream);
+SHL_FUNC shl_dot_scalars_mapped_info(uint64_t *flush, uint64_t *narrow_flush);
 /* The kernel of Evaluator_DotScalarsDevice on raw words at one level: a = [size][batch][K][N], scalars = [rows][batch][K],
  * r = [size][rows][K][N], distinct from the operands.  slices: 0 = the library's rule, 1 = one launch, 2 .. min(batch, 64) = that cut
  * of the batch; the scratch comes from the pool.  slices_used (may be NULL) receives the slices run; r == NULL only answers that.

@@ -91,6 +91,7 @@ Evaluator_MatMulItems shl_matmul_items shl_matmul_items_tile shl_matmul_items_in
 Evaluator_MatMulPlainItems shl_matmul_plain_items shl_matmul_plain_items_tile shl_matmul_plain_items_info
 Evaluator_MatMulScalarsItems shl_matmul_scalars shl_matmul_scalars_tile shl_matmul_scalars_info
 Evaluator_Conv2dScalarsItems shl_conv2d_scalars shl_conv2d_scalars_tile
+Evaluator_DotScalarsMapped shl_dot_scalars_mapped shl_dot_scalars_mapped_info
 KSwitchKeys_Create1 KSwitchKeys_Destroy KSwitchKeys_Size KSwitchKeys_SetKey KSwitchKeys_SetKeyFromDevice
 KSwitchKeys_SetKeyDigits KSwitchKeys_HasKey KSwitchKeys_DeviceBytes RelinKeys_GetIndex GaloisKeys_GetIndex GaloisTool_GetEltFromStep
 Evaluator_Create Evaluator_Destroy Evaluator_SetStream Evaluator_Synchronize Evaluator_CopyTo Evaluator_SetTransparentCheck

@@ -1659,6 +1659,24 @@ class Evaluator:
         N.check(N.lib().Evaluator_DotPlainMapped(self._h, a._h, C.c_void_p(ptr), C.c_uint64(plain_count), item_map._h, C.c_double(scale), d._h))
         return d
 
+    def dot_scalars_mapped(self, a, weights, weight_count, item_map, flags=0, scale=1.0, narrow=False, destination=None):
+        """item o of the result = the sum over the terms t of row o of item first[t] of `a` * the scalar weight second[t]: a sparse
+        matrix of scalar weights times a batch (sealhip.h: Evaluator_DotScalarsMapped).  weights, scale, narrow: those of
+        matmul_scalars_items - a DeviceBuffer of [weight_count][K] words at the ciphertext's level or, narrow, of [weight_count]
+        signed 32-bit integers, written before this call on the stream; weight_count is the map's second_batch.  flags: none is
+        defined.  destination None: a new Ciphertext of item_map.rows() items; otherwise a handle of that batch, distinct from `a`"""
+        if flags:
+            raise ValueError("flags: none is defined; narrow weights are the `narrow` argument")
+        need = -(-weight_count // 2) if narrow else weight_count * a.coeff_modulus_size()
+        if isinstance(weights, DeviceBuffer) and weights.words < need:
+            raise ValueError("%d words of weights for %d %s weights at this level: %d needed"
+                             % (weights.words, weight_count, "narrow" if narrow else "wide", need))
+        d = self._mapped_dest(item_map, destination)
+        ptr = weights.ptr if isinstance(weights, DeviceBuffer) else weights
+        N.check(N.lib().Evaluator_DotScalarsMapped(self._h, a._h, C.c_void_p(ptr), C.c_uint64(weight_count), item_map._h,
+                                                   C.c_uint64(4 if narrow else 0), C.c_double(scale), d._h))
+        return d
+
     # ---- a dense matrix of scalar weights times a batch (sealhip.h: Evaluator_DotScalarsDevice)
     def lift_scalars(self, values, parms_id, out=None):
         """BFV / BGV: host values modulo t -> DeviceBuffer of [count][K] words, scalar i being what transform_plain_to_ntt_device

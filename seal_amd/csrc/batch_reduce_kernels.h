@@ -79,6 +79,23 @@ namespace sealhip
                            size_t r_stride, unsigned n_log, unsigned K, size_t out_items, const ItemWalk &walk, unsigned slices,
                            uint64_t *scratch, hipStream_t s);
 
+    // A sparse matrix of scalar weights times the items of a batch: k_dot_plain_items over a mapped walk with ONE value per prime (or
+    // one for all primes) instead of [K][N] words per plaintext.  Term t of row o is item first[t] of a times weight second[t]:
+    //   r[p][o][k][j] = sum_t const(w[second[t]])_k a[p][first[t]][k][j] mod q_k,  offsets[o] <= t < offsets[o + 1]
+    // weights, wide (narrow false): [count][K] 64-bit words, word k of weight i at i * K + k - k_dot_scalars' scalars.  Narrow:
+    // [count] signed 32-bit integers; weight w stands for the K words w mod q, so the result words are the wide form's on those.
+    // The words are k_dot_plain_items' over the same walk with each weight expanded to [K][N].  Accumulation: the wide form's
+    // sums are reduced once per batch_reduce_dot_flush() terms, the narrow form's (the biased weight and the two exact sums of
+    // k_matmul_scalars) once per matmul_scalars_narrow_flush().  One thread = one pair of one plane (the planes are in the grid, as
+    // for k_sum_items, so any size is one launch).  From N = 128 on offsets, lists and weights are scalar loads through the constant
+    // cache: the weights must have been written by something earlier on the stream.  Weights are indexed in 64 bits: count * K has
+    // no bound of its own (count is a map's second_batch, below 2^32).  The walk must be mapped - consecutive items are
+    // k_dot_scalars'.  slices, scratch: the mapped cut as above with scratch of batch_reduce_scratch_words(slices, size, out_items,
+    // ...) words; the library's rule is asked with size * out_items * K * N / 2 threads and the walk.  r must not be an operand.
+    hipError_t k_dot_scalars_mapped(const ModDesc *mods, const void *weights, bool narrow, const uint64_t *a, size_t a_stride, uint64_t *r,
+                                    size_t r_stride, unsigned size, unsigned n_log, unsigned K, size_t out_items, const ItemWalk &walk,
+                                    unsigned slices, uint64_t *scratch, hipStream_t s);
+
     // Scalar weights: r[p][o][k][j] = sum_b a[p][b][k][j] * s[o][b][k] mod q_k for o < rows - a dense rows x batch matrix of scalar
     // plaintexts times the items of a batch.  scalars = [rows][batch][K] words: word k is the value every coefficient of prime k
     // holds in the NTT-form constant plaintext, so the words are those of k_dot_plain_items over the dense map with the scalars

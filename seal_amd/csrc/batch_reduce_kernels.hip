@@ -1,8 +1,8 @@
 // See batch_reduce_kernels.h.  Two skeletons, each with one launch path and one host path:
 // - reduce_items_kernel, one output item per thread: one thread = two adjacent words of one output row (N is even, rows are 16-byte
 //   aligned); the grid is flat in x (one thread per output pair).  What a reduction adds per term is its Term (SumTerm,
-//   DotPlainTerm, DotItemsTerm), which items its terms are is its Walk (ConsecutiveWalk, MappedWalk); launch_reduce and
-//   reduce_items are the launch and the host path.
+//   DotPlainTerm, DotItemsTerm, DotScalarsTerm), which items its terms are is its Walk (ConsecutiveWalk, MappedWalk); launch_reduce
+//   and reduce_items are the launch and the host path.
 // - the tiled products (the matrix products and the scalar weights), a TILE of output items per thread, so that each loaded operand
 //   word is used for all of them: one geometry (TileGeom), one prologue (TileThread), two bodies - matmul_words_kernel with its term
 //   (MatmulItemsTerm, MatmulPlainTerm) and matmul_scalars_kernel, whose weights are scalar loads -, launch_tiled and tiled_reduce;
@@ -89,7 +89,10 @@ namespace sealhip
 
         // ---- the terms.  A Term has kOut result planes per thread, kFlush terms between two reductions of its accumulators (Acc,
         // reduce), the unroll factor of its loop, the waves per SIMD it is built for (the register allocator is held to them:
-        // profiles/batch_reduce_unified.txt) and add(): load term t of one output pair and add it to acc[plane][word of the pair]
+        // profiles/batch_reduce_unified.txt) and add(): load term t of one output pair and add it to acc[plane][word of the pair].
+        // Where a term's second operand is, is the term's business: Second is its word type, second_base() the thread's pointer into
+        // item 0 of it (`at`: the thread's words from the start of plane 0 of the first item) and second_at() the pointer of a named
+        // item from there - the kernel only hands the walk's item number over
         struct U128
         {
             uint64_t lo, hi;
@@ -105,7 +108,20 @@ namespace sealhip
             mul_wide(a, b, lo, hi);
             add128(acc, lo, hi);
         }
-        struct Products // of operands, as 128-bit integers
+        // the second operand is items of [K][N] words like the first: plane p, the same words of the item
+        struct WordOperand
+        {
+            using Second = uint64_t;
+            static __device__ __forceinline__ const uint64_t *second_base(const uint64_t *b, unsigned p, unsigned, size_t at, const ReduceGeom &g)
+            {
+                return b + p * g.b_plane + at;
+            }
+            static __device__ __forceinline__ const uint64_t *second_at(const uint64_t *bp, unsigned item, const ReduceGeom &g)
+            {
+                return bp + (size_t)item * (unsigned)g.term; // the words of one item, below 2^32
+            }
+        };
+        struct Products : WordOperand // of operands, as 128-bit integers
         {
             using Acc = U128;
             static constexpr bool kOperands = true;
@@ -118,7 +134,7 @@ namespace sealhip
 
         // r[p][o] = sum_t a[p][o][t].  OPERANDS: the source is a ciphertext (read once: non-temporal) and not the scratch of the slices
         template <bool OPERANDS>
-        struct SumTerm
+        struct SumTerm : WordOperand
         {
             using Acc = uint64_t;
             static constexpr bool kOperands = OPERANDS;
@@ -225,7 +241,8 @@ namespace sealhip
             const ModDesc md = mods[k];
             unsigned t0, t1;
             size_t inner; // component k, coefficient j
-            const uint64_t *ap, *bp;
+            const uint64_t *ap;
+            const typename Term::Second *bp;
             if constexpr (Walk::kMapped)
             {
                 // the slice's part of row o: [off + s * per_slice, min(off + len, off + (s + 1) * per_slice)), empty past the row's end
@@ -235,7 +252,7 @@ namespace sealhip
                 t1 = len - r0 < g.per_slice ? off + len : t0 + g.per_slice;
                 inner = ((size_t)k << g.n_log) + j;
                 ap = a + p * g.a_plane + inner; // item 0: a term adds its item number times the words of an item
-                bp = b + p * g.b_plane + inner;
+                bp = Term::second_base(b, p, k, inner, g);
             }
             else
             {
@@ -244,7 +261,7 @@ namespace sealhip
                 inner = ((size_t)k << g.n_log) + j;
                 const size_t first = o * g.item + t0 * g.term + inner; // output item o, term t0, component k, coefficient j
                 ap = a + p * g.a_plane + first;
-                bp = b + p * g.b_plane + first;
+                bp = Term::second_base(b, p, k, first, g);
             }
             const size_t step = Walk::kMapped ? 0 : g.term; // consecutive items: the pointers walk; a map: they stay at item 0
             uint64_t tot[Term::kOut][2] = {};
@@ -256,7 +273,7 @@ namespace sealhip
                 for (; t < end; t++, ap += step, bp += step)
                 {
                     if constexpr (Walk::kMapped) // g.term: the words of one item, below 2^32
-                        Term::add(acc, ap + (size_t)Walk::ld(walk.first, t) * (unsigned)g.term, bp + (size_t)Walk::ld(walk.second, t) * (unsigned)g.term, g);
+                        Term::add(acc, ap + (size_t)Walk::ld(walk.first, t) * (unsigned)g.term, Term::second_at(bp, Walk::ld(walk.second, t), g), g);
                     else
                         Term::add(acc, ap, bp, g);
                 }
@@ -881,6 +898,79 @@ namespace sealhip
         // N = 8192, where the whole input fits the caches, it loses 4 - 9 % everywhere
         constexpr bool kConvNonTemporal = false;
 
+        // ---- a sparse matrix of scalar weights (batch_reduce_kernels.h: k_dot_scalars_mapped): a Term of the reduce_items skeleton on
+        // the mapped walks.  r[p][o] = sum_t const(w[second[t]]) a[p][first[t]]: the second operand of a term is not an item of
+        // [K][N] words but ONE value per prime (wide: word k of weight second[t], at second[t] * K + k of [count][K] words) or one
+        // signed 32-bit integer for all primes (narrow: at second[t] of [count]), indexed in 64 bits.  One thread = one pair of one
+        // plane: the planes are in the grid as for the sum - the weight is a scalar, so nothing would be gained by keeping it in
+        // registers over the planes as DotPlainTerm keeps its plaintext pair.
+        // Wide: the products' accumulator and interval.  Narrow: the biased weight u = w + 2^31 and the two exact sums of the
+        // scalar-weights product above (mac_narrow; sum a u and sum a), reduced once per kNarrowFlush terms to the same residue.
+        // UNIFORM (the walk's: N >= 128): the row is the wave's, so a term is a chain of scalar loads - the two list entries, then
+        // the weight, through the constant address space: the weights must have been WRITTEN BY SOMETHING EARLIER ON THE STREAM -
+        // and one vector load of the operand pair.  The loop is unrolled kUnroll times, which lets the scheduler issue the list
+        // and weight loads of the next terms ahead of the vector loads of these (profiles/dot_scalars_mapped.txt has what the ISA
+        // shows).  Per lane below that.  The operand loads carry the non-temporal hint like the other mapped terms'.
+        template <bool NARROW, bool UNIFORM>
+        struct DotScalarsTerm
+        {
+            struct NarrowSums
+            {
+                U128 biased, plain; // sum a u, sum a
+            };
+            using Acc = std::conditional_t<NARROW, NarrowSums, U128>;
+            using Second = std::conditional_t<NARROW, uint32_t, uint64_t>;
+            static constexpr bool kOperands = true;
+            // (waves: unrolled four times the wave-uniform kernels take 68 - 70 registers and spill at the 64 of eight waves; the
+            // per-lane ones, unrolled twice, take 70 - 86: profiles/dot_scalars_mapped.txt.  None uses scratch memory at these)
+            static constexpr unsigned kOut = 1, kFlush = NARROW ? kNarrowFlush : kDotFlush, kUnroll = UNIFORM ? 4 : 2, kWaves = UNIFORM ? 6 : 5;
+            static __device__ __forceinline__ const Second *second_base(const uint64_t *weights, unsigned, unsigned k, size_t, const ReduceGeom &)
+            {
+                return reinterpret_cast<const Second *>(weights) + (NARROW ? 0 : k);
+            }
+            static __device__ __forceinline__ const Second *second_at(const Second *wp, unsigned weight, const ReduceGeom &g)
+            {
+                return wp + (NARROW ? (size_t)weight : (size_t)weight * g.K);
+            }
+            static __device__ __forceinline__ uint64_t reduce(const Acc &acc, const ModDesc &md)
+            {
+                if constexpr (NARROW)
+                {
+                    // sum a w = P - 2^31 S exactly, as sign and magnitude, and ONE reduction of the magnitude: P < 2^128 by
+                    // kNarrowFlush's bound and 2^31 S < 2^31 2^10 2^60.  (scalars_flush reduces P and S apart and multiplies by
+                    // 2^31 mod q: three reductions per word where rows are a handful of terms long and this is most of the work -
+                    // at N = 8192 that form was 10 - 20 % behind DotPlainTerm on rows of 4 to 9 terms, profiles/dot_scalars_mapped.txt)
+                    const unsigned __int128 p = (unsigned __int128)acc.biased.hi << 64 | acc.biased.lo;
+                    const unsigned __int128 s = ((unsigned __int128)acc.plain.hi << 64 | acc.plain.lo) << 31;
+                    const bool negative = p < s;
+                    const unsigned __int128 magnitude = negative ? s - p : p - s;
+                    const uint64_t r = barrett128((uint64_t)magnitude, (uint64_t)(magnitude >> 64), md);
+                    return negative && r ? md.q - r : r;
+                }
+                else
+                    return barrett128(acc.lo, acc.hi, md);
+            }
+            static __device__ __forceinline__ void add(Acc (&acc)[kOut][2], const uint64_t *ap, const Second *wp, const ReduceGeom &)
+            {
+                uint64_t a0, a1;
+                ld2<true>(ap, a0, a1);
+                if constexpr (NARROW)
+                {
+                    const uint32_t u = (UNIFORM ? *SHL_UCONST32(wp) : *wp) ^ 0x80000000u;
+                    mac_narrow(acc[0][0].biased, a0, u);
+                    mac_narrow(acc[0][1].biased, a1, u);
+                    add128(acc[0][0].plain, a0, 0);
+                    add128(acc[0][1].plain, a1, 0);
+                }
+                else
+                {
+                    const uint64_t w = UNIFORM ? *SHL_UCONST(wp) : *wp;
+                    mac128(acc[0][0], a0, w);
+                    mac128(acc[0][1], a1, w);
+                }
+            }
+        };
+
         // ---- the built tiles of a product as a list, and the one dispatch on it: f(BuiltTile<TR, TC>{}) for the tile that is
         // TR x TC; false = not built
         template <unsigned TR, unsigned TC>
@@ -1097,6 +1187,26 @@ namespace sealhip
                             [=](const ReduceGeom &g, uint64_t *dst, unsigned ns, bool final) {
                                 return square ? launch_reduce<DotItemsTerm<true>>(mods, x, y, dst, g, ns, final, s, walk)
                                               : launch_reduce<DotItemsTerm<false>>(mods, x, y, dst, g, ns, final, s, walk);
+                            });
+    }
+
+    // the sum's geometry (the planes in the grid) with the scalar term on the map's walk: per wave from N = 128 on, per lane below
+    hipError_t k_dot_scalars_mapped(const ModDesc *mods, const void *weights, bool narrow, const uint64_t *a, size_t a_stride, uint64_t *r,
+                                    size_t r_stride, unsigned size, unsigned n_log, unsigned K, size_t out_items, const ItemWalk &walk,
+                                    unsigned slices, uint64_t *scratch, hipStream_t s)
+    {
+        if (!walk.mapped())
+            return hipErrorInvalidValue; // consecutive items are k_dot_scalars'
+        const uint64_t *w = static_cast<const uint64_t *>(weights);
+        return reduce_items(mods, a_stride, 0, r, r_stride, size, size, n_log, K, out_items, walk, slices, scratch, s,
+                            [=](const ReduceGeom &g, uint64_t *dst, unsigned ns, bool final) {
+                                const MappedWalk<true> wave{ walk.offsets, walk.first, walk.second };
+                                const MappedWalk<false> lane{ walk.offsets, walk.first, walk.second };
+                                if (n_log >= 7)
+                                    return narrow ? launch_walk<DotScalarsTerm<true, true>>(mods, a, w, dst, g, ns, final, s, wave)
+                                                  : launch_walk<DotScalarsTerm<false, true>>(mods, a, w, dst, g, ns, final, s, wave);
+                                return narrow ? launch_walk<DotScalarsTerm<true, false>>(mods, a, w, dst, g, ns, final, s, lane)
+                                              : launch_walk<DotScalarsTerm<false, false>>(mods, a, w, dst, g, ns, final, s, lane);
                             });
     }
 

@@ -344,6 +344,23 @@ extern "C"
                                                  *as<Ciphertext>(destination));
         SHL_CATCH
     }
+    // a sparse matrix of scalar weights over an item map (library extension); flags bit 2: the weights are signed 32-bit integers
+    // and not [K] words each - Evaluator_MatMulScalarsItems' bit; no other bit is defined
+    SHL_FUNC Evaluator_DotScalarsMapped(void *thisptr, void *encrypted, const void *device_weights, uint64_t weight_count, void *item_map,
+                                        uint64_t flags, double scale, void *destination)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(encrypted, SHL_E_POINTER);
+        IfNullRet(item_map, SHL_E_POINTER);
+        IfNullRet(destination, SHL_E_POINTER);
+        SHL_TRY
+        if (flags & ~uint64_t(4))
+            throw std::invalid_argument("unknown flags");
+        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
+        as<Evaluator>(thisptr)->dot_scalars_mapped(*as<Ciphertext>(encrypted), device_weights, (size_t)weight_count, (flags & 4) != 0,
+                                                   *as<ItemMap>(item_map), scale, *as<Ciphertext>(destination));
+        SHL_CATCH
+    }
     // scalar weights (library extensions): [count][K] words per scalar, and the dense matrix of them times a batch
     SHL_FUNC Evaluator_LiftScalars(void *thisptr, uint64_t count, const uint64_t *values_mod_t, uint64_t *parms_id, uint64_t *device_words)
     {

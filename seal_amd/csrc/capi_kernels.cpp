@@ -220,6 +220,34 @@ extern "C"
                                          "dot (mapped)");
                           });
     }
+    // k_dot_scalars_mapped on raw words, with shl_reduce_mapped's conventions: weights [weight_count][K] 64-bit words or, narrow,
+    // [weight_count] signed 32-bit integers, a [size][a_batch][K][N], r [size][rows][K][N]; slices == 0: the library's rule over
+    // size * rows * K * N / 2 threads; r == NULL: the query; scratch [slices][size][rows][K][N] words from the caller when cut
+    SHL_FUNC shl_dot_scalars_mapped(void *context, uint64_t chain_index, const void *weights, uint64_t weight_count, int narrow, const uint64_t *a,
+                                    uint64_t a_batch, uint64_t *r, uint64_t size, void *item_map, uint64_t slices, uint64_t *scratch,
+                                    uint64_t *slices_used, void *stream)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        IfNullRet(item_map, SHL_E_POINTER);
+        const ItemMap *m = as<ItemMap>(item_map);
+        const bool bad = !size || size > 16 || a_batch != m->first_batch() || weight_count != m->second_batch();
+        const size_t rows = m->rows();
+        const ItemWalk walk = m->walk();
+        return raw_reduce(context, chain_index, bad ? "1 <= size <= 16; the batch and the weight count are the map's" : nullptr, size, rows, walk, slices,
+                          slices_used, r, a && weights, scratch, [&](Context *c, const Level *l, size_t words, unsigned cut) {
+                              hip_ok(k_dot_scalars_mapped(c->dev_mods(), weights, narrow != 0, a, a_batch * words, r, rows * words, (unsigned)size,
+                                                          (unsigned)c->log_n(), l->K, rows, walk, cut, scratch, (hipStream_t)stream),
+                                     "dot_scalars (mapped)");
+                          });
+    }
+    SHL_FUNC shl_dot_scalars_mapped_info(uint64_t *flush, uint64_t *narrow_flush)
+    {
+        IfNullRet(flush, SHL_E_POINTER);
+        IfNullRet(narrow_flush, SHL_E_POINTER);
+        *flush = batch_reduce_dot_flush();
+        *narrow_flush = matmul_scalars_narrow_flush();
+        return SHL_S_OK;
+    }
     // k_dot_scalars on raw words: a [size][batch][K][N], scalars [rows][batch][K], r [size][rows][K][N]; slices == 0: the library's
     // rule; r == NULL: the query.  Scratch comes from the pool; the NULL stream, and the call returns when the work is done.
     // row_tile: 0 = the library's (what shl_dot_scalars runs); 2, 4, 8 are built for tools/dot_scalars_rate.py

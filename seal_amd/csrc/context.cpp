@@ -38,7 +38,8 @@ namespace sealhip
             {
                 size_t off = (words.size() + 1) & ~size_t(1); // 16-byte align
                 words.resize(off + (bytes + 7) / 8);
-                std::memcpy(words.data() + off, p, bytes);
+                if (bytes) // (nothing into an empty vector: its data() is null)
+                    std::memcpy(words.data() + off, p, bytes);
                 return off;
             }
             template <typename T>
@@ -543,7 +544,8 @@ namespace sealhip
 
         uint64_t *d = nullptr;
         check_hip(hipMalloc(&d, blk.words.size() * 8 + 16), "hipMalloc level block");
-        check_hip(hipMemcpy(d, blk.words.data(), blk.words.size() * 8, hipMemcpyHostToDevice), "upload level block");
+        if (!blk.words.empty()) // (a one-prime CKKS level has no tables: nothing to copy from an empty vector, whose data() is null)
+            check_hip(hipMemcpy(d, blk.words.data(), blk.words.size() * 8, hipMemcpyHostToDevice), "upload level block");
         lvl.dev_block = d;
         lvl.dev.inv_q_last_mod_q = reinterpret_cast<const ShoupOp *>(d + off.inv_q_last);
         lvl.dev.round_fix = d + off.round_fix;

@@ -1221,6 +1221,28 @@ namespace sealhip
                                               (unsigned)e.size(), n_log, K, rows, batch, slices, scratch, 0, stream_);
                      });
     }
+    // A sparse matrix of scalar weights times the items of a batch (include/sealhip.h: Evaluator_DotScalarsMapped): dot_plain_mapped
+    // with [K] words or one 32-bit integer per plaintext instead of [K][N] - its checks, metadata, settling and cut, the weights'
+    // own extent in the overlap checks - and the scalar term of the same kernel (batch_reduce_kernels.h: k_dot_scalars_mapped)
+    void Evaluator::dot_scalars_mapped(const Ciphertext &e, const void *weights, size_t weight_count, bool narrow, const ItemMap &map,
+                                       double scale, Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        check_plain_device(e, static_cast<const uint64_t *>(weights), weight_count, true, scale, dest, false, 1, narrow);
+        if (weight_count != map.second_batch())
+            throw std::invalid_argument("weight_count does not equal the map's second_batch");
+        size_t rows;
+        const ItemWalk walk = mapped_walk(e, map, rows);
+        const double new_scale = check_dot_plain(e, rows, scale, dest);
+        e.settle(); // the operand's words are read by what follows
+        // one thread per output pair, the planes in the grid
+        reduce_items(e, rows, walk, e.size(), reduce_threads(e, rows, e.size()), true, new_scale, e.correction_factor(), dest, "dot_scalars (mapped)",
+                     [&](unsigned slices, uint64_t *scratch) {
+                         return k_dot_scalars_mapped(context_.dev_mods(), weights, narrow, e.data_, e.plane_words(), dest.data_, dest.plane_words(),
+                                                     (unsigned)e.size(), (unsigned)context_.log_n(), e.level()->K, rows, walk, slices, scratch,
+                                                     stream_);
+                     });
+    }
     // plaintext matrix x ciphertext matrix (include/sealhip.h: Evaluator_MatMulPlainItems): dot_plain_mapped's checks, metadata and
     // settling over rows * cols output items that each add `inner` terms, and a kernel of its own, whose threads hold a tile of outputs
     void Evaluator::matmul_plain_items(const uint64_t *plain, const Ciphertext &e, size_t rows, size_t inner, size_t cols, bool second_transposed,

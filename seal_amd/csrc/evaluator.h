@@ -392,6 +392,9 @@ namespace sealhip
         void dot_plain_mapped(const Ciphertext &encrypted, const uint64_t *plain, size_t plain_count, const ItemMap &map, double scale,
                               Ciphertext &destination) const;
         void dot_items_mapped(const Ciphertext &encrypted1, const Ciphertext &encrypted2, const ItemMap &map, Ciphertext &destination) const;
+        // dot_plain_mapped with scalar weights in either form of matmul_scalars_items (include/sealhip.h: Evaluator_DotScalarsMapped)
+        void dot_scalars_mapped(const Ciphertext &encrypted, const void *weights, size_t weight_count, bool narrow, const ItemMap &map,
+                                double scale, Ciphertext &destination) const;
         // Ciphertext matrix x ciphertext matrix (include/sealhip.h: Evaluator_MatMulItems): item i * cols + j of destination, a batch
         // of rows * cols items, becomes the sum over k < inner of encrypted1_(i * inner + k) (x) encrypted2_(k * cols + j) - item
         // j * inner + k of encrypted2 when second_transposed - word for word dot_items_mapped over the dense pair map; checks,
