@@ -1097,9 +1097,10 @@ SHL_FUNC SealHip_PoolStats(uint64_t *bytes_held, uint64_t *cross_stream_waits);
  *     device reports a memory fault: its handler on the stack tells that case from a C++ one) and then lets the abort proceed
  *     with the default disposition.  A later call only changes the path. */
 SHL_FUNC SealHip_InstallAbortTrace(const char *path);
-/* Environment.  The product library reads twelve variables, each exercised by a test; everything else that earlier
- * rounds could switch at run time (superseded kernels, fork / no-fork of the side streams, ...) only exists in development
- * builds made with -DSEALHIP_AB_SWITCHES (seal_amd/csrc/modarith.h: shl_ab_getenv).
+/* Environment.  The product library reads twelve variables, each exercised by a test.  What tests and tools set beyond
+ * them (thresholds, traces, chunk sizes of the emulated runs) only exists in development builds made with
+ * -DSEALHIP_AB_SWITCHES (seal_amd/csrc/modarith.h: shl_ab_getenv); the A/B switches of settled measurements (superseded
+ * kernels, fork / no-fork of the side streams, ...) are retired: DESIGN section 9.
  *   SEALHIP_NO_FP=1                  every prime on the 64-bit integer back end (no exact double-precision arithmetic for
  *                                    primes below 2^50); same words, slower.  Read when a SEALContext is created.
  *   SEALHIP_KS_EAGER_TAIL=1          key switches complete their mod-down before they return (no deferred tails, below)

@@ -1582,12 +1582,9 @@ namespace sealhip
             // Round 6: batches whose key switch runs un-split at a two-pass size - the product is not formed now (LazyProduct): a
             // relinearize_inplace that follows forms it inside its own kernels, anything else that needs the words forms it first
             const bool defer = may_defer_product(lvl, e1.batch());
-            // (development builds, bound only: SEALHIP_AB_SKIP_TENSOR leaves the product unwritten after two real calls - what fusing the
-            // tensor product into its consumers could save at most, profiles/r06_lazy_product.txt)
-            static std::atomic<unsigned> tensor_calls{ 0 };
             if (defer)
                 defer_product(dest, &e1, &e2, nullptr);
-            else if (!ks_switches().skip_tensor || tensor_calls.fetch_add(1) < 2)
+            else
                 ck(k_ckks_multiply_2x2(context_.dev_mods(), context_.ntt_tables().fpd, nullptr, xw, yw, dest.data(), g, stream_), "ckks_multiply");
             dest.is_ntt_form() = true;
             dest.correction_factor() = 1;
@@ -1782,9 +1779,8 @@ namespace sealhip
         PlaneGeom gq{ n_log, K, (unsigned)B }, gb{ n_log, nBsk, (unsigned)B };
         // Two-pass sizes, 2 x 2: steps (4) and (5) are ONE pair of passes per base - the inverse transform's first pass forms the
         // product from the four operand polynomials as it loads them (NttBatch::prod_x), so the product is never stored in NTT form
-        // and read back: 7 plane crossings instead of 13 for the pair.  SEALHIP_BFV_NO_PRODUCT_SOURCE=1 (development builds): separate
-        static const bool product_source_ok = !shl_ab_getenv("SEALHIP_BFV_NO_PRODUCT_SOURCE");
-        const bool product_source = product_source_ok && s1 == 2 && s2 == 2 && ntt2_supports(context_.log_n());
+        // and read back: 7 plane crossings instead of 13 for the pair (profiles/r04_bfv_product_source.txt).
+        const bool product_source = s1 == 2 && s2 == 2 && ntt2_supports(context_.log_n());
         if (product_source)
         {
             NttBatch iq = plain_batch(d_q.p, (size_t)K * N, K, (unsigned)(3 * B), 0);

@@ -120,7 +120,7 @@ namespace sealhip
     // The key switch's environment switches: read here and nowhere else (defined, with the table of names, in evaluator_keyswitch.cpp).
     struct KsSwitches
     {
-        bool eager_tail, no_fold, class_fork, trace, galois_kernels, skip_tensor; // read once per process: ks_switches()
+        bool eager_tail, no_fold, trace; // read once per process: ks_switches()
         // read at every call (tests flip these inside one process)
         static unsigned split(unsigned chosen);  // SEALHIP_KS_SPLIT, else `chosen`
         static unsigned chunk(unsigned chosen);  // SEALHIP_KS_CHUNK, else `chosen`

@@ -140,15 +140,11 @@ namespace sealhip
     //                                                         src_resident(): the tails' first pass belongs to the transform engine
     //   SEALHIP_KS_NO_FOLD             development  once      tests/test_emu_parity.py (fresh process)
     //   SEALHIP_KS_TRACE               development  once      tests/test_emu_parity.py
-    //   SEALHIP_KS_CLASS_FORK          development  once      - (A/B: the integer class of a chunk on the launcher's side stream)
-    //   SEALHIP_GALOIS_KERNELS         development  once      - (A/B: rotations always through the permutation kernels)
-    //   SEALHIP_AB_SKIP_TENSOR         development  once      - (bound only: the tensor product left unwritten)
     // (development = only in builds made with -DSEALHIP_AB_SWITCHES, modarith.h: shl_ab_getenv)
     const KsSwitches &ks_switches()
     {
-        static const KsSwitches sw{ std::getenv("SEALHIP_KS_EAGER_TAIL") != nullptr,   shl_ab_getenv("SEALHIP_KS_NO_FOLD") != nullptr,
-                                    shl_ab_getenv("SEALHIP_KS_CLASS_FORK") != nullptr, shl_ab_getenv("SEALHIP_KS_TRACE") != nullptr,
-                                    shl_ab_getenv("SEALHIP_GALOIS_KERNELS") != nullptr, shl_ab_getenv("SEALHIP_AB_SKIP_TENSOR") != nullptr };
+        static const KsSwitches sw{ std::getenv("SEALHIP_KS_EAGER_TAIL") != nullptr, shl_ab_getenv("SEALHIP_KS_NO_FOLD") != nullptr,
+                                    shl_ab_getenv("SEALHIP_KS_TRACE") != nullptr };
         return sw;
     }
     static unsigned env_unsigned(const char *name, unsigned fallback)
@@ -229,7 +225,7 @@ namespace sealhip
         r.plan = ks_plan((unsigned)batch, (size_t)(K + 1) * K * context_.n(), (size_t)(K + 1) * (context_.n() >> 12), r.split == 1, !capturing_);
         return r;
     }
-    bool KsRoute::reads_through_map() const { return takes_product() && !ks_switches().galois_kernels; }
+    bool KsRoute::reads_through_map() const { return takes_product(); }
 
     // ---- relinearize (evaluator.cpp:1144-1199)
     void Evaluator::relinearize_inplace(Ciphertext &e, const KSwitchKeys &relin_keys) const
@@ -561,9 +557,9 @@ namespace sealhip
                         KsFusedArgs kc = fused_args(b0, nb, l);
                         // which pass-1 kernel: decided for the whole batch (ntt2_kernels.hip: launch_ks decides from the grid it is given)
                         kc.order1 = (size_t)B * (j1 - j0) * (N >> 12) >= 4096 ? 1 : 0;
-                        // (the two arithmetic classes of a chunk one after the other on its lane; SEALHIP_KS_CLASS_FORK=1 in development builds
-                        // forks the integer class to the launcher's side stream as the unchunked path does: profiles/r05_ks_chunked.txt)
-                        kc.no_class_fork = lanes > 1 && !ks_switches().class_fork;
+                        // (the two arithmetic classes of a chunk one after the other on its lane; forking the integer class to the
+                        // launcher's side stream as the unchunked path does was measured and not kept: profiles/r05_ks_chunked.txt)
+                        kc.no_class_fork = lanes > 1;
                         ck(ks_fused(tb, kc, st), "ks fused (chunk)");
                     }
                 }

@@ -8,75 +8,47 @@
 #include <cstdlib>
 #include <type_traits>
 
-// minimum waves per SIMD requested for the double-precision-only forward kernels (register budget
-// 512 / waves): 4 keeps them at 128 VGPRs with a handful of spilled words
-#ifndef SEALHIP_FP_WAVES_P1
-#define SEALHIP_FP_WAVES_P1 4
-#endif
-#ifndef SEALHIP_FP_WAVES_P2
-#define SEALHIP_FP_WAVES_P2 4
-#endif
-
 namespace sealhip
 {
     namespace
     {
         constexpr int kThreads = 256;
+        // minimum waves per SIMD requested for the double-precision-only forward kernels (register budget
+        // 512 / waves): 4 keeps them at 128 VGPRs with a handful of spilled words
+        constexpr int kFpWavesP1 = 4, kFpWavesP2 = 4;
         constexpr unsigned kMaxKeyComps = 64; // SEAL_COEFF_MOD_COUNT_MAX
         // Where word (e, tid) of a 4096-word row tile of the forward passes' intermediate sits (e = column block, tid = (row u = tid >> 4,
-        // column-in-block v = tid & 15)).  Tile order (default): e*256 + tid - the 16 rows of a workgroup interleaved in 2 KiB blocks, a
-        // workgroup of pass 2 reads one 32 KiB run.  -DSEALHIP_MID_WAVE_MAJOR (measured in round 4, profiles/r04_ntt_wave_major.txt): the
-        // four rows of a WAVE contiguous - wave*1024 + e*64 + lane - so that every wave of pass 2 reads its own 8 KiB run.
-        // Streaming hints (round 4): the intermediate of a two-pass transform is written once and read once, gigabytes later - it has no
-        // business displacing what the L2 holds for reuse (key tiles, digit tiles, twiddles).  SEALHIP_KS_NT is a bit mask of where the
-        // non-temporal form is used: 1 pass-1 stores, 2 ks2's double-precision loads, 4 the other forward pass-2 loads, 8 the inverse
-        // passes' intermediate (store and load), 16 single-use operands and results of the passes (plain sources, tail operands, final stores).  Measured in profiles/r04_nontemporal.txt; the default below is what won.
-#ifndef SEALHIP_KS_NT
-#define SEALHIP_KS_NT 31 // headline step 8.82 -> 9.18 k ct/s same-box (+4.0 %); 15: +2.5 %; with the tensor product's loads (32): +2.9 %
-#endif
-        // Wave priorities (round 5 experiment, profiles/r05_ldsdma_setprio.txt): a CU holds two to four workgroups of these kernels in
-        // different phases.  SEALHIP_PRIO = 0 none (default); 1: s_setprio 1 while a wave does arithmetic, 0 while it issues its
-        // loads; 2: the other way round (memory instructions first).
-#ifndef SEALHIP_PRIO
-#define SEALHIP_PRIO 0
-#endif
-        template <int WHEN> // 1 = entering the arithmetic, 2 = entering the load issue
-        __device__ __forceinline__ void prio_phase()
-        {
-#if defined(__HIP_DEVICE_COMPILE__)
-            if constexpr (SEALHIP_PRIO != 0)
-                __builtin_amdgcn_s_setprio(SEALHIP_PRIO == WHEN ? 1 : 0);
-#endif
-        }
-        template <int BIT>
+        // column-in-block v = tid & 15)).  Tile order: e*256 + tid - the 16 rows of a workgroup interleaved in 2 KiB blocks, a
+        // workgroup of pass 2 reads one 32 KiB run (a wave-major order was measured and left: profiles/r04_ntt_wave_major.txt).
+        // Streaming accesses (round 4, profiles/r04_nontemporal.txt: headline step 8.82 -> 9.18 k ct/s same-box, +4.0 %): the
+        // intermediate of a two-pass transform is written once and read once, gigabytes later - it has no business displacing what
+        // the L2 holds for reuse (key tiles, digit tiles, twiddles).  mid_ld / mid_st / mid_ld2 / mid_st2 are the non-temporal forms,
+        // used for pass 1's stores and pass 2's loads of the intermediate (ks2's double-precision loads: view_load64_nt), the
+        // inverse passes' intermediate in both directions, and the single-use operands and results of the passes (plain sources,
+        // tail operands, final stores).  What is read again stays plain: a mapped source shared by the components, the digits, the
+        // key words, the twiddles.
         __device__ __forceinline__ uint64_t mid_ld(const uint64_t *p)
         {
 #if defined(__HIP_DEVICE_COMPILE__)
-            if constexpr ((SEALHIP_KS_NT & BIT) != 0)
-                return __builtin_nontemporal_load(p);
-#endif
+            return __builtin_nontemporal_load(p);
+#else
             return *p;
+#endif
         }
-        template <int BIT>
         __device__ __forceinline__ void mid_st(uint64_t *p, uint64_t v)
         {
 #if defined(__HIP_DEVICE_COMPILE__)
-            if constexpr ((SEALHIP_KS_NT & BIT) != 0)
-            {
-                __builtin_nontemporal_store(v, p);
-                return;
-            }
-#endif
+            __builtin_nontemporal_store(v, p);
+#else
             *p = v;
+#endif
         }
         // two adjacent words (16-byte aligned) with one 16-byte access
-        template <int BIT>
         __device__ __forceinline__ void mid_ld2(const uint64_t *p, uint64_t &a, uint64_t &b)
         {
 #if defined(__HIP_DEVICE_COMPILE__)
             typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-            const u64x2 *q = reinterpret_cast<const u64x2 *>(p);
-            const u64x2 v = (SEALHIP_KS_NT & BIT) != 0 ? __builtin_nontemporal_load(q) : *q;
+            const u64x2 v = __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>(p));
             a = v.x;
             b = v.y;
 #else
@@ -84,29 +56,19 @@ namespace sealhip
             b = p[1];
 #endif
         }
-        template <int BIT>
         __device__ __forceinline__ void mid_st2(uint64_t *p, uint64_t a, uint64_t b)
         {
 #if defined(__HIP_DEVICE_COMPILE__)
             typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-            u64x2 *q = reinterpret_cast<u64x2 *>(p);
             const u64x2 v = { a, b };
-            if constexpr ((SEALHIP_KS_NT & BIT) != 0)
-                __builtin_nontemporal_store(v, q);
-            else
-                *q = v;
+            __builtin_nontemporal_store(v, reinterpret_cast<u64x2 *>(p));
 #else
             p[0] = a;
             p[1] = b;
 #endif
         }
-#ifdef SEALHIP_MID_WAVE_MAJOR
-        __device__ __forceinline__ unsigned mid_lane(unsigned tid) { return (tid >> 6) * 1024 + (tid & 63); }
-        constexpr unsigned kMidRow = 64;
-#else
         __device__ __forceinline__ unsigned mid_lane(unsigned tid) { return tid; }
         constexpr unsigned kMidRow = 256;
-#endif
         template <int D1>
         struct Geo
         {
@@ -123,7 +85,7 @@ namespace sealhip
         constexpr int kRowWords = 16 * 18;
         constexpr size_t kLds2Words = 16 * kRowWords;
 
-        // ---- Packed intermediate of the plain double-precision forward transform at N = 2^16 (round 5, SEALHIP_MID_PACK).
+        // ---- Packed intermediate of the plain double-precision forward transform at N = 2^16 (round 5, profiles/r05_mid_pack.txt).
         // Between the passes a residue of a prime below 2^50 is an integer with |x| <= q/2 < 2^49 held in a double (1.80 q < 2^51 with
         // the lean fix() placement): 64 bits for at most 52.
         // x + 1.5 * 2^52 has x + 2^51 in its 52 mantissa bits (offset binary; one v_add_f64 each way), and the 16 values a pass-1
@@ -135,11 +97,8 @@ namespace sealhip
         // (e, v) takes pack (cg = e, v)), decodes all sixteen rows and hands them to their owners (u, v) through LDS.
         // 13/16 of the intermediate's bytes in both directions; the values are the same doubles, so the results are the same words.
         constexpr unsigned kPackWords = 13, kPackBlock = kPackWords * 16; // words per pack / per 16 x 16 block
-        // SEALHIP_PACK_VEC16 (round 6): the twelve words 0..11 of a pack travel as six 16-byte pairs - pair j of column v at j*32 + v*2,
-        // word 12 at 192 + v - so that either pass issues 7 instead of 13 memory instructions per thread and the runs are 256 bytes
-#ifndef SEALHIP_PACK_VEC16
-#define SEALHIP_PACK_VEC16 1
-#endif
+        // Round 6: the twelve words 0..11 of a pack travel as six 16-byte pairs - pair j of column v at j*32 + v*2, word 12 at
+        // 192 + v - so that either pass issues 7 instead of 13 memory instructions per thread and the runs are 256 bytes
         constexpr double kPackMagic = 6755399441055744.0;                  // 2^52 + 2^51
         constexpr unsigned kPackLdsRow = 272;                              // words between the rows u of the hand-over buffer
         __device__ __forceinline__ void pack52(const double (&x)[16], uint64_t (&w)[13])
@@ -202,48 +161,24 @@ namespace sealhip
             else
                 body(std::integral_constant<int, 2>());
         }
-        // Which (tile, component, outer item) a workgroup of the two-pass kernels works on.  The hardware hands consecutive
-        // workgroups to consecutive XCDs (workgroup i -> XCD i mod 8).  With the tile index fastest, the eight XCDs stream eight
-        // NEIGHBOURING 32 KiB tiles at the same time - eight streams 32 KiB apart - and that is the one arrangement the memory
-        // system dislikes: a plain copy whose XCDs take runs of 8 / 16 / 32 KiB moves 6.0 / 5.9 / 5.5 TB/s where 4 KiB
-        // interleave, 256 KiB runs or one eighth of the buffer per XCD all move 6.3 (round 3,
-        // tools/microbench/copy_locality.hip, profiles/r03_microbench_copy_locality.txt).  So the XCDs are given different
-        // TRANSFORMS (N * 8 bytes apart) and each walks the tiles of its own: workgroup L -> XCD x = L mod 8, r = L / 8,
-        // tile = r mod TILES, slot = (r / TILES) * 8 + x, (component, outer) = slot; the last, incomplete group of 8 * TILES keeps
-        // the plain order.  MEASURED AND NOT KEPT (default 0): the 2^16 NTT leg 2.51 -> 2.49 TB/s, the headline step -0.6 %, BFV
-        // configs[3] -1 % (gpurun_out r3i, same box, alternating): the passes' workgroups are persistent loops that drift apart,
-        // so their concurrent streams are not the lock-step runs of the copy; what the copy shows is that the ceiling of a
-        // tile-shaped pass is ~5.4 TB/s, not the 6.3 of a 4 KiB-per-workgroup stream.
-#ifndef SEALHIP_XCD_SPREAD
-#define SEALHIP_XCD_SPREAD 0
-#endif
-        struct Blk
+        // The arithmetic a workgroup runs for component `prime` of a launch of class CLS (the kernels' template parameter: 0 = every
+        // component of the launch uses the integer back end, 1 = the double-precision one, anything else = decided per workgroup, which
+        // costs the registers of both bodies): body(std::bool_constant<FP>, std::integral_constant<int, ICLS>), one wave-uniform
+        // branch per kernel.  Mixed launches keep the guarded butterflies (class 2) for their integer components.
+        template <int CLS, class Body>
+        __device__ __forceinline__ void with_class(const NttTables &t, unsigned prime, Body body)
         {
-            unsigned tile, y, z;
-        };
-        __device__ __forceinline__ Blk spread_blocks()
-        {
-#if SEALHIP_XCD_SPREAD
-            const unsigned tiles = gridDim.x, slots = gridDim.y * gridDim.z;
-            const unsigned L = blockIdx.x + tiles * (blockIdx.y + gridDim.y * blockIdx.z);
-            const unsigned group = 8 * tiles, full = (slots / 8) * group;
-            unsigned tile, slot;
-            if (L < full)
-            {
-                const unsigned x = L & 7, r = L >> 3;
-                tile = r % tiles;
-                slot = (r / tiles) * 8 + x;
-            }
+            if constexpr (CLS == 1)
+                body(std::true_type(), std::integral_constant<int, 0>());
+            else if constexpr (CLS == 0)
+                with_int_class(t, prime, [&](auto ic) { body(std::false_type(), ic); });
+            else if (t.fpd[prime].qi)
+                body(std::true_type(), std::integral_constant<int, 0>());
             else
-            {
-                tile = L % tiles;
-                slot = L / tiles;
-            }
-            return Blk{ tile, slot % gridDim.y, slot / gridDim.y };
-#else
-            return Blk{ blockIdx.x, blockIdx.y, blockIdx.z };
-#endif
+                body(std::false_type(), std::integral_constant<int, 2>());
         }
+        // (The two-pass kernels take (tile, component, outer item) from blockIdx as it comes; handing the eight XCDs different
+        // transforms instead of neighbouring tiles was measured and not kept: DESIGN 3.2.)
 
         template <bool FP>
         __device__ __forceinline__ const typename Field<FP>::tw_t *tw_table(const NttTables &t, bool inverse, unsigned prime)
@@ -594,60 +529,24 @@ namespace sealhip
                 uint64_t w[13];
                 pack52(x, w);
                 uint64_t *o = mid_tr + (size_t)(hi * 16 + cg) * kPackBlock + c;
-#ifdef SEALHIP_P1_NOSTORE
-                uint64_t sink = 0; // measurement build: one word per thread keeps the arithmetic alive
-#pragma unroll
-                for (int k = 0; k < 13; k++)
-                    sink ^= w[k];
-                mid_st<1>(o, sink);
-#else
-#if SEALHIP_PACK_VEC16
                 uint64_t *o2 = o + c; // column c of the block: pair j at j*32 + c*2
 #pragma unroll
                 for (int j = 0; j < 6; j++)
-                    mid_st2<1>(o2 + j * 32, w[2 * j], w[2 * j + 1]);
-                mid_st<1>(o + 192, w[12]);
-#else
-#pragma unroll
-                for (int k = 0; k < 13; k++)
-                    mid_st<1>(o + k * 16, w[k]);
-#endif
-#endif
+                    mid_st2(o2 + j * 32, w[2 * j], w[2 * j + 1]);
+                mid_st(o + 192, w[12]);
                 return;
             }
             // tile order: ((hg*16 + col_hi)*16 + h_lo)*16 + col_lo, hg = ra, h_lo = rb, col = cg*C + c
             const unsigned col = cg * G::C + c;
-#ifdef SEALHIP_MID_WAVE_MAJOR
-            if constexpr (BS == 256)
-            {
-                // row hi*16 + rb of column col: wave rb >> 2 of tile hi, row-in-wave rb & 3, column block col >> 4
-                uint64_t *w = mid_tr + (size_t)hi * 4096 + (col >> 4) * 64 + (col & 15);
-#pragma unroll
-                for (int rb = 0; rb < 16; rb++)
-                    w[(rb >> 2) * 1024 + (rb & 3) * 16] = F::raw(x[rb]);
-                return;
-            }
-#endif
             uint64_t *o = mid_tr + (size_t)(hi * 16 + (col >> 4)) * BS + (col & 15);
-            if constexpr (BS == 256 && (SEALHIP_KS_NT & 1) != 0)
+#pragma unroll
+            for (int rb = 0; rb < 16; rb++)
             {
-#pragma unroll
-                for (int rb = 0; rb < 16; rb++)
-                    mid_st<1>(o + rb * 16, F::raw(x[rb]));
-                return;
+                if constexpr (BS == 256) // the intermediate in HBM is streamed (mid_st)
+                    mid_st(o + rb * 16, F::raw(x[rb]));
+                else
+                    o[rb * 16] = F::raw(x[rb]);
             }
-#ifdef SEALHIP_KS_NOMEM
-            // measurement build (tools/ab.sh nomem): the tile is not stored - one word per thread keeps the arithmetic alive
-            uint64_t sink = 0;
-#pragma unroll
-            for (int rb = 0; rb < 16; rb++)
-                sink ^= F::raw(x[rb]);
-            o[0] = sink;
-#else
-#pragma unroll
-            for (int rb = 0; rb < 16; rb++)
-                o[rb * 16] = F::raw(x[rb]);
-#endif
         }
 
         // ---------------------------------------------------------------------------------------
@@ -669,19 +568,9 @@ namespace sealhip
             }
         }
 
-        // twiddles of the two phases of pass 2 for tile hg: they depend on (prime, hg, thread) only, so a
-        // workgroup that transforms the same tile of many polynomials can load them once
-        template <bool FP, int D1>
-        __device__ __forceinline__ void p2_load_tw(TwRegs<FP> &ta, TwRegs<FP> &tb, const typename Field<FP>::tw_t *tab, unsigned hg, unsigned tid)
-        {
-            const unsigned v = tid & 15, u = tid >> 4;
-            const unsigned h = hg * 16 + u;
-            load_tw<FP, 4>(ta, tab, [&](int t) { return (1u << (D1 + t)) + (h << t); });
-            load_tw<FP, 4>(tb, tab, [&](int t) { return (1u << (D1 + 4 + t)) + ((h * 16 + v) << t); });
-        }
-
         // TWA_LDS: only phase A's row-shared twiddles come from LDS (twa), phase B's per-thread ones from global memory
-        // (LOWREG) or from the caller's registers (HOIST && TWA_LDS: pre_b only)
+        // (LOWREG) or from the caller's registers (HOIST, always together with TWA_LDS: pre_b - they depend on (prime, hg, thread)
+        // only, so a workgroup that transforms the same tile of many polynomials loads them once)
         // LEAN (see p1_tile): the input arrives with |x| <= 1.80 q; no fix() after phase A (-> 6.21 q), one after the first stage
         // of phase B (global stage 13: 7.88 q -> q/2), none at the end: the values leave with |x| <= 2.64 q, which the key
         // products take (|x k mod q| <= q (1/2 + 3/16 * 2.64) = 0.995 q with balanced key words; seven terms on top of a fixed
@@ -696,17 +585,14 @@ namespace sealhip
         __device__ __forceinline__ void p2_tile(
             typename Field<FP>::elem (&x)[16], const typename Field<FP>::Mod &m, const typename Field<FP>::tw_t *tab,
             const typename Field<FP>::tw_t *twa, const typename Field<FP>::tw_t *twb, uint64_t *lds_wave, unsigned hg, unsigned tid,
-            const TwRegs<FP> *pre_a = nullptr, const TwRegs<FP> *pre_b = nullptr)
+            const TwRegs<FP> *pre_b = nullptr)
         {
             typedef Field<FP> F;
+            static_assert(!HOIST || TWA_LDS, "resident phase-B twiddles come with phase A's in LDS");
             const unsigned v = tid & 15, u = tid >> 4;
             const unsigned h = hg * 16 + u;
             const unsigned ul = u & 3; // row inside this wave's buffer
-            if constexpr (HOIST && !TWA_LDS)
-            {
-                phase_fwd_end<FP, 4, !LEAN, ICLS, BIN>(x, m, [&](int t, int g) { return pre_a->get((1 << t) + g); });
-            }
-            else if constexpr ((LOWREG || HOIST) && (TW_LDS || TWA_LDS))
+            if constexpr ((LOWREG || HOIST) && (TW_LDS || TWA_LDS))
             {
                 phase_fwd_end<FP, 4, !LEAN, ICLS, BIN>(x, m, [&](int t, int g) { return twa[(16u << t) - 16u + (u << t) + g]; });
             }
@@ -795,7 +681,7 @@ namespace sealhip
             for (int k = 0; k < 16; k++)
             {
                 const unsigned row = k >> 2, col = (k & 3) * 64 + lane;
-                mid_st<16>(rows + row * 256 + col, lds_wave[row * kRowWords + col + 2 * (col >> 4)]);
+                mid_st(rows + row * 256 + col, lds_wave[row * kRowWords + col + 2 * (col >> 4)]);
             }
             __builtin_amdgcn_wave_barrier(); // a looping caller's next tile rewrites the buffer (program order in hardware; the emulator's lanes need it said)
         }
@@ -844,7 +730,7 @@ namespace sealhip
             for (int k = 0; k < 16; k++)
             {
                 const unsigned row = k >> 2, col = (k & 3) * 64 + lane;
-                lds_wave[row * kRowWords + col + 2 * (col >> 4)] = mid_ld<16>(rows + row * 256 + col);
+                lds_wave[row * kRowWords + col + 2 * (col >> 4)] = mid_ld(rows + row * 256 + col);
             }
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -874,7 +760,7 @@ namespace sealhip
             for (int k = 0; k < 16; k++)
             {
                 const unsigned row = k >> 2, col = (k & 3) * 64 + lane;
-                lds_wave[row * kRowWords + col + 2 * (col >> 4)] = mid_ld<16>(poly + galois_src_index(j0 + row * 256 + col, elt, n_log));
+                lds_wave[row * kRowWords + col + 2 * (col >> 4)] = mid_ld(poly + galois_src_index(j0 + row * 256 + col, elt, n_log));
             }
             __builtin_amdgcn_wave_barrier();
 #pragma unroll

@@ -77,11 +77,7 @@ namespace sealhip
                 {
                     const unsigned ra = e >> (4 - G::rA), rbh = e & ((1 << (4 - G::rA)) - 1);
                     const unsigned R = ra * 16 + (rbh << G::rA) + rbl;
-#ifdef SEALHIP_P1_NOLOAD
-                    nxt[e] = (uint64_t)(tid * 16 + e + z * 4099u + R) & 0xFFFFFFFFFFFFull; // measurement build: no loads (any word below 2^48 does)
-#else
-                    nxt[e] = a.src ? in[(size_t)R * 256] : mid_ld<16>(in + (size_t)R * 256); // (a mapped source is shared by the components)
-#endif
+                    nxt[e] = a.src ? in[(size_t)R * 256] : mid_ld(in + (size_t)R * 256); // (a mapped source is shared by the components)
                 }
             };
             const unsigned ostride = gridDim.z;
@@ -92,54 +88,36 @@ namespace sealhip
 #pragma unroll
                 for (int e = 0; e < 16; e++)
                     x[e] = map_src<FP>(nxt[e], sm, m);
-                prio_phase<2>();
                 if (outer + ostride < a.nouter)
                     fetch(outer + ostride);
-                prio_phase<1>();
                 uint64_t *mid_tr = a.mid + (((size_t)outer * a.ncomp + comp) << G::n);
-                // SEALHIP_P1_PLAIN_LEAN=1 (measured, not kept: 2925 vs 2941 GB/s on the leg, profiles/r05_p1_bound.txt): double precision,
-                // eight stages - every source mapping hands over |x| <= q (+ 2^32) <= kLeanEntry q, so ONE fix() after stage 6 would do
-                // (1.0 -> 1.69 -> 2.50 -> 3.47 -> 4.63 -> 5.99 -> 7.61 < 8, fix, -> 1.09 -> 1.80; the intermediate then leaves at 1.80 q,
-                // 52 bits when packed, which pass 2's first phase takes): 48 of the ~700 vector instructions per wave and tile less, and
-                // no time - what the pass waits for without memory traffic is its LDS exchange and barriers, not its issue slots
-#ifndef SEALHIP_P1_PLAIN_LEAN
-#define SEALHIP_P1_PLAIN_LEAN 0
-#endif
-                p1_tile<FP, D1, 256, SEALHIP_P1_PLAIN_LEAN && FP && G::rA == 4, ICLS, PACK>(x, m, tab, tw, lds, mid_tr, cg, tid);
+                // (the lean fix() placement of the key-switch kernels was measured here and not kept: 2925 vs 2941 GB/s on the leg,
+                // profiles/r05_p1_bound.txt - what the pass waits for is its LDS exchange and barriers, not its issue slots)
+                p1_tile<FP, D1, 256, false, ICLS, PACK>(x, m, tab, tw, lds, mid_tr, cg, tid);
             }
         }
 
-        // CLS: 0 = every component of the launch uses the integer back end, 1 = the double-precision one,
-        // 2 = decided per workgroup (costs the registers of both bodies)
+        // the packing pass needs ~150 VGPRs; at 128 it spills 64 bytes per lane and runs 6 % slower than the plain pass
+        constexpr int kPackWavesP1 = 3;
+        // CLS: as with_class(); 5 = as 1, storing the packed intermediate (kPackWords; N = 2^16 only)
         template <int D1, int CLS>
-#ifndef SEALHIP_PACK_WAVES_P1
-#define SEALHIP_PACK_WAVES_P1 3 // the packing pass needs ~150 VGPRs; at 128 it spills 64 bytes per lane and runs 6 % slower than the plain pass
-#endif
-        __global__ void __launch_bounds__(kThreads, CLS == 5 ? SEALHIP_PACK_WAVES_P1 : CLS == 1 ? SEALHIP_FP_WAVES_P1 : 2) ntt2_fwd_p1(FwdArgs a)
+        __global__ void __launch_bounds__(kThreads, CLS == 5 ? kPackWavesP1 : CLS == 1 ? kFpWavesP1 : 2) ntt2_fwd_p1(FwdArgs a)
         {
             HIP_DYNAMIC_SHARED(uint64_t, lds)
-            const Blk blk = spread_blocks();
-            const unsigned comp = blk.y + a.comp0, outer = blk.z;
+            const unsigned comp = blockIdx.y + a.comp0, outer = blockIdx.z, tile = blockIdx.x;
             const unsigned prime = SHL_UNIFORM(a.comp_prime ? a.comp_prime[comp] : a.prime_first + comp);
-            if constexpr (CLS == 5) // as 1, storing the packed intermediate (kPackWords; N = 2^16 only)
-                fwd_p1_body<true, D1, 0, D1 == 8>(a, prime, comp, outer, lds, blk.tile);
-            else if constexpr (CLS == 1)
-                fwd_p1_body<true, D1>(a, prime, comp, outer, lds, blk.tile);
-            else if constexpr (CLS == 0)
-                with_int_class(a.t, prime, [&](auto ic) { fwd_p1_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds, blk.tile); });
-            else if (a.t.fpd[prime].qi)
-                fwd_p1_body<true, D1>(a, prime, comp, outer, lds, blk.tile);
+            if constexpr (CLS == 5)
+                fwd_p1_body<true, D1, 0, D1 == 8>(a, prime, comp, outer, lds, tile);
             else
-                fwd_p1_body<false, D1, 2>(a, prime, comp, outer, lds, blk.tile); // mixed launches keep the guarded butterflies
+                with_class<CLS>(a.t, prime, [&](auto fp, auto ic) { fwd_p1_body<decltype(fp)::value, D1, decltype(ic)::value>(a, prime, comp, outer, lds, tile); });
         }
 
-        // HOIST (plain transforms of the double-precision back end, no epilogue): the tile's 30 twiddles stay in
-        // registers for every outer item of the workgroup's loop - a tile's twiddles are as many bytes as its
-        // coefficients.  Costs ~60 VGPRs: measured +4 % on the batched NTT, -3 % on the epilogue variants, hence
-        // only here.
-        // HOIST_LDS (CLS 4): the row-shared phase-A twiddles are staged once in LDS and only the 15 per-thread phase-B twiddles
-        // stay in registers: the same "no twiddle is re-read per transform" at 128 VGPRs (four waves per SIMD) instead of 214 (two)
-        template <bool FP, int D1, bool HOIST = false, bool HOIST_LDS = false, int ICLS = 0, bool PACK = false>
+        // HOIST_LDS (plain transforms of the double-precision back end, no epilogue; CLS 4): the row-shared phase-A twiddles are
+        // staged once in LDS and the 15 per-thread phase-B twiddles stay in registers for every outer item of the workgroup's
+        // loop - a tile's twiddles are as many bytes as its coefficients: no twiddle is re-read per transform, at 128 VGPRs (four
+        // waves per SIMD; all thirty in registers took 214, two waves).  Measured +4 % on the batched NTT, -3 % on the epilogue
+        // variants, hence only here.
+        template <bool FP, int D1, bool HOIST_LDS = false, int ICLS = 0, bool PACK = false>
         __device__ __forceinline__ void fwd_p2_body(const FwdArgs &a, unsigned prime, unsigned comp, unsigned outer, uint64_t *lds, unsigned tile)
         {
             typedef Field<FP> F;
@@ -154,7 +132,7 @@ namespace sealhip
                 const uint64_t *mp = mid0 + (((size_t)z * a.ncomp) << G::n);
 #pragma unroll
                 for (int e = 0; e < 16; e++)
-                    nxt[e] = mid_ld<4>(mp + e * kMidRow);
+                    nxt[e] = mid_ld(mp + e * kMidRow);
             };
             // packed intermediate (kPackWords above): thread (e = tid >> 4, v = tid & 15) loads pack (cg = e, v) of this row tile
             constexpr bool packed = PACK;
@@ -162,20 +140,14 @@ namespace sealhip
             [[maybe_unused]] const uint64_t *pk0 = a.mid + ((size_t)comp << G::n) + (size_t)(hg * 16 + (tid >> 4)) * kPackBlock + (tid & 15);
             [[maybe_unused]] auto fetch_packed = [&](unsigned z) {
                 const uint64_t *mp = pk0 + (((size_t)z * a.ncomp) << G::n);
-#if SEALHIP_PACK_VEC16
                 const uint64_t *m2 = mp + (tid & 15); // pair j of this thread's column at j*32 + v*2 (mp already holds + v)
 #pragma unroll
                 for (int j = 0; j < 6; j++)
-                    mid_ld2<4>(m2 + j * 32, nxt[2 * j], nxt[2 * j + 1]);
-                nxt[12] = mid_ld<4>(mp + 192);
-#else
-#pragma unroll
-                for (int k = 0; k < 13; k++)
-                    nxt[k] = mid_ld<4>(mp + k * 16);
-#endif
+                    mid_ld2(m2 + j * 32, nxt[2 * j], nxt[2 * j + 1]);
+                nxt[12] = mid_ld(mp + 192);
             };
             const unsigned ostride = gridDim.z;
-            TwRegs<FP> pre_a, pre_b;
+            TwRegs<FP> pre_b;
             const typename F::tw_t *twa = nullptr;
             if constexpr (HOIST_LDS)
             {
@@ -187,8 +159,6 @@ namespace sealhip
                 load_tw<FP, 4>(pre_b, tab, [&](int t) { return (1u << (D1 + 4 + t)) + ((h * 16 + v) << t); });
                 __syncthreads();
             }
-            else if constexpr (HOIST)
-                p2_load_tw<FP, D1>(pre_a, pre_b, tab, hg, tid);
             if constexpr (packed)
                 fetch_packed(outer);
             else
@@ -223,21 +193,17 @@ namespace sealhip
 #pragma unroll
             for (int e = 0; e < 16; e++)
                 x[e] = F::unraw(nxt[e]);
-            prio_phase<2>();
             if (outer + ostride < a.nouter)
                 fetch(outer + ostride);
-            prio_phase<1>();
             }
             if constexpr (HOIST_LDS)
-                p2_tile<FP, D1, false, false, true, true>(x, m, tab, twa, nullptr, lds_wave, hg, tid, &pre_a, &pre_b);
-            else if constexpr (HOIST)
-                p2_tile<FP, D1, false, false, true>(x, m, tab, nullptr, nullptr, lds_wave, hg, tid, &pre_a, &pre_b);
+                p2_tile<FP, D1, false, false, true, true>(x, m, tab, twa, nullptr, lds_wave, hg, tid, &pre_b);
             else
                 p2_tile<FP, D1, false, false, false, false, false, ICLS, kP1Out<ICLS, D1>>(x, m, tab, nullptr, nullptr, lds_wave, hg, tid);
             constexpr int BOUT = kP2Out<ICLS, D1>; // integer back end: bound of the results
             uint64_t val[16];
             const size_t row0 = ((size_t)comp << G::n) + ((size_t)(hg * 16 + (tid >> 6) * 4) << 8);
-            if ((HOIST || HOIST_LDS) || a.epi == 0) // the hoisted variants are launched for plain transforms only
+            if (HOIST_LDS || a.epi == 0) // the hoisted variant is launched for plain transforms only
             {
 #pragma unroll
                 for (int e = 0; e < 16; e++)
@@ -263,7 +229,7 @@ namespace sealhip
                     // A = c + S P^-1 already (KsFusedArgs::fold_c0): the ciphertext words are written, not updated
                     uint64_t *O = ((outer & 1) ? a.epi_out1 : a.epi_out0) + (size_t)(outer >> 1) * a.epi_out_stride + row0;
                     emit_rows(val, lds_wave, tid, [&](unsigned off, uint64_t tv) {
-                        O[off] = sub_mod(mid_ld<16>(A + off), mul_shoup(tv, mul.w, mul.wq, q), q);
+                        O[off] = sub_mod(mid_ld(A + off), mul_shoup(tv, mul.w, mul.wq, q), q);
                     });
                 }
                 else
@@ -278,26 +244,17 @@ namespace sealhip
         }
 
         template <int D1, int CLS>
-        __global__ void __launch_bounds__(kThreads, (CLS == 1 || CLS == 4 || CLS == 5) ? SEALHIP_FP_WAVES_P2 : 2) ntt2_fwd_p2(FwdArgs a)
+        __global__ void __launch_bounds__(kThreads, (CLS == 1 || CLS == 4 || CLS == 5) ? kFpWavesP2 : 2) ntt2_fwd_p2(FwdArgs a)
         {
             HIP_DYNAMIC_SHARED(uint64_t, lds)
-            const Blk blk = spread_blocks();
-            const unsigned comp = blk.y + a.comp0, outer = blk.z;
+            const unsigned comp = blockIdx.y + a.comp0, outer = blockIdx.z, tile = blockIdx.x;
             const unsigned prime = SHL_UNIFORM(a.comp_prime ? a.comp_prime[comp] : a.prime_first + comp);
             if constexpr (CLS == 5) // as 4, reading the packed intermediate (N = 2^16 only)
-                fwd_p2_body<true, D1, false, true, 0, D1 == 8>(a, prime, comp, outer, lds, blk.tile);
-            else if constexpr (CLS == 4) // as 3 with the row-shared half of the twiddles in LDS: four waves per SIMD
-                fwd_p2_body<true, D1, false, true>(a, prime, comp, outer, lds, blk.tile);
-            else if constexpr (CLS == 3) // double-precision back end, plain transform, twiddles hoisted
-                fwd_p2_body<true, D1, true>(a, prime, comp, outer, lds, blk.tile);
-            else if constexpr (CLS == 1)
-                fwd_p2_body<true, D1>(a, prime, comp, outer, lds, blk.tile);
-            else if constexpr (CLS == 0)
-                with_int_class(a.t, prime, [&](auto ic) { fwd_p2_body<false, D1, false, false, decltype(ic)::value>(a, prime, comp, outer, lds, blk.tile); });
-            else if (a.t.fpd[prime].qi)
-                fwd_p2_body<true, D1>(a, prime, comp, outer, lds, blk.tile);
+                fwd_p2_body<true, D1, true, 0, D1 == 8>(a, prime, comp, outer, lds, tile);
+            else if constexpr (CLS == 4) // double-precision back end, plain transform, twiddles resident (HOIST_LDS)
+                fwd_p2_body<true, D1, true>(a, prime, comp, outer, lds, tile);
             else
-                fwd_p2_body<false, D1, false, false, 2>(a, prime, comp, outer, lds, blk.tile);
+                with_class<CLS>(a.t, prime, [&](auto fp, auto ic) { fwd_p2_body<decltype(fp)::value, D1, false, decltype(ic)::value>(a, prime, comp, outer, lds, tile); });
         }
 
         // ---------------------------------------------------------------------------------------
@@ -399,7 +356,7 @@ namespace sealhip
                 const uint64_t *mp = mid0 + (((size_t)z * a.ncomp) << G::n);
 #pragma unroll
                 for (int e = 0; e < 16; e++)
-                    nxt[e] = mid_ld<4>(mp + e * kMidRow);
+                    nxt[e] = mid_ld(mp + e * kMidRow);
             };
             const unsigned ostride = gridDim.z;
             fetch(outer);
@@ -420,8 +377,8 @@ namespace sealhip
                 for (int k = 0; k < 16; k++)
                 {
                     const unsigned off = (k >> 2) * 256 + (k & 3) * 64 + (tid & 63);
-                    av[k] = mid_ld<16>(A + off);
-                    cv[k] = folded ? 0 : mid_ld<16>(C + off);
+                    av[k] = mid_ld(A + off);
+                    cv[k] = folded ? 0 : mid_ld(C + off);
                 }
                 p2_tile<FP, D1, false, false, false, false, false, ICLS, kP1Out<ICLS, D1>>(x, m, tab, nullptr, nullptr, lds_wave, hg, tid);
                 uint64_t val[16];
@@ -459,33 +416,32 @@ namespace sealhip
         __global__ void __launch_bounds__(kThreads, 2) ntt2_tail2_p1(Tail2Args a)
         {
             HIP_DYNAMIC_SHARED(uint64_t, lds)
-            const Blk blk = spread_blocks();
-            const unsigned comp = blk.y + a.f.comp0, outer = blk.z;
+            const unsigned comp = blockIdx.y + a.f.comp0, outer = blockIdx.z, tile = blockIdx.x;
             const unsigned prime = SHL_UNIFORM(a.f.prime_first + comp);
+            // (the ladder of with_class() written out: through the helper the mixed-class kernel comes out with other instructions)
             if constexpr (CLS == 1)
-                tail2_p1_body<true, D1, 0>(a, prime, comp, outer, lds, blk.tile);
+                tail2_p1_body<true, D1, 0>(a, prime, comp, outer, lds, tile);
             else if constexpr (CLS == 0)
-                with_int_class(a.f.t, prime, [&](auto ic) { tail2_p1_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds, blk.tile); });
+                with_int_class(a.f.t, prime, [&](auto ic) { tail2_p1_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds, tile); });
             else if (a.f.t.fpd[prime].qi)
-                tail2_p1_body<true, D1, 0>(a, prime, comp, outer, lds, blk.tile);
+                tail2_p1_body<true, D1, 0>(a, prime, comp, outer, lds, tile);
             else
-                tail2_p1_body<false, D1, 2>(a, prime, comp, outer, lds, blk.tile);
+                tail2_p1_body<false, D1, 2>(a, prime, comp, outer, lds, tile);
         }
         template <int D1, int CLS>
         __global__ void __launch_bounds__(kThreads, 2) ntt2_tail2_p2(Tail2Args a)
         {
             HIP_DYNAMIC_SHARED(uint64_t, lds)
-            const Blk blk = spread_blocks();
-            const unsigned comp = blk.y + a.f.comp0, outer = blk.z;
+            const unsigned comp = blockIdx.y + a.f.comp0, outer = blockIdx.z, tile = blockIdx.x;
             const unsigned prime = SHL_UNIFORM(a.f.prime_first + comp);
-            if constexpr (CLS == 1)
-                tail2_p2_body<true, D1, 0>(a, prime, comp, outer, lds, blk.tile);
+            if constexpr (CLS == 1) // (as ntt2_tail2_p1)
+                tail2_p2_body<true, D1, 0>(a, prime, comp, outer, lds, tile);
             else if constexpr (CLS == 0)
-                with_int_class(a.f.t, prime, [&](auto ic) { tail2_p2_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds, blk.tile); });
+                with_int_class(a.f.t, prime, [&](auto ic) { tail2_p2_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds, tile); });
             else if (a.f.t.fpd[prime].qi)
-                tail2_p2_body<true, D1, 0>(a, prime, comp, outer, lds, blk.tile);
+                tail2_p2_body<true, D1, 0>(a, prime, comp, outer, lds, tile);
             else
-                tail2_p2_body<false, D1, 2>(a, prime, comp, outer, lds, blk.tile);
+                tail2_p2_body<false, D1, 2>(a, prime, comp, outer, lds, tile);
         }
 
         // A resident source word as the target loop sees it: opaque to the compiler, so that the target-independent half of its
@@ -575,7 +531,7 @@ namespace sealhip
 #pragma unroll
                         for (int e = 0; e < 16; e++)
                             x[e] = map_src<FP>(resident_word(r1[e]), s1, m); // fixed: |x| <= q/2 (integer: below 4q)
-                        p1_tile<FP, D1, 256, SEALHIP_P1_PLAIN_LEAN && FP && G::rA == 4, ICLS>(x, m, tab, tw, lds, mid_tr, cg, tid);
+                        p1_tile<FP, D1, 256, false, ICLS>(x, m, tab, tw, lds, mid_tr, cg, tid);
                     }
                     else
                     {
@@ -616,11 +572,9 @@ namespace sealhip
         }
 
         // CLS: 0 = integer back end, 1 = double precision (a mixed run keeps the target-resident kernels); TWO: the folded tail
-#ifndef SEALHIP_SRC_P1T_FP2_WGS
-#define SEALHIP_SRC_P1T_FP2_WGS 2 // workgroups per CU the folded tail's double-precision body is compiled for (150 VGPRs: three fit)
-#endif
+        constexpr int kSrcP1tFp2Wgs = 2; // workgroups per CU the folded tail's double-precision body is compiled for (150 VGPRs: three fit)
         template <int D1, int CLS, bool TWO, bool SMALL2 = false>
-        __global__ void __launch_bounds__(kThreads, SMALL2 ? SEALHIP_SRC_P1T_FP2_WGS : 2) ntt2_src_p1t(Tail2Args a, unsigned nc)
+        __global__ void __launch_bounds__(kThreads, SMALL2 ? kSrcP1tFp2Wgs : 2) ntt2_src_p1t(Tail2Args a, unsigned nc)
         {
             static_assert(CLS == 0 || CLS == 1, "single-class runs only");
             HIP_DYNAMIC_SHARED(uint64_t, lds)
@@ -776,24 +730,16 @@ namespace sealhip
             uint64_t *mid_tr = a.mid + (((size_t)outer * a.ncomp + comp) << G::n) + ((size_t)hg << 12);
 #pragma unroll
             for (int e = 0; e < 16; e++)
-                mid_st<8>(mid_tr + e * 256 + tid, F::raw(x[e]));
+                mid_st(mid_tr + e * 256 + tid, F::raw(x[e]));
         }
 
         template <int D1, int CLS>
         __global__ void __launch_bounds__(kThreads) ntt2_inv_pa(InvArgs a)
         {
             HIP_DYNAMIC_SHARED(uint64_t, lds)
-            const Blk blk = spread_blocks();
-            const unsigned comp = blk.y + a.comp0, outer = blk.z;
+            const unsigned comp = blockIdx.y + a.comp0, outer = blockIdx.z, tile = blockIdx.x;
             const unsigned prime = SHL_UNIFORM(a.comp_prime ? a.comp_prime[comp] : a.prime_first + comp);
-            if constexpr (CLS == 1)
-                inv_pa_body<true, D1>(a, prime, comp, outer, lds, blk.tile);
-            else if constexpr (CLS == 0)
-                with_int_class(a.t, prime, [&](auto ic) { inv_pa_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds, blk.tile); });
-            else if (a.t.fpd[prime].qi)
-                inv_pa_body<true, D1>(a, prime, comp, outer, lds, blk.tile);
-            else
-                inv_pa_body<false, D1, 2>(a, prime, comp, outer, lds, blk.tile); // mixed launches keep the guarded butterflies
+            with_class<CLS>(a.t, prime, [&](auto fp, auto ic) { inv_pa_body<decltype(fp)::value, D1, decltype(ic)::value>(a, prime, comp, outer, lds, tile); });
         }
 
         template <bool FP, int D1, int ICLS = 2>
@@ -811,7 +757,7 @@ namespace sealhip
             typename F::elem x[16];
 #pragma unroll
             for (int rb = 0; rb < 16; rb++)
-                x[rb] = F::unraw(mid_ld<8>(i + rb * 16));
+                x[rb] = F::unraw(mid_ld(i + rb * 16));
             {
                 TwRegs<FP> tw;
                 load_tw<FP, 4>(tw, tab, [&](int t) { return (1u << (G::rA + t)) + (hi << t); });
@@ -857,7 +803,7 @@ namespace sealhip
                 uint64_t v = a.lazy ? F::inv_to_lazy(x[e], m) : F::inv_to_canon(x[e], m);
                 if (a.out_add)
                     v = csub(v + a.out_add, a.t.mods[prime].q);
-                mid_st<16>(o + (size_t)R * 256 + col, v);
+                mid_st(o + (size_t)R * 256 + col, v);
             }
         }
 
@@ -865,17 +811,16 @@ namespace sealhip
         __global__ void __launch_bounds__(kThreads) ntt2_inv_pb(InvArgs a)
         {
             HIP_DYNAMIC_SHARED(uint64_t, lds)
-            const Blk blk = spread_blocks();
-            const unsigned comp = blk.y + a.comp0, outer = blk.z;
+            const unsigned comp = blockIdx.y + a.comp0, outer = blockIdx.z, tile = blockIdx.x;
             const unsigned prime = SHL_UNIFORM(a.comp_prime ? a.comp_prime[comp] : a.prime_first + comp);
-            if constexpr (CLS == 1)
-                inv_pb_body<true, D1>(a, prime, comp, outer, lds, blk.tile);
+            if constexpr (CLS == 1) // (as ntt2_tail2_p1)
+                inv_pb_body<true, D1>(a, prime, comp, outer, lds, tile);
             else if constexpr (CLS == 0)
-                with_int_class(a.t, prime, [&](auto ic) { inv_pb_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds, blk.tile); });
+                with_int_class(a.t, prime, [&](auto ic) { inv_pb_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds, tile); });
             else if (a.t.fpd[prime].qi)
-                inv_pb_body<true, D1>(a, prime, comp, outer, lds, blk.tile);
+                inv_pb_body<true, D1>(a, prime, comp, outer, lds, tile);
             else
-                inv_pb_body<false, D1, 2>(a, prime, comp, outer, lds, blk.tile);
+                inv_pb_body<false, D1, 2>(a, prime, comp, outer, lds, tile);
         }
 
         // ---------------------------------------------------------------------------------------
@@ -909,35 +854,15 @@ namespace sealhip
         // double-precision kernels - two workgroups per CU at N = 2^13 (or one of each class, which is what a chain with both
         // kinds of primes launches side by side: 76 + 77 KiB of LDS, 4 x 128 registers per SIMD lane) and the one 1024-thread
         // workgroup a CU holds at N = 2^14.  Measured by hipcc's resource remarks (tools/quick/resources.py):
-        //  * TWB_REGS: pass 2's fifteen per-thread twiddles resident for the workgroup's loop are 60 VGPRs of Shoup pairs -> 183
+        //  * pass 2's fifteen per-thread twiddles resident for the workgroup's loop (TWB_REGS) are 60 VGPRs of Shoup pairs -> 183
         //    registers (two waves per SIMD) or 120-230 bytes of scratch at 128; they are re-read per transform instead (L2:
-        //    the table of one prime is 16 N bytes), each where it is used;
+        //    the table of one prime is 16 N bytes) - forward, each where it is used; inverse, the first phase's requested together
+        //    with the rows;
         //  * PF: the next transform's sixteen words in flight during this one (32 VGPRs) fits the forward kernel at 2^14 only
         //    (124 registers); elsewhere it spills 28-76 bytes, and at 2^13 the second workgroup of the CU covers the load.
-// forward: where pass 2's fifteen per-thread twiddles come from (0 fetched where used, 1 requested at the start of pass 2 of every
-// transform, 2 resident for the workgroup's loop), prefetch of the next transform at 2^13 / 2^14, waves per SIMD asked of the compiler
-#ifndef SEALHIP_FINT_FWD_TWB
-#define SEALHIP_FINT_FWD_TWB 0
-#endif
-#ifndef SEALHIP_FINT_FWD_PF13
-#define SEALHIP_FINT_FWD_PF13 0
-#endif
-#ifndef SEALHIP_FINT_FWD_PF14
-#define SEALHIP_FINT_FWD_PF14 1
-#endif
-#ifndef SEALHIP_FINT_FWD_WAVES
-#define SEALHIP_FINT_FWD_WAVES 4
-#endif
-// inverse: the first phase's per-thread twiddles fetched where used (0) or requested together with the rows (1); prefetch; waves
-#ifndef SEALHIP_FINT_INV_TWB
-#define SEALHIP_FINT_INV_TWB 1
-#endif
-#ifndef SEALHIP_FINT_INV_PF
-#define SEALHIP_FINT_INV_PF 0
-#endif
-#ifndef SEALHIP_FINT_INV_WAVES
-#define SEALHIP_FINT_INV_WAVES 4
-#endif
+        //    Double precision, 2^13, either direction: without the 32 prefetch registers nothing spills (inverse +10 %; forward +2 %
+        //    on the mixed chain, +5 % on a chain of primes below 2^50, 4.3 -> 4.5 TB/s).
+        constexpr int kFusedIntWaves = 4; // waves per SIMD asked of the compiler for the integer kernels, either direction
 
         template <bool FP, int D1, int ICLS = 0>
         __device__ __forceinline__ void fwd_fused2_body(const FwdArgs &a, unsigned prime, unsigned comp, unsigned outer, uint64_t *lds)
@@ -946,12 +871,8 @@ namespace sealhip
             typedef Geo<D1> G;
             typedef FusedGeo<D1, F::tw_words> FG;
             typedef typename F::tw_t tw_t;
-            constexpr bool TWB_REGS = FP || (D1 == 5 && SEALHIP_FINT_FWD_TWB == 2); // 2^14: one 1024-thread workgroup, 128 registers
-            constexpr bool TWB_EARLY = !FP && D1 == 5 && SEALHIP_FINT_FWD_TWB == 1;
-#ifndef SEALHIP_FP_FWD_PF13
-#define SEALHIP_FP_FWD_PF13 0 // as SEALHIP_FP_INV_PF: +2 % on the mixed chain, +5 % on a chain of primes below 2^50 (4.3 -> 4.5 TB/s)
-#endif
-            constexpr bool PF = FP ? (D1 != 5 || SEALHIP_FP_FWD_PF13) : ((D1 == 6 && SEALHIP_FINT_FWD_PF14) || (D1 == 5 && SEALHIP_FINT_FWD_PF13));
+            constexpr bool TWB_REGS = FP;
+            constexpr bool PF = FP ? D1 != 5 : D1 == 6;
             const unsigned team = threadIdx.x >> 8, tid = threadIdx.x & 255;
             const typename F::Mod m = F::make_mod(ld_uniform_mod(&a.t.mods[prime]), ld_uniform_fpd(&a.t.fpd[prime]));
             const tw_t *tab = tw_table<FP>(a.t, false, prime);
@@ -962,7 +883,7 @@ namespace sealhip
             stage_twa<D1>(twa, tab, team, tid); // read after several workgroup barriers
             const unsigned c = tid & (G::C - 1);
             const unsigned hi = SHL_UNIFORM(tid >> G::LC); // rbl in phase A, ra in phase B: the same in every lane of a wave
-            TwRegs<FP> twb, unused;
+            TwRegs<FP> twb;
             if constexpr (TWB_REGS)
             {
                 const unsigned h = team * 16 + (tid >> 4), v = tid & 15;
@@ -1031,16 +952,9 @@ namespace sealhip
                     for (int e = 0; e < 16; e++)
                         x[e] = F::unraw(mp[e * FG::BS]);
                 }
-                if constexpr (TWB_EARLY)
-                {
-                    // requested before phase A so that they arrive during it (fetched where they are used, every stage of phase B
-                    // waits for a round trip to L2)
-                    const unsigned h = team * 16 + (tid >> 4), v = tid & 15;
-                    load_tw<FP, 4>(twb, tab, [&](int t) { return (1u << (D1 + 4 + t)) + ((h * 16 + v) << t); });
-                }
                 __syncthreads(); // the intermediate is consumed: the area becomes the wave-local exchange buffers
-                if constexpr (TWB_REGS || TWB_EARLY)
-                    p2_tile<FP, D1, false, false, true, true, false, ICLS, kP1Out<ICLS, D1>>(x, m, tab, twa, nullptr, lds_wave, team, tid, &unused, &twb);
+                if constexpr (TWB_REGS)
+                    p2_tile<FP, D1, false, false, true, true, false, ICLS, kP1Out<ICLS, D1>>(x, m, tab, twa, nullptr, lds_wave, team, tid, &twb);
                 else
                     p2_tile<FP, D1, false, true, false, true, false, ICLS, kP1Out<ICLS, D1>>(x, m, tab, twa, nullptr, lds_wave, team, tid);
                 uint64_t val[16];
@@ -1053,15 +967,13 @@ namespace sealhip
 
         // CLS: 1 double-precision back end, 0 integer back end (one modulus class per workgroup)
         template <int D1, int CLS>
-        __global__ void __launch_bounds__(FusedGeo<D1>::TEAMS *kThreads, CLS == 1 ? 4 : SEALHIP_FINT_FWD_WAVES) ntt2_fwd_fused2(FwdArgs a)
+        __global__ void __launch_bounds__(FusedGeo<D1>::TEAMS *kThreads, CLS == 1 ? 4 : kFusedIntWaves) ntt2_fwd_fused2(FwdArgs a)
         {
+            static_assert(CLS == 0 || CLS == 1, "single-class runs only");
             HIP_DYNAMIC_SHARED(uint64_t, lds)
             const unsigned comp = blockIdx.y + a.comp0, outer = blockIdx.z;
             const unsigned prime = SHL_UNIFORM(a.comp_prime ? a.comp_prime[comp] : a.prime_first + comp);
-            if constexpr (CLS == 1)
-                fwd_fused2_body<true, D1>(a, prime, comp, outer, lds);
-            else
-                with_int_class(a.t, prime, [&](auto ic) { fwd_fused2_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds); });
+            with_class<CLS>(a.t, prime, [&](auto fp, auto ic) { fwd_fused2_body<decltype(fp)::value, D1, decltype(ic)::value>(a, prime, comp, outer, lds); });
         }
 
         // Inverse: team k undoes pass 2 on row tile k (rows -> intermediate in LDS), the teams meet, team k undoes
@@ -1074,10 +986,7 @@ namespace sealhip
             typedef FusedGeo<D1, F::tw_words> FG;
             typedef typename F::tw_t tw_t;
             static_assert(G::rA >= 1, "the N^-1 stage is handled in phase A");
-#ifndef SEALHIP_FP_INV_PF
-#define SEALHIP_FP_INV_PF 0 // 2^13, double precision: two workgroups per CU cover the loads; without the 32 prefetch registers nothing spills: +10 %
-#endif
-            constexpr bool PF = FP ? (SEALHIP_FP_INV_PF || D1 != 5) : (D1 == 5 && SEALHIP_FINT_INV_PF);
+            constexpr bool PF = FP && D1 != 5; // (FusedGeo's note; 2^13: two workgroups per CU cover the loads)
             const unsigned team = threadIdx.x >> 8, tid = threadIdx.x & 255;
             const unsigned v = tid & 15, u = tid >> 4, ul = u & 3, lane = tid & 63;
             const unsigned h = team * 16 + u;
@@ -1120,7 +1029,7 @@ namespace sealhip
                 if constexpr (!PF)
                     fetch(outer);
                 TwRegs<FP> twb_early;
-                if constexpr (!FP && SEALHIP_FINT_INV_TWB == 1) // the first phase's per-thread twiddles travel with the rows
+                if constexpr (!FP) // the first phase's per-thread twiddles travel with the rows
                     load_tw<FP, 4>(twb_early, tab, [&](int t) { return (1u << (D1 + 4 + t)) + ((h * 16 + v) << t); });
                 // ---- rows of tile `team`: coalesced words -> wave-local transposition -> (row u, cols 16 v + e)
 #pragma unroll
@@ -1147,10 +1056,8 @@ namespace sealhip
                         load_tw<FP, 4>(twb, tab, [&](int t) { return (1u << (D1 + 4 + t)) + ((h * 16 + v) << t); });
                         phase_inv<FP, 4, 0, ICLS, 0>(x, m, [&](int t, int g) { return twb.get((1 << t) + g); });
                     }
-                    else if constexpr (SEALHIP_FINT_INV_TWB == 1)
+                    else
                         phase_inv<FP, 4, 0, ICLS, 0>(x, m, [&](int t, int g) { return twb_early.get((1 << t) + g); });
-                    else // each twiddle fetched where it is used
-                        phase_inv<FP, 4, 0, ICLS, 0>(x, m, [&](int t, int g) { return tab[(1u << (D1 + 4 + t)) + ((h * 16 + v) << t) + g]; });
                 }
 #pragma unroll
                 for (int e = 0; e < 16; e++)
@@ -1219,26 +1126,19 @@ namespace sealhip
         }
 
         template <int D1, int CLS>
-        __global__ void __launch_bounds__(FusedGeo<D1>::TEAMS *kThreads, CLS == 1 ? 4 : SEALHIP_FINT_INV_WAVES) ntt2_inv_fused2(InvArgs a)
+        __global__ void __launch_bounds__(FusedGeo<D1>::TEAMS *kThreads, CLS == 1 ? 4 : kFusedIntWaves) ntt2_inv_fused2(InvArgs a)
         {
+            static_assert(CLS == 0 || CLS == 1, "single-class runs only");
             HIP_DYNAMIC_SHARED(uint64_t, lds)
             const unsigned comp = blockIdx.y + a.comp0, outer = blockIdx.z;
             const unsigned prime = SHL_UNIFORM(a.comp_prime ? a.comp_prime[comp] : a.prime_first + comp);
-            if constexpr (CLS == 1)
-                inv_fused2_body<true, D1>(a, prime, comp, outer, lds);
-            else
-                with_int_class(a.t, prime, [&](auto ic) { inv_fused2_body<false, D1, decltype(ic)::value>(a, prime, comp, outer, lds); });
+            with_class<CLS>(a.t, prime, [&](auto fp, auto ic) { inv_fused2_body<decltype(fp)::value, D1, decltype(ic)::value>(a, prime, comp, outer, lds); });
         }
 
         // The key-switch kernels of N = 2^16 (eight stages per pass) use the lean fix() placement of p1_tile / p2_tile (tile-order
-        // intermediate only; the lane-order geometry keeps its own).  SEALHIP_KS_LEAN_OFF at build time restores five fix() per pair.
-#ifdef SEALHIP_KS_LEAN_OFF
-        template <int D1>
-        constexpr bool kLeanKs = false;
-#else
+        // intermediate only; the lane-order geometry keeps its own).
         template <int D1>
         constexpr bool kLeanKs = D1 == 8;
-#endif
         // the lean placement takes an unfixed digit of magnitude up to kLeanEntry q_I (p1_tile)
         constexpr double kLeanEntry = 1.13;
 
@@ -1331,11 +1231,7 @@ namespace sealhip
                 {
                     const unsigned ra = e >> (4 - G::rA), rbh = e & ((1 << (4 - G::rA)) - 1);
                     const unsigned R = ra * 16 + (rbh << G::rA) + rbl;
-#ifdef SEALHIP_KS_NOMEM
-                    nxt[e] = (uint64_t)((tid << 4) + (unsigned)e + J * 4099u + R); // (any word below 2^50 does)
-#else
                     nxt[e] = in[(size_t)R * 256];
-#endif
                 }
             };
             const unsigned Jskip = a.skip_diag ? I : ~0u;
@@ -1503,9 +1399,6 @@ namespace sealhip
             NttTables tb;
         };
 
-#ifndef SEALHIP_KS2_INT_TWB3
-#define SEALHIP_KS2_INT_TWB3 1
-#endif
         template <bool FP, int D1, int ICLS = 0>
         __device__ __forceinline__ void ks2_body(const Ks2Args &a, uint64_t *lds, unsigned I, unsigned prime, unsigned koff, unsigned b, unsigned hg,
                                                  unsigned j0, unsigned j1, uint64_t *acc_part)
@@ -1529,14 +1422,12 @@ namespace sealhip
                     la[tid] = tab[(1u << (D1 + t)) + ((hg * 16) << t) + r];
                 }
                 twa = la;
-#if SEALHIP_KS2_INT_TWB3
                 // ... and the last stage's eight per-thread pairs (32 KiB: two workgroups per CU still fit): the same for every digit
                 typename F::tw_t *lb = la + 240;
 #pragma unroll
                 for (int g = 0; g < 8; g++)
                     lb[g * 256 + tid] = tab[(1u << (D1 + 7)) + ((hg * 256 + tid) << 3) + g];
                 twb = lb;
-#endif
                 __syncthreads();
             }
             if constexpr (FP)
@@ -1618,16 +1509,7 @@ namespace sealhip
                     const UniformView mv = uniform_view(mid0 + ((size_t)J << G::n));
 #pragma unroll
                     for (int e = 0; e < 16; e++)
-                    {
-#ifdef SEALHIP_KS_NOMEM
-                        nxt[e] = fp_to_bits((double)(int)((tid * 16 + e + J * 4099u) & 0xFFFFF) - 524288.0);
-#else
-                        if constexpr ((SEALHIP_KS_NT & 2) != 0)
-                            nxt[e] = view_load64_nt(mv, mid_lane(tid) * 8, e * (kMidRow * 8));
-                        else
-                            nxt[e] = view_load64(mv, mid_lane(tid) * 8, e * (kMidRow * 8));
-#endif
-                    }
+                        nxt[e] = view_load64_nt(mv, mid_lane(tid) * 8, e * (kMidRow * 8));
                 }
                 else
                 {
@@ -1636,32 +1518,18 @@ namespace sealhip
                     const uint64_t *mp = mid0_lane + ((size_t)J << G::n);
 #pragma unroll
                     for (int e = 0; e < 16; e++)
-                    {
-#ifdef SEALHIP_KS_NOMEM
-                        nxt[e] = ((uint64_t)(tid * 16 + e + J * 4099u) * 0x9E3779B97F4A7C15ull) >> 6;
-#else
-                        nxt[e] = mid_ld<4>(mp + e * kMidRow);
-#endif
-                    }
+                        nxt[e] = mid_ld(mp + e * kMidRow);
                 }
             };
-            // Integer back end: with 128-bit sums there were no registers for the prefetch (round 2: the overflow spilled to
-            // scratch gained nothing, one wave per SIMD lost 10 %); with 64-bit sums (round 3) digit J + 1 travels during digit J
-#ifndef SEALHIP_KS2_INT_PF
-#define SEALHIP_KS2_INT_PF 1
-#endif
-            constexpr bool PF = FP || SEALHIP_KS2_INT_PF;
-            if constexpr (PF)
-            {
-                if (j0 < j1)
-                    fetch(j0);
-            }
+            // Both back ends: digit J + 1 travels during digit J.  (Integer back end: with 128-bit sums there were no registers for
+            // the prefetch - round 2: the overflow spilled to scratch gained nothing, one wave per SIMD lost 10 % -; with 64-bit
+            // sums, round 3, there are.)
+            if (j0 < j1)
+                fetch(j0);
             for (unsigned J = j0; J < j1; J++)
             {
                 typename F::elem x[16];
                 const bool is_diag = has_diag && J == I;
-                if constexpr (!PF)
-                    fetch(J);
                 if (is_diag && diag_prod)
                 {
                     // nxt holds x1's sixteen words of this thread; y1's are loaded here, once per tile (the product's round trip through
@@ -1699,7 +1567,6 @@ namespace sealhip
                 // this component of digit J: N pairs of doubles (double-precision primes) or 2 x N (word, Shoup quotient) pairs
                 const size_t kslab = (size_t)(J - a.key_digit0) * a.key_digit_words + (size_t)koff * N;
                 typename F::key_t kr0[16], kr1[16];
-                prio_phase<2>();
                 if constexpr (FP)
                 {
                     // the key words of this digit and the next digit travel while this digit is transformed
@@ -1708,26 +1575,16 @@ namespace sealhip
                     for (int e = 0; e < 16; e++)
                     {
                         uint64_t w0, w1; // (first, second) key polynomial of this coefficient
-#ifdef SEALHIP_KS_NOMEM
-                        w0 = fp_to_bits((double)(int)((tid * 7 + e * 31 + J) & 0xFFFFF) - 500000.0), w1 = fp_to_bits((double)(int)((tid * 3 + e * 17 + J) & 0xFFFFF) - 400000.0);
-#else
                         view_load128(kv, tid * 16, e * 4096, w0, w1);
-#endif
                         kr0[e] = fp_from_bits(w0);
                         kr1[e] = fp_from_bits(w1);
                     }
-                    if (J + 1 < j1)
-                        fetch(J + 1);
                 }
-                else if constexpr (PF)
-                {
-                    if (J + 1 < j1)
-                        fetch(J + 1);
-                }
-                prio_phase<1>();
+                if (J + 1 < j1)
+                    fetch(J + 1);
                 if (!is_diag)
                 {
-                    p2_tile<FP, D1, FP, true, false, !FP, FP && kLeanKs<D1>, ICLS, kP1Out<ICLS, D1>, !FP && SEALHIP_KS2_INT_TWB3>(x, m, tab, twa, twb, lds_wave, hg, tid);
+                    p2_tile<FP, D1, FP, true, false, !FP, FP && kLeanKs<D1>, ICLS, kP1Out<ICLS, D1>, !FP>(x, m, tab, twa, twb, lds_wave, hg, tid);
                     // integer back end: the Shoup product takes any 64-bit x (the transform's results are below kP2Out q); the
                     // guarded class (moduli of 2^60 and above: never a key-switch target, kept for completeness) works in [0, 2q)
                 }
@@ -1748,11 +1605,7 @@ namespace sealhip
 #pragma unroll
                     for (int e = 0; e < 16; e++)
                     {
-#ifdef SEALHIP_KS_NOMEM
-                        const ShoupOp w0{ (uint64_t)(tid * 7 + e * 31 + J) * 0x9E3779B97F4A7C15ull >> 5, (uint64_t)(tid + e) * 0xD1B54A32D192ED03ull }, w1{ w0.wq >> 4, w0.w << 3 };
-#else
                         const ShoupOp w0 = p0[e * 256], w1 = p1[e * 256];
-#endif
                         if constexpr (ICLS == 2)
                         {
                             acc0[e] = F::guard(acc0[e] + F::mul_lazy(x[e], w0, m), m);
@@ -1812,7 +1665,7 @@ namespace sealhip
                 auto load16 = [&](const uint64_t *P, uint64_t (&v)[16]) {
 #pragma unroll
                     for (int k = 0; k < 16; k++)
-                        v[k] = mid_ld<16>(P + (k >> 2) * 256 + (k & 3) * 64 + (tid & 63));
+                        v[k] = mid_ld(P + (k >> 2) * 256 + (k & 3) * 64 + (tid & 63));
                 };
                 uint64_t p0[16], p1[16];
                 uint64_t *out1 = out + ((size_t)(a.K + 1) << G::n);
@@ -1832,7 +1685,7 @@ namespace sealhip
                     for (int e = 0; e < 16; e++)
                         val[e] = fp_to_bits(fp_mulmod(fp_fix(acc0[e], m.q, m.qinv), pmd, m.q, m.qinv));
                     emit_rows_k(val, lds_wave, tid, [&](int k, unsigned off, uint64_t sv) {
-                        mid_st<16>(out + off, fp_to_canon(fp_fix(fp_from_bits(sv) + cd[k], m.q, m.qinv), m));
+                        mid_st(out + off, fp_to_canon(fp_fix(fp_from_bits(sv) + cd[k], m.q, m.qinv), m));
                     });
                     load16(Y1, p1);
 #pragma unroll
@@ -1847,7 +1700,7 @@ namespace sealhip
                     for (int e = 0; e < 16; e++)
                         val[e] = fp_to_bits(fp_mulmod(fp_fix(acc1[e], m.q, m.qinv), pmd, m.q, m.qinv));
                     emit_rows_k(val, lds_wave, tid, [&](int k, unsigned off, uint64_t sv) {
-                        mid_st<16>(out1 + off, fp_to_canon(fp_fix(fp_from_bits(sv) + cd[k], m.q, m.qinv), m));
+                        mid_st(out1 + off, fp_to_canon(fp_fix(fp_from_bits(sv) + cd[k], m.q, m.qinv), m));
                     });
                     return;
                 }
@@ -1861,7 +1714,7 @@ namespace sealhip
                 for (int e = 0; e < 16; e++)
                     val[e] = sum_to_canon(acc0[e]);
                 emit_rows_k(val, lds_wave, tid, [&](int k, unsigned off, uint64_t sv) {
-                    mid_st<16>(out + off, add_mod(mul_shoup(sv, pm.w, pm.wq, q), cv[k], q));
+                    mid_st(out + off, add_mod(mul_shoup(sv, pm.w, pm.wq, q), cv[k], q));
                 });
                 load16(Y1, p1);
 #pragma unroll
@@ -1876,7 +1729,7 @@ namespace sealhip
                 for (int e = 0; e < 16; e++)
                     val[e] = sum_to_canon(acc1[e]);
                 emit_rows_k(val, lds_wave, tid, [&](int k, unsigned off, uint64_t sv) {
-                    mid_st<16>(out1 + off, add_mod(mul_shoup(sv, pm.w, pm.wq, q), cv[k], q));
+                    mid_st(out1 + off, add_mod(mul_shoup(sv, pm.w, pm.wq, q), cv[k], q));
                 });
                 return;
             }
@@ -1894,10 +1747,10 @@ namespace sealhip
                 {
                     const unsigned off = (k >> 2) * 256 + (k & 3) * 64 + (tid & 63);
                     if (a.gal) // the first addend is pi(c0) of a rotation, read through the index map
-                        cv0[k] = mid_ld<16>(a.fold_c0 + (((size_t)b * a.K + I) << G::n) + galois_src_index(((hg * 16 + (tid >> 6) * 4) << 8) + off, a.gal, G::n));
+                        cv0[k] = mid_ld(a.fold_c0 + (((size_t)b * a.K + I) << G::n) + galois_src_index(((hg * 16 + (tid >> 6) * 4) << 8) + off, a.gal, G::n));
                     else
-                        cv0[k] = mid_ld<16>(C0 + off);
-                    cv1[k] = C1 ? mid_ld<16>(C1 + off) : 0;
+                        cv0[k] = mid_ld(C0 + off);
+                    cv1[k] = C1 ? mid_ld(C1 + off) : 0;
                 }
                 uint64_t *out1 = out + ((size_t)(a.K + 1) << G::n);
                 if constexpr (FP)
@@ -1908,13 +1761,13 @@ namespace sealhip
                     for (int e = 0; e < 16; e++)
                         val[e] = fp_to_bits(fp_mulmod(fp_fix(acc0[e], m.q, m.qinv), pmd, m.q, m.qinv));
                     emit_rows_k(val, lds_wave, tid, [&](int k, unsigned off, uint64_t sv) {
-                        mid_st<16>(out + off, fp_to_canon(fp_fix(fp_from_bits(sv) + fp_from_u52(cv0[k]), m.q, m.qinv), m));
+                        mid_st(out + off, fp_to_canon(fp_fix(fp_from_bits(sv) + fp_from_u52(cv0[k]), m.q, m.qinv), m));
                     });
 #pragma unroll
                     for (int e = 0; e < 16; e++)
                         val[e] = fp_to_bits(fp_mulmod(fp_fix(acc1[e], m.q, m.qinv), pmd, m.q, m.qinv));
                     emit_rows_k(val, lds_wave, tid, [&](int k, unsigned off, uint64_t sv) {
-                        mid_st<16>(out1 + off, fp_to_canon(fp_fix(fp_from_bits(sv) + fp_from_u52(cv1[k]), m.q, m.qinv), m));
+                        mid_st(out1 + off, fp_to_canon(fp_fix(fp_from_bits(sv) + fp_from_u52(cv1[k]), m.q, m.qinv), m));
                     });
                     return;
                 }
@@ -1922,13 +1775,13 @@ namespace sealhip
                 for (int e = 0; e < 16; e++)
                     val[e] = sum_to_canon(acc0[e]);
                 emit_rows_k(val, lds_wave, tid, [&](int k, unsigned off, uint64_t sv) {
-                    mid_st<16>(out + off, add_mod(mul_shoup(sv, pm.w, pm.wq, q), cv0[k], q));
+                    mid_st(out + off, add_mod(mul_shoup(sv, pm.w, pm.wq, q), cv0[k], q));
                 });
 #pragma unroll
                 for (int e = 0; e < 16; e++)
                     val[e] = sum_to_canon(acc1[e]);
                 emit_rows_k(val, lds_wave, tid, [&](int k, unsigned off, uint64_t sv) {
-                    mid_st<16>(out1 + off, add_mod(mul_shoup(sv, pm.w, pm.wq, q), cv1[k], q));
+                    mid_st(out1 + off, add_mod(mul_shoup(sv, pm.w, pm.wq, q), cv1[k], q));
                 });
                 return;
             }
@@ -1944,10 +1797,7 @@ namespace sealhip
 
         // CLS: 0 integer-back-end targets only, 1 double-precision targets only
         template <int D1, int CLS>
-#ifndef SEALHIP_KS2_INT_WAVES
-#define SEALHIP_KS2_INT_WAVES 2
-#endif
-        __global__ void __launch_bounds__(kThreads, CLS == 0 ? SEALHIP_KS2_INT_WAVES : 2) ks2_kernel(Ks2Args a)
+        __global__ void __launch_bounds__(kThreads, 2) ks2_kernel(Ks2Args a)
         {
             typedef Geo<D1> G;
             HIP_DYNAMIC_SHARED(uint64_t, lds)
@@ -2119,7 +1969,7 @@ namespace sealhip
             bool ok = false;
             SideStream()
             {
-                ok = !shl_ab_getenv("SEALHIP_NTT_NOFORK") && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess &&
+                ok = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess &&
                      hipEventCreateWithFlags(&fork, hipEventDisableTiming) == hipSuccess &&
                      hipEventCreateWithFlags(&join, hipEventDisableTiming) == hipSuccess;
             }
@@ -2129,6 +1979,19 @@ namespace sealhip
             static thread_local SideStream s;
             return s;
         }
+        // side(stream) between a fork and a join event on the side stream, main(s) on `s`, which then waits for the join
+        template <class SideFn, class MainFn>
+        hipError_t fork_join(SideStream &ss, hipStream_t s, SideFn side, MainFn main)
+        {
+            hipError_t e;
+            if ((e = hipEventRecord(ss.fork, s)) != hipSuccess || (e = hipStreamWaitEvent(ss.stream, ss.fork, 0)) != hipSuccess)
+                return e;
+            if ((e = side(ss.stream)) != hipSuccess || (e = hipEventRecord(ss.join, ss.stream)) != hipSuccess)
+                return e;
+            if ((e = main(s)) != hipSuccess)
+                return e;
+            return hipStreamWaitEvent(s, ss.join, 0);
+        }
         // run(r, stream) launches the kernels of one run; the longest run stays on `s`
         template <class RunFn>
         hipError_t launch_runs(const std::vector<CompRun> &runs, hipStream_t s, RunFn run, bool may_fork = true)
@@ -2137,35 +2000,83 @@ namespace sealhip
             for (size_t i = 1; i < runs.size(); i++)
                 if (runs[i].nc > runs[longest].nc)
                     longest = i;
-            SideStream &ss = side_stream();
-            const bool fork = may_fork && runs.size() > 1 && ss.ok;
-            hipError_t e;
-            if (fork)
-            {
-                if ((e = hipEventRecord(ss.fork, s)) != hipSuccess || (e = hipStreamWaitEvent(ss.stream, ss.fork, 0)) != hipSuccess)
-                    return e;
-                for (size_t i = 0; i < runs.size(); i++)
-                    if (i != longest && (e = run(runs[i], ss.stream)) != hipSuccess)
-                        return e;
-                if ((e = hipEventRecord(ss.join, ss.stream)) != hipSuccess)
-                    return e;
-            }
-            for (size_t i = 0; i < runs.size(); i++)
-                if ((!fork || i == longest) && (e = run(runs[i], s)) != hipSuccess)
-                    return e;
-            if (fork && (e = hipStreamWaitEvent(s, ss.join, 0)) != hipSuccess)
+            // every run but `skip`, one after the other on `st`
+            auto all_but = [&](size_t skip, hipStream_t st) {
+                hipError_t e = hipSuccess;
+                for (size_t i = 0; i < runs.size() && e == hipSuccess; i++)
+                    if (i != skip)
+                        e = run(runs[i], st);
                 return e;
-            return hipSuccess;
+            };
+            SideStream &ss = side_stream();
+            if (!(may_fork && runs.size() > 1 && ss.ok))
+                return all_but(runs.size(), s);
+            return fork_join(ss, s, [&](hipStream_t st) { return all_but(longest, st); }, [&](hipStream_t st) { return run(runs[longest], st); });
         }
 
-#ifndef SEALHIP_FUSED_FORK14
-#define SEALHIP_FUSED_FORK14 1 // 2^14: the single-launch kernels of the two classes side by side (a CU holds ONE 1024-thread workgroup of either)
-#endif
-        // single-launch kernels for the integer back end (N = 2^13, 2^14); SEALHIP_NTT_NOFUSED_INT=1 keeps its two-launch engine (A/B runs)
-        inline bool fused_int()
+        // launches kern_of(std::integral_constant<int, CLS>) - the <D1, CLS> instance of a kernel - for a run of class cls: 1, 0, else mixed (2)
+        template <class KernOf, class Args>
+        hipError_t launch_cls(int cls, KernOf kern_of, dim3 grid, size_t lds, hipStream_t st, const Args &g)
         {
-            static const bool on = !shl_ab_getenv("SEALHIP_NTT_NOFUSED_INT");
-            return on;
+            if (cls == 1)
+                hipLaunchKernelGGL(kern_of(std::integral_constant<int, 1>()), grid, dim3(kThreads), lds, st, g);
+            else if (cls == 0)
+                hipLaunchKernelGGL(kern_of(std::integral_constant<int, 0>()), grid, dim3(kThreads), lds, st, g);
+            else
+                hipLaunchKernelGGL(kern_of(std::integral_constant<int, 2>()), grid, dim3(kThreads), lds, st, g);
+            return hipGetLastError();
+        }
+        // A kernel's dynamic LDS raised above the default 64 KiB (gfx950 has 160 KiB per CU), once per kernel and PROCESS: the flag
+        // does not know about devices or threads - what every launcher here did on its own before.
+        template <auto Kern>
+        hipError_t raise_lds(size_t bytes)
+        {
+            static bool raised = false;
+            if (!raised)
+            {
+                if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+                    return hipErrorInvalidValue;
+                raised = true;
+            }
+            return hipSuccess;
+        }
+        // fn(std::integral_constant<int, D1>) for N = 2^log_n = 2^(D1 + 8)
+        template <class Fn>
+        hipError_t with_d1(int log_n, Fn fn)
+        {
+            switch (log_n)
+            {
+            case 13:
+                return fn(std::integral_constant<int, 5>());
+            case 14:
+                return fn(std::integral_constant<int, 6>());
+            case 15:
+                return fn(std::integral_constant<int, 7>());
+            case 16:
+                return fn(std::integral_constant<int, 8>());
+            default:
+                return hipErrorInvalidValue;
+            }
+        }
+        // Workgroups per component (gridDim.z) of the single-launch kernels (N = 2^13: two workgroups per CU; 2^14: one of 1024
+        // threads): a few loop iterations per workgroup so that the prefetch and the resident twiddles pay.
+        template <int D1>
+        unsigned fused_chunks(unsigned ncomp, unsigned nouter, bool inverse)
+        {
+            const unsigned want = D1 == 5 ? 2048 : 1024;
+            unsigned fchunks = (want + ncomp - 1) / ncomp;
+            // round 5 (profiles/r05_configs1_bisect.txt): the 2^13 inverse re-reads its phase-B twiddles per transform anyway, so
+            // long loops buy it nothing - about FOUR transforms per workgroup is its optimum (8192 polynomials: 2048 workgroups
+            // per component +3.3 % over 512; 4096 polynomials: 1024 = 512, 2048 - two transforms each - loses 5 %)
+            if (inverse && D1 == 5 && nouter / 4 > fchunks)
+                fchunks = nouter / 4;
+            if (const char *f = std::getenv("SEALHIP_NTT_FCHUNKS")) // tests: force the per-workgroup loop at small batches
+                fchunks = (unsigned)std::atoi(f) ? (unsigned)std::atoi(f) : 1;
+            if (fchunks > nouter)
+                fchunks = nouter;
+            if (fchunks > 65535) // gridDim.z (nouter / 4 is not bounded by `want`)
+                fchunks = 65535;
+            return fchunks;
         }
 
         // Which order pass 1 of a mapped-source transform takes (the plain rounding tails and the folded one).  This is the only
@@ -2174,17 +2085,16 @@ namespace sealhip
         // (ntt2_fwd_p1 / ntt2_tail2_p1, whose grid does not shrink with the batch) otherwise: small batches, a run of one target,
         // a mixed-class run.  SEALHIP_TAIL_P1_ORDER=0 / 1 forces the one or the other wherever the new kernel exists at all
         // (read once; tests/test_tail_order.py, tests/test_gpu_tail_order.py in fresh processes).
-#ifndef SEALHIP_SRC_P1T_MIN_WGS
-#define SEALHIP_SRC_P1T_MIN_WGS 512 // two workgroups per CU.  Headline step at N = 2^16, order forced either way (profiles/r08_tail_source_resident.txt):
-                                    // 64 / 128 workgroups -3 % / -1 %, 256 a tie, 512 +0.6 ... +1.2 %, 1024 (rotate + rescale, batch 32) +1.2 %, 2048 / 8192 +1.6 %
-#endif
+        // two workgroups per CU.  Headline step at N = 2^16, order forced either way (profiles/r08_tail_source_resident.txt):
+        // 64 / 128 workgroups -3 % / -1 %, 256 a tie, 512 +0.6 ... +1.2 %, 1024 (rotate + rescale, batch 32) +1.2 %, 2048 / 8192 +1.6 %
+        constexpr size_t kSrcP1tMinWgs = 512;
         inline bool src_resident(unsigned tiles, unsigned nouter, const CompRun &r)
         {
             static const char *order_env = std::getenv("SEALHIP_TAIL_P1_ORDER");
             // development builds: the threshold (the emulated tests cross it at batches they can finish) and one line per decision
             static const char *min_env = shl_ab_getenv("SEALHIP_TAIL_P1_MIN_WGS");
             static const bool trace = shl_ab_getenv("SEALHIP_TAIL_P1_TRACE") != nullptr;
-            static const size_t min_wgs = min_env ? (size_t)std::atol(min_env) : (size_t)SEALHIP_SRC_P1T_MIN_WGS;
+            static const size_t min_wgs = min_env ? (size_t)std::atol(min_env) : kSrcP1tMinWgs;
             bool yes = false;
             if (r.cls != 0 && r.cls != 1)
                 yes = false;
@@ -2219,10 +2129,9 @@ namespace sealhip
             // enough workgroups to fill the chip several times over, each looping over its share of
             // the outer items with the next tile in flight
             unsigned per = G::TILES * a.ncomp;
-#ifndef SEALHIP_NTT_WG_TARGET
-#define SEALHIP_NTT_WG_TARGET 8192 // round 5: 8192 workgroups per launch +1.3 % on the 2^16 leg over 4096 (four same-box rounds), 2048 -4 %, 16384 +1 % (profiles/r05_ntt_grid_variants.txt)
-#endif
-            unsigned chunks = (SEALHIP_NTT_WG_TARGET + per - 1) / per;
+            // round 5: 8192 workgroups per launch +1.3 % on the 2^16 leg over 4096 (four same-box rounds), 2048 -4 %, 16384 +1 % (profiles/r05_ntt_grid_variants.txt)
+            constexpr unsigned kWgTarget = 8192;
+            unsigned chunks = (kWgTarget + per - 1) / per;
             if (const char *f = shl_ab_getenv("SEALHIP_NTT_CHUNKS")) // development / emulated builds: force the per-workgroup loop at small batches
                 chunks = (unsigned)std::atoi(f) ? (unsigned)std::atoi(f) : 1;
             if (chunks > nouter)
@@ -2230,58 +2139,40 @@ namespace sealhip
             if (chunks > 65535)
                 chunks = 65535;
             size_t l1 = G::rA > 0 ? G::lds1_words * 8 : 8;
-            // single-launch kernels (plain in-place transforms, N = 2^13, 2^14); SEALHIP_NTT_NOFUSED=1 keeps the two-launch engine
+            // single-launch kernels of either back end (plain in-place transforms, N = 2^13, 2^14); everything else there, and the
+            // other sizes, take the two launches
             bool fused = false;
             unsigned fchunks = 1;
             if constexpr (D1 == 5 || D1 == 6)
             {
-                static const bool fused_ok = !shl_ab_getenv("SEALHIP_NTT_NOFUSED");
-                if (fused_ok && (!a.src || a.src_mode == 0) && a.epi == 0)
+                if ((!a.src || a.src_mode == 0) && a.epi == 0)
                 {
-                    static bool raised = false;
-                    if (!raised)
-                    {
-                        // above the default 64 KiB of dynamic LDS
-                        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt2_fwd_fused2<D1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedGeo<D1>::lds_bytes) != hipSuccess ||
-                            hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt2_fwd_fused2<D1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FusedGeo<D1, 2>::lds_bytes)) != hipSuccess)
-                            return hipErrorInvalidValue;
-                        raised = true;
-                    }
+                    if (raise_lds<&ntt2_fwd_fused2<D1, 1>>(FusedGeo<D1>::lds_bytes) != hipSuccess || raise_lds<&ntt2_fwd_fused2<D1, 0>>(FusedGeo<D1, 2>::lds_bytes) != hipSuccess)
+                        return hipErrorInvalidValue;
                     fused = true;
-                    // two workgroups per CU (N = 2^13) or one 1024-thread workgroup (N = 2^14);
-                    // a few loop iterations per workgroup so that the prefetch and the hoisted twiddles pay
-                    const unsigned want = D1 == 5 ? 2048 : 1024;
-                    fchunks = (want + a.ncomp - 1) / a.ncomp;
-                    if (const char *f = std::getenv("SEALHIP_NTT_FCHUNKS")) // tests: force the per-workgroup loop at small batches
-                        fchunks = (unsigned)std::atoi(f) ? (unsigned)std::atoi(f) : 1;
-                    if (fchunks > nouter)
-                        fchunks = nouter;
-                    if (fchunks > 65535)
-                        fchunks = 65535;
+                    fchunks = fused_chunks<D1>(a.ncomp, nouter, false);
                 }
             }
             return launch_runs(comp_runs(a.t, a.comp_prime, a.prime_first, a.ncomp, a.cls_hint), s, [&](const CompRun &r, hipStream_t st) {
                 FwdArgs g = a;
                 g.comp0 = r.c0;
-#ifndef SEALHIP_MID_PACK
-#define SEALHIP_MID_PACK 1
-#endif
                 // N = 2^16, plain transform, double-precision components: the intermediate in 13 words per 16 values (kPackWords)
                 // (only together with the hoisted pass 2, i.e. when the workgroups loop: the small-batch kernels stay as they are)
-                g.mid_pack = SEALHIP_MID_PACK && D1 == 8 && r.cls == 1 && a.epi == 0 && chunks < nouter ? 1 : 0;
+                g.mid_pack = D1 == 8 && r.cls == 1 && a.epi == 0 && chunks < nouter ? 1 : 0;
                 if constexpr (D1 == 5 || D1 == 6)
                 {
+                    // (workgroups per component of the integer class alone, 256 ... 4096 at 4096 polynomials: the default is the best
+                    // or equal, profiles/r05_configs1_bisect.txt)
+                    const dim3 fgrid(1, r.nc, fchunks), fthreads(FusedGeo<D1>::TEAMS * kThreads);
+                    constexpr size_t lds_fp = FusedGeo<D1>::lds_bytes, lds_int = FusedGeo<D1, 2>::lds_bytes;
                     if (fused && r.cls == 1)
                     {
-                        hipLaunchKernelGGL((ntt2_fwd_fused2<D1, 1>), dim3(1, r.nc, fchunks), dim3(FusedGeo<D1>::TEAMS * kThreads), FusedGeo<D1>::lds_bytes, st, g);
+                        hipLaunchKernelGGL((ntt2_fwd_fused2<D1, 1>), fgrid, fthreads, lds_fp, st, g);
                         return hipGetLastError();
                     }
-                    if (fused && r.cls == 0 && fused_int())
+                    if (fused && r.cls == 0)
                     {
-                        constexpr size_t lds_int = FusedGeo<D1, 2>::lds_bytes;
-                        // (workgroups per component of the integer class alone, 256 ... 4096 at 4096 polynomials: the default is the best
-                        // or equal, profiles/r05_configs1_bisect.txt)
-                        hipLaunchKernelGGL((ntt2_fwd_fused2<D1, 0>), dim3(1, r.nc, fchunks), dim3(FusedGeo<D1>::TEAMS * kThreads), lds_int, st, g);
+                        hipLaunchKernelGGL((ntt2_fwd_fused2<D1, 0>), fgrid, fthreads, lds_int, st, g);
                         return hipGetLastError();
                     }
                 }
@@ -2312,34 +2203,18 @@ namespace sealhip
                     }
                 }
                 // one source component mapped into every target (plain rescale / mod-switch, the un-deferred key-switch tail)
-                if (a.src && (a.src_mode == 2 || a.src_mode == 3) && a.src_ncomp == 1 && src_resident(G::TILES, nouter, r))
-                {
-                    hipError_t e1 = launch_src_p1t<D1, false>(Tail2Args{ g, NttTail2{} }, r, nouter, st);
-                    if (e1 != hipSuccess)
-                        return e1;
-                }
-                else if (r.cls == 1)
-                    hipLaunchKernelGGL((ntt2_fwd_p1<D1, 1>), grid, dim3(kThreads), l1, st, g);
-                else if (r.cls == 0)
-                    hipLaunchKernelGGL((ntt2_fwd_p1<D1, 0>), grid, dim3(kThreads), l1, st, g);
-                else
-                    hipLaunchKernelGGL((ntt2_fwd_p1<D1, 2>), grid, dim3(kThreads), l1, st, g);
-                hipError_t e = hipGetLastError();
+                const hipError_t e = a.src && (a.src_mode == 2 || a.src_mode == 3) && a.src_ncomp == 1 && src_resident(G::TILES, nouter, r)
+                                         ? launch_src_p1t<D1, false>(Tail2Args{ g, NttTail2{} }, r, nouter, st)
+                                         : launch_cls(r.cls, [](auto c) { return ntt2_fwd_p1<D1, decltype(c)::value>; }, grid, l1, st, g);
                 if (e != hipSuccess)
                     return e;
-                static const int p2_hoist = shl_ab_getenv("SEALHIP_P2_HOIST") ? std::atoi(shl_ab_getenv("SEALHIP_P2_HOIST")) : 4;
-                if (r.cls == 1 && a.epi == 0 && chunks < nouter && p2_hoist == 4)
+                if (r.cls == 1 && a.epi == 0 && chunks < nouter) // the workgroups loop: twiddles resident
+                {
                     hipLaunchKernelGGL((ntt2_fwd_p2<D1, 4>), grid, dim3(kThreads), (kLds2Words + 240) * 8, st, g);
-                else if (r.cls == 1 && a.epi == 0 && chunks < nouter && p2_hoist == 3)
-                    hipLaunchKernelGGL((ntt2_fwd_p2<D1, 3>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                else if (r.cls == 1)
-                    hipLaunchKernelGGL((ntt2_fwd_p2<D1, 1>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                else if (r.cls == 0)
-                    hipLaunchKernelGGL((ntt2_fwd_p2<D1, 0>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                else
-                    hipLaunchKernelGGL((ntt2_fwd_p2<D1, 2>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                return hipGetLastError();
-            }, !(fused && fused_int()) || (D1 == 6 && SEALHIP_FUSED_FORK14));
+                    return hipGetLastError();
+                }
+                return launch_cls(r.cls, [](auto c) { return ntt2_fwd_p2<D1, decltype(c)::value>; }, grid, kLds2Words * 8, st, g);
+            }, !fused || D1 == 6);
             // single-launch kernels of both classes at 2^13: one after the other (at 2^14 a CU holds ONE 1024-thread workgroup of either class,
             // side by side costs nothing and the mixed chain {60,6x50,60} runs at 0.32 / 0.34 instead of 0.29 / 0.29).  Side by side at 2^13 a CU holds one workgroup of each (LDS), and
             // each class loses the partner workgroup that covers its latencies: measured at configs[1]'s chain {60,40,40,60}, 8192
@@ -2351,10 +2226,8 @@ namespace sealhip
         {
             typedef Geo<D1> G;
             unsigned per = G::TILES * a.f.ncomp;
-#ifndef SEALHIP_TAIL2_WG_TARGET
-#define SEALHIP_TAIL2_WG_TARGET 4096
-#endif
-            unsigned chunks = (SEALHIP_TAIL2_WG_TARGET + per - 1) / per;
+            constexpr unsigned kWgTarget = 4096; // workgroups per launch (as launch_fwd's)
+            unsigned chunks = (kWgTarget + per - 1) / per;
             if (chunks > nouter)
                 chunks = nouter;
             if (chunks > 65535)
@@ -2364,28 +2237,11 @@ namespace sealhip
                 Tail2Args g = a;
                 g.f.comp0 = r.c0;
                 dim3 grid(G::TILES, r.nc, chunks);
-                if (src_resident(G::TILES, nouter, r))
-                {
-                    hipError_t e1 = launch_src_p1t<D1, true>(g, r, nouter, st);
-                    if (e1 != hipSuccess)
-                        return e1;
-                }
-                else if (r.cls == 1)
-                    hipLaunchKernelGGL((ntt2_tail2_p1<D1, 1>), grid, dim3(kThreads), l1, st, g);
-                else if (r.cls == 0)
-                    hipLaunchKernelGGL((ntt2_tail2_p1<D1, 0>), grid, dim3(kThreads), l1, st, g);
-                else
-                    hipLaunchKernelGGL((ntt2_tail2_p1<D1, 2>), grid, dim3(kThreads), l1, st, g);
-                hipError_t e = hipGetLastError();
+                const hipError_t e = src_resident(G::TILES, nouter, r) ? launch_src_p1t<D1, true>(g, r, nouter, st)
+                                                                        : launch_cls(r.cls, [](auto c) { return ntt2_tail2_p1<D1, decltype(c)::value>; }, grid, l1, st, g);
                 if (e != hipSuccess)
                     return e;
-                if (r.cls == 1)
-                    hipLaunchKernelGGL((ntt2_tail2_p2<D1, 1>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                else if (r.cls == 0)
-                    hipLaunchKernelGGL((ntt2_tail2_p2<D1, 0>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                else
-                    hipLaunchKernelGGL((ntt2_tail2_p2<D1, 2>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                return hipGetLastError();
+                return launch_cls(r.cls, [](auto c) { return ntt2_tail2_p2<D1, decltype(c)::value>; }, grid, kLds2Words * 8, st, g);
             });
         }
 
@@ -2397,31 +2253,12 @@ namespace sealhip
             unsigned fchunks = 1;
             if constexpr (D1 == 5 || D1 == 6)
             {
-                static const bool fused_ok = !shl_ab_getenv("SEALHIP_NTT_NOFUSED");
-                if (fused_ok && !a.prod_x && !a.src_gal) // (the product and automorphism sources are features of the two-pass kernels)
+                if (!a.prod_x && !a.src_gal) // (the product and automorphism sources are features of the two-pass kernels)
                 {
-                    static bool raised = false;
-                    if (!raised)
-                    {
-                        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt2_inv_fused2<D1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FusedGeo<D1>::lds_bytes) != hipSuccess ||
-                            hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt2_inv_fused2<D1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FusedGeo<D1, 2>::lds_bytes)) != hipSuccess)
-                            return hipErrorInvalidValue;
-                        raised = true;
-                    }
+                    if (raise_lds<&ntt2_inv_fused2<D1, 1>>(FusedGeo<D1>::lds_bytes) != hipSuccess || raise_lds<&ntt2_inv_fused2<D1, 0>>(FusedGeo<D1, 2>::lds_bytes) != hipSuccess)
+                        return hipErrorInvalidValue;
                     fused = true;
-                    const unsigned want = D1 == 5 ? 2048 : 1024;
-                    fchunks = (want + a.ncomp - 1) / a.ncomp;
-                    // round 5 (profiles/r05_configs1_bisect.txt): the 2^13 inverse re-reads its phase-B twiddles per transform anyway, so
-                    // long loops buy it nothing - about FOUR transforms per workgroup is its optimum (8192 polynomials: 2048 workgroups
-                    // per component +3.3 % over 512; 4096 polynomials: 1024 = 512, 2048 - two transforms each - loses 5 %)
-                    if (D1 == 5 && nouter / 4 > fchunks)
-                        fchunks = nouter / 4;
-                    if (const char *f = std::getenv("SEALHIP_NTT_FCHUNKS"))
-                        fchunks = (unsigned)std::atoi(f) ? (unsigned)std::atoi(f) : 1;
-                    if (fchunks > nouter)
-                        fchunks = nouter;
-                    if (fchunks > 65535) // gridDim.z (nouter / 4 is not bounded by `want` any more)
-                        fchunks = 65535;
+                    fchunks = fused_chunks<D1>(a.ncomp, nouter, true);
                 }
             }
             return launch_runs(comp_runs(a.t, a.comp_prime, a.prime_first, a.ncomp, a.cls_hint), s, [&](const CompRun &r, hipStream_t st) {
@@ -2430,46 +2267,25 @@ namespace sealhip
                 g.nouter = nouter;
                 if constexpr (D1 == 5 || D1 == 6)
                 {
+                    const dim3 fgrid(1, r.nc, fchunks), fthreads(FusedGeo<D1>::TEAMS * kThreads);
+                    constexpr size_t lds_fp = FusedGeo<D1>::lds_bytes, lds_int = FusedGeo<D1, 2>::lds_bytes;
                     if (fused && r.cls == 1)
                     {
-                        hipLaunchKernelGGL((ntt2_inv_fused2<D1, 1>), dim3(1, r.nc, fchunks), dim3(FusedGeo<D1>::TEAMS * kThreads), FusedGeo<D1>::lds_bytes, st, g);
+                        hipLaunchKernelGGL((ntt2_inv_fused2<D1, 1>), fgrid, fthreads, lds_fp, st, g);
                         return hipGetLastError();
                     }
-                    if (fused && r.cls == 0 && fused_int())
+                    if (fused && r.cls == 0)
                     {
-                        constexpr size_t lds_int = FusedGeo<D1, 2>::lds_bytes;
-                        hipLaunchKernelGGL((ntt2_inv_fused2<D1, 0>), dim3(1, r.nc, fchunks), dim3(FusedGeo<D1>::TEAMS * kThreads), lds_int, st, g);
+                        hipLaunchKernelGGL((ntt2_inv_fused2<D1, 0>), fgrid, fthreads, lds_int, st, g);
                         return hipGetLastError();
                     }
                 }
                 dim3 grid(G::TILES, r.nc, nouter);
-                if (r.cls == 1)
-                    hipLaunchKernelGGL((ntt2_inv_pa<D1, 1>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                else if (r.cls == 0)
-                    hipLaunchKernelGGL((ntt2_inv_pa<D1, 0>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                else
-                    hipLaunchKernelGGL((ntt2_inv_pa<D1, 2>), grid, dim3(kThreads), kLds2Words * 8, st, g);
-                hipError_t e = hipGetLastError();
+                const hipError_t e = launch_cls(r.cls, [](auto c) { return ntt2_inv_pa<D1, decltype(c)::value>; }, grid, kLds2Words * 8, st, g);
                 if (e != hipSuccess)
                     return e;
-                // development builds, TIMING ONLY (wrong words): the step without the inverse transforms' last pass - the most that
-                // fusing it into the next kernel's prologue could return (profiles/r05_inv_pb_fusion_bound.txt)
-                // (value = number of inverse launches that still run it: the warm-up leaves realistic words in the recycled buffers -
-                // with stale zeros in them the key switch's arithmetic draws less power and the chip clocks 10 % higher, which is not
-                // the saving being measured)
-                static const char *skip_env = shl_ab_getenv("SEALHIP_AB_SKIP_INV_PB");
-                static long skip_after = skip_env ? std::atol(skip_env) : -1;
-                static std::atomic<long> inv_launches{ 0 };
-                if (skip_after >= 0 && inv_launches.fetch_add(1) >= skip_after)
-                    return (hipError_t)hipSuccess;
-                if (r.cls == 1)
-                    hipLaunchKernelGGL((ntt2_inv_pb<D1, 1>), grid, dim3(kThreads), G::lds1_words * 8, st, g);
-                else if (r.cls == 0)
-                    hipLaunchKernelGGL((ntt2_inv_pb<D1, 0>), grid, dim3(kThreads), G::lds1_words * 8, st, g);
-                else
-                    hipLaunchKernelGGL((ntt2_inv_pb<D1, 2>), grid, dim3(kThreads), G::lds1_words * 8, st, g);
-                return hipGetLastError();
-            }, !(fused && fused_int()) || (D1 == 6 && SEALHIP_FUSED_FORK14));
+                return launch_cls(r.cls, [](auto c) { return ntt2_inv_pb<D1, decltype(c)::value>; }, grid, G::lds1_words * 8, st, g);
+            }, !fused || D1 == 6); // (launch_fwd's note on the classes side by side)
         }
 
         template <int D1>
@@ -2482,29 +2298,11 @@ namespace sealhip
             const unsigned vbatch = batch * a1.parts; // (digit group, batch item) pairs
             const unsigned groups = vbatch * G::TILES;
             const unsigned n_fp = a1.ntargets - n_int;
-            const size_t l2_fp = kLds2Words * 8 + (240 + 3840) * sizeof(double); // the tile's twiddles staged in LDS
-            const size_t l2_int = kLds2Words * 8 + (240 + (SEALHIP_KS2_INT_TWB3 ? 2048 : 0)) * sizeof(ShoupOp);
-            if (n_int && l2_int > 65536)
-            {
-                static bool raised_int = false;
-                if (!raised_int)
-                {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&ks2_kernel<D1, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2_int) != hipSuccess)
-                        return hipErrorInvalidValue;
-                    raised_int = true;
-                }
-            }
-            if (n_fp && l2_fp > 65536)
-            {
-                // more than the default 64 KiB of dynamic LDS per workgroup (gfx950 has 160 KiB per CU)
-                static bool raised = false;
-                if (!raised)
-                {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&ks2_kernel<D1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2_fp) != hipSuccess)
-                        return hipErrorInvalidValue;
-                    raised = true;
-                }
-            }
+            // the tile's twiddles staged in LDS (ks2_body): both phases' / phase A's and the last stage's.  68 and 72 KiB
+            constexpr size_t l2_fp = kLds2Words * 8 + (240 + 3840) * sizeof(double), l2_int = kLds2Words * 8 + (240 + 2048) * sizeof(ShoupOp);
+            static_assert(l2_fp > 65536 && l2_int > 65536, "above the default: raised below");
+            if ((n_int && raise_lds<&ks2_kernel<D1, 0>>(l2_int) != hipSuccess) || (n_fp && raise_lds<&ks2_kernel<D1, 1>>(l2_fp) != hipSuccess))
+                return hipErrorInvalidValue;
             // both passes for the targets of one arithmetic class (targets = [integer moduli..., double-precision moduli...])
             auto run_class = [&](bool fp, hipStream_t st) -> hipError_t {
                 const unsigned t0 = fp ? n_int : 0, nt = fp ? n_fp : n_int;
@@ -2562,21 +2360,10 @@ namespace sealhip
             // The integer-back-end targets (60-bit moduli) are latency-bound at two waves per SIMD, the
             // double-precision ones are issue-bound: on two streams their workgroups share the CUs.
             SideStream &ss = side_stream();
-            static const bool fork_ok = !shl_ab_getenv("SEALHIP_KS_NOFORK");
-            hipError_t e;
-            if (n_int && n_fp && ss.ok && fork_ok && !no_class_fork)
-            {
-                if ((e = hipEventRecord(ss.fork, s)) != hipSuccess || (e = hipStreamWaitEvent(ss.stream, ss.fork, 0)) != hipSuccess)
-                    return e;
-                if ((e = run_class(false, ss.stream)) != hipSuccess || (e = hipEventRecord(ss.join, ss.stream)) != hipSuccess)
-                    return e;
-                if ((e = run_class(true, s)) != hipSuccess)
-                    return e;
-                return hipStreamWaitEvent(s, ss.join, 0);
-            }
-            if ((e = run_class(false, s)) != hipSuccess)
-                return e;
-            return run_class(true, s);
+            if (n_int && n_fp && ss.ok && !no_class_fork)
+                return fork_join(ss, s, [&](hipStream_t st) { return run_class(false, st); }, [&](hipStream_t st) { return run_class(true, st); });
+            const hipError_t e = run_class(false, s);
+            return e != hipSuccess ? e : run_class(true, s);
         }
     } // namespace
 
@@ -2641,34 +2428,10 @@ namespace sealhip
             // NttTail2: mapped source 2 + the double-division tail; prime of a component = prime_first + comp
             if (!b.src || (b.src_mode != 2 && b.src_mode != 3) || b.comp_prime || !b.epi_a || !b.epi_mul || !b.epi_out0 || !b.epi_out1)
                 return hipErrorInvalidValue;
-            Tail2Args t2{ a, *b.tail2 };
-            switch (t.log_n)
-            {
-            case 13:
-                return launch_tail2<5>(t2, b.nouter, stream);
-            case 14:
-                return launch_tail2<6>(t2, b.nouter, stream);
-            case 15:
-                return launch_tail2<7>(t2, b.nouter, stream);
-            case 16:
-                return launch_tail2<8>(t2, b.nouter, stream);
-            default:
-                return hipErrorInvalidValue;
-            }
+            const Tail2Args t2{ a, *b.tail2 };
+            return with_d1(t.log_n, [&](auto d) { return launch_tail2<decltype(d)::value>(t2, b.nouter, stream); });
         }
-        switch (t.log_n)
-        {
-        case 13:
-            return launch_fwd<5>(a, b.nouter, stream);
-        case 14:
-            return launch_fwd<6>(a, b.nouter, stream);
-        case 15:
-            return launch_fwd<7>(a, b.nouter, stream);
-        case 16:
-            return launch_fwd<8>(a, b.nouter, stream);
-        default:
-            return hipErrorInvalidValue;
-        }
+        return with_d1(t.log_n, [&](auto d) { return launch_fwd<decltype(d)::value>(a, b.nouter, stream); });
     }
 
     hipError_t ntt2_inverse(const NttTables &t, const NttBatch &b, int out_lazy, uint64_t *mid, hipStream_t stream)
@@ -2720,24 +2483,7 @@ namespace sealhip
             az.data = a.data + (size_t)z0 * a.outer_stride;
             az.src = a.src + (size_t)z0 * a.src_outer_stride;
             az.mid = a.mid + (((size_t)z0 * a.ncomp) << t.log_n);
-            hipError_t e;
-            switch (t.log_n)
-            {
-            case 13:
-                e = launch_inv<5>(az, nz, stream);
-                break;
-            case 14:
-                e = launch_inv<6>(az, nz, stream);
-                break;
-            case 15:
-                e = launch_inv<7>(az, nz, stream);
-                break;
-            case 16:
-                e = launch_inv<8>(az, nz, stream);
-                break;
-            default:
-                return hipErrorInvalidValue;
-            }
+            const hipError_t e = with_d1(t.log_n, [&](auto d) { return launch_inv<decltype(d)::value>(az, nz, stream); });
             if (e != hipSuccess)
                 return e;
         }
@@ -2787,19 +2533,7 @@ namespace sealhip
         if (k.galois_elt && (!(k.galois_elt & 1) || !k.target_ntt || !k.fold_c0 || k.fold_c1 || k.fold_x))
             return hipErrorInvalidValue; // a rotation: target and first addend through the index map, the second addend zero
         a2.tb = t;
-        switch (t.log_n)
-        {
-        case 13:
-            return launch_ks<5>(a1, a2, k.batch, k.n_int, stream, k.order1, k.no_class_fork);
-        case 14:
-            return launch_ks<6>(a1, a2, k.batch, k.n_int, stream, k.order1, k.no_class_fork);
-        case 15:
-            return launch_ks<7>(a1, a2, k.batch, k.n_int, stream, k.order1, k.no_class_fork);
-        case 16:
-            return launch_ks<8>(a1, a2, k.batch, k.n_int, stream, k.order1, k.no_class_fork);
-        default:
-            return hipErrorInvalidValue;
-        }
+        return with_d1(t.log_n, [&](auto d) { return launch_ks<decltype(d)::value>(a1, a2, k.batch, k.n_int, stream, k.order1, k.no_class_fork); });
     }
 
     hipError_t key_to_register_order(const NttTables &t, const uint64_t *in, uint64_t *out, unsigned L, size_t digits, hipStream_t stream)

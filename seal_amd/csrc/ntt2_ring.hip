@@ -98,7 +98,7 @@ namespace sealhip
                 const uint64_t *in = in0 + (size_t)(slice + k * Z) * a.outer_stride;
 #pragma unroll
                 for (int e = 0; e < 16; e++)
-                    nxt[e] = mid_ld<16>(in + (size_t)(e * 16 + hi) * 256);
+                    nxt[e] = mid_ld(in + (size_t)(e * 16 + hi) * 256);
             };
             auto window = [](const uint64_t *p) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint64_t *>(p), 0, 0x7fffffff, 0x00020000); };
             auto fetch_b = [&](unsigned j) {
@@ -228,7 +228,7 @@ namespace sealhip
                     fetch_a(k + 1);
                 if (run2)
                 {
-                    p2_tile<true, D1, false, false, true, true>(x, m, tab, twa, nullptr, lds_wave, tile, tid, nullptr, &pre_b);
+                    p2_tile<true, D1, false, false, true, true>(x, m, tab, twa, nullptr, lds_wave, tile, tid, &pre_b);
                     constexpr int BOUT = kP2Out<0, D1>;
                     uint64_t val[16];
 #pragma unroll
@@ -343,7 +343,7 @@ namespace sealhip
                     const uint64_t *in = in0 + (size_t)(slice + k * Z) * a.outer_stride;
 #pragma unroll
                     for (int e = 0; e < 16; e++)
-                        nxt[e] = mid_ld<16>(in + (size_t)(e * 16 + hi) * 256);
+                        nxt[e] = mid_ld(in + (size_t)(e * 16 + hi) * 256);
                 };
                 __syncthreads(); // s_have
                 if (iters)
@@ -453,7 +453,7 @@ namespace sealhip
                         if (wave == 0 && lane < 32)
                             polled = __hip_atomic_load(prog + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
-                    p2_tile<true, D1, false, false, true, true>(x, m, tab, twa, nullptr, lds_wave, tile, tid, nullptr, &pre_b);
+                    p2_tile<true, D1, false, false, true, true>(x, m, tab, twa, nullptr, lds_wave, tile, tid, &pre_b);
                     constexpr int BOUT = kP2Out<0, D1>;
                     uint64_t val[16];
 #pragma unroll

@@ -10,14 +10,12 @@ namespace sealhip
     namespace
     {
         constexpr unsigned kBlock = 256;
-#ifndef SEALHIP_EW_GRID_CAP
-#define SEALHIP_EW_GRID_CAP 2048
-#endif
+        constexpr size_t kGridCap = 2048; // workgroups of a grid-stride element-wise kernel
         inline unsigned grid_for(size_t work)
         {
             size_t b = (work + kBlock - 1) / kBlock;
-            if (b > SEALHIP_EW_GRID_CAP)
-                b = SEALHIP_EW_GRID_CAP;
+            if (b > kGridCap)
+                b = kGridCap;
             if (b == 0)
                 b = 1;
             return (unsigned)b;
@@ -606,15 +604,12 @@ namespace sealhip
         hipStream_t s)
     {
         size_t w = g.words();
-#ifndef SEALHIP_TENSOR_WIDE
-#define SEALHIP_TENSOR_WIDE 1
-#endif
         // large batches: one 4 KiB chunk per workgroup, 16 bytes per thread (ckks_multiply_2x2_wide_kernel); the grid-stride kernel keeps
         // the small ones, where a launch of a few workgroups is all there is
         const size_t pairs = w / 2, wide_blocks = (pairs + kBlock - 1) / kBlock;
         static const char *min_env = shl_ab_getenv("SEALHIP_TENSOR_WIDE_MIN"); // development / emulated builds: take the wide kernel from this many workgroups on
         const size_t wide_min = min_env ? (size_t)std::atol(min_env) : 2048;
-        if (SEALHIP_TENSOR_WIDE && g.n_log >= 7 && w % 2 == 0 && wide_blocks > wide_min && wide_blocks < (size_t)0x7fffffff &&
+        if (g.n_log >= 7 && w % 2 == 0 && wide_blocks > wide_min && wide_blocks < (size_t)0x7fffffff &&
             ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && ((uintptr_t)out % 16 == 0))
         {
             hipLaunchKernelGGL(ckks_multiply_2x2_wide_kernel, dim3((unsigned)wide_blocks), dim3(kBlock), 0, s, mods, fpd, comp_prime, x, y, out,

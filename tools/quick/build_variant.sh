@@ -1,6 +1,6 @@
 #!/bin/bash
 # build seal_amd/lib/variants/NAME.so = the product library with some kernel sources compiled with extra flags
-# usage: tools/quick/build_variant.sh NAME "-DSEALHIP_KS_NT=15 ..." [FILES="ntt2_kernels.hip evaluator_keyswitch.cpp"]   (default: ntt2_kernels.hip)
+# usage: tools/quick/build_variant.sh NAME "EXTRA HIPCC FLAGS" [FILES="ntt2_kernels.hip evaluator_keyswitch.cpp"]   (default: ntt2_kernels.hip)
 # every listed file is also compiled with -DSEALHIP_AB_SWITCHES: its development environment switches (shl_ab_getenv) work in the variant
 set -eu
 NAME=$1; FLAGS=${2:-}; FILES=${3:-ntt2_kernels.hip}
