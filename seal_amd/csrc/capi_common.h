@@ -12,6 +12,7 @@
 #include "xof.h"
 #include <atomic>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 
@@ -99,5 +100,22 @@ namespace
         if (src != dst)
             *dst = *src;
         return *dst;
+    }
+
+    // The body of an Evaluator_* operation (capi_evaluator.cpp): E_POINTER when thisptr or one of `handles` is null - the handles an
+    // entry dereferences itself; a pointer the C++ layer refuses (std::invalid_argument) is not listed.  Then body(evaluator) runs
+    // inside the exception ladder and under a StreamScope on the evaluator's stream: the one scope an operation needs, whichever
+    // thread calls (evaluator.h: Evaluator::stream_).  A template, so outside every extern "C" block.
+    template <class Body>
+    SHL_HRESULT ev_call(void *thisptr, std::initializer_list<const void *> handles, Body body)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        for (const void *handle : handles)
+            IfNullRet(handle, SHL_E_POINTER);
+        SHL_TRY
+        Evaluator &ev = *as<Evaluator>(thisptr);
+        StreamScope stream_scope(ev.stream());
+        body(ev);
+        SHL_CATCH
     }
 } // namespace

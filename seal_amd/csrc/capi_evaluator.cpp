@@ -2,6 +2,48 @@
 #include "capi_common.h"
 #include "batch_reduce_kernels.h"
 
+namespace
+{
+    // what a handle is (checked by ev_call before a body runs)
+    Ciphertext &ct(void *p)
+    {
+        return *as<Ciphertext>(p);
+    }
+    Plaintext &pt(void *p)
+    {
+        return *as<Plaintext>(p);
+    }
+    KSwitchKeys &keys(void *p)
+    {
+        return *as<KSwitchKeys>(p);
+    }
+    Plaintext &prepare_plain_dest(void *plain, void *destination)
+    {
+        Plaintext *src = as<Plaintext>(plain), *dst = as<Plaintext>(destination);
+        if (src != dst)
+            *dst = *src;
+        return *dst;
+    }
+    std::vector<const Ciphertext *> ct_list(uint64_t count, void **encrypteds)
+    {
+        std::vector<const Ciphertext *> v;
+        for (uint64_t i = 0; i < count; i++)
+            v.push_back(as<Ciphertext>(encrypteds[i]));
+        return v;
+    }
+    void check_flags(uint64_t flags, uint64_t defined)
+    {
+        if (flags & ~defined)
+            throw std::invalid_argument("unknown flags");
+    }
+    Evaluator::KsExchange exchange_of(int how)
+    {
+        if (how != 0 && how != 1)
+            throw std::invalid_argument("exchange: 0 = all-reduce, 1 = reduce-scatter + all-gather");
+        return how ? Evaluator::KsExchange::reduce_scatter : Evaluator::KsExchange::all_reduce;
+    }
+} // namespace
+
 extern "C"
 {
     // ------------------------------------------------------------------ KSwitchKeys
@@ -85,6 +127,8 @@ extern "C"
     }
 
     // ------------------------------------------------------------------ Evaluator
+    // Lifetime, stream and recording are not operations: they run outside ev_call's scope (set_stream and the recording change the
+    // stream that scope would be on).  Every operation below is one ev_call: the handles whose NULL is E_POINTER, and the call.
     SHL_FUNC Evaluator_Create(void *context, void **evaluator)
     {
         IfNullRet(context, SHL_E_POINTER);
@@ -123,12 +167,7 @@ extern "C"
     }
     SHL_FUNC Evaluator_LaunchGraph(void *thisptr, void *graph)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(graph, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->launch_graph(static_cast<const Evaluator::Graph *>(graph));
-        SHL_CATCH
+        return ev_call(thisptr, { graph }, [&](Evaluator &ev) { ev.launch_graph(static_cast<const Evaluator::Graph *>(graph)); });
     }
     SHL_FUNC Graph_Destroy(void *graph)
     {
@@ -142,150 +181,117 @@ extern "C"
         as<Evaluator>(thisptr)->set_transparent_check(enabled);
         return SHL_S_OK;
     }
+    SHL_FUNC Evaluator_ContextUsingKeyswitching(void *thisptr, bool *using_keyswitching)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        IfNullRet(using_keyswitching, SHL_E_POINTER);
+        *using_keyswitching = as<Evaluator>(thisptr)->context().using_keyswitching();
+        return SHL_S_OK;
+    }
     // destination := encrypted on the evaluator's stream (a pipeline with several evaluators / streams copies its inputs in
     // stream order; Ciphertext_Set works on the calling thread's stream)
     SHL_FUNC Evaluator_CopyTo(void *thisptr, void *encrypted, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        if (encrypted != destination)
-            *as<Ciphertext>(destination) = *as<Ciphertext>(encrypted);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &) { prepare_dest(encrypted, destination); });
     }
     SHL_FUNC Evaluator_Synchronize(void *thisptr)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->synchronize();
-        SHL_CATCH
+        return ev_call(thisptr, {}, [&](Evaluator &ev) { ev.synchronize(); });
     }
-#define EV_UNARY(fn, call)                                           \
-    SHL_FUNC fn(void *thisptr, void *encrypted, void *destination)   \
-    {                                                                \
-        IfNullRet(thisptr, SHL_E_POINTER);                           \
-        IfNullRet(encrypted, SHL_E_POINTER);                         \
-        IfNullRet(destination, SHL_E_POINTER);                       \
-        SHL_TRY                                                      \
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());   \
-        auto ev = as<Evaluator>(thisptr);                            \
-        Ciphertext &d = prepare_dest(encrypted, destination);        \
-        ev->call(d);                                                 \
-        SHL_CATCH                                                    \
+    SHL_FUNC Evaluator_Negate(void *thisptr, void *encrypted, void *destination)
+    {
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) { ev.negate_inplace(prepare_dest(encrypted, destination)); });
     }
-#define EV_UNARY_POOL(fn, call)                                                  \
-    SHL_FUNC fn(void *thisptr, void *encrypted, void *destination, void *pool)   \
-    {                                                                            \
-        (void)pool;                                                              \
-        IfNullRet(thisptr, SHL_E_POINTER);                                       \
-        IfNullRet(encrypted, SHL_E_POINTER);                                     \
-        IfNullRet(destination, SHL_E_POINTER);                                   \
-        SHL_TRY                                                                  \
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());               \
-        auto ev = as<Evaluator>(thisptr);                                        \
-        Ciphertext &d = prepare_dest(encrypted, destination);                    \
-        ev->call(d);                                                             \
-        SHL_CATCH                                                                \
+    SHL_FUNC Evaluator_TransformToNTT2(void *thisptr, void *encrypted, void *destination)
+    {
+        return ev_call(thisptr, { encrypted, destination },
+                       [&](Evaluator &ev) { ev.transform_to_ntt_inplace(prepare_dest(encrypted, destination)); });
     }
-    EV_UNARY(Evaluator_Negate, negate_inplace)
-    EV_UNARY(Evaluator_TransformToNTT2, transform_to_ntt_inplace)
-    EV_UNARY(Evaluator_TransformFromNTT, transform_from_ntt_inplace)
-    EV_UNARY_POOL(Evaluator_Square, square_inplace)
-    EV_UNARY_POOL(Evaluator_ModSwitchToNext1, mod_switch_to_next_inplace)
-    EV_UNARY_POOL(Evaluator_RescaleToNext, rescale_to_next_inplace)
-    EV_UNARY_POOL(Evaluator_ModReduceToNext, mod_reduce_to_next_inplace)
+    SHL_FUNC Evaluator_TransformFromNTT(void *thisptr, void *encrypted, void *destination)
+    {
+        return ev_call(thisptr, { encrypted, destination },
+                       [&](Evaluator &ev) { ev.transform_from_ntt_inplace(prepare_dest(encrypted, destination)); });
+    }
+    SHL_FUNC Evaluator_Square(void *thisptr, void *encrypted, void *destination, void *)
+    {
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) { ev.square_inplace(prepare_dest(encrypted, destination)); });
+    }
+    SHL_FUNC Evaluator_ModSwitchToNext1(void *thisptr, void *encrypted, void *destination, void *)
+    {
+        return ev_call(thisptr, { encrypted, destination },
+                       [&](Evaluator &ev) { ev.mod_switch_to_next_inplace(prepare_dest(encrypted, destination)); });
+    }
+    SHL_FUNC Evaluator_RescaleToNext(void *thisptr, void *encrypted, void *destination, void *)
+    {
+        return ev_call(thisptr, { encrypted, destination },
+                       [&](Evaluator &ev) { ev.rescale_to_next_inplace(prepare_dest(encrypted, destination)); });
+    }
+    SHL_FUNC Evaluator_ModReduceToNext(void *thisptr, void *encrypted, void *destination, void *)
+    {
+        return ev_call(thisptr, { encrypted, destination },
+                       [&](Evaluator &ev) { ev.mod_reduce_to_next_inplace(prepare_dest(encrypted, destination)); });
+    }
 
     // ------------------------------------------------------------------ plaintext operands, many-operand forms
-#define EV_PLAIN(fn, call)                                                       \
-    SHL_FUNC fn(void *thisptr, void *encrypted, void *plain, void *destination)  \
-    {                                                                            \
-        IfNullRet(thisptr, SHL_E_POINTER);                                       \
-        IfNullRet(encrypted, SHL_E_POINTER);                                     \
-        IfNullRet(plain, SHL_E_POINTER);                                         \
-        IfNullRet(destination, SHL_E_POINTER);                                   \
-        SHL_TRY                                                                  \
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());               \
-        as<Evaluator>(thisptr)->call(prepare_dest(encrypted, destination), *as<Plaintext>(plain)); \
-        SHL_CATCH                                                                \
-    }
-    EV_PLAIN(Evaluator_AddPlain, add_plain_inplace)
-    EV_PLAIN(Evaluator_SubPlain, sub_plain_inplace)
-    SHL_FUNC Evaluator_MultiplyPlain(void *thisptr, void *encrypted, void *plain, void *destination, void *pool)
+    SHL_FUNC Evaluator_AddPlain(void *thisptr, void *encrypted, void *plain, void *destination)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(plain, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->multiply_plain_inplace(prepare_dest(encrypted, destination), *as<Plaintext>(plain));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, plain, destination },
+                       [&](Evaluator &ev) { ev.add_plain_inplace(prepare_dest(encrypted, destination), pt(plain)); });
+    }
+    SHL_FUNC Evaluator_SubPlain(void *thisptr, void *encrypted, void *plain, void *destination)
+    {
+        return ev_call(thisptr, { encrypted, plain, destination },
+                       [&](Evaluator &ev) { ev.sub_plain_inplace(prepare_dest(encrypted, destination), pt(plain)); });
+    }
+    SHL_FUNC Evaluator_MultiplyPlain(void *thisptr, void *encrypted, void *plain, void *destination, void *)
+    {
+        return ev_call(thisptr, { encrypted, plain, destination },
+                       [&](Evaluator &ev) { ev.multiply_plain_inplace(prepare_dest(encrypted, destination), pt(plain)); });
     }
     // one plaintext per item, raw device words (library extensions): no copy into the destination first - the host code shapes it
-#define EV_PLAIN_DEVICE(fn, call)                                                                                          \
-    SHL_FUNC fn(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, bool plain_is_ntt, double scale, \
-                void *destination)                                                                                         \
-    {                                                                                                                      \
-        IfNullRet(thisptr, SHL_E_POINTER);                                                                                 \
-        IfNullRet(encrypted, SHL_E_POINTER);                                                                               \
-        IfNullRet(destination, SHL_E_POINTER);                                                                             \
-        SHL_TRY                                                                                                            \
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());                                                        \
-        as<Evaluator>(thisptr)->call(*as<Ciphertext>(encrypted), device_plain, (size_t)batch, plain_is_ntt, scale,         \
-                                     *as<Ciphertext>(destination));                                                        \
-        SHL_CATCH                                                                                                          \
+    SHL_FUNC Evaluator_AddPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, bool plain_is_ntt, double scale,
+                                      void *destination)
+    {
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) {
+            ev.add_plain_device(ct(encrypted), device_plain, (size_t)batch, plain_is_ntt, scale, ct(destination));
+        });
     }
-    EV_PLAIN_DEVICE(Evaluator_AddPlainDevice, add_plain_device)
-    EV_PLAIN_DEVICE(Evaluator_SubPlainDevice, sub_plain_device)
-    EV_PLAIN_DEVICE(Evaluator_MultiplyPlainDevice, multiply_plain_device)
+    SHL_FUNC Evaluator_SubPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, bool plain_is_ntt, double scale,
+                                      void *destination)
+    {
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) {
+            ev.sub_plain_device(ct(encrypted), device_plain, (size_t)batch, plain_is_ntt, scale, ct(destination));
+        });
+    }
+    SHL_FUNC Evaluator_MultiplyPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, bool plain_is_ntt,
+                                           double scale, void *destination)
+    {
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) {
+            ev.multiply_plain_device(ct(encrypted), device_plain, (size_t)batch, plain_is_ntt, scale, ct(destination));
+        });
+    }
     SHL_FUNC Evaluator_TransformPlainToNTTDevice(void *thisptr, const uint64_t *device_coefficients, uint64_t batch, uint64_t *parms_id,
                                                  uint64_t *device_words)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(parms_id, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->transform_plain_to_ntt_device(device_coefficients, (size_t)batch, parms_id, device_words);
-        SHL_CATCH
+        return ev_call(thisptr, { parms_id },
+                       [&](Evaluator &ev) { ev.transform_plain_to_ntt_device(device_coefficients, (size_t)batch, parms_id, device_words); });
     }
     // sums over the items of a batch (library extensions): the destination is another handle, shaped by the host code
     SHL_FUNC Evaluator_SumItems(void *thisptr, void *encrypted, uint64_t group, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->sum_items(*as<Ciphertext>(encrypted), (size_t)group, *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) { ev.sum_items(ct(encrypted), (size_t)group, ct(destination)); });
     }
     SHL_FUNC Evaluator_DotPlainDevice(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t batch, uint64_t group, double scale,
                                       void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->dot_plain_device(*as<Ciphertext>(encrypted), device_plain, (size_t)batch, (size_t)group, scale,
-                                                 *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) {
+            ev.dot_plain_device(ct(encrypted), device_plain, (size_t)batch, (size_t)group, scale, ct(destination));
+        });
     }
     SHL_FUNC Evaluator_DotItems(void *thisptr, void *encrypted1, void *encrypted2, uint64_t group, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted1, SHL_E_POINTER);
-        IfNullRet(encrypted2, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->dot_items(*as<Ciphertext>(encrypted1), *as<Ciphertext>(encrypted2), (size_t)group,
-                                          *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted1, encrypted2, destination },
+                       [&](Evaluator &ev) { ev.dot_items(ct(encrypted1), ct(encrypted2), (size_t)group, ct(destination)); });
     }
     // item maps (library extensions): a CSR list of item numbers in device memory, and the three reductions over the items it names
     SHL_FUNC ItemMap_Create(void *context, uint64_t rows, const uint64_t *row_offsets, const uint64_t *first_items, const uint64_t *second_items,
@@ -322,346 +328,182 @@ extern "C"
     }
     SHL_FUNC Evaluator_SumItemsMapped(void *thisptr, void *encrypted, void *item_map, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(item_map, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->sum_items_mapped(*as<Ciphertext>(encrypted), *as<ItemMap>(item_map), *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, item_map, destination },
+                       [&](Evaluator &ev) { ev.sum_items_mapped(ct(encrypted), *as<ItemMap>(item_map), ct(destination)); });
     }
     SHL_FUNC Evaluator_DotPlainMapped(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t plain_count, void *item_map,
                                       double scale, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(item_map, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->dot_plain_mapped(*as<Ciphertext>(encrypted), device_plain, (size_t)plain_count, *as<ItemMap>(item_map), scale,
-                                                 *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, item_map, destination }, [&](Evaluator &ev) {
+            ev.dot_plain_mapped(ct(encrypted), device_plain, (size_t)plain_count, *as<ItemMap>(item_map), scale, ct(destination));
+        });
+    }
+    SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination)
+    {
+        return ev_call(thisptr, { encrypted1, encrypted2, item_map, destination }, [&](Evaluator &ev) {
+            ev.dot_items_mapped(ct(encrypted1), ct(encrypted2), *as<ItemMap>(item_map), ct(destination));
+        });
     }
     // a sparse matrix of scalar weights over an item map (library extension); flags bit 2: the weights are signed 32-bit integers
     // and not [K] words each - Evaluator_MatMulScalarsItems' bit; no other bit is defined
     SHL_FUNC Evaluator_DotScalarsMapped(void *thisptr, void *encrypted, const void *device_weights, uint64_t weight_count, void *item_map,
                                         uint64_t flags, double scale, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(item_map, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        if (flags & ~uint64_t(4))
-            throw std::invalid_argument("unknown flags");
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->dot_scalars_mapped(*as<Ciphertext>(encrypted), device_weights, (size_t)weight_count, (flags & 4) != 0,
-                                                   *as<ItemMap>(item_map), scale, *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, item_map, destination }, [&](Evaluator &ev) {
+            check_flags(flags, 4);
+            ev.dot_scalars_mapped(ct(encrypted), device_weights, (size_t)weight_count, (flags & 4) != 0, *as<ItemMap>(item_map), scale,
+                                  ct(destination));
+        });
     }
     // scalar weights (library extensions): [count][K] words per scalar, and the dense matrix of them times a batch
     SHL_FUNC Evaluator_LiftScalars(void *thisptr, uint64_t count, const uint64_t *values_mod_t, uint64_t *parms_id, uint64_t *device_words)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(parms_id, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->lift_scalars((size_t)count, values_mod_t, parms_id, device_words);
-        SHL_CATCH
+        return ev_call(thisptr, { parms_id }, [&](Evaluator &ev) { ev.lift_scalars((size_t)count, values_mod_t, parms_id, device_words); });
     }
     SHL_FUNC Evaluator_DotScalarsDevice(void *thisptr, void *encrypted, const uint64_t *device_scalars, uint64_t rows, uint64_t batch, double scale,
                                         void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->dot_scalars_device(*as<Ciphertext>(encrypted), device_scalars, (size_t)rows, (size_t)batch, scale,
-                                                   *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) {
+            ev.dot_scalars_device(ct(encrypted), device_scalars, (size_t)rows, (size_t)batch, scale, ct(destination));
+        });
     }
     // ciphertext matrix x ciphertext matrix (library extension); flags bit 0: encrypted2 is stored [cols][inner]
     SHL_FUNC Evaluator_MatMulItems(void *thisptr, void *encrypted1, void *encrypted2, uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags,
                                    void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted1, SHL_E_POINTER);
-        IfNullRet(encrypted2, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        if (flags & ~uint64_t(1))
-            throw std::invalid_argument("unknown flags");
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->matmul_items(*as<Ciphertext>(encrypted1), *as<Ciphertext>(encrypted2), (size_t)rows, (size_t)inner, (size_t)cols,
-                                             (flags & 1) != 0, *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted1, encrypted2, destination }, [&](Evaluator &ev) {
+            check_flags(flags, 1);
+            ev.matmul_items(ct(encrypted1), ct(encrypted2), (size_t)rows, (size_t)inner, (size_t)cols, (flags & 1) != 0, ct(destination));
+        });
     }
     // plaintext matrix x ciphertext matrix (library extension); flags bit 0: encrypted is stored [cols][inner], bit 1: the result
     // is stored [cols][rows]
     SHL_FUNC Evaluator_MatMulPlainItems(void *thisptr, const uint64_t *device_plain, void *encrypted, uint64_t rows, uint64_t inner, uint64_t cols,
                                         uint64_t flags, double scale, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        if (flags & ~uint64_t(3))
-            throw std::invalid_argument("unknown flags");
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->matmul_plain_items(device_plain, *as<Ciphertext>(encrypted), (size_t)rows, (size_t)inner, (size_t)cols,
-                                                   (flags & 1) != 0, (flags & 2) != 0, scale, *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) {
+            check_flags(flags, 3);
+            ev.matmul_plain_items(device_plain, ct(encrypted), (size_t)rows, (size_t)inner, (size_t)cols, (flags & 1) != 0, (flags & 2) != 0, scale,
+                                  ct(destination));
+        });
     }
     // scalar weight matrix x ciphertext matrix (library extension); flags bits 0 and 1 as above, bit 2: the weights are signed 32-bit
     // integers and not [K] words each
     SHL_FUNC Evaluator_MatMulScalarsItems(void *thisptr, const void *device_weights, void *encrypted, uint64_t rows, uint64_t inner, uint64_t cols,
                                           uint64_t flags, double scale, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        if (flags & ~uint64_t(7))
-            throw std::invalid_argument("unknown flags");
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->matmul_scalars_items(device_weights, (flags & 4) != 0, *as<Ciphertext>(encrypted), (size_t)rows, (size_t)inner,
-                                                     (size_t)cols, (flags & 1) != 0, (flags & 2) != 0, scale, *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) {
+            check_flags(flags, 7);
+            ev.matmul_scalars_items(device_weights, (flags & 4) != 0, ct(encrypted), (size_t)rows, (size_t)inner, (size_t)cols, (flags & 1) != 0,
+                                    (flags & 2) != 0, scale, ct(destination));
+        });
     }
     // 2-D convolution of scalar weights over a grid of items (library extension); flags bit 0: the input is stored channel-last,
     // bit 1: the result is, bit 2: narrow weights
     SHL_FUNC Evaluator_Conv2dScalarsItems(void *thisptr, const void *device_weights, void *encrypted, const SHL_CONV2D *shape, uint64_t flags,
                                           double scale, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        if (!shape)
-            throw std::invalid_argument("shape is null");
-        if (flags & ~uint64_t(7))
-            throw std::invalid_argument("unknown flags");
-        const Conv2dShape c{ shape->in_channels, shape->height,   shape->width,    shape->out_channels, shape->kernel_h,
-                             shape->kernel_w,    shape->stride_h, shape->stride_w, shape->pad_h,        shape->pad_w };
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->conv2d_scalars_items(device_weights, (flags & 4) != 0, *as<Ciphertext>(encrypted), c, (flags & 1) != 0,
-                                                     (flags & 2) != 0, scale, *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, destination }, [&](Evaluator &ev) {
+            if (!shape)
+                throw std::invalid_argument("shape is null");
+            check_flags(flags, 7);
+            const Conv2dShape c{ shape->in_channels, shape->height,   shape->width,    shape->out_channels, shape->kernel_h,
+                                 shape->kernel_w,    shape->stride_h, shape->stride_w, shape->pad_h,        shape->pad_w };
+            ev.conv2d_scalars_items(device_weights, (flags & 4) != 0, ct(encrypted), c, (flags & 1) != 0, (flags & 2) != 0, scale,
+                                    ct(destination));
+        });
     }
-    SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination)
+    SHL_FUNC Evaluator_TransformToNTT1(void *thisptr, void *plain, uint64_t *parms_id, void *destination_ntt, void *)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted1, SHL_E_POINTER);
-        IfNullRet(encrypted2, SHL_E_POINTER);
-        IfNullRet(item_map, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->dot_items_mapped(*as<Ciphertext>(encrypted1), *as<Ciphertext>(encrypted2), *as<ItemMap>(item_map),
-                                                 *as<Ciphertext>(destination));
-        SHL_CATCH
-    }
-    static Plaintext &prepare_plain_dest(void *plain, void *destination)
-    {
-        Plaintext *src = as<Plaintext>(plain), *dst = as<Plaintext>(destination);
-        if (src != dst)
-            *dst = *src;
-        return *dst;
-    }
-    SHL_FUNC Evaluator_TransformToNTT1(void *thisptr, void *plain, uint64_t *parms_id, void *destination_ntt, void *pool)
-    {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(plain, SHL_E_POINTER);
-        IfNullRet(parms_id, SHL_E_POINTER);
-        IfNullRet(destination_ntt, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->transform_to_ntt_inplace(prepare_plain_dest(plain, destination_ntt), parms_id);
-        SHL_CATCH
+        return ev_call(thisptr, { plain, parms_id, destination_ntt },
+                       [&](Evaluator &ev) { ev.transform_to_ntt_inplace(prepare_plain_dest(plain, destination_ntt), parms_id); });
     }
     SHL_FUNC Evaluator_ModSwitchToNext2(void *thisptr, void *plain, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(plain, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->mod_switch_to_next_inplace(prepare_plain_dest(plain, destination));
-        SHL_CATCH
+        return ev_call(thisptr, { plain, destination }, [&](Evaluator &ev) { ev.mod_switch_to_next_inplace(prepare_plain_dest(plain, destination)); });
     }
     SHL_FUNC Evaluator_ModSwitchTo2(void *thisptr, void *plain, uint64_t *parms_id, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(plain, SHL_E_POINTER);
-        IfNullRet(parms_id, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->mod_switch_to_inplace(prepare_plain_dest(plain, destination), parms_id);
-        SHL_CATCH
+        return ev_call(thisptr, { plain, parms_id, destination },
+                       [&](Evaluator &ev) { ev.mod_switch_to_inplace(prepare_plain_dest(plain, destination), parms_id); });
     }
     SHL_FUNC Evaluator_AddMany(void *thisptr, uint64_t count, void **encrypteds, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypteds, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        std::vector<const Ciphertext *> v;
-        for (uint64_t i = 0; i < count; i++)
-            v.push_back(as<Ciphertext>(encrypteds[i]));
-        as<Evaluator>(thisptr)->add_many(v, *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypteds, destination }, [&](Evaluator &ev) { ev.add_many(ct_list(count, encrypteds), ct(destination)); });
     }
-    SHL_FUNC Evaluator_MultiplyMany(void *thisptr, uint64_t count, void **encrypteds, void *relin_keys, void *destination, void *pool)
+    SHL_FUNC Evaluator_MultiplyMany(void *thisptr, uint64_t count, void **encrypteds, void *relin_keys, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypteds, SHL_E_POINTER);
-        IfNullRet(relin_keys, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        std::vector<const Ciphertext *> v;
-        for (uint64_t i = 0; i < count; i++)
-            v.push_back(as<Ciphertext>(encrypteds[i]));
-        as<Evaluator>(thisptr)->multiply_many(v, *as<KSwitchKeys>(relin_keys), *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypteds, relin_keys, destination },
+                       [&](Evaluator &ev) { ev.multiply_many(ct_list(count, encrypteds), keys(relin_keys), ct(destination)); });
     }
-    SHL_FUNC Evaluator_Exponentiate(void *thisptr, void *encrypted, uint64_t exponent, void *relin_keys, void *destination, void *pool)
+    SHL_FUNC Evaluator_Exponentiate(void *thisptr, void *encrypted, uint64_t exponent, void *relin_keys, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(relin_keys, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->exponentiate_inplace(prepare_dest(encrypted, destination), exponent, *as<KSwitchKeys>(relin_keys));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, relin_keys, destination },
+                       [&](Evaluator &ev) { ev.exponentiate_inplace(prepare_dest(encrypted, destination), exponent, keys(relin_keys)); });
     }
 
     SHL_FUNC Evaluator_Add(void *thisptr, void *encrypted1, void *encrypted2, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted1, SHL_E_POINTER);
-        IfNullRet(encrypted2, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        auto ev = as<Evaluator>(thisptr);
-        if (encrypted2 == destination && encrypted1 != destination)
-            ev->add_inplace(*as<Ciphertext>(destination), *as<Ciphertext>(encrypted1)); // evaluator.h add(): commutes
-        else
-            ev->add_inplace(prepare_dest(encrypted1, destination), *as<Ciphertext>(encrypted2));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted1, encrypted2, destination }, [&](Evaluator &ev) {
+            if (encrypted2 == destination && encrypted1 != destination)
+                ev.add_inplace(ct(destination), ct(encrypted1)); // evaluator.h add(): commutes
+            else
+                ev.add_inplace(prepare_dest(encrypted1, destination), ct(encrypted2));
+        });
     }
     SHL_FUNC Evaluator_Sub(void *thisptr, void *encrypted1, void *encrypted2, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted1, SHL_E_POINTER);
-        IfNullRet(encrypted2, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        auto ev = as<Evaluator>(thisptr);
-        if (encrypted2 == destination && encrypted1 != destination)
-        {
-            // evaluator.h sub(): destination = e2 - e1, then negate
-            ev->sub_inplace(*as<Ciphertext>(destination), *as<Ciphertext>(encrypted1));
-            ev->negate_inplace(*as<Ciphertext>(destination));
-        }
-        else
-            ev->sub_inplace(prepare_dest(encrypted1, destination), *as<Ciphertext>(encrypted2));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted1, encrypted2, destination }, [&](Evaluator &ev) {
+            if (encrypted2 == destination && encrypted1 != destination)
+            {
+                // evaluator.h sub(): destination = e2 - e1, then negate
+                ev.sub_inplace(ct(destination), ct(encrypted1));
+                ev.negate_inplace(ct(destination));
+            }
+            else
+                ev.sub_inplace(prepare_dest(encrypted1, destination), ct(encrypted2));
+        });
     }
-    SHL_FUNC Evaluator_Multiply(void *thisptr, void *encrypted1, void *encrypted2, void *destination, void *pool)
+    SHL_FUNC Evaluator_Multiply(void *thisptr, void *encrypted1, void *encrypted2, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted1, SHL_E_POINTER);
-        IfNullRet(encrypted2, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        auto ev = as<Evaluator>(thisptr);
-        if (encrypted1 == encrypted2 && encrypted1 == destination)
-            ev->multiply_inplace(*as<Ciphertext>(destination), *as<Ciphertext>(destination));
-        else
-            ev->multiply(*as<Ciphertext>(encrypted1), *as<Ciphertext>(encrypted2), *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted1, encrypted2, destination }, [&](Evaluator &ev) {
+            if (encrypted1 == encrypted2 && encrypted1 == destination)
+                ev.multiply_inplace(ct(destination), ct(destination));
+            else
+                ev.multiply(ct(encrypted1), ct(encrypted2), ct(destination));
+        });
     }
-    SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *pool)
+    SHL_FUNC Evaluator_Relinearize(void *thisptr, void *encrypted, void *relinKeys, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(relinKeys, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->relinearize_inplace(prepare_dest(encrypted, destination), *as<KSwitchKeys>(relinKeys));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, relinKeys, destination },
+                       [&](Evaluator &ev) { ev.relinearize_inplace(prepare_dest(encrypted, destination), keys(relinKeys)); });
     }
     SHL_FUNC Evaluator_SwitchKeyAccWords(void *thisptr, void *encrypted, uint64_t *words)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(words, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        *words = as<Evaluator>(thisptr)->switch_key_acc_words(*as<Ciphertext>(encrypted));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, words }, [&](Evaluator &ev) { *words = ev.switch_key_acc_words(ct(encrypted)); });
     }
     SHL_FUNC Evaluator_RelinearizePartial(void *thisptr, void *encrypted, void *relinKeys, uint64_t digit_first, uint64_t digit_count,
                                           uint64_t *device_acc)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(relinKeys, SHL_E_POINTER);
-        IfNullRet(device_acc, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->relinearize_partial(*as<Ciphertext>(encrypted), *as<KSwitchKeys>(relinKeys), (unsigned)digit_first,
-                                                    (unsigned)(digit_first + digit_count), device_acc);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, relinKeys, device_acc }, [&](Evaluator &ev) {
+            ev.relinearize_partial(ct(encrypted), keys(relinKeys), (unsigned)digit_first, (unsigned)(digit_first + digit_count), device_acc);
+        });
     }
     SHL_FUNC Evaluator_RelinearizeFinish(void *thisptr, void *encrypted, uint64_t *device_acc, uint64_t parts)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(device_acc, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->relinearize_finish(*as<Ciphertext>(encrypted), device_acc, (unsigned)parts);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, device_acc }, [&](Evaluator &ev) { ev.relinearize_finish(ct(encrypted), device_acc, (unsigned)parts); });
     }
     SHL_FUNC Evaluator_ApplyGaloisPartial(void *thisptr, void *encrypted, uint32_t galois_elt, void *galoisKeys, uint64_t digit_first,
                                           uint64_t digit_count, uint64_t *device_acc)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(galoisKeys, SHL_E_POINTER);
-        IfNullRet(device_acc, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->apply_galois_partial(*as<Ciphertext>(encrypted), galois_elt, *as<KSwitchKeys>(galoisKeys),
-                                                     (unsigned)digit_first, (unsigned)(digit_first + digit_count), device_acc);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, galoisKeys, device_acc }, [&](Evaluator &ev) {
+            ev.apply_galois_partial(ct(encrypted), galois_elt, keys(galoisKeys), (unsigned)digit_first, (unsigned)(digit_first + digit_count),
+                                    device_acc);
+        });
     }
     SHL_FUNC Evaluator_ApplyGaloisFinish(void *thisptr, void *encrypted, uint64_t *device_acc, uint64_t parts)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(device_acc, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->apply_galois_finish(*as<Ciphertext>(encrypted), device_acc, (unsigned)parts);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, device_acc }, [&](Evaluator &ev) { ev.apply_galois_finish(ct(encrypted), device_acc, (unsigned)parts); });
     }
     // ------------------------------------------------------------------ communicator + digit-parallel forms with the exchange
     // inside the library (sealhip.h section 1c; comm.h)
@@ -732,207 +574,93 @@ extern "C"
         as<Comm>(comm)->broadcast(device_words, (size_t)count, root, (hipStream_t)hip_stream);
         SHL_CATCH
     }
-    static Evaluator::KsExchange exchange_of(int how)
-    {
-        if (how != 0 && how != 1)
-            throw std::invalid_argument("exchange: 0 = all-reduce, 1 = reduce-scatter + all-gather");
-        return how ? Evaluator::KsExchange::reduce_scatter : Evaluator::KsExchange::all_reduce;
-    }
     SHL_FUNC Evaluator_RelinearizeDigitParallel(void *thisptr, void *encrypted, void *relinKeys, void *comm, int exchange, void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(relinKeys, SHL_E_POINTER);
-        IfNullRet(comm, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->relinearize_inplace(prepare_dest(encrypted, destination), *as<KSwitchKeys>(relinKeys), *as<Comm>(comm),
-                                                    exchange_of(exchange));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, relinKeys, comm, destination }, [&](Evaluator &ev) {
+            ev.relinearize_inplace(prepare_dest(encrypted, destination), keys(relinKeys), *as<Comm>(comm), exchange_of(exchange));
+        });
     }
     SHL_FUNC Evaluator_ApplyGaloisDigitParallel(void *thisptr, void *encrypted, uint32_t galois_elt, void *galoisKeys, void *comm, int exchange,
                                                 void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(galoisKeys, SHL_E_POINTER);
-        IfNullRet(comm, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->apply_galois_inplace(prepare_dest(encrypted, destination), galois_elt, *as<KSwitchKeys>(galoisKeys),
-                                                     *as<Comm>(comm), exchange_of(exchange));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, galoisKeys, comm, destination }, [&](Evaluator &ev) {
+            ev.apply_galois_inplace(prepare_dest(encrypted, destination), galois_elt, keys(galoisKeys), *as<Comm>(comm), exchange_of(exchange));
+        });
     }
     SHL_FUNC Evaluator_RotateVectorDigitParallel(void *thisptr, void *encrypted, int steps, void *galoisKeys, void *comm, int exchange,
                                                  void *destination)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(galoisKeys, SHL_E_POINTER);
-        IfNullRet(comm, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->rotate_vector_inplace(prepare_dest(encrypted, destination), steps, *as<KSwitchKeys>(galoisKeys), *as<Comm>(comm),
-                                                      exchange_of(exchange));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, galoisKeys, comm, destination }, [&](Evaluator &ev) {
+            ev.rotate_vector_inplace(prepare_dest(encrypted, destination), steps, keys(galoisKeys), *as<Comm>(comm), exchange_of(exchange));
+        });
     }
     SHL_FUNC Evaluator_BroadcastKeyDigits(void *thisptr, void *kswitch_keys, uint64_t index, uint64_t *device_staging, void *comm, int root)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(kswitch_keys, SHL_E_POINTER);
-        IfNullRet(device_staging, SHL_E_POINTER);
-        IfNullRet(comm, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->broadcast_key_digits(*as<KSwitchKeys>(kswitch_keys), (size_t)index, device_staging, *as<Comm>(comm), root);
-        SHL_CATCH
+        return ev_call(thisptr, { kswitch_keys, device_staging, comm }, [&](Evaluator &ev) {
+            ev.broadcast_key_digits(keys(kswitch_keys), (size_t)index, device_staging, *as<Comm>(comm), root);
+        });
     }
     // the local phases of the reduce-scatter exchange (tests emulate the ranks in one process)
     SHL_FUNC Evaluator_SwitchKeySlots(void *thisptr, void *encrypted, uint64_t nranks, uint64_t *slots)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(slots, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        *slots = as<Evaluator>(thisptr)->switch_key_slots(*as<Ciphertext>(encrypted), (unsigned)nranks);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, slots }, [&](Evaluator &ev) { *slots = ev.switch_key_slots(ct(encrypted), (unsigned)nranks); });
     }
     SHL_FUNC Evaluator_SwitchKeyPackTargets(void *thisptr, void *encrypted, const uint64_t *device_acc, uint64_t nranks, uint64_t *device_send,
                                             uint64_t *device_special)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->switch_key_pack_targets(*as<Ciphertext>(encrypted), device_acc, (unsigned)nranks, device_send, device_special);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted }, [&](Evaluator &ev) {
+            ev.switch_key_pack_targets(ct(encrypted), device_acc, (unsigned)nranks, device_send, device_special);
+        });
     }
     SHL_FUNC Evaluator_SwitchKeyFinishOwned(void *thisptr, void *encrypted, const uint64_t *device_recv, const uint64_t *device_special,
                                             uint64_t nranks, uint64_t rank, uint64_t *device_own)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->switch_key_finish_owned(*as<Ciphertext>(encrypted), device_recv, device_special, (unsigned)nranks, (unsigned)rank,
-                                                        device_own);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted }, [&](Evaluator &ev) {
+            ev.switch_key_finish_owned(ct(encrypted), device_recv, device_special, (unsigned)nranks, (unsigned)rank, device_own);
+        });
     }
     SHL_FUNC Evaluator_SwitchKeyAddGathered(void *thisptr, void *encrypted, const uint64_t *device_all, uint64_t nranks)
     {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->switch_key_add_gathered(*as<Ciphertext>(encrypted), device_all, (unsigned)nranks);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted }, [&](Evaluator &ev) { ev.switch_key_add_gathered(ct(encrypted), device_all, (unsigned)nranks); });
     }
-    SHL_FUNC Evaluator_ModSwitchTo1(void *thisptr, void *encrypted, uint64_t *parms_id, void *destination, void *pool)
+    SHL_FUNC Evaluator_ModSwitchTo1(void *thisptr, void *encrypted, uint64_t *parms_id, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(parms_id, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->mod_switch_to_inplace(prepare_dest(encrypted, destination), parms_id);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, parms_id, destination },
+                       [&](Evaluator &ev) { ev.mod_switch_to_inplace(prepare_dest(encrypted, destination), parms_id); });
     }
-    SHL_FUNC Evaluator_RescaleTo(void *thisptr, void *encrypted, uint64_t *parms_id, void *destination, void *pool)
+    SHL_FUNC Evaluator_RescaleTo(void *thisptr, void *encrypted, uint64_t *parms_id, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(parms_id, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->rescale_to_inplace(prepare_dest(encrypted, destination), parms_id);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, parms_id, destination },
+                       [&](Evaluator &ev) { ev.rescale_to_inplace(prepare_dest(encrypted, destination), parms_id); });
     }
-    SHL_FUNC Evaluator_ModReduceTo(void *thisptr, void *encrypted, uint64_t *parms_id, void *destination, void *pool)
+    SHL_FUNC Evaluator_ModReduceTo(void *thisptr, void *encrypted, uint64_t *parms_id, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(parms_id, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->mod_reduce_to_inplace(prepare_dest(encrypted, destination), parms_id);
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, parms_id, destination },
+                       [&](Evaluator &ev) { ev.mod_reduce_to_inplace(prepare_dest(encrypted, destination), parms_id); });
     }
-    SHL_FUNC Evaluator_ApplyGalois(void *thisptr, void *encrypted, uint32_t galois_elt, void *galoisKeys, void *destination, void *pool)
+    SHL_FUNC Evaluator_ApplyGalois(void *thisptr, void *encrypted, uint32_t galois_elt, void *galoisKeys, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(galoisKeys, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->apply_galois(*as<Ciphertext>(encrypted), galois_elt, *as<KSwitchKeys>(galoisKeys), *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, galoisKeys, destination },
+                       [&](Evaluator &ev) { ev.apply_galois(ct(encrypted), galois_elt, keys(galoisKeys), ct(destination)); });
     }
-    SHL_FUNC Evaluator_RotateRows(void *thisptr, void *encrypted, int steps, void *galoisKeys, void *destination, void *pool)
+    SHL_FUNC Evaluator_RotateRows(void *thisptr, void *encrypted, int steps, void *galoisKeys, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(galoisKeys, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->rotate_rows(*as<Ciphertext>(encrypted), steps, *as<KSwitchKeys>(galoisKeys), *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, galoisKeys, destination },
+                       [&](Evaluator &ev) { ev.rotate_rows(ct(encrypted), steps, keys(galoisKeys), ct(destination)); });
     }
-    SHL_FUNC Evaluator_RotateColumns(void *thisptr, void *encrypted, void *galois_keys, void *destination, void *pool)
+    SHL_FUNC Evaluator_RotateColumns(void *thisptr, void *encrypted, void *galois_keys, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(galois_keys, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->rotate_columns(*as<Ciphertext>(encrypted), *as<KSwitchKeys>(galois_keys), *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, galois_keys, destination },
+                       [&](Evaluator &ev) { ev.rotate_columns(ct(encrypted), keys(galois_keys), ct(destination)); });
     }
-    SHL_FUNC Evaluator_RotateVector(void *thisptr, void *encrypted, int steps, void *galoisKeys, void *destination, void *pool)
+    SHL_FUNC Evaluator_RotateVector(void *thisptr, void *encrypted, int steps, void *galoisKeys, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(galoisKeys, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->rotate_vector(*as<Ciphertext>(encrypted), steps, *as<KSwitchKeys>(galoisKeys), *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, galoisKeys, destination },
+                       [&](Evaluator &ev) { ev.rotate_vector(ct(encrypted), steps, keys(galoisKeys), ct(destination)); });
     }
-    SHL_FUNC Evaluator_ComplexConjugate(void *thisptr, void *encrypted, void *galoisKeys, void *destination, void *pool)
+    SHL_FUNC Evaluator_ComplexConjugate(void *thisptr, void *encrypted, void *galoisKeys, void *destination, void *)
     {
-        (void)pool;
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(encrypted, SHL_E_POINTER);
-        IfNullRet(galoisKeys, SHL_E_POINTER);
-        IfNullRet(destination, SHL_E_POINTER);
-        SHL_TRY
-        StreamScope stream_scope(as<Evaluator>(thisptr)->stream());
-        as<Evaluator>(thisptr)->complex_conjugate(*as<Ciphertext>(encrypted), *as<KSwitchKeys>(galoisKeys), *as<Ciphertext>(destination));
-        SHL_CATCH
+        return ev_call(thisptr, { encrypted, galoisKeys, destination },
+                       [&](Evaluator &ev) { ev.complex_conjugate(ct(encrypted), keys(galoisKeys), ct(destination)); });
     }
-    SHL_FUNC Evaluator_ContextUsingKeyswitching(void *thisptr, bool *using_keyswitching)
-    {
-        IfNullRet(thisptr, SHL_E_POINTER);
-        IfNullRet(using_keyswitching, SHL_E_POINTER);
-        *using_keyswitching = as<Evaluator>(thisptr)->context().using_keyswitching();
-        return SHL_S_OK;
-    }
-
 }

@@ -95,6 +95,16 @@ namespace
         launch(c, l, n_log, (size_t)l->K * c->n(), (unsigned)slices, scratch ? scratch->p : nullptr, s);
         SHL_CATCH
     }
+    // What the entries without a stream argument add to their _tile form, which ran on the NULL stream: the call returns when the
+    // work is done.  A refusal or a query (r == NULL) has queued nothing and is handed back as it is.
+    SHL_HRESULT then_synchronise(SHL_HRESULT hr, const uint64_t *r, const char *what)
+    {
+        if (hr != SHL_S_OK || !r)
+            return hr;
+        SHL_TRY
+        hip_ok(hipStreamSynchronize(nullptr), what);
+        SHL_CATCH
+    }
     constexpr const char *kMatmulShape = "1 <= rows, inner, cols; rows * inner, inner * cols, rows * cols < 2^32; a built tile";
     constexpr const char *kMatmulSlices = "1 <= slices <= min(inner, 64)";
 } // namespace
@@ -269,12 +279,9 @@ extern "C"
     SHL_FUNC shl_dot_scalars(void *context, uint64_t chain_index, const uint64_t *a, const uint64_t *scalars, uint64_t *r, uint64_t size,
                              uint64_t rows, uint64_t batch, uint64_t slices, uint64_t *slices_used)
     {
-        const SHL_HRESULT hr = shl_dot_scalars_tile(context, chain_index, a, scalars, r, size, rows, batch, slices, slices_used, 0, nullptr);
-        if (hr != SHL_S_OK || !r)
-            return hr;
-        SHL_TRY
-        hip_ok(hipStreamSynchronize(nullptr), "dot_scalars sync");
-        SHL_CATCH
+        return then_synchronise(
+            shl_dot_scalars_tile(context, chain_index, a, scalars, r, size, rows, batch, slices, slices_used, 0, nullptr),
+            r, "dot_scalars sync");
     }
     SHL_FUNC shl_dot_scalars_info(uint64_t *row_tile, uint64_t *flush)
     {
@@ -304,12 +311,9 @@ extern "C"
     SHL_FUNC shl_matmul_items(void *context, uint64_t chain_index, const uint64_t *x, const uint64_t *y, uint64_t *r, uint64_t rows, uint64_t inner,
                               uint64_t cols, int y_transposed, uint64_t slices, uint64_t *slices_used)
     {
-        const SHL_HRESULT hr = shl_matmul_items_tile(context, chain_index, x, y, r, rows, inner, cols, y_transposed, slices, slices_used, 0, nullptr);
-        if (hr != SHL_S_OK || !r)
-            return hr;
-        SHL_TRY
-        hip_ok(hipStreamSynchronize(nullptr), "matmul_items sync");
-        SHL_CATCH
+        return then_synchronise(
+            shl_matmul_items_tile(context, chain_index, x, y, r, rows, inner, cols, y_transposed, slices, slices_used, 0, nullptr),
+            r, "matmul_items sync");
     }
     SHL_FUNC shl_matmul_items_info(uint64_t *tile_rows, uint64_t *tile_cols, uint64_t *flush)
     {
@@ -348,12 +352,9 @@ extern "C"
     SHL_FUNC shl_matmul_plain_items(void *context, uint64_t chain_index, const uint64_t *pl, const uint64_t *a, uint64_t *r, uint64_t size,
                                     uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used)
     {
-        const SHL_HRESULT hr = shl_matmul_plain_items_tile(context, chain_index, pl, a, r, size, rows, inner, cols, flags, slices, slices_used, 0, nullptr);
-        if (hr != SHL_S_OK || !r)
-            return hr;
-        SHL_TRY
-        hip_ok(hipStreamSynchronize(nullptr), "matmul_plain_items sync");
-        SHL_CATCH
+        return then_synchronise(
+            shl_matmul_plain_items_tile(context, chain_index, pl, a, r, size, rows, inner, cols, flags, slices, slices_used, 0, nullptr),
+            r, "matmul_plain_items sync");
     }
     SHL_FUNC shl_matmul_plain_items_info(uint64_t *tile_rows, uint64_t *tile_cols, uint64_t *flush)
     {
@@ -392,12 +393,9 @@ extern "C"
     SHL_FUNC shl_matmul_scalars(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
                                 uint64_t rows, uint64_t inner, uint64_t cols, uint64_t flags, uint64_t slices, uint64_t *slices_used)
     {
-        const SHL_HRESULT hr = shl_matmul_scalars_tile(context, chain_index, weights, a, r, size, rows, inner, cols, flags, slices, slices_used, 0, nullptr);
-        if (hr != SHL_S_OK || !r)
-            return hr;
-        SHL_TRY
-        hip_ok(hipStreamSynchronize(nullptr), "matmul_scalars sync");
-        SHL_CATCH
+        return then_synchronise(
+            shl_matmul_scalars_tile(context, chain_index, weights, a, r, size, rows, inner, cols, flags, slices, slices_used, 0, nullptr),
+            r, "matmul_scalars sync");
     }
     SHL_FUNC shl_matmul_scalars_info(uint64_t *row_tile, uint64_t *narrow_row_tile, uint64_t *flush, uint64_t *narrow_flush)
     {
@@ -446,12 +444,9 @@ extern "C"
     SHL_FUNC shl_conv2d_scalars(void *context, uint64_t chain_index, const void *weights, const uint64_t *a, uint64_t *r, uint64_t size,
                                 const SHL_CONV2D *shape, uint64_t flags, uint64_t slices, uint64_t *slices_used)
     {
-        const SHL_HRESULT hr = shl_conv2d_scalars_tile(context, chain_index, weights, a, r, size, shape, flags, slices, slices_used, 0, 0, nullptr);
-        if (hr != SHL_S_OK || !r)
-            return hr;
-        SHL_TRY
-        hip_ok(hipStreamSynchronize(nullptr), "conv2d_scalars sync");
-        SHL_CATCH
+        return then_synchronise(
+            shl_conv2d_scalars_tile(context, chain_index, weights, a, r, size, shape, flags, slices, slices_used, 0, 0, nullptr),
+            r, "conv2d_scalars sync");
     }
     SHL_FUNC shl_apply_galois(
         void *context, uint64_t chain_index, int ntt_form, uint32_t galois_elt, const uint64_t *in, uint64_t *out, uint64_t polys,

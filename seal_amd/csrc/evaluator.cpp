@@ -23,14 +23,12 @@ namespace sealhip
     }
     void Evaluator::defer_tail(Ciphertext &e, uint64_t *acc, bool with_addend) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         e.lazy_ = new LazyTail{ this, acc, with_addend };
         std::lock_guard<std::mutex> lock(lazy_mu_);
         lazy_cts_.push_back(&e);
     }
     LazyTail Evaluator::detach_tail(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         const LazyTail t = *e.lazy_;
         delete e.lazy_;
         e.lazy_ = nullptr;
@@ -40,7 +38,7 @@ namespace sealhip
     }
     void Evaluator::forget_tail(const Ciphertext &e, LazyTail t) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         {
             std::lock_guard<std::mutex> lock(lazy_mu_);
             lazy_cts_.erase(std::remove(lazy_cts_.begin(), lazy_cts_.end(), &e), lazy_cts_.end());
@@ -51,7 +49,7 @@ namespace sealhip
     void Evaluator::complete_tail(Ciphertext &e, LazyTail t) const
     {
         const hipStream_t caller = DevicePool::thread_stream(); // (read before this call's own scope replaces it)
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         {
             std::lock_guard<std::mutex> lock(lazy_mu_);
             lazy_cts_.erase(std::remove(lazy_cts_.begin(), lazy_cts_.end(), &e), lazy_cts_.end());
@@ -457,9 +455,37 @@ namespace sealhip
             throw std::invalid_argument(std::string(what) + " is not valid for encryption parameters");
     }
 
+    void Evaluator::check_context(const Ciphertext &ct, const char *what) const
+    {
+        if (&ct.context() != &context_ || !ct.level())
+            throw std::invalid_argument(std::string(what) + " is not valid for encryption parameters");
+    }
+    void Evaluator::check_batching() const
+    {
+        if (!context_.using_batching())
+            throw std::logic_error("encryption parameters do not support batching");
+    }
+    const Level *Evaluator::target_level(const Level *level, const uint64_t *parms_id) const
+    {
+        const Level *target = context_.level_by_parms_id(parms_id);
+        if (!target)
+            throw std::invalid_argument("parms_id is not valid for encryption parameters");
+        if (level->chain_index < target->chain_index)
+            throw std::invalid_argument("cannot switch to higher level modulus");
+        return target;
+    }
+    // rows x inner times inner x cols: every dimension and every product of two fits 32 bits (the tiled products' index arithmetic)
+    void Evaluator::check_matmul_shape(size_t rows, size_t inner, size_t cols) const
+    {
+        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
+            ((rows * cols) >> 32))
+            throw std::invalid_argument("1 <= rows, inner, cols and rows * inner, inner * cols, rows * cols < 2^32");
+    }
+
     bool Evaluator::is_transparent(const Ciphertext &ct) const
     {
         // Ciphertext::is_transparent (ciphertext.h:451-456)
+        StreamScope pool_scope(stream_); // (public, and Ciphertext_IsTransparent calls it on an evaluator of its own)
         if (!ct.word_count() || ct.size() < 2)
             return true;
         Scratch word(1); // per call: concurrent checks on different ciphertexts must not share the flag
@@ -474,7 +500,7 @@ namespace sealhip
     }
     void Evaluator::throw_if_transparent(const Ciphertext &ct) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         if (transparent_check_ && is_transparent(ct))
             throw std::logic_error("result ciphertext is transparent");
     }
@@ -482,7 +508,7 @@ namespace sealhip
     // ---- negate / add / sub (evaluator.cpp:130-350)
     void Evaluator::negate_inplace(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         PlaneGeom g{ (unsigned)context_.log_n(), e.level()->K, (unsigned)e.batch() };
         if (e.size())
@@ -492,48 +518,18 @@ namespace sealhip
 
     void Evaluator::add_inplace(Ciphertext &e1, const Ciphertext &e2) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        check_valid(e1, "encrypted1");
-        check_valid(e2, "encrypted2");
-        if (e1.level() != e2.level())
-            throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
-        if (e1.is_ntt_form() != e2.is_ntt_form())
-            throw std::invalid_argument("NTT form mismatch");
-        if (!are_close(e1.scale(), e2.scale()))
-            throw std::invalid_argument("scale mismatch");
-        if (e1.batch() != e2.batch())
-            throw std::invalid_argument("batch mismatch");
-        if (e1.correction_factor() != e2.correction_factor())
-        {
-            // balance the correction factors and scale both operands first (BGV, evaluator.cpp:173-192)
-            uint64_t f, m1, m2;
-            balance_correction_factors(e1.correction_factor(), e2.correction_factor(), context_.plain_modulus(), f, m1, m2);
-            PlaneGeom gg{ (unsigned)context_.log_n(), e1.level()->K, (unsigned)e1.batch() };
-            if (e1.size())
-                ck(k_mul_scalar(context_.dev_mods(), e1.data(), e1.data(), m1, gg, (unsigned)e1.size(), stream_), "add: scale encrypted1");
-            Ciphertext copy(e2);
-            if (copy.size())
-                ck(k_mul_scalar(context_.dev_mods(), copy.data(), copy.data(), m2, gg, (unsigned)copy.size(), stream_), "add: scale encrypted2");
-            e1.correction_factor() = f;
-            copy.correction_factor() = f;
-            add_inplace(e1, copy);
-            return;
-        }
-        size_t s1 = e1.size(), s2 = e2.size();
-        size_t mx = std::max(s1, s2), mn = std::min(s1, s2);
-        e1.resize(e1.level(), mx, stream_);
-        PlaneGeom g{ (unsigned)context_.log_n(), e1.level()->K, (unsigned)e1.batch() };
-        if (mn)
-            ck(k_addsub(context_.dev_mods(), e1.data(), e2.data(), e1.data(), 0, g, (unsigned)mn, stream_), "add");
-        if (s1 < s2)
-            ck(hipMemcpyAsync(e1.plane(s1), e2.plane(mn), (s2 - s1) * e1.plane_words() * 8, hipMemcpyDeviceToDevice, stream_),
-               "add copy tail");
-        throw_if_transparent(e1);
+        StreamScope pool_scope(stream_);
+        addsub(e1, e2, 0);
     }
-
     void Evaluator::sub_inplace(Ciphertext &e1, const Ciphertext &e2) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
+        addsub(e1, e2, 1);
+    }
+    // e1 <- e1 + e2 (op 0) or e1 - e2 (op 1); where e2 is the longer one its tail is copied or negated
+    void Evaluator::addsub(Ciphertext &e1, const Ciphertext &e2, int op) const
+    {
+        expect_scope();
         check_valid(e1, "encrypted1");
         check_valid(e2, "encrypted2");
         if (e1.level() != e2.level())
@@ -546,18 +542,20 @@ namespace sealhip
             throw std::invalid_argument("batch mismatch");
         if (e1.correction_factor() != e2.correction_factor())
         {
-            // evaluator.cpp:259-278
+            // balance the correction factors and scale both operands first (BGV, evaluator.cpp:173-192, 259-278)
             uint64_t f, m1, m2;
             balance_correction_factors(e1.correction_factor(), e2.correction_factor(), context_.plain_modulus(), f, m1, m2);
             PlaneGeom gg{ (unsigned)context_.log_n(), e1.level()->K, (unsigned)e1.batch() };
             if (e1.size())
-                ck(k_mul_scalar(context_.dev_mods(), e1.data(), e1.data(), m1, gg, (unsigned)e1.size(), stream_), "sub: scale encrypted1");
+                ck(k_mul_scalar(context_.dev_mods(), e1.data(), e1.data(), m1, gg, (unsigned)e1.size(), stream_),
+                   op ? "sub: scale encrypted1" : "add: scale encrypted1");
             Ciphertext copy(e2);
             if (copy.size())
-                ck(k_mul_scalar(context_.dev_mods(), copy.data(), copy.data(), m2, gg, (unsigned)copy.size(), stream_), "sub: scale encrypted2");
+                ck(k_mul_scalar(context_.dev_mods(), copy.data(), copy.data(), m2, gg, (unsigned)copy.size(), stream_),
+                   op ? "sub: scale encrypted2" : "add: scale encrypted2");
             e1.correction_factor() = f;
             copy.correction_factor() = f;
-            sub_inplace(e1, copy);
+            addsub(e1, copy, op);
             return;
         }
         size_t s1 = e1.size(), s2 = e2.size();
@@ -565,8 +563,11 @@ namespace sealhip
         e1.resize(e1.level(), mx, stream_);
         PlaneGeom g{ (unsigned)context_.log_n(), e1.level()->K, (unsigned)e1.batch() };
         if (mn)
-            ck(k_addsub(context_.dev_mods(), e1.data(), e2.data(), e1.data(), 1, g, (unsigned)mn, stream_), "sub");
-        if (s1 < s2)
+            ck(k_addsub(context_.dev_mods(), e1.data(), e2.data(), e1.data(), op, g, (unsigned)mn, stream_), op ? "sub" : "add");
+        if (s1 < s2 && op == 0)
+            ck(hipMemcpyAsync(e1.plane(s1), e2.plane(mn), (s2 - s1) * e1.plane_words() * 8, hipMemcpyDeviceToDevice, stream_),
+               "add copy tail");
+        else if (s1 < s2)
             ck(k_addsub(context_.dev_mods(), e2.plane(mn), nullptr, e1.plane(mn), 2, g, (unsigned)(s2 - mn), stream_), "sub negate tail");
         throw_if_transparent(e1);
     }
@@ -574,7 +575,7 @@ namespace sealhip
     // ---- transforms (evaluator.cpp:2289-2382)
     void Evaluator::transform_to_ntt_inplace(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         if (e.is_ntt_form())
             throw std::invalid_argument("encrypted is already in NTT form");
@@ -586,7 +587,7 @@ namespace sealhip
     }
     void Evaluator::transform_from_ntt_inplace(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         if (!e.is_ntt_form())
             throw std::invalid_argument("encrypted_ntt is not in NTT form");
@@ -687,7 +688,7 @@ namespace sealhip
 
     void Evaluator::transform_to_ntt_inplace(Plaintext &plain, const uint64_t *parms_id) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(plain);
         const Level *lvl = context_.level_by_parms_id(parms_id);
         if (!lvl)
@@ -713,7 +714,7 @@ namespace sealhip
 
     void Evaluator::mod_switch_to_next_inplace(Plaintext &plain) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         // mod_switch_drop_to_next(Plaintext) (evaluator.cpp:1369-1402): the flat [K][N] array keeps its first K-1 components
         check_valid(plain);
         if (!plain.is_ntt_form())
@@ -728,22 +729,18 @@ namespace sealhip
     }
     void Evaluator::mod_switch_to_inplace(Plaintext &plain, const uint64_t *parms_id) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(plain);
-        const Level *target = context_.level_by_parms_id(parms_id);
         if (!plain.is_ntt_form())
             throw std::invalid_argument("plain is not in NTT form");
-        if (!target)
-            throw std::invalid_argument("parms_id is not valid for encryption parameters");
-        if (plain.level()->chain_index < target->chain_index)
-            throw std::invalid_argument("cannot switch to higher level modulus");
+        const Level *target = target_level(plain.level(), parms_id);
         while (plain.level() != target)
             mod_switch_to_next_inplace(plain);
     }
 
     void Evaluator::add_plain_inplace(Ciphertext &e, const Plaintext &plain) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         // add_plain_inplace / sub_plain_inplace share everything but the sign
         check_valid(e, "encrypted");
         check_valid(plain);
@@ -751,14 +748,14 @@ namespace sealhip
     }
     void Evaluator::sub_plain_inplace(Ciphertext &e, const Plaintext &plain) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         check_valid(plain);
         addsub_plain(e, plain, 1, e);
     }
     void Evaluator::multiply_plain_inplace(Ciphertext &e, const Plaintext &plain) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         check_valid(plain);
         multiply_plain(e, plain, e);
@@ -841,21 +838,21 @@ namespace sealhip
     void Evaluator::add_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
                                      Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_plain_device(e, plain, batch, plain_is_ntt, scale, dest);
         addsub_plain(e, PlainOperand(context_, e.level(), plain, plain_is_ntt, scale), 0, dest);
     }
     void Evaluator::sub_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
                                      Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_plain_device(e, plain, batch, plain_is_ntt, scale, dest);
         addsub_plain(e, PlainOperand(context_, e.level(), plain, plain_is_ntt, scale), 1, dest);
     }
     void Evaluator::multiply_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, bool plain_is_ntt, double scale,
                                           Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_plain_device(e, plain, batch, plain_is_ntt, scale, dest);
         multiply_plain(e, PlainOperand(context_, e.level(), plain, plain_is_ntt, scale), dest);
     }
@@ -993,7 +990,7 @@ namespace sealhip
 
     void Evaluator::transform_plain_to_ntt_device(const uint64_t *coefficients, size_t batch, const uint64_t *parms_id, uint64_t *out) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (!coefficients || !out)
             throw std::invalid_argument("device pointer is null");
         if ((uintptr_t)coefficients % 16 || (uintptr_t)out % 16)
@@ -1140,7 +1137,7 @@ namespace sealhip
     }
     void Evaluator::sum_items(const Ciphertext &e, size_t group, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         size_t rows;
         const ItemWalk walk = consecutive_walk(e, group, rows);
@@ -1148,7 +1145,7 @@ namespace sealhip
     }
     void Evaluator::sum_items_mapped(const Ciphertext &e, const ItemMap &map, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         size_t rows;
         const ItemWalk walk = mapped_walk(e, map, rows);
@@ -1184,7 +1181,7 @@ namespace sealhip
     void Evaluator::dot_plain_device(const Ciphertext &e, const uint64_t *plain, size_t batch, size_t group, double scale,
                                      Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_plain_device(e, plain, batch, true, scale, dest);
         size_t rows;
         const ItemWalk walk = consecutive_walk(e, group, rows);
@@ -1193,7 +1190,7 @@ namespace sealhip
     void Evaluator::dot_plain_mapped(const Ciphertext &e, const uint64_t *plain, size_t plain_count, const ItemMap &map, double scale,
                                      Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_plain_device(e, plain, plain_count, true, scale, dest, false);
         if (plain_count != map.second_batch())
             throw std::invalid_argument("plain_count does not equal the map's second_batch");
@@ -1208,7 +1205,7 @@ namespace sealhip
     void Evaluator::dot_scalars_device(const Ciphertext &e, const uint64_t *scalars, size_t rows, size_t batch, double scale,
                                        Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (!rows || (rows >> 32) || (batch >> 32) || ((rows * batch) >> 32))
             throw std::invalid_argument("1 <= rows and rows * batch < 2^32");
         check_plain_device(e, scalars, batch, true, scale, dest, true, rows);
@@ -1227,7 +1224,7 @@ namespace sealhip
     void Evaluator::dot_scalars_mapped(const Ciphertext &e, const void *weights, size_t weight_count, bool narrow, const ItemMap &map,
                                        double scale, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_plain_device(e, static_cast<const uint64_t *>(weights), weight_count, true, scale, dest, false, 1, narrow);
         if (weight_count != map.second_batch())
             throw std::invalid_argument("weight_count does not equal the map's second_batch");
@@ -1248,10 +1245,8 @@ namespace sealhip
     void Evaluator::matmul_plain_items(const uint64_t *plain, const Ciphertext &e, size_t rows, size_t inner, size_t cols, bool second_transposed,
                                        bool result_transposed, double scale, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
-            ((rows * cols) >> 32))
-            throw std::invalid_argument("1 <= rows, inner, cols and rows * inner, inner * cols, rows * cols < 2^32");
+        StreamScope pool_scope(stream_);
+        check_matmul_shape(rows, inner, cols);
         check_plain_device(e, plain, rows * inner, true, scale, dest, false);
         if (e.batch() != inner * cols)
             throw std::invalid_argument("the ciphertext's batch does not equal inner * cols");
@@ -1273,10 +1268,8 @@ namespace sealhip
     void Evaluator::matmul_scalars_items(const void *weights, bool narrow, const Ciphertext &e, size_t rows, size_t inner, size_t cols,
                                          bool second_transposed, bool result_transposed, double scale, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
-            ((rows * cols) >> 32))
-            throw std::invalid_argument("1 <= rows, inner, cols and rows * inner, inner * cols, rows * cols < 2^32");
+        StreamScope pool_scope(stream_);
+        check_matmul_shape(rows, inner, cols);
         check_plain_device(e, static_cast<const uint64_t *>(weights), inner, true, scale, dest, false, rows, narrow);
         if (e.batch() != inner * cols)
             throw std::invalid_argument("the ciphertext's batch does not equal inner * cols");
@@ -1299,7 +1292,7 @@ namespace sealhip
     void Evaluator::conv2d_scalars_items(const void *weights, bool narrow, const Ciphertext &e, const Conv2dShape &shape, bool in_last,
                                          bool out_last, double scale, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         size_t oh, ow;
         if (const char *wrong = conv2d_shape_error(shape, oh, ow))
             throw std::invalid_argument(wrong);
@@ -1324,7 +1317,7 @@ namespace sealhip
     // (evaluator.cpp:2243-2282) - and the forward transform of a constant is that constant at every position
     void Evaluator::lift_scalars(size_t count, const uint64_t *values, const uint64_t *parms_id, uint64_t *words) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (!values || !words)
             throw std::invalid_argument(values ? "device_words cannot be null" : "values cannot be null");
         if ((uintptr_t)words % 16)
@@ -1395,7 +1388,7 @@ namespace sealhip
     }
     void Evaluator::dot_items(const Ciphertext &e1, const Ciphertext &e2, size_t group, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e1, "encrypted1");
         check_valid(e2, "encrypted2");
         check_dot_items_scheme(context_.scheme());
@@ -1407,7 +1400,7 @@ namespace sealhip
     }
     void Evaluator::dot_items_mapped(const Ciphertext &e1, const Ciphertext &e2, const ItemMap &map, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e1, "encrypted1");
         check_valid(e2, "encrypted2");
         check_dot_items_scheme(context_.scheme());
@@ -1423,13 +1416,11 @@ namespace sealhip
     void Evaluator::matmul_items(const Ciphertext &e1, const Ciphertext &e2, size_t rows, size_t inner, size_t cols, bool second_transposed,
                                  Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e1, "encrypted1");
         check_valid(e2, "encrypted2");
         check_dot_items_scheme(context_.scheme());
-        if (!rows || !inner || !cols || (rows >> 32) || (inner >> 32) || (cols >> 32) || ((rows * inner) >> 32) || ((inner * cols) >> 32) ||
-            ((rows * cols) >> 32))
-            throw std::invalid_argument("1 <= rows, inner, cols and rows * inner, inner * cols, rows * cols < 2^32");
+        check_matmul_shape(rows, inner, cols);
         if (e1.batch() != rows * inner || e2.batch() != inner * cols)
             throw std::invalid_argument("batch mismatch");
         double new_scale;
@@ -1450,7 +1441,7 @@ namespace sealhip
 
     void Evaluator::add_many(const std::vector<const Ciphertext *> &encrypteds, Ciphertext &destination) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (encrypteds.empty())
             throw std::invalid_argument("encrypteds cannot be empty");
         for (const Ciphertext *c : encrypteds)
@@ -1463,15 +1454,14 @@ namespace sealhip
 
     void Evaluator::multiply_many(const std::vector<const Ciphertext *> &encrypteds, const KSwitchKeys &relin_keys, Ciphertext &destination) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         // the product tree of evaluator.cpp:1649-1723, every product relinearized
         if (encrypteds.empty())
             throw std::invalid_argument("encrypteds vector must not be empty");
         for (const Ciphertext *c : encrypteds)
             if (!c || c == &destination)
                 throw std::invalid_argument("encrypteds must be different from destination");
-        if (&encrypteds[0]->context() != &context_ || !encrypteds[0]->level())
-            throw std::invalid_argument("encrypteds is not valid for encryption parameters");
+        check_context(*encrypteds[0], "encrypteds");
         if (context_.scheme() != Scheme::bfv && context_.scheme() != Scheme::bgv)
             throw std::logic_error("unsupported scheme");
         if (encrypteds.size() == 1)
@@ -1510,9 +1500,8 @@ namespace sealhip
 
     void Evaluator::exponentiate_inplace(Ciphertext &e, uint64_t exponent, const KSwitchKeys &relin_keys) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (&e.context() != &context_ || !e.level())
-            throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        StreamScope pool_scope(stream_);
+        check_context(e);
         if (relin_keys.context() != &context_)
             throw std::invalid_argument("relin_keys is not valid for encryption parameters");
         if (exponent == 0)
@@ -1527,19 +1516,31 @@ namespace sealhip
     }
 
     // ---- multiply (evaluator.cpp:352-708)
-    void Evaluator::multiply_inplace(Ciphertext &e1, const Ciphertext &e2) const
+    void Evaluator::check_product_operands(const Ciphertext &e1, const Ciphertext &e2) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         check_valid(e1, "encrypted1");
         check_valid(e2, "encrypted2");
         if (e1.level() != e2.level())
             throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
         if (e1.batch() != e2.batch())
             throw std::invalid_argument("batch mismatch");
+    }
+    size_t Evaluator::product_size(size_t s1, size_t s2) const
+    {
+        if (s1 < 2 || s2 < 2)
+            throw std::invalid_argument("encrypted size must be at least 2");
+        if (s1 + s2 - 1 > 16)
+            throw std::logic_error("invalid parameters");
+        return s1 + s2 - 1;
+    }
+    void Evaluator::multiply_inplace(Ciphertext &e1, const Ciphertext &e2) const
+    {
+        StreamScope pool_scope(stream_);
+        check_product_operands(e1, e2);
         switch (context_.scheme())
         {
         case Scheme::bfv:
-            bfv_multiply(e1, e2);
+            bfv_multiply_to(e1, e2, e1);
             break;
         case Scheme::ckks:
             ckks_multiply(e1, e2);
@@ -1554,7 +1555,7 @@ namespace sealhip
     }
     void Evaluator::multiply(const Ciphertext &e1, const Ciphertext &e2, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         // evaluator.h:239-247: destination = encrypted1; multiply_inplace(destination, encrypted2).
         // Device-resident fast path: the common size-2 x size-2 CKKS product writes the three result
         // polynomials straight into `dest` instead of copying encrypted1 first.
@@ -1565,12 +1566,7 @@ namespace sealhip
         if (context_.scheme() == Scheme::ckks && e1.size() == 2 && e2.size() == 2 && &dest.context() == &context_ &&
             dest.batch() == e1.batch())
         {
-            check_valid(e1, "encrypted1");
-            check_valid(e2, "encrypted2");
-            if (e1.level() != e2.level())
-                throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
-            if (e1.batch() != e2.batch())
-                throw std::invalid_argument("batch mismatch");
+            check_product_operands(e1, e2);
             if (!(e1.is_ntt_form() && e2.is_ntt_form()))
                 throw std::invalid_argument("encrypted1 or encrypted2 must be in NTT form");
             const Level &lvl = *e1.level();
@@ -1598,12 +1594,7 @@ namespace sealhip
         {
             // BFV: the same checks as multiply_inplace, then the product straight into `dest` (no copy of encrypted1: 6.8 GB per
             // step at BASELINE configs[3])
-            check_valid(e1, "encrypted1");
-            check_valid(e2, "encrypted2");
-            if (e1.level() != e2.level())
-                throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
-            if (e1.batch() != e2.batch())
-                throw std::invalid_argument("batch mismatch");
+            check_product_operands(e1, e2);
             bfv_multiply_to(e1, e2, dest);
             dest.is_ntt_form() = false;
             dest.scale() = e1.scale();
@@ -1620,71 +1611,61 @@ namespace sealhip
 
     void Evaluator::square_inplace(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         // ckks_square / bfv_square compute (c0^2, 2 c0 c1, c1^2) = the product of e with itself
         // (evaluator.cpp:878-1142); canonical results coincide with multiply(e, e).
         check_valid(e, "encrypted");
         multiply_inplace(e, e);
     }
 
-    // (c0, c1) x (d0, d1) -> three polynomials in e1, NTT form (evaluator.cpp:626-707).  When e1's slab has room the product is
-    // formed in place (every thread reads its four words before it writes its three); otherwise it goes straight into a new
-    // slab that e1 adopts - no copy of the two old polynomials, no zeroing of the third.
-    void Evaluator::tensor_2x2(Ciphertext &e1, const Ciphertext &e2, const Level &lvl, const PlaneGeom &g) const
+    // e1 <- the tensor product of the NTT-form operands e1 and e2, `size` polynomials (evaluator.cpp:626-707, 760-841).  The common
+    // (c0, c1) x (d0, d1) is formed in place when e1's slab has room (every thread reads its four words before it writes its three);
+    // everything else goes straight into a new slab that e1 adopts - no copy of the old polynomials, no zeroing of the new ones.
+    void Evaluator::tensor_ntt(Ciphertext &e1, const Ciphertext &e2, size_t size) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        const size_t words = 3 * g.words();
+        expect_scope();
+        const Level &lvl = *e1.level();
+        const PlaneGeom g{ (unsigned)context_.log_n(), lvl.K, (unsigned)e1.batch() };
+        const size_t words = size * g.words();
         const uint64_t *x = e1.data(), *y = (&e1 == &e2) ? x : e2.data(); // (completes a pending key-switch tail)
-        if (e1.capacity_words() >= words)
+        if (size == 3 && e1.capacity_words() >= words)
         {
             e1.reshape_uninitialized(&lvl, 3); // enough room: the words stay where they are
             ck(k_ckks_multiply_2x2(context_.dev_mods(), context_.ntt_tables().fpd, nullptr, x, y, e1.data(), g, stream_), "multiply 2x2");
+            return;
         }
-        else
-        {
-            uint64_t *out = DevicePool::global().alloc_words(words, stream_);
+        uint64_t *out = DevicePool::global().alloc_words(words, stream_);
+        if (size == 3)
             ck(k_ckks_multiply_2x2(context_.dev_mods(), context_.ntt_tables().fpd, nullptr, x, y, out, g, stream_), "multiply 2x2");
-            e1.adopt(&lvl, 3, out, words);
-        }
+        else
+            ck(k_multiply_general(context_.dev_mods(), nullptr, x, (unsigned)e1.size(), y, (unsigned)e2.size(), out, g, stream_),
+               context_.scheme() == Scheme::ckks ? "ckks_multiply general" : "bgv_multiply general");
+        e1.adopt(&lvl, size, out, words);
     }
 
     void Evaluator::ckks_multiply(Ciphertext &e1, const Ciphertext &e2) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         if (!(e1.is_ntt_form() && e2.is_ntt_form()))
             throw std::invalid_argument("encrypted1 or encrypted2 must be in NTT form");
         const Level &lvl = *e1.level();
-        size_t s1 = e1.size(), s2 = e2.size();
-        if (s1 < 2 || s2 < 2)
-            throw std::invalid_argument("encrypted size must be at least 2");
-        size_t dest = s1 + s2 - 1;
-        if (dest > 16)
-            throw std::logic_error("invalid parameters");
-        const bool self = (&e1 == &e2);
-        double new_scale = e1.scale() * e2.scale();
-        PlaneGeom g{ (unsigned)context_.log_n(), lvl.K, (unsigned)e1.batch() };
-        if (dest == 3 && may_defer_product(lvl, e1.batch()))
+        const size_t size = product_size(e1.size(), e2.size());
+        const double new_scale = e1.scale() * e2.scale();
+        if (size == 3 && may_defer_product(lvl, e1.batch()))
         {
             // Round 6 (LazyProduct, in place): e1's slab - its two polynomials as they are now, whatever was pending on them completed -
             // goes to the record, e1 gets a fresh slab of three whose words are pending.  Nothing is copied and nothing is computed here.
+            const bool self = (&e1 == &e2);
             (void)e1.data();
             if (!self)
                 (void)e2.data();
-            const size_t words = 3 * g.words();
+            const size_t words = 3 * e1.plane_words();
             uint64_t *fresh = DevicePool::global().alloc_words(words, stream_);
             uint64_t *old = e1.exchange_slab(&lvl, 3, fresh, words);
             defer_product(e1, nullptr, self ? nullptr : &e2, old);
         }
-        else if (dest == 3)
-            tensor_2x2(e1, self ? e1 : e2, lvl, g);
         else
-        {
-            size_t words = dest * g.words();
-            uint64_t *out = DevicePool::global().alloc_words(words);
-            ck(k_multiply_general(context_.dev_mods(), nullptr, e1.data(), (unsigned)s1, e2.data(), (unsigned)s2, out, g, stream_),
-               "ckks_multiply general");
-            e1.adopt(&lvl, dest, out, words);
-        }
+            tensor_ntt(e1, e2, size);
         e1.scale() = new_scale;
         if (!scale_within_bounds(e1.scale(), lvl))
             throw std::invalid_argument("scale out of bounds");
@@ -1694,41 +1675,19 @@ namespace sealhip
     // NTT-form operands; the scale is untouched and the correction factors multiply modulo t.
     void Evaluator::bgv_multiply(Ciphertext &e1, const Ciphertext &e2) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
         if (!(e1.is_ntt_form() && e2.is_ntt_form()))
             throw std::invalid_argument("encrypted1 or encrypted2 must be in NTT form");
-        const Level &lvl = *e1.level();
-        size_t s1 = e1.size(), s2 = e2.size();
-        if (s1 < 2 || s2 < 2)
-            throw std::invalid_argument("encrypted size must be at least 2");
-        size_t dest = s1 + s2 - 1;
-        if (dest > 16)
-            throw std::logic_error("invalid parameters");
-        const bool self = (&e1 == &e2);
+        const size_t size = product_size(e1.size(), e2.size());
         const uint64_t cf = host::mulmod(e1.correction_factor(), e2.correction_factor(), context_.plain_modulus());
-        PlaneGeom g{ (unsigned)context_.log_n(), lvl.K, (unsigned)e1.batch() };
-        if (dest == 3)
-            tensor_2x2(e1, self ? e1 : e2, lvl, g);
-        else
-        {
-            size_t words = dest * g.words();
-            uint64_t *out = DevicePool::global().alloc_words(words);
-            ck(k_multiply_general(context_.dev_mods(), nullptr, e1.data(), (unsigned)s1, e2.data(), (unsigned)s2, out, g, stream_),
-               "bgv_multiply general");
-            e1.adopt(&lvl, dest, out, words);
-        }
+        tensor_ntt(e1, e2, size);
         e1.correction_factor() = cf;
     }
 
-    void Evaluator::bfv_multiply(Ciphertext &e1, const Ciphertext &e2) const
-    {
-        bfv_multiply_to(e1, e2, e1);
-    }
     // the product of e1 and e2 into dest (dest may be e1): BEHZ reads its operands through the first transform pass and builds the
     // result in a new slab, so an out-of-place product needs no copy of e1 (evaluator.h:239-247 copies it first)
     void Evaluator::bfv_multiply_to(const Ciphertext &e1, const Ciphertext &e2, Ciphertext &dst) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         if (e1.is_ntt_form() || e2.is_ntt_form())
             throw std::invalid_argument("encrypted1 or encrypted2 cannot be in NTT form");
         const Level &lvl = *e1.level();
@@ -1736,12 +1695,7 @@ namespace sealhip
         const unsigned K = lvl.K, nBsk = lv.nBsk;
         const size_t N = context_.n(), B = e1.batch();
         const unsigned n_log = (unsigned)context_.log_n();
-        size_t s1 = e1.size(), s2 = e2.size();
-        if (s1 < 2 || s2 < 2)
-            throw std::invalid_argument("encrypted size must be at least 2");
-        size_t dest = s1 + s2 - 1;
-        if (dest > 16)
-            throw std::logic_error("invalid parameters");
+        const size_t s1 = e1.size(), s2 = e2.size(), dest = product_size(s1, s2);
         const bool self = (&e1 == &e2);
         const NttTables &tb = context_.ntt_tables();
         const ModDesc *mods = context_.dev_mods();

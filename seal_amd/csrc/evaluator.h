@@ -446,6 +446,7 @@ namespace sealhip
         void rotate_columns(const Ciphertext &encrypted, const KSwitchKeys &galois_keys, Ciphertext &destination) const;
         void rotate_vector(const Ciphertext &encrypted, int steps, const KSwitchKeys &galois_keys, Ciphertext &destination) const;
         void complex_conjugate(const Ciphertext &encrypted, const KSwitchKeys &galois_keys, Ciphertext &destination) const;
+        // in place = the operand as destination
         void rotate_rows_inplace(Ciphertext &encrypted, int steps, const KSwitchKeys &galois_keys) const;
         void rotate_columns_inplace(Ciphertext &encrypted, const KSwitchKeys &galois_keys) const;
         void rotate_vector_inplace(Ciphertext &encrypted, int steps, const KSwitchKeys &galois_keys) const;
@@ -523,9 +524,16 @@ namespace sealhip
     private:
         friend class Encryptor; // public-key encryption ends with one modulus switch from the level above (encryptor.cpp:139-186)
         void check_valid(const Ciphertext &ct, const char *what) const;
+        void check_context(const Ciphertext &ct, const char *what = "encrypted") const; // of this context and at a level: the walkers' and rotations' check
+        void check_batching() const;
         void check_native_form(const Ciphertext &ct) const; // coefficient form for BFV, NTT form for CKKS and BGV
         bool scale_within_bounds(double scale, const Level &lvl) const;
-        void bfv_multiply(Ciphertext &e1, const Ciphertext &e2) const;
+        // the level parms_id names, refused when there is none or it lies above `level` (the *_to walkers)
+        const Level *target_level(const Level *level, const uint64_t *parms_id) const;
+        void addsub(Ciphertext &e1, const Ciphertext &e2, int op) const; // op 0 add, 1 sub
+        void check_product_operands(const Ciphertext &e1, const Ciphertext &e2) const; // both valid, one level, one batch
+        size_t product_size(size_t size1, size_t size2) const;                         // -> size1 + size2 - 1, refused outside 3 .. 16
+        void check_matmul_shape(size_t rows, size_t inner, size_t cols) const;
         void bfv_multiply_to(const Ciphertext &e1, const Ciphertext &e2, Ciphertext &dst) const;
         void bgv_multiply(Ciphertext &e1, const Ciphertext &e2) const;
         void check_valid(const Plaintext &plain) const;
@@ -566,12 +574,14 @@ namespace sealhip
             Scratch &delta, const uint64_t *a, size_t a_stride, const ShoupOp *mul, unsigned ncomp, size_t items, uint64_t *out0,
             uint64_t *out1, size_t out_stride, int epi) const;
         void ckks_multiply(Ciphertext &e1, const Ciphertext &e2) const;
-        void tensor_2x2(Ciphertext &e1, const Ciphertext &e2, const Level &lvl, const struct PlaneGeom &g) const;
+        // e1 <- the NTT-domain tensor product of e1 and e2, `size` polynomials (ckks_multiply, bgv_multiply)
+        void tensor_ntt(Ciphertext &e1, const Ciphertext &e2, size_t size) const;
         void mod_switch_scale_to_next(Ciphertext &encrypted) const;
         void mod_switch_drop_to_next(Ciphertext &encrypted) const;
         void rotate_internal(Ciphertext &encrypted, int steps, const KSwitchKeys &galois_keys) const;
         void rotate_internal(const Ciphertext &encrypted, int steps, const KSwitchKeys &galois_keys, Ciphertext &destination) const;
-        void conjugate_internal(Ciphertext &encrypted, const KSwitchKeys &galois_keys) const;
+        // rotate_columns and complex_conjugate: the automorphism of step 0 (element 2N - 1), each for the schemes it serves
+        void conjugate(bool scheme_served, const Ciphertext &encrypted, const KSwitchKeys &galois_keys, Ciphertext &destination) const;
         void throw_if_transparent(const Ciphertext &ct) const;
         // ---- the key switch proper (evaluator_keyswitch.cpp).  ks_route decides everything once; the callers branch on it and hand the same
         // object down.  digit_parallel: the sums of [j0, j1) leave for the caller's exchange - one group, nothing folded, no tail here.
@@ -604,7 +614,24 @@ namespace sealhip
         const KsTargets &ks_targets(unsigned K) const;
 
         const Context &context_;
+        // The stream this evaluator's work is enqueued on, and THE RULE for StreamScope (pool.h tags a freed block with the calling
+        // thread's scope stream, so pool traffic of a call has to happen under a scope on stream_ whichever thread calls).  A method
+        // opens `StreamScope pool_scope(stream_)` only if it can be the outermost Evaluator call on a thread:
+        //   * the public methods - the C layer calls them, and so does the Encryptor (decryptor.cpp: evaluator_), outside any scope;
+        //     one that only checks and forwards to another public method needs none;
+        //   * mod_switch_scale_to_next - private, but the Encryptor calls it directly as a friend;
+        //   * the hooks a Ciphertext calls from arbitrary host code through settle(), drop_*() or its destructor: complete_tail,
+        //     forget_tail, complete_product, forget_product.
+        // Every other private method only runs under one of these and opens none; one that allocates from or frees to the pool
+        // begins with expect_scope() instead, so the emulated build checks the rule on every path the CPU suite runs.
         hipStream_t stream_ = nullptr;
+        void expect_scope() const
+        {
+#ifdef SEALHIP_CHECK_BOUNDS
+            if (!(DevicePool::thread_has_scope() && DevicePool::thread_stream() == stream_))
+                throw std::logic_error("an Evaluator helper ran outside a StreamScope on the evaluator's stream (evaluator.h: stream_)");
+#endif
+        }
         hipStream_t capture_stream_ = nullptr, saved_stream_ = nullptr;
         bool capturing_ = false;
         bool transparent_check_ = false;

@@ -230,7 +230,7 @@ namespace sealhip
     // ---- relinearize (evaluator.cpp:1144-1199)
     void Evaluator::relinearize_inplace(Ciphertext &e, const KSwitchKeys &relin_keys) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (&e.context() != &context_ || !e.level())
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         if (relin_keys.context() != &context_)
@@ -275,7 +275,7 @@ namespace sealhip
         const LazyProduct p = detach_product(e); // from here on e is an ordinary size-3 ciphertext whose words are not there yet
         lazy_product_count_fused();
         uint64_t *target = e.data_ + 2 * e.plane_words(); // (names the polynomial; neither read nor written: x1 y1 is formed from the operands where it is used)
-        StreamScope pool_scope(stream_);
+        expect_scope();
         try
         {
             Scratch acc(switch_key_acc_words(e));
@@ -306,7 +306,7 @@ namespace sealhip
 
     void Evaluator::relinearize_partial(Ciphertext &e, const KSwitchKeys &relin_keys, unsigned j0, unsigned j1, uint64_t *acc) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (&e.context() != &context_ || !e.level())
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         if (relin_keys.context() != &context_ && !(j0 == j1 && !relin_keys.context())) // a rank without digits may hold no key
@@ -317,7 +317,7 @@ namespace sealhip
     }
     void Evaluator::relinearize_finish(Ciphertext &e, uint64_t *acc, unsigned parts) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (&e.context() != &context_ || !e.level() || e.size() != 3)
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         switch_key_finish(e, acc, parts, false, true);
@@ -327,7 +327,7 @@ namespace sealhip
     void Evaluator::apply_galois_partial(
         Ciphertext &e, uint32_t galois_elt, const KSwitchKeys &galois_keys, unsigned j0, unsigned j1, uint64_t *acc) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         if (galois_keys.context() != &context_ && !(j0 == j1 && !galois_keys.context()))
             throw std::invalid_argument("galois_keys is not valid for encryption parameters");
@@ -351,7 +351,7 @@ namespace sealhip
     }
     void Evaluator::apply_galois_finish(Ciphertext &e, uint64_t *acc, unsigned parts) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (&e.context() != &context_ || !e.level() || e.size() != 2)
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         switch_key_finish(e, acc, parts, false, true);
@@ -372,7 +372,7 @@ namespace sealhip
     void Evaluator::switch_key_partial(const Ciphertext &e, const uint64_t *target, const KSwitchKeys &keys, size_t key_index, uint64_t *acc_out,
                                        const KsRoute &route, const KsAddend &addend) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         check_valid(e, "encrypted");
         if (!target)
             throw std::invalid_argument("target_iter");
@@ -598,7 +598,7 @@ namespace sealhip
 
     void Evaluator::switch_key_finish(Ciphertext &e, uint64_t *acc, unsigned parts, bool acc_has_addend, bool may_defer) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         check_valid(e, "encrypted");
         if (!acc)
             throw std::invalid_argument("acc");
@@ -711,7 +711,7 @@ namespace sealhip
     void Evaluator::switch_key_inplace(Ciphertext &e, const uint64_t *target, const KSwitchKeys &keys, size_t key_index, const KsRoute &route,
                                        const KsAddend &addend) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         if (&e.context() != &context_ || !e.level())
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         const unsigned K = e.level()->K, split = route.split;
@@ -741,7 +741,7 @@ namespace sealhip
     // (inverse transforms of the sums, mod-down by P), then rns.cpp:789-828 (divide_and_round_q_last_inplace) on the result.
     void Evaluator::switch_key_finish_modswitch_bfv(Ciphertext &e, uint64_t *acc_p, const Level *next) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         const Level &lvl = *e.level();
         const Level &klvl = context_.key_level();
         const unsigned K = lvl.K, L = klvl.K;
@@ -774,7 +774,7 @@ namespace sealhip
     // (divide_and_round_q_last_ntt_inplace); see NttTail2 (ntt_kernels.h) for the algebra.
     void Evaluator::switch_key_finish_rescale(Ciphertext &e, uint64_t *acc_p, const Level *next, double destination_scale, bool acc_has_addend) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         const Level &lvl = *e.level();
         const Level &klvl = context_.key_level();
         const unsigned K = lvl.K, L = klvl.K;
@@ -912,7 +912,7 @@ namespace sealhip
 
     void Evaluator::switch_key_pack_targets(const Ciphertext &e, const uint64_t *acc, unsigned nranks, uint64_t *send, uint64_t *sp) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         const unsigned m = switch_key_slots(e, nranks);
         if (!acc || !send || !sp)
             throw std::invalid_argument("buffer");
@@ -922,7 +922,7 @@ namespace sealhip
     void Evaluator::switch_key_finish_owned(
         const Ciphertext &e, const uint64_t *recv, const uint64_t *sp, unsigned nranks, unsigned rank, uint64_t *own) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         const unsigned m = switch_key_slots(e, nranks);
         if (rank >= nranks)
             throw std::invalid_argument("rank");
@@ -994,7 +994,7 @@ namespace sealhip
 
     void Evaluator::switch_key_add_gathered(Ciphertext &e, const uint64_t *all, unsigned nranks) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         const unsigned m = switch_key_slots(e, nranks);
         if (!all)
             throw std::invalid_argument("buffer");
@@ -1007,7 +1007,7 @@ namespace sealhip
 
     void Evaluator::switch_key_exchange_finish(Ciphertext &e, uint64_t *acc, Comm &comm, KsExchange how) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         const unsigned G = (unsigned)comm.size();
         const size_t words = switch_key_acc_words(e);
         if (how == KsExchange::all_reduce || context_.scheme() != Scheme::ckks)
@@ -1030,7 +1030,7 @@ namespace sealhip
 
     void Evaluator::relinearize_inplace(Ciphertext &e, const KSwitchKeys &relin_keys, Comm &comm, KsExchange how) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (&e.context() != &context_ || !e.level())
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         unsigned first, count;
@@ -1044,7 +1044,7 @@ namespace sealhip
 
     void Evaluator::apply_galois_inplace(Ciphertext &e, uint32_t galois_elt, const KSwitchKeys &galois_keys, Comm &comm, KsExchange how) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (&e.context() != &context_ || !e.level())
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         unsigned first, count;
@@ -1057,7 +1057,7 @@ namespace sealhip
 
     void Evaluator::rotate_vector_inplace(Ciphertext &e, int steps, const KSwitchKeys &galois_keys, Comm &comm, KsExchange how) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (context_.scheme() != Scheme::ckks)
             throw std::logic_error("unsupported scheme");
         if (&e.context() != &context_ || !e.level())

@@ -7,7 +7,7 @@ namespace sealhip
     // ---- modulus switching (evaluator.cpp:1201-1647)
     void Evaluator::mod_switch_scale_to_next(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         const Scheme scheme = context_.scheme();
         check_native_form(e);
         const Level &lvl = *e.level();
@@ -141,7 +141,7 @@ namespace sealhip
 
     void Evaluator::mod_switch_drop_to_next(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         check_native_form(e);
         const Level &lvl = *e.level();
         const Level *next = context_.next_level(lvl);
@@ -158,7 +158,7 @@ namespace sealhip
 
     void Evaluator::mod_switch_to_next_inplace(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         if (e.level() == &context_.last_level())
             throw std::invalid_argument("end of modulus switching chain reached");
@@ -181,21 +181,16 @@ namespace sealhip
 
     void Evaluator::mod_switch_to_inplace(Ciphertext &e, const uint64_t *parms_id) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        const Level *target = context_.level_by_parms_id(parms_id);
-        if (&e.context() != &context_ || !e.level())
-            throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        if (!target)
-            throw std::invalid_argument("parms_id is not valid for encryption parameters");
-        if (e.level()->chain_index < target->chain_index)
-            throw std::invalid_argument("cannot switch to higher level modulus");
+        StreamScope pool_scope(stream_);
+        check_context(e);
+        const Level *target = target_level(e.level(), parms_id);
         while (e.level() != target)
             mod_switch_to_next_inplace(e);
     }
 
     void Evaluator::rescale_to_next_inplace(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         if (e.level() == &context_.last_level())
             throw std::invalid_argument("end of modulus switching chain reached");
@@ -215,13 +210,9 @@ namespace sealhip
 
     void Evaluator::rescale_to_inplace(Ciphertext &e, const uint64_t *parms_id) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
-        const Level *target = context_.level_by_parms_id(parms_id);
-        if (!target)
-            throw std::invalid_argument("parms_id is not valid for encryption parameters");
-        if (e.level()->chain_index < target->chain_index)
-            throw std::invalid_argument("cannot switch to higher level modulus");
+        const Level *target = target_level(e.level(), parms_id);
         if (context_.scheme() != Scheme::ckks)
             throw std::invalid_argument("unsupported operation for scheme type");
         while (e.level() != target)
@@ -231,7 +222,7 @@ namespace sealhip
 
     void Evaluator::mod_reduce_to_next_inplace(Ciphertext &e) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         check_valid(e, "encrypted");
         if (e.level() == &context_.last_level())
             throw std::invalid_argument("end of modulus switching chain reached");
@@ -242,14 +233,9 @@ namespace sealhip
     // evaluator.cpp:1625-1647
     void Evaluator::mod_reduce_to_inplace(Ciphertext &e, const uint64_t *parms_id) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (&e.context() != &context_ || !e.level())
-            throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        const Level *target = context_.level_by_parms_id(parms_id);
-        if (!target)
-            throw std::invalid_argument("parms_id is not valid for encryption parameters");
-        if (e.level()->chain_index < target->chain_index)
-            throw std::invalid_argument("cannot switch to higher level modulus");
+        StreamScope pool_scope(stream_);
+        check_context(e);
+        const Level *target = target_level(e.level(), parms_id);
         while (e.level() != target)
             mod_reduce_to_next_inplace(e);
     }
@@ -272,7 +258,7 @@ namespace sealhip
     // into a new slab either way, so the out-of-place form reads `encrypted` where it lies: no copy of the operand
     void Evaluator::apply_galois(const Ciphertext &e, uint32_t galois_elt, const KSwitchKeys &galois_keys, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        StreamScope pool_scope(stream_);
         if (&dest != &e && (&dest.context() != &context_ || dest.batch() != e.batch()))
         {
             dest = e; // a destination of another shape: the reference's two steps
@@ -381,16 +367,15 @@ namespace sealhip
     }
 
     // out-of-place forms (evaluator.h:1130-1315: destination = encrypted; *_inplace(destination)): with the exact key present the
-    // operand is read where it lies; the NAF fallback copies first like the reference
+    // operand is read where it lies; the NAF fallback copies first like the reference.  The in-place forms are these with the
+    // operand as destination (evaluator.h)
     void Evaluator::rotate_internal(const Ciphertext &e, int steps, const KSwitchKeys &galois_keys, Ciphertext &dest) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
+        expect_scope();
         if (&dest == &e)
             return rotate_internal(dest, steps, galois_keys);
-        if (&e.context() != &context_ || !e.level())
-            throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        if (!context_.using_batching())
-            throw std::logic_error("encryption parameters do not support batching");
+        check_context(e);
+        check_batching();
         if (galois_keys.context() != &context_)
             throw std::invalid_argument("galois_keys is not valid for encryption parameters");
         const uint32_t elt = steps ? galois_elt_from_step(steps) : 0;
@@ -401,43 +386,56 @@ namespace sealhip
     }
     void Evaluator::rotate_rows(const Ciphertext &e, int steps, const KSwitchKeys &gk, Ciphertext &dest) const
     {
+        StreamScope pool_scope(stream_);
         if (context_.scheme() != Scheme::bfv && context_.scheme() != Scheme::bgv)
             throw std::logic_error("unsupported scheme");
         rotate_internal(e, steps, gk, dest);
     }
     void Evaluator::rotate_vector(const Ciphertext &e, int steps, const KSwitchKeys &gk, Ciphertext &dest) const
     {
+        StreamScope pool_scope(stream_);
         if (context_.scheme() != Scheme::ckks)
             throw std::logic_error("unsupported scheme");
         rotate_internal(e, steps, gk, dest);
     }
+    // (checks and forwards to apply_galois: no scope of its own)
+    void Evaluator::conjugate(bool scheme_served, const Ciphertext &e, const KSwitchKeys &gk, Ciphertext &dest) const
+    {
+        if (!scheme_served)
+            throw std::logic_error("unsupported scheme");
+        check_context(e);
+        check_batching();
+        apply_galois(e, galois_elt_from_step(0), gk, dest);
+    }
     void Evaluator::rotate_columns(const Ciphertext &e, const KSwitchKeys &gk, Ciphertext &dest) const
     {
-        if (context_.scheme() != Scheme::bfv && context_.scheme() != Scheme::bgv)
-            throw std::logic_error("unsupported scheme");
-        if (&e.context() != &context_ || !e.level())
-            throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        if (!context_.using_batching())
-            throw std::logic_error("encryption parameters do not support batching");
-        apply_galois(e, galois_elt_from_step(0), gk, dest);
+        conjugate(context_.scheme() == Scheme::bfv || context_.scheme() == Scheme::bgv, e, gk, dest);
     }
     void Evaluator::complex_conjugate(const Ciphertext &e, const KSwitchKeys &gk, Ciphertext &dest) const
     {
-        if (context_.scheme() != Scheme::ckks)
-            throw std::logic_error("unsupported scheme");
-        if (&e.context() != &context_ || !e.level())
-            throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        if (!context_.using_batching())
-            throw std::logic_error("encryption parameters do not support batching");
-        apply_galois(e, galois_elt_from_step(0), gk, dest);
+        conjugate(context_.scheme() == Scheme::ckks, e, gk, dest);
+    }
+    void Evaluator::rotate_rows_inplace(Ciphertext &e, int steps, const KSwitchKeys &gk) const
+    {
+        rotate_rows(e, steps, gk, e);
+    }
+    void Evaluator::rotate_columns_inplace(Ciphertext &e, const KSwitchKeys &gk) const
+    {
+        rotate_columns(e, gk, e);
+    }
+    void Evaluator::rotate_vector_inplace(Ciphertext &e, int steps, const KSwitchKeys &gk) const
+    {
+        rotate_vector(e, steps, gk, e);
+    }
+    void Evaluator::complex_conjugate_inplace(Ciphertext &e, const KSwitchKeys &gk) const
+    {
+        complex_conjugate(e, gk, e);
     }
     void Evaluator::rotate_internal(Ciphertext &e, int steps, const KSwitchKeys &galois_keys) const
     {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (&e.context() != &context_ || !e.level())
-            throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        if (!context_.using_batching())
-            throw std::logic_error("encryption parameters do not support batching");
+        expect_scope();
+        check_context(e);
+        check_batching();
         if (galois_keys.context() != &context_)
             throw std::invalid_argument("galois_keys is not valid for encryption parameters");
         if (steps == 0)
@@ -457,42 +455,5 @@ namespace sealhip
                 if ((size_t)std::abs(step) != (coeff_count >> 1))
                     rotate_internal(e, step, galois_keys);
         }
-    }
-    void Evaluator::conjugate_internal(Ciphertext &e, const KSwitchKeys &galois_keys) const
-    {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (&e.context() != &context_ || !e.level())
-            throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        if (!context_.using_batching())
-            throw std::logic_error("encryption parameters do not support batching");
-        apply_galois_inplace(e, galois_elt_from_step(0), galois_keys);
-    }
-    void Evaluator::rotate_rows_inplace(Ciphertext &e, int steps, const KSwitchKeys &gk) const
-    {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (context_.scheme() != Scheme::bfv && context_.scheme() != Scheme::bgv)
-            throw std::logic_error("unsupported scheme");
-        rotate_internal(e, steps, gk);
-    }
-    void Evaluator::rotate_columns_inplace(Ciphertext &e, const KSwitchKeys &gk) const
-    {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (context_.scheme() != Scheme::bfv && context_.scheme() != Scheme::bgv)
-            throw std::logic_error("unsupported scheme");
-        conjugate_internal(e, gk);
-    }
-    void Evaluator::rotate_vector_inplace(Ciphertext &e, int steps, const KSwitchKeys &gk) const
-    {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (context_.scheme() != Scheme::ckks)
-            throw std::logic_error("unsupported scheme");
-        rotate_internal(e, steps, gk);
-    }
-    void Evaluator::complex_conjugate_inplace(Ciphertext &e, const KSwitchKeys &gk) const
-    {
-        StreamScope pool_scope(stream_); // pool traffic of this call is ordered on the evaluator's stream whoever calls (pool.h)
-        if (context_.scheme() != Scheme::ckks)
-            throw std::logic_error("unsupported scheme");
-        conjugate_internal(e, gk);
     }
 } // namespace sealhip
