@@ -20,6 +20,38 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _parms_id(getter, handle):
+    """a parms_id getter of the C layer -> 4-tuple"""
+    out = (C.c_uint64 * 4)()
+    N.check(getattr(N.lib(), getter)(handle, out))
+    return tuple(out)
+
+
+def _save_bytes(size, save):
+    """size(byref(capacity)) names the buffer, save(buffer, c_uint64(capacity), byref(written)) fills it -> the bytes written"""
+    cap = C.c_int64()
+    N.check(size(C.byref(cap)))
+    buf = (C.c_uint8 * cap.value)()
+    n = C.c_int64()
+    N.check(save(buf, C.c_uint64(cap.value), C.byref(n)))
+    return C.string_at(buf, n.value)
+
+
+def _object_bytes(kind, handle, compr_mode):
+    """<kind>_SaveSize + <kind>_Save of an object"""
+    L, mode = N.lib(), C.c_uint8(compr_mode)
+    return _save_bytes(lambda cap: getattr(L, kind + "_SaveSize")(handle, mode, cap),
+                       lambda buf, cap, n: getattr(L, kind + "_Save")(handle, buf, cap, mode, n))
+
+
+def _load_bytes(load, data, *before):
+    """load(*before, stream, c_uint64(size), byref(read)) parses `data` in place -> the bytes read"""
+    data = bytes(data)
+    n = C.c_int64()
+    N.check(load(*before, C.cast(C.c_char_p(data), C.c_void_p), C.c_uint64(len(data)), C.byref(n)))
+    return n.value
+
+
 class CoeffModulus:
     @staticmethod
     def Create(poly_modulus_degree, bit_sizes):
@@ -82,9 +114,7 @@ class EncryptionParameters:
         return v.value
 
     def parms_id(self):
-        out = (C.c_uint64 * 4)()
-        N.check(N.lib().EncParams_GetParmsId(self._h, out))
-        return tuple(out)
+        return _parms_id("EncParams_GetParmsId", self._h)
 
     def copy(self):
         h = C.c_void_p()
@@ -109,20 +139,13 @@ class EncryptionParameters:
 
     def save_bytes(self, compr_mode=0):
         """EncryptionParameters::save (compr_mode 0 none, 1 zlib, 2 zstd)"""
-        cap = C.c_int64()
-        N.check(N.lib().EncParams_SaveSize(self._h, C.c_uint8(compr_mode), C.byref(cap)))
-        buf = (C.c_uint8 * cap.value)()
-        n = C.c_int64()
-        N.check(N.lib().EncParams_Save(self._h, buf, C.c_uint64(cap.value), C.c_uint8(compr_mode), C.byref(n)))
-        return C.string_at(buf, n.value)
+        return _object_bytes("EncParams", self._h, compr_mode)
 
     def load_bytes(self, data):
         """EncryptionParameters::load; returns the bytes read"""
-        data = bytes(data)
-        n = C.c_int64()
-        N.check(N.lib().EncParams_Load(self._h, C.cast(C.c_char_p(data), C.c_void_p), C.c_uint64(len(data)), C.byref(n)))
+        n = _load_bytes(N.lib().EncParams_Load, data, self._h)
         self.scheme = {v: k for k, v in SCHEME.items()}[self.scheme_id()]
-        return n.value
+        return n
 
 
 class SEALContext:
@@ -262,9 +285,7 @@ class ContextData:
         return v.value
 
     def parms_id(self):
-        out = (C.c_uint64 * 4)()
-        N.check(N.lib().ContextData_ParmsId(self._h, out))
-        return tuple(out)
+        return _parms_id("ContextData_ParmsId", self._h)
 
     def parms(self):
         h = C.c_void_p()
@@ -365,9 +386,7 @@ class Ciphertext:
         return self._get("Ciphertext_CorrectionFactor", C.c_uint64)
 
     def parms_id(self):
-        out = (C.c_uint64 * 4)()
-        N.check(N.lib().Ciphertext_ParmsId(self._h, out))
-        return tuple(out)
+        return _parms_id("Ciphertext_ParmsId", self._h)
 
     def chain_index(self):
         return self.context.chain_index(self.parms_id())
@@ -478,15 +497,9 @@ class Ciphertext:
     # -- the reference's wire format (Ciphertext::save / load / unsafe_load, ciphertext.cpp:153-403)
     def load_bytes(self, data, unsafe=False, item=None):
         """seal::Ciphertext::load (unsafe=True: unsafe_load) of a serialized stream; item = slot of a batch.  Returns bytes read."""
-        data = bytes(data)
-        buf = C.cast(C.c_char_p(data), C.c_void_p)  # the stream is parsed in place
-        n = C.c_int64()
         if item is not None:
-            N.check(N.lib().Ciphertext_LoadItem(self._h, self.context._h, C.c_uint64(item), buf, C.c_uint64(len(data)), C.byref(n)))
-        else:
-            fn = N.lib().Ciphertext_UnsafeLoad if unsafe else N.lib().Ciphertext_Load
-            N.check(fn(self._h, self.context._h, buf, C.c_uint64(len(data)), C.byref(n)))
-        return n.value
+            return _load_bytes(N.lib().Ciphertext_LoadItem, data, self._h, self.context._h, C.c_uint64(item))
+        return _load_bytes(N.lib().Ciphertext_UnsafeLoad if unsafe else N.lib().Ciphertext_Load, data, self._h, self.context._h)
 
     def save_size(self, compr_mode=0):
         return self._get2("Ciphertext_SaveSize", C.c_uint8(compr_mode), C.c_int64)
@@ -498,14 +511,11 @@ class Ciphertext:
 
     def save_bytes(self, item=None, compr_mode=0):
         """seal::Ciphertext::save(compr_mode_type::none) of the ciphertext (or of slot `item` of a batch)"""
-        cap = self.save_size(compr_mode)
-        buf = (C.c_uint8 * cap)()
-        n = C.c_int64()
-        if item is not None:
-            N.check(N.lib().Ciphertext_SaveItem(self._h, C.c_uint64(item), buf, C.c_uint64(cap), C.c_uint8(compr_mode), C.byref(n)))
-        else:
-            N.check(N.lib().Ciphertext_Save(self._h, buf, C.c_uint64(cap), C.c_uint8(compr_mode), C.byref(n)))
-        return C.string_at(buf, n.value)
+        if item is None:
+            return _object_bytes("Ciphertext", self._h, compr_mode)
+        L, mode = N.lib(), C.c_uint8(compr_mode)
+        return _save_bytes(lambda cap: L.Ciphertext_SaveSize(self._h, mode, cap),
+                           lambda buf, cap, n: L.Ciphertext_SaveItem(self._h, C.c_uint64(item), buf, cap, mode, n))
 
     @staticmethod
     def from_numpy(context, array, parms_id, is_ntt_form, scale=1.0, correction_factor=1):
@@ -574,9 +584,7 @@ class Plaintext:
         return v.value
 
     def parms_id(self):
-        pid = (C.c_uint64 * 4)()
-        N.check(N.lib().Plaintext_GetParmsId(self._h, pid))
-        return tuple(pid)
+        return _parms_id("Plaintext_GetParmsId", self._h)
 
     def set_parms_id(self, parms_id):
         pid = (C.c_uint64 * 4)(*parms_id)
@@ -597,21 +605,11 @@ class Plaintext:
 
     # -- the reference's wire format (Plaintext::save / load / unsafe_load)
     def load_bytes(self, data, unsafe=False):
-        data = bytes(data)
-        buf = C.cast(C.c_char_p(data), C.c_void_p)
-        n = C.c_int64()
-        fn = N.lib().Plaintext_UnsafeLoad if unsafe else N.lib().Plaintext_Load
-        N.check(fn(self._h, self.context._h, buf, C.c_uint64(len(data)), C.byref(n)))
-        return n.value
+        return _load_bytes(N.lib().Plaintext_UnsafeLoad if unsafe else N.lib().Plaintext_Load, data, self._h, self.context._h)
 
     def save_bytes(self, compr_mode=0):
         """Plaintext::save; compr_mode 0 none, 1 zlib, 2 zstd"""
-        cap = C.c_int64()
-        N.check(N.lib().Plaintext_SaveSize(self._h, C.c_uint8(compr_mode), C.byref(cap)))
-        buf = (C.c_uint8 * cap.value)()
-        n = C.c_int64()
-        N.check(N.lib().Plaintext_Save(self._h, buf, C.c_uint64(cap.value), C.c_uint8(compr_mode), C.byref(n)))
-        return C.string_at(buf, n.value)
+        return _object_bytes("Plaintext", self._h, compr_mode)
 
 
 class KSwitchKeys:
@@ -643,21 +641,11 @@ class KSwitchKeys:
 
     def load_bytes(self, data, unsafe=False):
         """KSwitchKeys::load / unsafe_load of a serialized RelinKeys / GaloisKeys stream (seeded or full).  Returns bytes read."""
-        data = bytes(data)
-        buf = C.cast(C.c_char_p(data), C.c_void_p)  # the stream is parsed in place
-        n = C.c_int64()
-        fn = N.lib().KSwitchKeys_UnsafeLoad if unsafe else N.lib().KSwitchKeys_Load
-        N.check(fn(self._h, self.context._h, buf, C.c_uint64(len(data)), C.byref(n)))
-        return n.value
+        return _load_bytes(N.lib().KSwitchKeys_UnsafeLoad if unsafe else N.lib().KSwitchKeys_Load, data, self._h, self.context._h)
 
     def save_bytes(self, compr_mode=0):
         """KSwitchKeys::save of the full keys (compr_mode 0 none, 1 zlib, 2 zstd)"""
-        cap = C.c_int64()
-        N.check(N.lib().KSwitchKeys_SaveSize(self._h, C.c_uint8(compr_mode), C.byref(cap)))
-        buf = (C.c_uint8 * cap.value)()
-        n = C.c_int64()
-        N.check(N.lib().KSwitchKeys_Save(self._h, buf, C.c_uint64(cap.value), C.c_uint8(compr_mode), C.byref(n)))
-        return C.string_at(buf, n.value)
+        return _object_bytes("KSwitchKeys", self._h, compr_mode)
 
     def has_index(self, index):
         b = C.c_bool()
@@ -706,9 +694,7 @@ class KSwitchKeys:
         N.check(N.lib().KSwitchKeys_ClearDataAndReserve(self._h, C.c_uint64(size)))
 
     def parms_id(self):
-        out = (C.c_uint64 * 4)()
-        N.check(N.lib().KSwitchKeys_GetParmsId(self._h, out))
-        return tuple(out)
+        return _parms_id("KSwitchKeys_GetParmsId", self._h)
 
     def set_parms_id(self, parms_id):
         N.check(N.lib().KSwitchKeys_SetParmsId(self._h, (C.c_uint64 * 4)(*parms_id)))
@@ -767,17 +753,10 @@ class SecretKey:
 
     def save_bytes(self, compr_mode=0):
         """SecretKey::save (compr_mode 0 none, 1 zlib, 2 zstd)"""
-        cap = C.c_int64()
-        N.check(N.lib().SecretKey_SaveSize(self._h, C.c_uint8(compr_mode), C.byref(cap)))
-        buf = (C.c_uint8 * cap.value)()
-        n = C.c_int64()
-        N.check(N.lib().SecretKey_Save(self._h, buf, C.c_uint64(cap.value), C.c_uint8(compr_mode), C.byref(n)))
-        return C.string_at(buf, n.value)
+        return _object_bytes("SecretKey", self._h, compr_mode)
 
     def parms_id(self):
-        out = (C.c_uint64 * 4)()
-        N.check(N.lib().SecretKey_ParmsId(self._h, out))
-        return tuple(out)
+        return _parms_id("SecretKey_ParmsId", self._h)
 
     def copy(self):
         k = SecretKey.__new__(SecretKey)
@@ -789,11 +768,7 @@ class SecretKey:
         N.check(N.lib().SecretKey_Assign(self._h, other._h))
 
     def load_bytes(self, data, unsafe=False):
-        data = bytes(data)
-        n = C.c_int64()
-        fn = N.lib().SecretKey_UnsafeLoad if unsafe else N.lib().SecretKey_Load
-        N.check(fn(self._h, self.context._h, C.cast(C.c_char_p(data), C.c_void_p), C.c_uint64(len(data)), C.byref(n)))
-        return n.value
+        return _load_bytes(N.lib().SecretKey_UnsafeLoad if unsafe else N.lib().SecretKey_Load, data, self._h, self.context._h)
 
 
 class Decryptor:
@@ -949,17 +924,10 @@ class PublicKey:
 
     def save_bytes(self, compr_mode=0):
         """PublicKey::save (compr_mode 0 none, 1 zlib, 2 zstd)"""
-        cap = C.c_int64()
-        N.check(N.lib().PublicKey_SaveSize(self._h, C.c_uint8(compr_mode), C.byref(cap)))
-        buf = (C.c_uint8 * cap.value)()
-        n = C.c_int64()
-        N.check(N.lib().PublicKey_Save(self._h, buf, C.c_uint64(cap.value), C.c_uint8(compr_mode), C.byref(n)))
-        return C.string_at(buf, n.value)
+        return _object_bytes("PublicKey", self._h, compr_mode)
 
     def parms_id(self):
-        out = (C.c_uint64 * 4)()
-        N.check(N.lib().PublicKey_ParmsId(self._h, out))
-        return tuple(out)
+        return _parms_id("PublicKey_ParmsId", self._h)
 
     def copy(self):
         k = PublicKey.__new__(PublicKey)
@@ -971,11 +939,7 @@ class PublicKey:
         N.check(N.lib().PublicKey_Assign(self._h, other._h))
 
     def load_bytes(self, data, unsafe=False):
-        data = bytes(data)
-        n = C.c_int64()
-        fn = N.lib().PublicKey_UnsafeLoad if unsafe else N.lib().PublicKey_Load
-        N.check(fn(self._h, self.context._h, C.cast(C.c_char_p(data), C.c_void_p), C.c_uint64(len(data)), C.byref(n)))
-        return n.value
+        return _load_bytes(N.lib().PublicKey_UnsafeLoad if unsafe else N.lib().PublicKey_Load, data, self._h, self.context._h)
 
 
 class KeyGenerator:
@@ -1177,12 +1141,7 @@ class Encryptor:
         return self._encrypt_device(N.lib().Encryptor_EncryptDevice, words, batch, parms_id, scale, seeds, destination)
 
     def _save(self, parms_id, call):
-        cap = C.c_int64()
-        N.check(N.lib().Encryptor_SymmetricSaveSize(self._h, (C.c_uint64 * 4)(*parms_id), C.byref(cap)))
-        buf = (C.c_uint8 * cap.value)()
-        n = C.c_int64()
-        N.check(call(buf, C.c_uint64(cap.value), C.byref(n)))
-        return C.string_at(buf, n.value)
+        return _save_bytes(lambda cap: N.lib().Encryptor_SymmetricSaveSize(self._h, (C.c_uint64 * 4)(*parms_id), cap), call)
 
     def encrypt_zero_symmetric_save(self, parms_id):
         pid = (C.c_uint64 * 4)(*parms_id)

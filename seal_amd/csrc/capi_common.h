@@ -15,6 +15,7 @@
 #include <initializer_list>
 #include <new>
 #include <string>
+#include <type_traits>
 
 namespace sealhip
 {
@@ -102,20 +103,83 @@ namespace
         return *dst;
     }
 
-    // The body of an Evaluator_* operation (capi_evaluator.cpp): E_POINTER when thisptr or one of `handles` is null - the handles an
-    // entry dereferences itself; a pointer the C++ layer refuses (std::invalid_argument) is not listed.  Then body(evaluator) runs
-    // inside the exception ladder and under a StreamScope on the evaluator's stream: the one scope an operation needs, whichever
-    // thread calls (evaluator.h: Evaluator::stream_).  A template, so outside every extern "C" block.
+    // The body of every entry: E_POINTER when one of `handles` is null - the pointers an entry dereferences itself; a pointer that
+    // is optional or that the C++ layer refuses (std::invalid_argument) is not listed.  Then body() runs inside the exception
+    // ladder; it returns nothing (S_OK) or an SHL_HRESULT of its own.  A template, so outside every extern "C" block.
+    template <class Body>
+    SHL_HRESULT guarded(std::initializer_list<const void *> handles, Body body)
+    {
+        for (const void *handle : handles)
+            IfNullRet(handle, SHL_E_POINTER);
+        SHL_TRY
+        if constexpr (std::is_void<decltype(body())>::value)
+            body();
+        else
+            return body();
+        SHL_CATCH
+    }
+
+    // The body of an Evaluator_* operation (capi_evaluator.cpp): guarded, thisptr first, and body(evaluator) under a StreamScope on
+    // the evaluator's stream: the one scope an operation needs, whichever thread calls (evaluator.h: Evaluator::stream_).
     template <class Body>
     SHL_HRESULT ev_call(void *thisptr, std::initializer_list<const void *> handles, Body body)
     {
         IfNullRet(thisptr, SHL_E_POINTER);
-        for (const void *handle : handles)
-            IfNullRet(handle, SHL_E_POINTER);
-        SHL_TRY
-        Evaluator &ev = *as<Evaluator>(thisptr);
-        StreamScope stream_scope(ev.stream());
-        body(ev);
-        SHL_CATCH
+        return guarded(handles, [&] {
+            Evaluator &ev = *as<Evaluator>(thisptr);
+            StreamScope stream_scope(ev.stream());
+            body(ev);
+        });
+    }
+
+    static const uint64_t kParmsIdZero[4] = { 0, 0, 0, 0 };
+    // a parms_id getter: the level's, parms_id_zero without one
+    inline void copy_parms_id(uint64_t *parms_id, const Level *level)
+    {
+        std::memcpy(parms_id, level ? level->parms_id : kParmsIdZero, 32);
+    }
+
+    // ---- the object streams (serial.h).  A serialisable object supplies raw_bytes() - the size of its uncompressed stream - and
+    // write(dst, capacity), which lays the stream down (serial::Writer or a serial::save_* refuses a short dst) and copies its
+    // words from the device.  *_SaveSize and *_Save are these two, inside guarded.
+    template <class RawBytes>
+    void save_size(uint8_t compr_mode, int64_t *result, RawBytes raw_bytes)
+    {
+        if (!serial::compr_mode_supported(compr_mode))
+            throw std::invalid_argument("unsupported compression mode");
+        *result = (int64_t)serial::compress_bound(raw_bytes(), compr_mode);
+    }
+    // uncompressed: straight into the caller's buffer, whose capacity write() checks; compressed: through a host image of the raw
+    // stream, and serial::compress_stream checks the capacity
+    template <class RawBytes, class Write>
+    void save_stream(uint8_t *outptr, uint64_t size, uint8_t compr_mode, int64_t *out_bytes, RawBytes raw_bytes, Write write)
+    {
+        if (!serial::compr_mode_supported(compr_mode))
+            throw std::invalid_argument("unsupported compression mode");
+        const size_t bytes = raw_bytes();
+        if (compr_mode == 0)
+        {
+            write(outptr, (size_t)size);
+            *out_bytes = (int64_t)bytes;
+            return;
+        }
+        std::vector<uint8_t> raw(bytes);
+        write(raw.data(), bytes);
+        *out_bytes = (int64_t)serial::compress_stream(raw.data(), bytes, compr_mode, outptr, (size_t)size);
+    }
+    // *_Load / *_UnsafeLoad of an object that takes a context: parse(object, context) returns the bytes read
+    template <class Object, class Parse>
+    SHL_HRESULT load_stream(void *thisptr, void *context, uint8_t *inptr, int64_t *in_bytes, Parse parse)
+    {
+        return guarded({ thisptr, context, inptr, in_bytes }, [&] { *in_bytes = (int64_t)parse(*as<Object>(thisptr), *as<Context>(context)); });
+    }
+    // the seeded piece of an image whose words go to `dst` (serial.h: pending_words after the stored ones), as the device's job (xof.h)
+    inline XofJob seeded_piece(const serial::CiphertextImage &img, uint64_t *dst)
+    {
+        XofJob job;
+        std::memcpy(job.seed, img.pending_seed, sizeof(job.seed));
+        job.prng_type = img.pending_type;
+        job.dst = dst + img.stored_words;
+        return job;
     }
 } // namespace

@@ -177,15 +177,6 @@ namespace sealhip
 
         namespace
         {
-            struct Header
-            {
-                uint16_t magic;
-                uint8_t header_size, version_major, version_minor, compr_mode;
-                uint16_t reserved;
-                uint64_t size;
-            };
-            static_assert(sizeof(Header) == 16, "SEALHeader is 16 bytes");
-
             // an istream over a memory buffer, reduced to what Serialization::Load needs: a failed read is the
             // reference's ios_base::failure -> runtime_error("I/O error")
             struct Reader
@@ -425,34 +416,7 @@ namespace sealhip
                     return false;
                 return true;
             }
-            // the coefficient range part of is_data_valid_for (valcheck.cpp:310-346)
             typedef uint64_t unaligned_u64 __attribute__((aligned(1)));
-            bool data_in_range(const Context &ctx, const CiphertextImage &c)
-            {
-                const size_t n = ctx.n();
-                const unaligned_u64 *p = reinterpret_cast<const unaligned_u64 *>(c.stored);
-                size_t left = c.stored_words; // words still to come from the stored piece; then the expanded one
-                for (uint64_t i = 0; i < c.size; i++)
-                    for (unsigned j = 0; j < c.level->K; j++)
-                    {
-                        if (left == 0 && c.pending_words)
-                            return true; // the rest is expanded on the device, reduced by construction
-                        if (left == 0)
-                        {
-                            p = reinterpret_cast<const unaligned_u64 *>(c.expanded.data());
-                            left = c.expanded.size();
-                        }
-                        const uint64_t q = ctx.coeff_modulus()[j];
-                        uint64_t over = 0;
-                        for (size_t k = 0; k < n; k++)
-                            over |= (uint64_t)(p[k] >= q);
-                        if (over)
-                            return false;
-                        p += n;
-                        left -= n;
-                    }
-                return true;
-            }
 
             // a seed expansion postponed by the caller (KSwitchKeys: one independent PRNG per digit, expanded on several threads)
             struct ExpandJob
@@ -535,7 +499,7 @@ namespace sealhip
                 // (ciphertext.cpp:384-396), for unsafe_load as well
                 if (ctx.scheme() == Scheme::bgv && !out.is_ntt_form && out.word_count() != 0)
                 {
-                    if (!metadata_valid(ctx, lvl, n64, K64, size64, scale, correction_factor, false) || !data_in_range(ctx, out))
+                    if (!metadata_valid(ctx, lvl, n64, K64, size64, scale, correction_factor, false) || !ciphertext_in_range(ctx, out))
                         throw std::logic_error("ciphertext data is invalid");
                 }
             }
@@ -579,7 +543,7 @@ namespace sealhip
                 // Ciphertext::load = unsafe_load + is_valid_for (ciphertext.h:533-545; valcheck.cpp): data levels only,
                 // every coefficient reduced
                 if (!metadata_valid(ctx, img.level, ctx.n(), img.level->K, img.size, img.scale, img.correction_factor, false) ||
-                    !data_in_range(ctx, img))
+                    !ciphertext_in_range(ctx, img))
                     throw std::logic_error("ciphertext data is invalid");
             }
             out = std::move(img);
@@ -673,7 +637,7 @@ namespace sealhip
                 // KSwitchKeys::load = unsafe_load + is_valid_for (kswitchkeys.h:236-246; valcheck.cpp)
                 for (auto &a : img.keys)
                     for (auto &b : a)
-                        if (!data_in_range(ctx, b))
+                        if (!ciphertext_in_range(ctx, b))
                             throw std::logic_error("KSwitchKeys data is invalid");
             }
             img.inflated = std::move(r.inflated);
@@ -729,6 +693,33 @@ namespace sealhip
             img.inflated = std::move(r.inflated);
             out = std::move(img);
             return bytes;
+        }
+
+        bool ciphertext_in_range(const Context &ctx, const CiphertextImage &c)
+        {
+            const size_t n = ctx.n();
+            const unaligned_u64 *p = reinterpret_cast<const unaligned_u64 *>(c.stored);
+            size_t left = c.stored_words; // words still to come from the stored piece; then the expanded one
+            for (uint64_t i = 0; i < c.size; i++)
+                for (unsigned j = 0; j < c.level->K; j++)
+                {
+                    if (left == 0 && c.pending_words)
+                        return true; // the rest is expanded on the device, reduced by construction
+                    if (left == 0)
+                    {
+                        p = reinterpret_cast<const unaligned_u64 *>(c.expanded.data());
+                        left = c.expanded.size();
+                    }
+                    const uint64_t q = ctx.coeff_modulus()[j];
+                    uint64_t over = 0;
+                    for (size_t k = 0; k < n; k++)
+                        over |= (uint64_t)(p[k] >= q);
+                    if (over)
+                        return false;
+                    p += n;
+                    left -= n;
+                }
+            return true;
         }
 
         bool plaintext_in_range(const Context &ctx, const PlaintextImage &img)
@@ -807,31 +798,44 @@ namespace sealhip
         size_t save_plaintext(const uint64_t *parms_id, uint64_t coeff_count, double scale, const uint64_t *words, uint8_t *out,
                               size_t capacity, size_t *data_offset)
         {
+            const size_t total = plaintext_save_size(coeff_count);
+            Writer w(out, capacity, total);
+            w.header(total);
+            w.put(parms_id, 32);
+            w.put64(coeff_count);
+            w.put(&scale, 8);
+            w.dynarray(coeff_count, words, data_offset);
+            return total;
+        }
+
+        Writer::Writer(uint8_t *out, size_t capacity, size_t total) : base(out), p(out)
+        {
             if (!out)
                 throw std::invalid_argument("out cannot be null");
             if (capacity < sizeof(Header))
                 throw std::invalid_argument("insufficient size");
-            const size_t total = plaintext_save_size(coeff_count);
             if (capacity < total)
                 throw std::runtime_error("I/O error");
-            uint8_t *p = out;
-            auto put = [&](const void *src, size_t bytes) {
-                std::memcpy(p, src, bytes);
-                p += bytes;
-            };
-            Header h{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, (uint64_t)total };
+        }
+        void Writer::put(const void *src, size_t bytes)
+        {
+            std::memcpy(p, src, bytes);
+            p += bytes;
+        }
+        void Writer::header(uint64_t size)
+        {
+            const Header h{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, size };
             put(&h, sizeof(h));
-            put(parms_id, 32);
-            put(&coeff_count, 8);
-            put(&scale, 8);
-            Header hd{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, (uint64_t)(sizeof(Header) + 8 + coeff_count * 8) };
-            put(&hd, sizeof(hd));
-            put(&coeff_count, 8);
+        }
+        void Writer::dynarray(uint64_t count, const uint64_t *words, size_t *data_offset)
+        {
+            header(sizeof(Header) + 8 + count * 8);
+            put64(count);
             if (data_offset)
-                *data_offset = (size_t)(p - out);
-            if (coeff_count && words)
-                put(words, (size_t)coeff_count * 8);
-            return total;
+                *data_offset = offset();
+            if (count && words)
+                std::memcpy(p, words, (size_t)count * 8);
+            skip((size_t)count * 8);
         }
 
         bool compr_mode_supported(uint8_t compr_mode)
@@ -926,46 +930,35 @@ namespace sealhip
             return sizeof(Header) + members + dyn + info;
         }
 
+        namespace
+        {
+            // Ciphertext::save_members up to the DynArray (ciphertext.cpp:198-228)
+            void ciphertext_head(Writer &w, size_t total, const uint64_t *parms_id, bool is_ntt_form, uint64_t size, uint64_t n, uint64_t K,
+                                 double scale, uint64_t correction_factor)
+            {
+                w.header(total);
+                w.put(parms_id, 32);
+                const uint8_t ntt = is_ntt_form ? 1 : 0;
+                w.put(&ntt, 1);
+                w.put64(size);
+                w.put64(n);
+                w.put64(K);
+                w.put(&scale, 8);
+                w.put64(correction_factor);
+            }
+        } // namespace
+
         size_t save_seeded_ciphertext(const uint64_t *parms_id, bool is_ntt_form, uint64_t n, uint64_t K, double scale,
                                       uint64_t correction_factor, const uint64_t *c0_words, uint8_t prng_type, const uint64_t *seed,
                                       uint8_t *out, size_t capacity, size_t *data_offset)
         {
-            if (!out)
-                throw std::invalid_argument("out cannot be null");
-            if (capacity < sizeof(Header))
-                throw std::invalid_argument("insufficient size");
             const size_t total = seeded_ciphertext_save_size(n, K);
-            if (capacity < total)
-                throw std::runtime_error("I/O error");
-            uint8_t *p = out;
-            auto put = [&](const void *src, size_t bytes) {
-                std::memcpy(p, src, bytes);
-                p += bytes;
-            };
-            Header h{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, (uint64_t)total };
-            put(&h, sizeof(h));
-            put(parms_id, 32);
-            const uint8_t ntt = is_ntt_form ? 1 : 0;
-            put(&ntt, 1);
-            const uint64_t size = 2;
-            put(&size, 8);
-            put(&n, 8);
-            put(&K, 8);
-            put(&scale, 8);
-            put(&correction_factor, 8);
-            const uint64_t count = n * K;
-            Header hd{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, (uint64_t)(sizeof(Header) + 8 + count * 8) };
-            put(&hd, sizeof(hd));
-            put(&count, 8);
-            if (data_offset)
-                *data_offset = (size_t)(p - out);
-            if (c0_words)
-                std::memcpy(p, c0_words, (size_t)count * 8);
-            p += (size_t)count * 8;
-            Header hi{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, (uint64_t)(sizeof(Header) + 1 + 64) };
-            put(&hi, sizeof(hi));
-            put(&prng_type, 1);
-            put(seed, 64);
+            Writer w(out, capacity, total);
+            ciphertext_head(w, total, parms_id, is_ntt_form, 2, n, K, scale, correction_factor);
+            w.dynarray(n * K, c0_words, data_offset);
+            w.header(sizeof(Header) + 1 + 64);
+            w.put(&prng_type, 1);
+            w.put(seed, 64);
             return total;
         }
 
@@ -980,37 +973,10 @@ namespace sealhip
         size_t save_ciphertext(const uint64_t *parms_id, bool is_ntt_form, uint64_t size, uint64_t n, uint64_t K, double scale,
                                uint64_t correction_factor, const uint64_t *words, uint8_t *out, size_t capacity, size_t *data_offset)
         {
-            // Serialization::Save(save_members, raw_size, out, size, compr_mode) (serialization.cpp:232-340, 541-557)
-            if (!out)
-                throw std::invalid_argument("out cannot be null");
-            if (capacity < sizeof(Header))
-                throw std::invalid_argument("insufficient size");
             const size_t total = ciphertext_save_size(size, n, K);
-            if (capacity < total)
-                throw std::runtime_error("I/O error"); // the reference's ArrayPutBuffer overflows: ios failure
-            uint8_t *p = out;
-            auto put = [&](const void *src, size_t bytes) {
-                std::memcpy(p, src, bytes);
-                p += bytes;
-            };
-            Header h{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, (uint64_t)total };
-            put(&h, sizeof(h));
-            put(parms_id, 32);
-            const uint8_t ntt = is_ntt_form ? 1 : 0;
-            put(&ntt, 1);
-            put(&size, 8);
-            put(&n, 8);
-            put(&K, 8);
-            put(&scale, 8);
-            put(&correction_factor, 8);
-            const uint64_t count = size * n * K;
-            Header hd{ kMagic, kHeaderSize, kVersionMajor, kVersionMinor, 0, 0, (uint64_t)(sizeof(Header) + 8 + count * 8) };
-            put(&hd, sizeof(hd));
-            put(&count, 8);
-            if (data_offset)
-                *data_offset = (size_t)(p - out);
-            if (count && words)
-                put(words, (size_t)count * 8);
+            Writer w(out, capacity, total);
+            ciphertext_head(w, total, parms_id, is_ntt_form, size, n, K, scale, correction_factor);
+            w.dynarray(size * n * K, words, data_offset);
             return total;
         }
     } // namespace serial

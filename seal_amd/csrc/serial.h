@@ -34,6 +34,30 @@ namespace sealhip
         constexpr uint16_t kMagic = 0xA15E;
         constexpr uint8_t kHeaderSize = 0x10;
         constexpr uint8_t kVersionMajor = 4, kVersionMinor = 4; // the reference release this format follows (4.4.x)
+        struct Header // SEALHeader
+        {
+            uint16_t magic;
+            uint8_t header_size, version_major, version_minor, compr_mode;
+            uint16_t reserved;
+            uint64_t size;
+        };
+        static_assert(sizeof(Header) == 16, "SEALHeader is 16 bytes");
+
+        // The counterpart of the parser's Reader: lays an uncompressed stream of `total` bytes down in a caller's buffer.  The
+        // constructor is the prologue of Serialization::Save (serialization.cpp:232-340, 541-557): a null buffer or one below a
+        // header is std::invalid_argument, one the stream does not fit is the reference's ArrayPutBuffer overflowing ("I/O error").
+        struct Writer
+        {
+            uint8_t *base, *p;
+            Writer(uint8_t *out, size_t capacity, size_t total);
+            size_t offset() const { return (size_t)(p - base); }
+            void skip(size_t bytes) { p += bytes; } // bytes the caller writes itself (a device slab, a nested object)
+            void put(const void *src, size_t bytes);
+            void put64(uint64_t v) { put(&v, 8); }
+            void header(uint64_t size); // a SEALHeader (compr_mode none) that frames `size` bytes, itself included
+            // a DynArray of `count` words: frame, count and - when given - the words; *data_offset = where the words go
+            void dynarray(uint64_t count, const uint64_t *words, size_t *data_offset);
+        };
 
         // host image of one seal::Ciphertext: metadata + [size][K][N] words (seed already expanded)
         struct CiphertextImage
@@ -106,6 +130,9 @@ namespace sealhip
         size_t load_plaintext(const Context &ctx, const uint8_t *in, size_t size, bool check_data, PlaintextImage &out);
         // the coefficient range part of is_data_valid_for(const Plaintext &) (valcheck.cpp:348-396)
         bool plaintext_in_range(const Context &ctx, const PlaintextImage &img);
+        // ... and of is_data_valid_for(const Ciphertext &) (valcheck.cpp:310-346): the words that came with the stream (a piece left
+        // to the device's expansion is reduced by construction)
+        bool ciphertext_in_range(const Context &ctx, const CiphertextImage &img);
         size_t plaintext_save_size(uint64_t coeff_count);
         // as save_ciphertext: words == nullptr leaves the coefficient words to the caller (*data_offset)
         size_t save_plaintext(const uint64_t *parms_id, uint64_t coeff_count, double scale, const uint64_t *words, uint8_t *out,

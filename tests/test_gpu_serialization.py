@@ -148,3 +148,14 @@ def test_keygen(gpu, scheme, n, bits):
 def test_shake256_seeded_streams(gpu, scheme, n, bits):
     """the device SHAKE256 expansion (one thread per 4096-byte PRNG buffer), incl. primes with hundreds of redrawn words"""
     SC.case_shake256_seeded_streams(scheme, n, bits)
+
+
+def test_object_save_matrix_and_load_order(gpu):
+    """the C layer's pinned answers (tests/capi_object_cases.py) on the device, CKKS N = 4096 {40, 30, 40}: every cell of the save
+    matrix, the special cases of the saves, the order of refusals of the loads, the key copies"""
+    import capi_object_cases as cases
+    objects = cases.Objects(gpu, 4096, [40, 30, 40], 22)
+    assert [r for r in cases.save_matrix(objects) if r[3] != r[4]] == []
+    assert cases.mismatches(cases.save_special_cases(objects), cases.SAVE_SPECIAL) == []
+    assert cases.mismatches(cases.load_order(objects), cases.LOAD_ORDER) == []
+    assert cases.mismatches(cases.key_copies(objects), cases.KEY_COPIES) == []
