@@ -456,13 +456,7 @@ extern "C"
             }
             if (e == hipSuccess && to_ntt)
             {
-                NttBatch b{};
-                b.data = tmp;
-                b.outer_stride = poly_words;
-                b.ncomp = (unsigned)K;
-                b.nouter = (unsigned)img.size;
-                b.prime_first = 0;
-                e = ntt_forward(c.ntt_tables(), b, 0, nullptr);
+                e = ntt_forward(c.ntt_tables(), plain_batch(tmp, poly_words, (unsigned)K, (unsigned)img.size, 0), 0, nullptr);
             }
             for (size_t p = 0; e == hipSuccess && p < img.size; p++)
                 e = hipMemcpyAsync(ct.plane(p) + item * poly_words, tmp + p * poly_words, poly_words * 8, hipMemcpyDeviceToDevice, nullptr);

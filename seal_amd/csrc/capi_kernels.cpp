@@ -120,12 +120,7 @@ extern "C"
         auto c = as<Context>(context);
         if (first_prime + comps > c->pool_primes().size())
             throw std::out_of_range("first_prime + comps");
-        NttBatch b{};
-        b.data = data;
-        b.outer_stride = (size_t)comps * c->n();
-        b.ncomp = (unsigned)comps;
-        b.nouter = (unsigned)polys;
-        b.prime_first = (unsigned)first_prime;
+        const NttBatch b = plain_batch(data, (size_t)comps * c->n(), (unsigned)comps, (unsigned)polys, (unsigned)first_prime);
         hip_ok(ntt_forward(c->ntt_tables(), b, lazy, (hipStream_t)stream), "ntt_forward");
         SHL_CATCH
     }
@@ -137,12 +132,7 @@ extern "C"
         auto c = as<Context>(context);
         if (first_prime + comps > c->pool_primes().size())
             throw std::out_of_range("first_prime + comps");
-        NttBatch b{};
-        b.data = data;
-        b.outer_stride = (size_t)comps * c->n();
-        b.ncomp = (unsigned)comps;
-        b.nouter = (unsigned)polys;
-        b.prime_first = (unsigned)first_prime;
+        const NttBatch b = plain_batch(data, (size_t)comps * c->n(), (unsigned)comps, (unsigned)polys, (unsigned)first_prime);
         hip_ok(ntt_inverse(c->ntt_tables(), b, lazy, (hipStream_t)stream), "ntt_inverse");
         SHL_CATCH
     }
@@ -498,30 +488,16 @@ extern "C"
                 throw std::invalid_argument("level has a single modulus");
             const unsigned K = l->K;
             const size_t N = c->n();
-            Scratch copy(polys * K * N), tt(polys * (K - 1) * N);
+            Scratch copy(polys * K * N);
             hip_ok(hipMemcpyAsync(copy.p, in, polys * K * N * 8, hipMemcpyDeviceToDevice, s), "copy");
             uint64_t *last = copy.p + (size_t)(K - 1) * N;
-            NttBatch bi{};
-            bi.data = last;
-            bi.outer_stride = (size_t)K * N;
-            bi.ncomp = 1;
-            bi.nouter = (unsigned)polys;
-            bi.prime_first = K - 1;
-            hip_ok(ntt_inverse(c->ntt_tables(), bi, 0, s), "intt last");
-            NttBatch b{};
-            b.data = tt.p;
-            b.outer_stride = (size_t)(K - 1) * N;
-            b.ncomp = K - 1;
-            b.nouter = (unsigned)polys;
-            b.src = last;
-            b.src_outer_stride = (size_t)K * N;
-            b.src_ncomp = 1;
-            b.src_mode = 2;
-            b.src_half = l->dev.half_q_last;
-            b.src_q = l->dev.q_last;
-            b.src_fix = l->dev.round_fix;
-            hip_ok(ntt_forward(c->ntt_tables(), b, 1, s), "ntt correction");
-            hip_ok(k_rescale_combine(c->dev_mods(), l->dev.inv_q_last_mod_q, copy.p, tt.p, out, n_log, K, polys, s), "combine");
+            hip_ok(ntt_inverse(c->ntt_tables(), plain_batch(last, (size_t)K * N, 1, (unsigned)polys, K - 1), 0, s), "intt last");
+            hip_ok(ntt_forward(c->ntt_tables(),
+                               plain_batch(nullptr, (size_t)(K - 1) * N, K - 1, (unsigned)polys, 0)
+                                   .rounded_src(last, (size_t)K * N, 1, 2, l->dev.half_q_last, l->dev.q_last, l->dev.round_fix)
+                                   .epilogue(1, copy.p, (size_t)K * N, l->dev.inv_q_last_mod_q, out, nullptr, (size_t)(K - 1) * N),
+                               1, s),
+                   "ntt correction + combine");
             hip_ok(hipStreamSynchronize(s), "sync");
         }
         else

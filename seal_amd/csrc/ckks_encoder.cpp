@@ -276,13 +276,7 @@ namespace sealhip
             a.n_log = n_log;
             a.block_log = b;
             ck(k_ckks_encode(a, (unsigned)items, nullptr), "ckks encode");
-            NttBatch nb{};
-            nb.data = a.words;
-            nb.outer_stride = K * n;
-            nb.ncomp = (unsigned)K;
-            nb.nouter = (unsigned)items;
-            nb.prime_first = 0;
-            ck(ntt_forward(context_.ntt_tables(), nb, 0, nullptr), "ntt plaintexts");
+            ck(ntt_forward(context_.ntt_tables(), plain_batch(a.words, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "ntt plaintexts");
         }
         unsigned f = 0;
         ck(hipMemcpy(&f, fail.p, 4, hipMemcpyDeviceToHost), "encode sync");
@@ -495,13 +489,7 @@ namespace sealhip
         {
             const size_t items = std::min(chunk, batch - c0);
             ck(hipMemcpyAsync(copy.p, words + c0 * K * n, items * K * n * 8, hipMemcpyDeviceToDevice, nullptr), "copy words");
-            NttBatch nb{};
-            nb.data = copy.p;
-            nb.outer_stride = K * n;
-            nb.ncomp = (unsigned)K;
-            nb.nouter = (unsigned)items;
-            nb.prime_first = 0;
-            ck(ntt_inverse(context_.ntt_tables(), nb, 0, nullptr), "intt plaintexts");
+            ck(ntt_inverse(context_.ntt_tables(), plain_batch(copy.p, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "intt plaintexts");
             CkksDecodeArgs a{};
             a.residues = copy.p;
             a.mods = context_.dev_mods();

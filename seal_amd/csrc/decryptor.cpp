@@ -10,20 +10,6 @@
 
 namespace sealhip
 {
-    namespace
-    {
-        NttBatch polys(uint64_t *data, size_t K, size_t n, size_t count)
-        {
-            NttBatch b{};
-            b.data = data;
-            b.outer_stride = K * n;
-            b.ncomp = (unsigned)K;
-            b.nouter = (unsigned)count;
-            b.prime_first = 0;
-            return b;
-        }
-    } // namespace
-
     SecretKey::~SecretKey()
     {
         if (dev_)
@@ -156,17 +142,17 @@ namespace sealhip
             ck(k_decrypt_dot(context_.dev_mods(), e.plane(0), e.plane(1), plane_words, (unsigned)e.size(), sk, phase, n_log, (unsigned)K, nullptr),
                "decrypt dot product");
             if (to_coeff_form)
-                ck(ntt_inverse(tb, polys(phase, K, n, B), 0, nullptr), "decrypt intt");
+                ck(ntt_inverse(tb, plain_batch(phase, K * n, (unsigned)K, (unsigned)B, 0), 0, nullptr), "decrypt intt");
         }
         else
         {
             // coefficient-form input (BFV): c_1.. are transformed, multiplied, summed, transformed back, then c_0 is added
             Scratch tmp((e.size() - 1) * plane_words);
             ck(hipMemcpyAsync(tmp.p, e.plane(1), (e.size() - 1) * plane_words * 8, hipMemcpyDeviceToDevice, nullptr), "decrypt copy");
-            ck(ntt_forward(tb, polys(tmp.p, K, n, (e.size() - 1) * B), 0, nullptr), "decrypt ntt");
+            ck(ntt_forward(tb, plain_batch(tmp.p, K * n, (unsigned)K, (unsigned)((e.size() - 1) * B), 0), 0, nullptr), "decrypt ntt");
             ck(k_decrypt_dot(context_.dev_mods(), nullptr, tmp.p, plane_words, (unsigned)e.size(), sk, phase, n_log, (unsigned)K, nullptr),
                "decrypt dot product");
-            ck(ntt_inverse(tb, polys(phase, K, n, B), 0, nullptr), "decrypt intt");
+            ck(ntt_inverse(tb, plain_batch(phase, K * n, (unsigned)K, (unsigned)B, 0), 0, nullptr), "decrypt intt");
             ck(k_add_inplace(context_.dev_mods(), phase, e.plane(0), plane_words, n_log, (unsigned)K, nullptr), "decrypt add c0");
             ck(hipStreamSynchronize(nullptr), "decrypt sync"); // tmp goes back to the pool
         }
@@ -333,13 +319,7 @@ namespace sealhip
             throw std::invalid_argument("values / coefficients");
         const unsigned n_log = (unsigned)context_.log_n();
         ck(k_slot_scatter(map_, values, coefficients, n_log, batch, is_signed ? context_.plain_modulus() : 0, nullptr), "slot scatter");
-        NttBatch b{};
-        b.data = coefficients;
-        b.outer_stride = context_.n();
-        b.ncomp = 1;
-        b.nouter = batch;
-        b.prime_first = (unsigned)context_.plain_prime_index();
-        ck(ntt_inverse(context_.ntt_tables(), b, 0, nullptr), "intt mod t");
+        ck(ntt_inverse(context_.ntt_tables(), plain_batch(coefficients, context_.n(), 1, batch, (unsigned)context_.plain_prime_index()), 0, nullptr), "intt mod t");
     }
     void BatchEncoder::decode_device(const uint64_t *coefficients, unsigned batch, bool is_signed, uint64_t *values) const
     {
@@ -348,13 +328,7 @@ namespace sealhip
         const size_t words = (size_t)batch * context_.n();
         Scratch tmp(words);
         ck(hipMemcpyAsync(tmp.p, coefficients, words * 8, hipMemcpyDeviceToDevice, nullptr), "copy coefficients");
-        NttBatch b{};
-        b.data = tmp.p;
-        b.outer_stride = context_.n();
-        b.ncomp = 1;
-        b.nouter = batch;
-        b.prime_first = (unsigned)context_.plain_prime_index();
-        ck(ntt_forward(context_.ntt_tables(), b, 0, nullptr), "ntt mod t");
+        ck(ntt_forward(context_.ntt_tables(), plain_batch(tmp.p, context_.n(), 1, batch, (unsigned)context_.plain_prime_index()), 0, nullptr), "ntt mod t");
         ck(k_slot_gather(map_, tmp.p, values, (unsigned)context_.log_n(), batch, is_signed ? context_.plain_modulus() : 0, nullptr), "slot gather");
         ck(hipStreamSynchronize(nullptr), "decode sync"); // tmp goes back to the pool
     }
@@ -738,7 +712,7 @@ namespace sealhip
             {
                 // the noise goes straight to where it is transformed and consumed: the item's c0
                 ck(k_expand_small_batch(mods, dsmall, small_stride, c0c, 0, n_log, (unsigned)K, 1, items, nullptr), "expand noise");
-                ck(ntt_forward(tb, polys(c0c, K, n, items), 0, nullptr), "ntt noise");
+                ck(ntt_forward(tb, plain_batch(c0c, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "ntt noise");
                 const uint64_t *m = plain ? plain + b0 * words : nullptr;
                 if (lift)
                 {
@@ -746,7 +720,7 @@ namespace sealhip
                     ck(k_plain_lift_batch(mods, host::make_mod(context_.plain_modulus()), 1, plain + b0 * n, n, n, lvl.dev.plain_upper_half_threshold,
                                           lvl.dev.upper_half_inc, lifted.p, n_log, (unsigned)K, items, nullptr),
                        "plain lift");
-                    ck(ntt_forward(tb, polys(lifted.p, K, n, items), 0, nullptr), "plain ntt");
+                    ck(ntt_forward(tb, plain_batch(lifted.p, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "plain ntt");
                     m = lifted.p;
                 }
                 ck(k_encrypt_sym_tail(mods, sk_, c1c, c0c, m, noise_factor, false, n_log, (unsigned)K, items, nullptr), "c0");
@@ -758,12 +732,12 @@ namespace sealhip
                 if (coeff_a)
                 {
                     ck(hipMemcpyAsync(a_ntt.p, c1c, (size_t)items * words * 8, hipMemcpyDeviceToDevice, nullptr), "copy a");
-                    ck(ntt_forward(tb, polys(a_ntt.p, K, n, items), 0, nullptr), "ntt a");
+                    ck(ntt_forward(tb, plain_batch(a_ntt.p, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "ntt a");
                 }
                 ck(k_encrypt_sym_tail(mods, sk_, coeff_a ? a_ntt.p : c1c, c0c, nullptr, 1, true, n_log, (unsigned)K, items, nullptr), "a s");
-                ck(ntt_inverse(tb, polys(c0c, K, n, items), 0, nullptr), "intt a s");
+                ck(ntt_inverse(tb, plain_batch(c0c, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "intt a s");
                 if (!coeff_a)
-                    ck(ntt_inverse(tb, polys(c1c, K, n, items), 0, nullptr), "intt a");
+                    ck(ntt_inverse(tb, plain_batch(c1c, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "intt a");
                 ck(k_encrypt_bfv_finish(mods, bfv_plain_const(context_, lvl), dsmall, small_stride, plain ? plain + b0 * n : nullptr, c0c, 0, 1, true,
                                         n_log, (unsigned)K, items, nullptr),
                    "c0");
@@ -848,23 +822,23 @@ namespace sealhip
                         ck(hipMemcpy(dsmall + i * small_stride, host_small.data(), 3 * n, hipMemcpyHostToDevice), "upload u, e");
                     }
                 ck(k_expand_small_batch(mods, dsmall, small_stride, du.p, 0, n_log, (unsigned)K, 1, items, nullptr), "expand u");
-                ck(ntt_forward(tb, polys(du.p, K, n, items), 0, nullptr), "ntt u");
+                ck(ntt_forward(tb, plain_batch(du.p, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "ntt u");
                 if (ntt_form)
                 {
                     // e_0, e_1 go straight to where they are transformed and consumed: the item's two planes
                     ck(k_expand_small_batch(mods, dsmall + n, small_stride, c, plane_stride, n_log, (unsigned)K, 2, items, nullptr), "expand e");
                     if (items == batch)
-                        ck(ntt_forward(tb, polys(c, K, n, 2 * (size_t)items), 0, nullptr), "ntt noise");
+                        ck(ntt_forward(tb, plain_batch(c, K * n, (unsigned)K, (unsigned)(2 * (size_t)items), 0), 0, nullptr), "ntt noise");
                     else
                         for (size_t j = 0; j < 2; j++)
-                            ck(ntt_forward(tb, polys(c + j * plane_stride, K, n, items), 0, nullptr), "ntt noise");
+                            ck(ntt_forward(tb, plain_batch(c + j * plane_stride, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "ntt noise");
                     ck(k_encrypt_pk_tail(mods, pk_, L * n, du.p, c, plane_stride, noise_factor, false, n_log, (unsigned)K, items, nullptr), "pk u + e");
                 }
                 else
                 {
                     ck(k_encrypt_pk_tail(mods, pk_, L * n, du.p, c, plane_stride, 1, true, n_log, (unsigned)K, items, nullptr), "pk u");
                     for (size_t j = 0; j < 2; j++)
-                        ck(ntt_inverse(tb, polys(c + j * plane_stride, K, n, items), 0, nullptr), "intt pk u");
+                        ck(ntt_inverse(tb, plain_batch(c + j * plane_stride, K * n, (unsigned)K, (unsigned)items, 0), 0, nullptr), "intt pk u");
                     ck(k_encrypt_bfv_finish(mods, bfv_plain_const(context_, at), dsmall + n, small_stride, nullptr, c, plane_stride, 2, false, n_log,
                                             (unsigned)K, items, nullptr),
                        "c + e");

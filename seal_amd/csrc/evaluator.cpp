@@ -83,9 +83,9 @@ namespace sealhip
         formed = g_prod_formed.load();
         dropped = g_prod_dropped.load();
     }
-    // CKKS at a two-pass size, a batch whose key switch runs un-split (the fused relinearisation's configuration) - asked of the shape's
-    // half of the route's rule, no key being known yet.  SEALHIP_LAZY_PRODUCT_MIN_WGS moves the threshold of that rule (1024 pass-2
-    // workgroups): tests reach the fused path at small batches with it, together with SEALHIP_KS_SPLIT=1
+    // CKKS at a two-pass size (ntt2_supports chooses whether a product may stay pending: only that engine forms it while loading,
+    // NttBatch::prod_x), a batch whose key switch runs un-split - the shape's half of the route's rule, no key being known yet.
+    // SEALHIP_LAZY_PRODUCT_MIN_WGS moves that rule's threshold (1024 pass-2 workgroups): tests reach the fused path at small batches with it and SEALHIP_KS_SPLIT=1
     bool Evaluator::may_defer_product(const Level &lvl, size_t batch) const
     {
         if (!KsSwitches::lazy_product() || capturing_ || transparent_check_ || lvl.K < 2 || !ntt2_supports(context_.log_n()))
@@ -1733,7 +1733,7 @@ namespace sealhip
         PlaneGeom gq{ n_log, K, (unsigned)B }, gb{ n_log, nBsk, (unsigned)B };
         // Two-pass sizes, 2 x 2: steps (4) and (5) are ONE pair of passes per base - the inverse transform's first pass forms the
         // product from the four operand polynomials as it loads them (NttBatch::prod_x), so the product is never stored in NTT form
-        // and read back: 7 plane crossings instead of 13 for the pair (profiles/r04_bfv_product_source.txt).
+        // and read back: 7 plane crossings instead of 13 (profiles/r04_bfv_product_source.txt).  ntt2_supports chooses that or the stored product.
         const bool product_source = s1 == 2 && s2 == 2 && ntt2_supports(context_.log_n());
         if (product_source)
         {

@@ -102,19 +102,6 @@ namespace sealhip
         {
             return BfvPlainConst{ host::make_mod(ctx.plain_modulus()), lvl.dev.q_mod_t, lvl.dev.plain_upper_half_threshold, lvl.dev.delta_mod_q };
         }
-
-        NttBatch plain_batch(uint64_t *data, size_t outer_stride, unsigned ncomp, unsigned nouter, unsigned prime_first)
-        {
-            NttBatch b{};
-            b.data = data;
-            b.outer_stride = outer_stride;
-            b.ncomp = ncomp;
-            b.nouter = nouter;
-            b.comp_prime = nullptr;
-            b.prime_first = prime_first;
-            b.src = nullptr;
-            return b;
-        }
     } // namespace
 
     // The key switch's environment switches: read here and nowhere else (defined, with the table of names, in evaluator_keyswitch.cpp).

@@ -195,6 +195,7 @@ namespace sealhip
         const KsSwitches &sw = ks_switches();
         const Scheme sch = context_.scheme();
         KsRoute r;
+        // chooses whether the tail is deferred: the folded tails (NttTail2, src_mode 3, out_add) are the two-pass engine's alone
         r.defer = !sw.eager_tail && (sch == Scheme::ckks || sch == Scheme::bfv) && ntt2_supports(context_.log_n()) && lvl.K >= 2;
         r.fold = r.defer && !sw.no_fold && sch == Scheme::ckks;
         r.plan = KsPlan{ (unsigned)batch, 1 };
@@ -433,7 +434,7 @@ namespace sealhip
         const KsPlan &plan = route.plan;
         const bool chunked = plan.chunk < B;
         const bool inverse_in_lane = chunked && !read_in_place && ntt_target;
-        // the opening inverse transform of the items [b0, b0 + nb): out of place, the two-pass engine reads the target and writes t
+        // the opening inverse transform of the items [b0, b0 + nb): out of place, it reads the target and writes t
         const auto inverse_batch = [&](unsigned b0, unsigned nb) {
             NttBatch bt = plain_batch(t.p + b0 * poly_words, poly_words, K, nb, 0);
             bt.src = target + b0 * poly_words;
@@ -449,14 +450,10 @@ namespace sealhip
             }
             return bt;
         };
-        if (ntt_target && !inverse_in_lane && ntt2_supports(context_.log_n()))
+        if (ntt_target && !inverse_in_lane)
             ck(ntt_inverse(tb, inverse_batch(0, B), 0, stream_), "ks intt target");
         else if (!read_in_place && !inverse_in_lane)
-        {
             ck(hipMemcpyAsync(t.p, target, (size_t)B * poly_words * 8, hipMemcpyDeviceToDevice, stream_), "ks copy target");
-            if (ntt_target)
-                ck(ntt_inverse(tb, plain_batch(t.p, poly_words, K, B, 0), 0, stream_), "ks intt target");
-        }
 
         if (route.fused)
         {
@@ -579,17 +576,8 @@ namespace sealhip
             // (evaluator.cpp:2663-2701).  The reference skips the transform when I == J in CKKS because
             // NTT_J(INTT_J(x)) = x; computing it gives the same canonical words.
             Scratch u((size_t)B * (K + 1) * K * N);
-            NttBatch b{};
-            b.data = u.p;
-            b.outer_stride = (size_t)(K + 1) * K * N;
-            b.ncomp = (K + 1) * K;
-            b.nouter = B;
+            NttBatch b = plain_batch(u.p, (size_t)(K + 1) * K * N, (K + 1) * K, B, 0).rounded_src(digits, (size_t)K * N, K, 1);
             b.comp_prime = map;
-            b.prime_first = 0;
-            b.src = digits;
-            b.src_outer_stride = (size_t)K * N;
-            b.src_ncomp = K;
-            b.src_mode = 1;
             ck(ntt_forward(tb, b, 0, stream_), "ks ntt digits");
             // inner product with the key (evaluator.cpp:2703-2755)
             ck(k_keyswitch_mac(mods, u.p, key.dev, acc_out, n_log, K, L, B, j0, j1, (unsigned)key.digit0, stream_), "ks mac");
@@ -608,6 +596,7 @@ namespace sealhip
             throw std::invalid_argument("encrypted size must be at least 2");
         if (parts < 1 || parts > 8)
             throw std::invalid_argument("parts"); // 8 canonical residues below 2^60 still fit a 64-bit word
+        // chooses the caller's contract: sums that carry the addend need epilogue 3, which only the two-pass engine has
         if (acc_has_addend && !(parts == 1 && context_.scheme() == Scheme::ckks && ntt2_supports(context_.log_n())))
             throw std::invalid_argument("acc_has_addend");
         const Scheme scheme = context_.scheme();
@@ -660,40 +649,14 @@ namespace sealhip
         {
             NttBatch bi = plain_batch(acc + (size_t)K * N, (size_t)(K + 1) * N, 1, 2 * B, L - 1);
             ck(ntt_inverse(tb, bi, 0, stream_), "ks intt special");
-            Scratch tt(ntt2_supports(context_.log_n()) ? 1 : (size_t)B * 2 * K * N);
-            NttBatch b{};
-            b.data = tt.p;
-            b.outer_stride = (size_t)K * N;
-            b.ncomp = K;
-            b.nouter = 2 * B;
-            b.comp_prime = nullptr;
-            b.prime_first = 0;
-            b.src = acc + (size_t)K * N;
-            b.src_outer_stride = (size_t)(K + 1) * N;
-            b.src_ncomp = 1;
-            b.src_mode = 2;
-            b.src_half = P >> 1;
-            b.src_q = P;
-            b.src_fix = klvl.dev.round_fix;
-            if (ntt2_supports(context_.log_n()))
-            {
-                // the tail is the epilogue of the transform: tt is never stored
-                b.data = nullptr;
-                b.epi = acc_has_addend ? 3 : 2; // 3: acc = c + S P^-1 already (switch_key_partial, fold_addend)
-                b.epi_a = acc;
-                b.epi_a_stride = (size_t)(K + 1) * N;
-                b.epi_mul = klvl.dev.inv_q_last_mod_q;
-                b.epi_out0 = e.plane(0);
-                b.epi_out1 = e.plane(1);
-                b.epi_out_stride = (size_t)K * N;
-                ck(ntt_forward(tb, b, 1, stream_), "ks ntt correction + tail");
-            }
-            else
-            {
-                ck(ntt_forward(tb, b, 1, stream_), "ks ntt correction");
-                ck(k_keyswitch_tail_ckks(mods, klvl.dev.inv_q_last_mod_q, e.plane(0), e.plane(1), acc, tt.p, n_log, K, B, stream_),
-                   "ks tail");
-            }
+            // the tail is the epilogue of the transform; 3: acc = c + S P^-1 already (switch_key_partial, fold_addend)
+            ck(ntt_forward(tb,
+                           plain_batch(nullptr, (size_t)K * N, K, 2 * B, 0)
+                               .rounded_src(acc + (size_t)K * N, (size_t)(K + 1) * N, 1, 2, P >> 1, P, klvl.dev.round_fix)
+                               .epilogue(acc_has_addend ? 3 : 2, acc, (size_t)(K + 1) * N, klvl.dev.inv_q_last_mod_q, e.plane(0), e.plane(1),
+                                         (size_t)K * N),
+                           1, stream_),
+               "ks ntt correction + tail");
         }
         else
         {
@@ -810,28 +773,13 @@ namespace sealhip
         else
         {
             // the relinearised ciphertext's LAST component (the one rescale divides by), completed alone: c += (S - NTT(v)) P^-1
-            NttBatch b{};
-            b.data = nullptr;
-            b.outer_stride = N;
-            b.ncomp = 1;
-            b.nouter = 2 * B;
-            b.comp_prime = nullptr;
-            b.prime_first = K - 1;
-            b.src = acc_p + (size_t)K * N;
-            b.src_outer_stride = (size_t)(K + 1) * N;
-            b.src_ncomp = 1;
-            b.src_mode = 3;
-            b.src_half = P >> 1;
-            b.src_q = P;
-            b.src_fix = klvl.dev.round_fix + (K - 1);
-            b.epi = 2;
-            b.epi_a = acc_p + (size_t)(K - 1) * N;
-            b.epi_a_stride = (size_t)(K + 1) * N;
-            b.epi_mul = klvl.dev.inv_q_last_mod_q + (K - 1);
-            b.epi_out0 = c0 + (size_t)(K - 1) * N;
-            b.epi_out1 = c1 + (size_t)(K - 1) * N;
-            b.epi_out_stride = (size_t)K * N;
-            ck(ntt_forward(tb, b, 1, stream_), "ks ntt correction + tail, last component");
+            ck(ntt_forward(tb,
+                           plain_batch(nullptr, N, 1, 2 * B, K - 1)
+                               .rounded_src(acc_p + (size_t)K * N, (size_t)(K + 1) * N, 1, 3, P >> 1, P, klvl.dev.round_fix + (K - 1))
+                               .epilogue(2, acc_p + (size_t)(K - 1) * N, (size_t)(K + 1) * N, klvl.dev.inv_q_last_mod_q + (K - 1),
+                                         c0 + (size_t)(K - 1) * N, c1 + (size_t)(K - 1) * N, (size_t)K * N),
+                           1, stream_),
+               "ks ntt correction + tail, last component");
         }
         // t_last: its coefficient form, in place (that component is dropped by the rescale)
         if (!acc_has_addend)
@@ -866,27 +814,11 @@ namespace sealhip
                 t2.src2_stride = (size_t)2 * (K + 1) * N;
                 t2.a_has_c = 1;
             }
-            NttBatch b{};
-            b.data = nullptr;
-            b.outer_stride = (size_t)(K - 1) * N;
-            b.ncomp = K - 1;
-            b.nouter = 2 * B;
-            b.comp_prime = nullptr;
-            b.prime_first = 0;
-            b.src = acc_p + (size_t)K * N;
-            b.src_outer_stride = (size_t)(K + 1) * N;
-            b.src_ncomp = 1;
-            b.src_mode = 3;
-            b.src_half = P >> 1;
-            b.src_q = P;
-            b.src_fix = klvl.dev.round_fix;
-            b.epi = 0;
-            b.epi_a = acc_p;
-            b.epi_a_stride = (size_t)(K + 1) * N;
-            b.epi_mul = lvl.dev.inv_q_last_mod_q;
-            b.epi_out0 = out;
-            b.epi_out1 = out + (size_t)B * (K - 1) * N;
-            b.epi_out_stride = (size_t)(K - 1) * N;
+            // (epi 0: with tail2 the epilogue's fields name S, q_last^-1 and the two output planes)
+            NttBatch b = plain_batch(nullptr, (size_t)(K - 1) * N, K - 1, 2 * B, 0)
+                             .rounded_src(acc_p + (size_t)K * N, (size_t)(K + 1) * N, 1, 3, P >> 1, P, klvl.dev.round_fix)
+                             .epilogue(0, acc_p, (size_t)(K + 1) * N, lvl.dev.inv_q_last_mod_q, out, out + (size_t)B * (K - 1) * N,
+                                       (size_t)(K - 1) * N);
             b.tail2 = &t2;
             ck(ntt_forward(tb, b, 1, stream_), "mod-down + rescale in one transform");
         }
@@ -955,40 +887,13 @@ namespace sealhip
         // increments of the owned moduli, compact planes [2][batch][count][N] (the tail adds into them: start from zero)
         Scratch inc((size_t)2 * B * count * N);
         ck(hipMemsetAsync(inc.p, 0, (size_t)2 * B * count * N * 8, stream_), "ks zero increments");
-        Scratch tt(ntt2_supports(context_.log_n()) ? 1 : (size_t)B * 2 * count * N);
-        NttBatch b{};
-        b.data = tt.p;
-        b.outer_stride = (size_t)count * N;
-        b.ncomp = count;
-        b.nouter = 2 * B;
-        b.comp_prime = nullptr;
-        b.prime_first = first;
-        b.src = acc3.p + (size_t)count * N;
-        b.src_outer_stride = (size_t)(count + 1) * N;
-        b.src_ncomp = 1;
-        b.src_mode = 2;
-        b.src_half = P >> 1;
-        b.src_q = P;
-        b.src_fix = klvl.dev.round_fix + first;
-        uint64_t *inc0 = inc.p, *inc1 = inc.p + (size_t)B * count * N;
-        if (ntt2_supports(context_.log_n()))
-        {
-            b.data = nullptr;
-            b.epi = 2;
-            b.epi_a = acc3.p;
-            b.epi_a_stride = (size_t)(count + 1) * N;
-            b.epi_mul = klvl.dev.inv_q_last_mod_q + first;
-            b.epi_out0 = inc0;
-            b.epi_out1 = inc1;
-            b.epi_out_stride = (size_t)count * N;
-            ck(ntt_forward(tb, b, 1, stream_), "ks ntt correction + tail (owned moduli)");
-        }
-        else
-        {
-            ck(ntt_forward(tb, b, 1, stream_), "ks ntt correction (owned moduli)");
-            ck(k_keyswitch_tail_ckks(mods + first, klvl.dev.inv_q_last_mod_q + first, inc0, inc1, acc3.p, tt.p, n_log, count, B, stream_),
-               "ks tail (owned moduli)");
-        }
+        ck(ntt_forward(tb,
+                       plain_batch(nullptr, (size_t)count * N, count, 2 * B, first)
+                           .rounded_src(acc3.p + (size_t)count * N, (size_t)(count + 1) * N, 1, 2, P >> 1, P, klvl.dev.round_fix + first)
+                           .epilogue(2, acc3.p, (size_t)(count + 1) * N, klvl.dev.inv_q_last_mod_q + first, inc.p,
+                                     inc.p + (size_t)B * count * N, (size_t)count * N),
+                       1, stream_),
+           "ks ntt correction + tail (owned moduli)");
         ck(k_ks_pack_owned(inc.p, own, n_log, count, m, B, stream_), "ks pack owned");
     }
 
@@ -1092,41 +997,13 @@ namespace sealhip
         Scratch &delta, const uint64_t *a, size_t a_stride, const ShoupOp *mul, unsigned ncomp, size_t items, uint64_t *out0,
         uint64_t *out1, size_t out_stride, int epi) const
     {
-        const size_t N = context_.n();
-        const unsigned n_log = (unsigned)context_.log_n();
-        const NttTables &tb = context_.ntt_tables();
-        const ModDesc *mods = context_.dev_mods();
-        if (ntt2_supports(context_.log_n()))
-        {
-            NttBatch b{};
-            b.data = nullptr;
-            b.outer_stride = (size_t)ncomp * N;
-            b.ncomp = ncomp;
-            b.nouter = (unsigned)items;
-            b.prime_first = 0;
-            b.src = delta.p;
-            b.src_outer_stride = (size_t)ncomp * N;
-            b.src_ncomp = ncomp;
-            b.src_mode = 0;
-            b.epi = epi;
-            b.epi_a = a;
-            b.epi_a_stride = a_stride;
-            b.epi_mul = mul;
-            b.epi_out0 = out0;
-            b.epi_out1 = out1;
-            b.epi_out_stride = out_stride;
-            ck(ntt_forward(tb, b, 1, stream_), "bgv ntt correction + combine");
-            return;
-        }
-        ck(ntt_forward(tb, plain_batch(delta.p, (size_t)ncomp * N, ncomp, (unsigned)items, 0), 1, stream_), "bgv ntt correction");
-        if (epi == 1)
-        {
-            if (a_stride != (size_t)(ncomp + 1) * N)
-                throw std::logic_error("bgv combine layout");
-            ck(k_rescale_combine(mods, mul, a, delta.p, out0, n_log, ncomp + 1, items, stream_), "bgv combine");
-        }
-        else
-            ck(k_keyswitch_tail_ckks(mods, mul, out0, out1, a, delta.p, n_log, ncomp, (unsigned)(items / 2), stream_), "bgv ks tail");
+        const size_t row = (size_t)ncomp * context_.n();
+        ck(ntt_forward(context_.ntt_tables(),
+                       plain_batch(nullptr, row, ncomp, (unsigned)items, 0)
+                           .rounded_src(delta.p, row, ncomp, 0)
+                           .epilogue(epi, a, a_stride, mul, out0, out1, out_stride),
+                       1, stream_),
+           "bgv ntt correction + combine");
     }
 
 } // namespace sealhip

@@ -26,7 +26,8 @@ namespace sealhip
         if (scheme == Scheme::ckks && e.lazy_ && e.lazy_->owner == this && e.size() == 2 && K >= 2 &&
             ntt2_supports(context_.log_n()))
         {
-            // the key switch that produced e left its mod-down undone (LazyTail): both rounding divisions in one pass
+            // the key switch that produced e left its mod-down undone (LazyTail): both rounding divisions in one pass.  (The ring test
+            // chooses the folded tail, NttBatch::tail2, which only the two-pass engine has; no route defers elsewhere.)
             const LazyTail t = detach_tail(e);
             try
             {
@@ -91,38 +92,12 @@ namespace sealhip
                 const NttTables &tb = context_.ntt_tables();
                 uint64_t *last = e.data() + (size_t)(K - 1) * N;
                 ck(ntt_inverse(tb, plain_batch(last, (size_t)K * N, 1, (unsigned)items, K - 1), 0, stream_), "rescale intt last");
-                Scratch tt(ntt2_supports(context_.log_n()) ? 1 : words);
-                NttBatch b{};
-                b.data = tt.p;
-                b.outer_stride = (size_t)(K - 1) * N;
-                b.ncomp = K - 1;
-                b.nouter = (unsigned)items;
-                b.comp_prime = nullptr;
-                b.prime_first = 0;
-                b.src = last;
-                b.src_outer_stride = (size_t)K * N;
-                b.src_ncomp = 1;
-                b.src_mode = 2;
-                b.src_half = lvl.dev.half_q_last;
-                b.src_q = lvl.dev.q_last;
-                b.src_fix = lvl.dev.round_fix;
-                if (ntt2_supports(context_.log_n()))
-                {
-                    b.data = nullptr;
-                    b.epi = 1;
-                    b.epi_a = e.data();
-                    b.epi_a_stride = (size_t)K * N;
-                    b.epi_mul = lvl.dev.inv_q_last_mod_q;
-                    b.epi_out0 = out;
-                    b.epi_out1 = nullptr;
-                    b.epi_out_stride = (size_t)(K - 1) * N;
-                    ck(ntt_forward(tb, b, 1, stream_), "rescale ntt correction + combine");
-                }
-                else
-                {
-                    ck(ntt_forward(tb, b, 1, stream_), "rescale ntt correction");
-                    ck(k_rescale_combine(mods, lvl.dev.inv_q_last_mod_q, e.data(), tt.p, out, n_log, K, items, stream_), "rescale combine");
-                }
+                ck(ntt_forward(tb,
+                               plain_batch(nullptr, (size_t)(K - 1) * N, K - 1, (unsigned)items, 0)
+                                   .rounded_src(last, (size_t)K * N, 1, 2, lvl.dev.half_q_last, lvl.dev.q_last, lvl.dev.round_fix)
+                                   .epilogue(1, e.data(), (size_t)K * N, lvl.dev.inv_q_last_mod_q, out, nullptr, (size_t)(K - 1) * N),
+                               1, stream_),
+                   "rescale ntt correction + combine");
             }
         }
         catch (...)

@@ -15,16 +15,6 @@ namespace sealhip
             if (e != hipSuccess)
                 throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
         }
-        NttBatch polys(uint64_t *data, size_t K, size_t n, size_t count)
-        {
-            NttBatch b{};
-            b.data = data;
-            b.outer_stride = K * n;
-            b.ncomp = (unsigned)K;
-            b.nouter = (unsigned)count;
-            b.prime_first = 0;
-            return b;
-        }
     } // namespace
 
     KeyGenerator::KeyGenerator(const Context &context, const uint64_t *seed8) : context_(context), sk_(context)
@@ -98,7 +88,7 @@ namespace sealhip
                 break;
             host_sampling = true;
         }
-        ck(ntt_forward(context_.ntt_tables(), polys(s, L, n, 1), 0, nullptr), "ntt s");
+        ck(ntt_forward(context_.ntt_tables(), plain_batch(s, L * n, (unsigned)L, 1, 0), 0, nullptr), "ntt s");
         // the seed and the draws s was made from go back to the pool cleared (the reference's seal_memzero of its secret-key copies)
         ck(hipMemsetAsync(dseed.p, 0, sizeof(seed), nullptr), "clear seed");
         ck(hipMemsetAsync(ds.p, 0, (small_words + 1) * 8, nullptr), "clear s bytes");

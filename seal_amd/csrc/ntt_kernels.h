@@ -61,6 +61,12 @@ namespace sealhip
     // One batched launch: transforms live at data + outer*outer_stride + comp*N, comp in
     // [0, ncomp), outer in [0, nouter); prime of a component = comp_prime[comp] (device array) or
     // prime_first + comp when comp_prime == nullptr.
+    //
+    // Every ring has: the plain in-place transform, the separate source in modes 0 - 2 (forward), the epilogues 1 and 2 (forward;
+    // outside the two-pass rings the transform goes to scratch of ntt_forward's own and one element-wise kernel applies the
+    // epilogue) and a plain out-of-place `src` of the inverse transform (there: a copy on the stream, then in place).
+    // Only the two-pass engine (rings 2^13 .. 2^16) has: src_mode 3, epi 3, tail2, out_add, prod_x and src_galois_elt; the entry
+    // points answer hipErrorInvalidValue for them on every other ring.
     struct NttBatch
     {
         uint64_t *data;
@@ -76,7 +82,7 @@ namespace sealhip
         //               (the "+half, mod q_i, -half" rounding step fused into the load:
         //                rns.cpp:858-881 rescale, evaluator.cpp:2813-2832 key-switch mod-down)
         //   src_mode 3: x mod q + src_fix[comp]: mode 2 for a source whose producer has already added src_half (out_add below;
-        //               two-pass engine only)
+        //               two-pass rings only)
         const uint64_t *src;
         size_t src_outer_stride;
         unsigned src_ncomp;
@@ -84,13 +90,14 @@ namespace sealhip
         uint64_t src_half;
         uint64_t src_q;
         const uint64_t *src_fix; // [ncomp], device
-        // Optional fused epilogue of the forward transform (two-pass engine only): instead of storing
+        // Optional epilogue of the forward transform (`data` is not used and may be null): instead of storing
         // the transform T to `data`, combine it with a resident operand and store the result,
         //   v = (A[outer][comp] - T) * mul[comp]  mod q                        (A canonical)
         //   epi 1: out[outer][comp] = v                      rescale tail, rns.cpp:890-899
         //   epi 2: ct_{outer&1}[outer>>1][comp] += v         key-switch tail, evaluator.cpp:2845-2863
         //   epi 3: ct_{outer&1}[outer>>1][comp] = A[outer][comp] - T * mul[comp]: the same tail when the key switch has left
-        //          A = c + S P^-1 behind (KsFusedArgs::fold_c0)
+        //          A = c + S P^-1 behind (KsFusedArgs::fold_c0; two-pass rings only)
+        // The epilogue's moduli are prime_first + comp.
         // A = epi_a + outer*epi_a_stride + comp*N; epi 1 writes epi_out0 + outer*epi_out_stride + comp*N,
         // epi 2 updates epi_out{0,1} + (outer>>1)*epi_out_stride + comp*N.
         int epi;
@@ -126,7 +133,35 @@ namespace sealhip
         // back ends and guards every integer butterfly -, 0 every prime on the integer back end (single-class kernels, the
         // unguarded butterflies where the prime's size allows), 1 every prime on the double-precision one.
         int cls_hint = -1;
+
+        // The two field groups that are filled together; each returns the batch, so a call site reads
+        // plain_batch(...).rounded_src(...).epilogue(...).
+        NttBatch &rounded_src(const uint64_t *s, size_t stride, unsigned ncomp_, int mode, uint64_t half = 0, uint64_t q = 0,
+                              const uint64_t *fix = nullptr)
+        {
+            src = s, src_outer_stride = stride, src_ncomp = ncomp_, src_mode = mode;
+            src_half = half, src_q = q, src_fix = fix;
+            return *this;
+        }
+        NttBatch &epilogue(int which, const uint64_t *a, size_t a_stride, const ShoupOp *mul, uint64_t *out0, uint64_t *out1, size_t out_stride)
+        {
+            epi = which, epi_a = a, epi_a_stride = a_stride, epi_mul = mul;
+            epi_out0 = out0, epi_out1 = out1, epi_out_stride = out_stride;
+            return *this;
+        }
     };
+
+    // the plain batch: `nouter` polynomials of `ncomp` components over the primes prime_first .., transformed in place
+    inline NttBatch plain_batch(uint64_t *data, size_t outer_stride, unsigned ncomp, unsigned nouter, unsigned prime_first)
+    {
+        NttBatch b{};
+        b.data = data;
+        b.outer_stride = outer_stride;
+        b.ncomp = ncomp;
+        b.nouter = nouter;
+        b.prime_first = prime_first;
+        return b;
+    }
 
     // out_range: 0 = canonical [0,q); 1 = lazy ([0,4q) forward / [0,2q) inverse).
     hipError_t ntt_forward(const NttTables &t, const NttBatch &b, int out_lazy, hipStream_t stream);

@@ -511,6 +511,41 @@ namespace sealhip
             }
         }
 
+        // ------------------------------------------------------------------------------------
+        // The epilogues 1 and 2 of NttBatch where the two-pass engine does not run: one element-wise pass over
+        // the lazy transform t = [nouter][ncomp][N], words in [0, 4q).  A is canonical, so A + 4q - T is in (0, 5q).
+        // ------------------------------------------------------------------------------------
+        struct EpiArgs
+        {
+            const ModDesc *mods; // of component 0 (prime_first applied)
+            const ShoupOp *mul;  // [ncomp]
+            const uint64_t *t, *a;
+            uint64_t *out0, *out1;
+            size_t a_stride, out_stride, words;
+            unsigned log_n, ncomp;
+            int epi;
+        };
+        __global__ void __launch_bounds__(256) ntt_epilogue(EpiArgs e)
+        {
+            for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < e.words; i += (size_t)gridDim.x * 256)
+            {
+                const size_t row = i >> e.log_n; // outer * ncomp + comp
+                const unsigned comp = (unsigned)(row % e.ncomp);
+                const size_t outer = row / e.ncomp;
+                const size_t j = ((size_t)comp << e.log_n) + (i & ((size_t(1) << e.log_n) - 1));
+                const uint64_t q = e.mods[comp].q;
+                const ShoupOp m = e.mul[comp];
+                const uint64_t v = mul_shoup(e.a[outer * e.a_stride + j] + 4 * q - e.t[i], m.w, m.wq, q);
+                if (e.epi == 1)
+                    e.out0[outer * e.out_stride + j] = v;
+                else
+                {
+                    uint64_t *ct = ((outer & 1) ? e.out1 : e.out0) + (outer >> 1) * e.out_stride + j;
+                    *ct = add_mod(*ct, v, q);
+                }
+            }
+        }
+
         // ---- pass plan -----------------------------------------------------------------------
         struct Plan
         {
@@ -668,8 +703,6 @@ namespace sealhip
 
     hipError_t ntt_forward(const NttTables &t, const NttBatch &b, int out_lazy, hipStream_t stream)
     {
-        if ((b.epi || b.tail2) && !ntt2_supports(t.log_n))
-            return hipErrorInvalidValue;
         if (ntt2_supports(t.log_n))
         {
             // (round 5: chunks of the outer items sized to the Infinity Cache, dealt to forked streams, measured 4 - 27 % SLOWER than
@@ -685,7 +718,26 @@ namespace sealhip
             }
             return ntt2_forward(t, b, out_lazy, mid.p, stream);
         }
-        return run(t, b, out_lazy, false, stream);
+        // first-generation passes: no folded tail, no pre-added half, and of the epilogues the two that need only A and T
+        if (b.tail2 || b.epi < 0 || b.epi > 2 || (b.src && b.src_mode == 3) || (b.epi && b.comp_prime))
+            return hipErrorInvalidValue;
+        if (!b.epi)
+            return run(t, b, out_lazy, false, stream);
+        const size_t words = ((size_t)b.nouter * b.ncomp) << t.log_n;
+        if (!words)
+            return hipSuccess;
+        Scratch tt(words); // the transform, lazy: what the fused epilogue keeps in registers
+        NttBatch bt = b;
+        bt.data = tt.p;
+        bt.outer_stride = (size_t)b.ncomp << t.log_n;
+        const hipError_t err = run(t, bt, 1, false, stream);
+        if (err != hipSuccess)
+            return err;
+        const EpiArgs e{ t.mods + b.prime_first, b.epi_mul, tt.p, b.epi_a, b.epi_out0, b.epi_out1, b.epi_a_stride, b.epi_out_stride, words,
+                         (unsigned)t.log_n, b.ncomp, b.epi };
+        const size_t grid = (words + 255) / 256;
+        hipLaunchKernelGGL(ntt_epilogue, dim3((unsigned)(grid < 2048 ? grid : 2048)), dim3(256), 0, stream, e);
+        return hipGetLastError();
     }
     hipError_t ntt_inverse(const NttTables &t, const NttBatch &b, int out_lazy, hipStream_t stream)
     {
@@ -694,8 +746,23 @@ namespace sealhip
             Scratch mid(((size_t)b.nouter * b.ncomp) << t.log_n);
             return ntt2_inverse(t, b, out_lazy, mid.p, stream);
         }
-        if (b.src || b.out_add || b.prod_x)
-            return hipErrorInvalidValue; // out-of-place input, out_add and the product source are features of the two-pass engine only
+        if (b.out_add || b.prod_x || b.src_galois_elt)
+            return hipErrorInvalidValue; // out_add, the product source and the Galois gather are features of the two-pass engine only
+        if (b.ncomp == 0 || b.nouter == 0)
+            return hipSuccess;
+        if (b.src && b.src != b.data)
+        {
+            // a plain out-of-place source: copy on the stream (one copy where the polynomials are dense), then in place
+            const size_t row = (size_t)b.ncomp << t.log_n;
+            const bool dense = b.outer_stride == row && b.src_outer_stride == row;
+            for (size_t o = 0; o < (dense ? 1 : b.nouter); o++)
+            {
+                const hipError_t err = hipMemcpyAsync(b.data + o * b.outer_stride, b.src + o * b.src_outer_stride,
+                                                      (dense ? b.nouter : 1) * row * 8, hipMemcpyDeviceToDevice, stream);
+                if (err != hipSuccess)
+                    return err;
+            }
+        }
         return run(t, b, out_lazy, true, stream);
     }
 } // namespace sealhip

@@ -511,7 +511,7 @@ namespace sealhip
         if (keys_[index].dev)
             (void)hipFree(keys_[index].dev);
         void *p = nullptr;
-        const bool reorder = ntt2_supports(ctx.log_n());
+        const bool reorder = ntt2_supports(ctx.log_n()); // chooses the key's layout: the fused key switch (two-pass rings) reads register order
         // register order carries a second plane: the Shoup quotients of the integer back end's components
         ck(hipMalloc(&p, reorder ? key_register_order_words(ctx.ntt_tables(), (unsigned)L, digits) * 8 : bytes), "hipMalloc key");
         if (reorder)

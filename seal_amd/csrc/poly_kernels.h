@@ -51,11 +51,6 @@ namespace sealhip
         const ModDesc *mods, const uint64_t *in, uint64_t *out, uint32_t galois_elt, int ntt_form, PlaneGeom g,
         unsigned planes, hipStream_t s);
 
-    // CKKS rescale tail: out[item][i] = (c[item][i] - t[item][i]) * q_last^-1 mod q_i, i < K-1;
-    // c has K comps per item, t and out K-1; t is lazy (< 4 q_i).
-    hipError_t k_rescale_combine(
-        const ModDesc *mods, const ShoupOp *inv_q_last, const uint64_t *c, const uint64_t *t, uint64_t *out,
-        unsigned n_log, unsigned K, size_t items, hipStream_t s);
     // BGV correction polynomial of mod_t_and_divide_q_last_ntt_inplace (rns.cpp:1203-1229) and of the
     // BGV key-switch mod-down (evaluator.cpp:2762-2791), coefficient form:
     //   k = -(c mod t) * q_last^-1 mod t;   delta[item][i] = ((k mod q_i) * (q_last mod q_i) + (c mod q_i)) mod q_i
@@ -105,11 +100,6 @@ namespace sealhip
     hipError_t k_ks_add_gathered(
         const ModDesc *mods, uint64_t *ct0, uint64_t *ct1, const uint64_t *all, unsigned n_log, unsigned K, unsigned G, unsigned m,
         unsigned batch, hipStream_t s);
-    // Key-switch tail (CKKS): ct_k[b][i] += (acc[b][k][i] - t[b][k][i]) * P^-1 mod q_i.
-    // ct planes: ct0 and ct1, each [batch][K][N]; acc [batch][2][K+1][N]; t [batch][2][K][N] lazy.
-    hipError_t k_keyswitch_tail_ckks(
-        const ModDesc *mods, const ShoupOp *inv_p, uint64_t *ct0, uint64_t *ct1, const uint64_t *acc,
-        const uint64_t *t, unsigned n_log, unsigned K, unsigned batch, hipStream_t s);
     // Key-switch tail (BFV): acc comps 0..K-1 already in coefficient form (canonical); r = acc comp K
     // in coefficient form canonical; ct_k[b][i] += (acc_i - ((r+half mod P) mod q_i - half mod q_i)) * P^-1.
     hipError_t k_keyswitch_tail_bfv(

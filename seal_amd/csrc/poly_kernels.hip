@@ -217,26 +217,6 @@ namespace sealhip
             }
         }
 
-        __global__ void __launch_bounds__(kBlock) rescale_combine_kernel(
-            const ModDesc *mods, const ShoupOp *inv_q_last, const uint64_t *c, const uint64_t *t, uint64_t *out,
-            unsigned n_log, unsigned K, size_t out_words)
-        {
-            const unsigned Km1 = K - 1;
-            for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < out_words; i += (size_t)gridDim.x * kBlock)
-            {
-                const size_t row = i >> n_log; // item*(K-1) + comp
-                const unsigned comp = (unsigned)(row % Km1);
-                const size_t item = row / Km1;
-                const size_t j = i & ((size_t(1) << n_log) - 1);
-                const uint64_t q = mods[comp].q;
-                const ShoupOp iq = inv_q_last[comp];
-                uint64_t cv = c[((item * K + comp) << n_log) + j];
-                uint64_t tv = t[i];
-                // c in [0,q), t in [0,4q): c + 4q - t in (0, 5q)
-                out[i] = mul_shoup(cv + 4 * q - tv, iq.w, iq.wq, q);
-            }
-        }
-
         __global__ void __launch_bounds__(kBlock) mul_scalar_kernel(
             const ModDesc *mods, const uint64_t *a, uint64_t *r, uint64_t scalar, unsigned n_log, unsigned K, size_t words)
         {
@@ -501,30 +481,6 @@ namespace sealhip
             }
         }
 
-        __global__ void __launch_bounds__(kBlock) keyswitch_tail_ckks_kernel(
-            const ModDesc *mods, const ShoupOp *inv_p, uint64_t *ct0, uint64_t *ct1, const uint64_t *acc,
-            const uint64_t *t, unsigned n_log, unsigned K, size_t words /* batch*K*N */)
-        {
-            for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < words; i += (size_t)gridDim.x * kBlock)
-            {
-                const size_t row = i >> n_log; // b*K + comp
-                const unsigned comp = (unsigned)(row % K);
-                const size_t b = row / K;
-                const size_t j = i & ((size_t(1) << n_log) - 1);
-                const uint64_t q = mods[comp].q;
-                const ShoupOp ip = inv_p[comp];
-#pragma unroll
-                for (unsigned k = 0; k < 2; k++)
-                {
-                    uint64_t a = acc[(((b * 2 + k) * (K + 1) + comp) << n_log) + j];
-                    uint64_t tv = t[(((b * 2 + k) * K + comp) << n_log) + j];
-                    uint64_t v = mul_shoup(a + 4 * q - tv, ip.w, ip.wq, q);
-                    uint64_t *ct = k ? ct1 : ct0;
-                    ct[i] = add_mod(ct[i], v, q);
-                }
-            }
-        }
-
         __global__ void __launch_bounds__(kBlock) keyswitch_tail_bfv_kernel(
             const ModDesc *mods, const ShoupOp *inv_p, const uint64_t *round_fix, uint64_t half_p, uint64_t p,
             uint64_t *ct0, uint64_t *ct1, const uint64_t *acc, unsigned n_log, unsigned K, size_t words)
@@ -657,16 +613,6 @@ namespace sealhip
             hipLaunchKernelGGL(galois_coeff_kernel, dim3(grid_for(w)), dim3(kBlock), 0, s, mods, in, out, elt, g.n_log, g.K, w);
         return hipGetLastError();
     }
-    hipError_t k_rescale_combine(
-        const ModDesc *mods, const ShoupOp *inv_q_last, const uint64_t *c, const uint64_t *t, uint64_t *out,
-        unsigned n_log, unsigned K, size_t items, hipStream_t s)
-    {
-        size_t w = (items * (K - 1)) << n_log;
-        if (!w)
-            return hipSuccess;
-        hipLaunchKernelGGL(rescale_combine_kernel, dim3(grid_for(w)), dim3(kBlock), 0, s, mods, inv_q_last, c, t, out, n_log, K, w);
-        return hipGetLastError();
-    }
     hipError_t k_mul_scalar(
         const ModDesc *mods, const uint64_t *a, uint64_t *r, uint64_t scalar, PlaneGeom g, unsigned planes, hipStream_t s)
     {
@@ -775,15 +721,6 @@ namespace sealhip
         if (!words)
             return hipSuccess;
         hipLaunchKernelGGL(ks_add_gathered_kernel, dim3(grid_for(words)), dim3(kBlock), 0, s, mods, ct0, ct1, all, n_log, K, G, m, batch, words);
-        return hipGetLastError();
-    }
-    hipError_t k_keyswitch_tail_ckks(
-        const ModDesc *mods, const ShoupOp *inv_p, uint64_t *ct0, uint64_t *ct1, const uint64_t *acc, const uint64_t *t,
-        unsigned n_log, unsigned K, unsigned batch, hipStream_t s)
-    {
-        size_t w = ((size_t)batch * K) << n_log;
-        hipLaunchKernelGGL(
-            keyswitch_tail_ckks_kernel, dim3(grid_for(w)), dim3(kBlock), 0, s, mods, inv_p, ct0, ct1, acc, t, n_log, K, w);
         return hipGetLastError();
     }
     hipError_t k_keyswitch_tail_bfv(

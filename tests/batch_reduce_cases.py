@@ -9,6 +9,7 @@ import numpy as np
 
 import seal_amd as S
 import sealref
+from harness import two_pass_ring
 from plain_batch_cases import Side, _client, _expect
 
 # include/sealhip.h, batch_reduce_kernels.hip: with primes below 2^60, 2^(64 - 60) words fit 64 bits and 2^(128 - 120) products 128 bits
@@ -392,7 +393,7 @@ def case_pending(n, bits, batch=4, group=2, seed=73):
         tails1, products1 = S.tail_stats(), S.product_stats()
     with _Env(SEALHIP_KS_SPLIT=1, SEALHIP_LAZY_PRODUCT=0, SEALHIP_KS_EAGER_TAIL=1):
         eager = run()
-    if 13 <= n.bit_length() - 1 <= 16:   # the sizes at which the library defers
+    if two_pass_ring(n):   # the sizes at which the library defers
         assert tails1[1] - tails0[1] >= 1, "sum_items completed a deferred tail"
         assert products1[1] - products0[1] >= 1, "sum_items formed a pending product"
         assert products1[2] - products0[2] >= 1, "the destination's pending product was discarded"

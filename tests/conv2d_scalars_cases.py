@@ -15,6 +15,7 @@ import seal_amd as S
 import batch_reduce_cases as BR
 import dot_scalars_cases as DS
 import matmul_scalars_cases as MS
+from harness import two_pass_ring
 from batch_reduce_cases import meta, _columns
 from matmul_scalars_cases import Weights, row_tile, flush_interval, row_counts, INT_MIN, INT_MAX, NARROW, TILES
 from plain_batch_cases import Side, _expect
@@ -481,7 +482,7 @@ def case_pending(n, bits, seed=73):
             tails1, products1 = S.tail_stats(), S.product_stats()
         with _Env(SEALHIP_KS_SPLIT=1, SEALHIP_LAZY_PRODUCT=0, SEALHIP_KS_EAGER_TAIL=1):
             eager, shape_e = run()
-        if 13 <= n.bit_length() - 1 <= 16:   # the sizes at which the library defers
+        if two_pass_ring(n):   # the sizes at which the library defers
             assert tails1[1] - tails0[1] >= 1, "the call completed a deferred tail"
             assert products1[1] - products0[1] >= 1, "the call formed a pending product"
             assert products1[2] - products0[2] >= 1, "the destination's pending product was discarded"

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 import seal_amd as S
+from harness import two_pass_ring
 from batch_reduce_cases import meta, rule_slices, SLICE_BELOW
 from plain_batch_cases import Side, _expect
 
@@ -354,7 +355,7 @@ def case_pending(n, bits, batch=4, group=2, seed=73):
         tails1, products1 = S.tail_stats(), S.product_stats()
     with _Env(SEALHIP_KS_SPLIT=1, SEALHIP_LAZY_PRODUCT=0, SEALHIP_KS_EAGER_TAIL=1):
         eager, shape_e = run()
-    if 13 <= n.bit_length() - 1 <= 16:   # the sizes at which the library defers
+    if two_pass_ring(n):   # the sizes at which the library defers
         assert tails1[1] - tails0[1] >= 1, "dot_items completed a deferred tail"
         assert products1[1] - products0[1] >= 1, "the product reading y was formed when y was overwritten"
     assert shape == shape_e == (3, batch // group, (True, side.scale ** 3, 1))

@@ -17,6 +17,7 @@ import dot_scalars_cases as DS
 import item_map_cases as IM
 import matmul_scalars_cases as MS
 import conv2d_scalars_cases as CV
+from harness import two_pass_ring
 from batch_reduce_cases import meta, _columns
 from item_map_cases import SOURCE, ROWS, SECOND_OF_3, CUT_LENGTHS, draw_rows
 from matmul_scalars_cases import INT_MIN, INT_MAX
@@ -456,7 +457,7 @@ def case_pending(n, bits, seed=73):
             tails1, products1 = S.tail_stats(), S.product_stats()
         with _Env(SEALHIP_KS_SPLIT=1, SEALHIP_LAZY_PRODUCT=0, SEALHIP_KS_EAGER_TAIL=1):
             eager, shape_e = run()
-        if 13 <= n.bit_length() - 1 <= 16:   # the sizes at which the library defers
+        if two_pass_ring(n):   # the sizes at which the library defers
             assert tails1[1] - tails0[1] >= 1, "the call completed a deferred tail"
             assert products1[1] - products0[1] >= 1, "the call formed a pending product"
             assert products1[2] - products0[2] >= 1, "the destination's pending product was discarded"

@@ -5,6 +5,12 @@ import numpy as np
 import seal_amd as S
 
 
+def two_pass_ring(n):
+    """is 2^13 <= n <= 2^16: the rings the two-pass transform engine serves (ntt2_supports, ntt2_kernels.h) - where the library
+    defers key-switch tails and folds rounding divisions"""
+    return 13 <= n.bit_length() - 1 <= 16
+
+
 class DeviceSide:
     def __init__(self, scheme, n, primes, plain_modulus=0):
         self.scheme, self.n, self.primes, self.t = scheme, n, list(primes), plain_modulus

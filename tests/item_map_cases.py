@@ -11,6 +11,7 @@ import numpy as np
 import seal_amd as S
 import batch_reduce_cases as BR
 import dot_items_cases as DI
+from harness import two_pass_ring
 from batch_reduce_cases import meta, forms, _columns, SUM_FLUSH, DOT_FLUSH
 from plain_batch_cases import Side, _expect
 
@@ -387,7 +388,7 @@ def case_pending(n, bits, seed=73):
         tails1, products1 = S.tail_stats(), S.product_stats()
     with _Env(SEALHIP_KS_SPLIT=1, SEALHIP_LAZY_PRODUCT=0, SEALHIP_KS_EAGER_TAIL=1):
         eager = run()
-    if 13 <= n.bit_length() - 1 <= 16:   # the sizes at which the library defers
+    if two_pass_ring(n):   # the sizes at which the library defers
         assert tails1[1] - tails0[1] >= 2, "the mapped calls completed deferred tails"
         assert products1[1] - products0[1] >= 1, "sum_items_mapped formed a pending product"
         assert products1[2] - products0[2] >= 1, "the destination's pending product was discarded"

@@ -177,8 +177,9 @@ class _Side:
             self.d.ev.mod_switch_to_next_inplace(c)
 
     def defers(self):
-        # mirrors Evaluator::ks_route (evaluator_keyswitch.cpp: r.defer) - keep in step with it; ntt2_supports is 2^13 .. 2^16
-        return self.scheme in ("ckks", "bfv") and 13 <= self.n.bit_length() - 1 <= 16 and self.K >= 2 and not self.eager
+        # mirrors Evaluator::ks_route (evaluator_keyswitch.cpp: r.defer) - keep in step with it; ntt2_supports is harness.two_pass_ring
+        from harness import two_pass_ring
+        return self.scheme in ("ckks", "bfv") and two_pass_ring(self.n) and self.K >= 2 and not self.eager
 
     def same(self, c, expected, what):
         """every item of the device ciphertext c == the oracle's (words, info)"""

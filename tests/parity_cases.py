@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 import seal_amd as S
-from harness import DeviceSide
+from harness import DeviceSide, two_pass_ring
 from oracle import Oracle, coeff_modulus_create, plain_modulus_batching, rand_ct
 
 
@@ -201,7 +201,7 @@ def _deferred_tails(d, o, xs, ys, primes, K, n, batch, steps, elts):
         # without anything reading the ciphertext in between does both rounding divisions in one pass.  Same words as the
         # reference's two separate steps (evaluator.cpp:2806-2864, rns.cpp:830-901).
         sc = float(primes[K - 1]) * 2.0 ** 10
-        defers = 13 <= n.bit_length() - 1 <= 16 and not os.environ.get("SEALHIP_KS_EAGER_TAIL")  # the two-pass sizes
+        defers = two_pass_ring(n) and not os.environ.get("SEALHIP_KS_EAGER_TAIL")  # the two-pass sizes
         folded0, plain0, dropped0 = S.tail_stats()
         cz, cw = d.ct(xs, scale=2.0 ** 10), d.ct(ys, scale=2.0 ** 10)
         d.ev.multiply_inplace(cz, cw)
@@ -554,7 +554,7 @@ def case_bfv_pipeline(n, primes, t, batch=2, seed=4):
         # ciphertext in between - does the mod-down by the special prime and the division by q_last in ONE element-wise pass
         # (evaluator.cpp:2806-2864 then rns.cpp:789-828: the same words as the reference's two steps); a reader in between gets the
         # completed ciphertext, a destination that is overwritten drops the pending sums.
-        defers = 13 <= n.bit_length() - 1 <= 16 and not os.environ.get("SEALHIP_KS_EAGER_TAIL")  # the two-pass sizes
+        defers = two_pass_ring(n) and not os.environ.get("SEALHIP_KS_EAGER_TAIL")  # the two-pass sizes
         folded0, plain0, dropped0 = S.tail_stats()
         cz, cw = d.ct(xs), d.ct(ys)
         d.ev.multiply_inplace(cz, cw)
@@ -749,7 +749,7 @@ def case_digit_parallel(scheme, n, primes, t=0, parts=2, batch=2, seed=7, key_pa
     if scheme == "ckks" and K >= 2:
         # BASELINE configs[4] is rotate + rescale: at the two-pass sizes `*Finish` leaves the mod-down pending like the single-GPU
         # key switch does and the rescale folds both divisions (sealhip.h section 1b); smaller sizes finish at once
-        defers = 13 <= n.bit_length() - 1 <= 16 and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
+        defers = two_pass_ring(n) and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
         sc = float(primes[K - 1]) * 2.0 ** 10
         words = d.ev.switch_key_acc_words(d.ct(x2, scale=sc))
         total = np.zeros(words, dtype=np.uint64)
@@ -1001,6 +1001,24 @@ def case_rns_stages(n, primes, t, seed=5):
     run("fastbconv_sk", e2, K)
 
 
+# ---- shl_rns_stage "divide_and_round_q_last_ntt" (rns.cpp:830-901) on raw words: the rounding division of a CKKS rescale, polynomial
+#      by polynomial.  Expected: the reference's own stage where oracle/_ref is built, the port's rescale otherwise (the same function).
+def case_rns_stage_divide_ntt(n, bits, polys=3, seed=19):
+    primes = coeff_modulus_create(n, bits)
+    K = len(primes) - 1
+    o = Oracle("ckks", n, primes)
+    d = DeviceSide("ckks", n, primes)
+    x = rand_ct(np.random.default_rng(seed), primes, K, n, size=polys)
+    if o.kind == "reference":
+        exp = np.stack([o.rns_stage(K, "divide_and_round_q_last_ntt", x[i], K)[:K - 1] for i in range(polys)])
+    else:
+        exp = o.rescale(x)
+    src, dst = S.DeviceBuffer.from_numpy(x), S.DeviceBuffer(polys * (K - 1) * n)
+    S.rns_stage(d.ctx, d.chain_index_for_K(K), "divide_and_round_q_last_ntt", src, dst, polys)
+    _eq(dst.to_numpy((polys, K - 1, n)), exp, "divide_and_round_q_last_ntt, N %d" % n)
+    _eq(src.to_numpy((polys, K, n)), x, "the stage's input")
+
+
 def default_bfv_params(n, bits, t_bits):
     return coeff_modulus_create(n, bits), plain_modulus_batching(n, t_bits)
 
@@ -1101,7 +1119,7 @@ def case_multi_level_ckks(n, bits, batch=2, seed=41, step=1):
     rng = np.random.default_rng(seed)
     xs = [rand_ct(rng, primes, K, n) for _ in range(batch)]
     ys = [rand_ct(rng, primes, K, n) for _ in range(batch)]
-    defers = 13 <= n.bit_length() - 1 <= 16 and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
+    defers = two_pass_ring(n) and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
     levels = 3
     target_K = K - levels
     dropped = 1.0
@@ -1243,7 +1261,7 @@ def case_deferred_tail_two_readers(n=8192, bits=(50, 40, 40, 60), rounds=6):
     z1, z2 = rand_ct(rng, primes, K, n), rand_ct(rng, primes, K, n)
     ref_relin = o.relinearize(o.multiply(x, y))
     qk = np.array(primes[:K], dtype=np.uint64)[None, :, None]
-    defers = 13 <= n.bit_length() - 1 <= 16 and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
+    defers = two_pass_ring(n) and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
     ev2 = S.Evaluator(d.ctx)
     for r in range(rounds):
         a, b = d.ct([x], scale=2.0 ** 10), d.ct([y], scale=2.0 ** 10)
@@ -1290,7 +1308,7 @@ def case_pending_product_threads(n=8192, bits=(50, 40, 40, 60), rounds=4):
     z1, z2 = rand_ct(rng, primes, K, n, size=3), rand_ct(rng, primes, K, n, size=3)
     ref_prod, ref_prod2 = o.multiply(x, y), o.multiply(x2, y)
     qk = np.array(primes[:K], dtype=np.uint64)[None, :, None]
-    defers = 13 <= n.bit_length() - 1 <= 16 and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
+    defers = two_pass_ring(n) and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
     ev2 = S.Evaluator(d.ctx)
     with _Env(SEALHIP_KS_SPLIT=1, SEALHIP_LAZY_PRODUCT_MIN_WGS=0, SEALHIP_LAZY_PRODUCT=None):
         for r in range(rounds):
@@ -1596,7 +1614,7 @@ def case_lazy_product(n, bits, batch=3, seed=61):
     import gc
     # the launcher's rule keeps small batches eager; the test reaches the deferred path with the two knobs it documents
     with _Env(SEALHIP_KS_SPLIT=1, SEALHIP_LAZY_PRODUCT_MIN_WGS=0, SEALHIP_LAZY_PRODUCT=None):
-        defers = 13 <= n.bit_length() - 1 <= 16 and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
+        defers = two_pass_ring(n) and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
 
         def fresh():
             return d.ct(xs, scale=2.0 ** 10), d.ct(ys, scale=2.0 ** 10), S.Ciphertext(d.ctx, batch=batch)
@@ -1880,5 +1898,5 @@ def case_rotate_gather(n, bits, batch=3, steps=(1, -1), seed=71):
         for b in range(batch):
             _eq(got[b], o.rescale(o.apply_galois(o.relinearize(o.multiply(xs[b], ys[b])), e0)), "multiply + relinearize + rotate + rescale, item %d" % b)
     g1 = S.galois_stats()
-    two_pass = 13 <= n.bit_length() - 1 <= 16 and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
+    two_pass = two_pass_ring(n) and not os.environ.get("SEALHIP_KS_EAGER_TAIL")
     assert (g1[0] - g0[0], g1[1] - g0[1]) == ((4 * len(steps) + 2, 0) if two_pass else (0, 4 * len(steps) + 2)), "rotation paths: %r" % ((g1[0] - g0[0], g1[1] - g0[1]),)

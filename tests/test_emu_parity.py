@@ -214,6 +214,20 @@ def test_rns_stages(emu):
     P.case_rns_stages(64, primes, t)
 
 
+# The rounding divisions where the two-pass engine does not run: the transform goes to scratch and one element-wise kernel
+# (ntt_kernels.hip: ntt_epilogue) applies the epilogue.  K = 2 (one output component) at N = 2 (the single-kernel plan), 64 and 4096;
+# the key switch's tail (epilogue 2) takes its plane from the low bit of the outer index: batch 1 and batch 3
+@pytest.mark.parametrize("n,bits,batch,steps", [(2, [30, 30, 30], 1, ()), (64, [40, 30, 40], 3, (1,)), (4096, [50, 40, 50], 1, (1,))])
+def test_rounding_epilogues_small_rings(emu, n, bits, batch, steps):
+    P.case_ckks_pipeline(n, bits, batch=batch, steps=steps, check_transforms=False)
+
+
+# ... and shl_rns_stage's rounding division (epilogue 1) over an odd number of polynomials; N = 8192: the fused epilogue
+@pytest.mark.parametrize("n,bits", [(2, [30, 30, 30]), (64, [40, 30, 40]), (4096, [50, 40, 50]), (1024, [50, 40, 40, 50]), (8192, [50, 40, 40, 50])])
+def test_rns_stage_divide_ntt(emu, n, bits):
+    P.case_rns_stage_divide_ntt(n, bits, polys=3)
+
+
 def test_kats_on_device_path(emu):
     """The reference's NTT / Galois known answers (native/tests/seal/util/ntt.cpp:75-101,
     galois.cpp:86-120) through the device path."""

@@ -312,6 +312,19 @@ def test_plain_operands_and_many(gpu, scheme, n, bits, tb, batch):
     P.case_plain_ops(scheme, n, primes, t, batch=batch)
 
 
+# The rounding divisions where the two-pass engine does not run (ntt_kernels.hip: ntt_epilogue): K = 2 at N = 2, 64 and 4096; the key
+# switch's tail takes its plane from the low bit of the outer index: batch 1 and batch 3
+@pytest.mark.parametrize("n,bits,batch,steps", [(2, [30, 30, 30], 1, ()), (64, [40, 30, 40], 3, (1,)), (4096, [50, 40, 50], 1, (1,))])
+def test_rounding_epilogues_small_rings(gpu, n, bits, batch, steps):
+    P.case_ckks_pipeline(n, bits, batch=batch, steps=steps, check_transforms=False)
+
+
+# ... and shl_rns_stage's rounding division over an odd number of polynomials; N = 8192: the fused epilogue
+@pytest.mark.parametrize("n,bits", [(2, [30, 30, 30]), (64, [40, 30, 40]), (4096, [50, 40, 50]), (1024, [50, 40, 40, 50]), (8192, [50, 40, 40, 50])])
+def test_rns_stage_divide_ntt(gpu, n, bits):
+    P.case_rns_stage_divide_ntt(n, bits, polys=3)
+
+
 def test_rns_stages(gpu):
     primes, t = P.default_bfv_params(2048, [50, 50, 50, 50], 20)
     P.case_rns_stages(2048, primes, t)
