@@ -2,6 +2,7 @@
 // seal_amd/csrc/field.h against 128-bit integer arithmetic (built with g++ against the emulator's
 // stand-in hip_runtime.h; the same source the kernels include).
 #include "field.h"
+#include "fp_field_cases.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -20,7 +21,8 @@ static uint64_t canon(i128 v, uint64_t q)
     return (uint64_t)r;
 }
 
-int main()
+// field_check [FILE]: with FILE, the digest of the shared case body is also written there as JSON (tests/golden/fp_field_digest.json)
+int main(int argc, char **argv)
 {
     std::mt19937_64 rng(0x5EA1);
     // primes = 1 (mod 2^17) just under each bit size (primality is irrelevant to the arithmetic identities)
@@ -198,6 +200,35 @@ int main()
                     if (e <= 4) { EXPECT(IntBounds<0>::inv_exp(r, idx, 0, e) <= IntBounds<0>::lim_exp, "tight inverse exponent"); }
                     EXPECT(IntBounds<1>::inv_exp(r, idx, 0, e) <= IntBounds<1>::lim_exp, "roomy inverse exponent");
                 }
+    }
+    // ---- double-precision back end at its bounds: the case body shared with tests/device_fp_field_check.hip (fp_field_cases.h),
+    //      the streams of the digest run serially
+    {
+        using namespace fpcases;
+        static Result res[kNumPrimes];
+        static double utab[kNumPrimes * kUniTw];
+        for (unsigned p = 0; p < kNumPrimes; p++)
+        {
+            const FpDesc m = make_desc(primes()[p]);
+            fill_uniform_tw(primes()[p], p, utab + p * kUniTw);
+            for (unsigned t = 0; t < kDigestBlocks * kThreadsPerBlock; t++)
+            {
+                Sink sk = sink_zero(true);
+                for (unsigned r = 0; r < kDigestRounds; r++)
+                    run_round(m, utab + p * kUniTw, p, t / kThreadsPerBlock, t, r, sk);
+                merge(res[p], sk);
+            }
+        }
+        unsigned long long digest = 0;
+        fails += (int)report("fp_field_check", res, &digest);
+        if (argc > 1 && !fails)
+        {
+            FILE *f = fopen(argv[1], "w");
+            if (!f) { printf("cannot write %s\n", argv[1]); return 2; }
+            fprintf(f, "{\n  \"digest\": \"%016llx\",\n  \"primes\": %u,\n  \"threads_per_prime\": %u,\n  \"rounds\": %u\n}\n", digest, kNumPrimes,
+                    kDigestBlocks * kThreadsPerBlock, kDigestRounds);
+            fclose(f);
+        }
     }
     if (fails) { printf("%d failures\n", fails); return 1; }
     printf("field_check ok\n");

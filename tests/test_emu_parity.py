@@ -131,8 +131,13 @@ def test_golden_engine_digests_index_arithmetic(emu):
 
 def test_field_arithmetic_exact():
     """seal_amd/csrc/field.h: the double-precision residue arithmetic is exact and stays inside its
-    documented ranges (checked against 128-bit integers, 2.8 M random and adversarial cases)."""
+    documented ranges (checked against 128-bit integers, 2.8 M random and adversarial cases); then the case body of
+    tests/fp_field_cases.h, which steers operands to the ties and ladder values where those ranges are tight and runs the phase
+    templates of ntt2_device.h.  The digest of every double it produced is the one the device check has to reproduce
+    (tests/golden/fp_field_digest.json, written by this program: field_check FILE)."""
+    import json
     import os
+    import re
     import subprocess
     here = os.path.dirname(os.path.abspath(__file__))
     root = os.path.dirname(here)
@@ -142,6 +147,10 @@ def test_field_arithmetic_exact():
                            "-I" + os.path.join(root, "seal_amd", "csrc"), os.path.join(here, "field_check.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "field_check ok" in out.stdout, out.stdout + out.stderr
+    digest = re.search(r"^fp_field_check digest ([0-9a-f]{16})$", out.stdout, re.M)
+    assert digest, out.stdout
+    with open(os.path.join(here, "golden", "fp_field_digest.json")) as f:
+        assert digest.group(1) == json.load(f)["digest"], out.stdout
 
 
 def test_dyadic(emu):

@@ -639,6 +639,27 @@ def test_device_field_check(gpu):
     assert out.returncode == 0 and "device_field_check ok" in out.stdout, out.stdout + out.stderr
 
 
+def test_device_fp_field_check(gpu):
+    """the double-precision back end and the phase templates that place its range reductions, at the bounds field.h documents,
+    compiled with the library's flags and compared with 128-bit arithmetic on the device itself (tests/device_fp_field_check.hip,
+    the case body of tests/fp_field_cases.h); every double it produces on the streams it shares with the host check has the
+    host's bits (tests/golden/fp_field_digest.json, written by tests/field_check.cpp)"""
+    import json
+    import os
+    import re
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "seal_amd", "lib", "device_fp_field_check")
+    assert os.path.exists(exe), "seal_amd/lib/device_fp_field_check is not built (make -C seal_amd/csrc gpu)"
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(out.stdout)
+    assert out.returncode == 0 and "device_fp_field_check ok" in out.stdout, out.stdout + out.stderr
+    digest = re.search(r"^device_fp_field_check digest ([0-9a-f]{16})$", out.stdout, re.M)
+    assert digest, out.stdout
+    with open(os.path.join(root, "tests", "golden", "fp_field_digest.json")) as f:
+        assert digest.group(1) == json.load(f)["digest"], out.stdout
+
+
 def test_mod_reduce(gpu):
     import sealref
     if not sealref.available():
