@@ -969,7 +969,11 @@ SHL_FUNC shl_apply_galois(void *context, uint64_t chain_index, int ntt_form, uin
  *   2 fast_floor         q U Bsk -> Bsk       (rns.cpp:1041)     in K+|Bsk|,        out |Bsk|
  *   3 fastbconv_sk       Bsk -> q             (rns.cpp:903)      in |Bsk|,          out K
  *   4 divide_and_round_q_last_inplace         (rns.cpp:789)      in K,              out K-1
- *   5 divide_and_round_q_last_ntt_inplace     (rns.cpp:830)      in K,              out K-1 */
+ *   5 divide_and_round_q_last_ntt_inplace     (rns.cpp:830)      in K,              out K-1
+ *   6 lift       = stages 0 then 1 as the one fused kernel Evaluator::multiply runs          in K,        out |Bsk|
+ *   7 floor_sk   = (x t), then stages 2 then 3 as the one fused kernel (evaluator.cpp:549-566)
+ *                                                                 in K+|Bsk| (the q part first, as stage 2), out K
+ * Stages 0-3, 6 and 7 exist for BFV contexts only. */
 SHL_FUNC shl_rns_stage(void *context, uint64_t chain_index, int which, const uint64_t *in, uint64_t *out, uint64_t polys, void *stream);
 /* ------------------------------------------------------------------------------------------------
  * 1d. The container surface a sealc binding uses besides the hot path (seal_amd/csrc/capi_containers.cpp)

@@ -1873,7 +1873,7 @@ def apply_galois(context, chain_index, ntt_form, galois_elt, src, dst, polys, st
 
 
 RNS_STAGE = {"fastbconv_m_tilde": 0, "sm_mrq": 1, "fast_floor": 2, "fastbconv_sk": 3,
-             "divide_and_round_q_last": 4, "divide_and_round_q_last_ntt": 5}
+             "divide_and_round_q_last": 4, "divide_and_round_q_last_ntt": 5, "lift": 6, "floor_sk": 7}
 
 
 def rns_stage(context, chain_index, which, src, dst, polys, stream=None):

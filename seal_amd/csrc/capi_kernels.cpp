@@ -500,6 +500,28 @@ extern "C"
                    "ntt correction + combine");
             hip_ok(hipStreamSynchronize(s), "sync");
         }
+        else if (which == 6 || which == 7)
+        {
+            // the fused kernels Evaluator::multiply / square run for BFV, on the caller's words
+            if (c->scheme() != Scheme::bfv)
+                throw std::logic_error("BEHZ stages exist only for BFV contexts");
+            if (which == 6)
+                hip_ok(k_behz_lift(c->dev_mods(), l->dev, in, out, n_log, polys, s), "behz lift");
+            else if (polys)
+            {
+                // the kernel takes the base-q and the base-Bsk parts as two slabs of strides K N and |Bsk| N
+                const size_t N = c->n(), q_words = (size_t)l->K * N, b_words = (size_t)l->dev.nBsk * N;
+                Scratch dq(polys * q_words), dbsk(polys * b_words);
+                for (uint64_t p = 0; p < polys; p++)
+                {
+                    const uint64_t *src = in + p * (q_words + b_words);
+                    hip_ok(hipMemcpyAsync(dq.p + p * q_words, src, q_words * 8, hipMemcpyDeviceToDevice, s), "copy");
+                    hip_ok(hipMemcpyAsync(dbsk.p + p * b_words, src + q_words, b_words * 8, hipMemcpyDeviceToDevice, s), "copy");
+                }
+                hip_ok(k_behz_floor_sk(c->dev_mods(), l->dev, dq.p, dbsk.p, out, n_log, polys, s), "behz floor + sk");
+                hip_ok(hipStreamSynchronize(s), "sync");
+            }
+        }
         else
             throw std::invalid_argument("unknown stage");
         SHL_CATCH
