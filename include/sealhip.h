@@ -511,6 +511,8 @@ SHL_FUNC Evaluator_SumItemsMapped(void *thisptr, void *encrypted, void *item_map
 SHL_FUNC Evaluator_DotPlainMapped(void *thisptr, void *encrypted, const uint64_t *device_plain, uint64_t plain_count, void *item_map,
                                   double scale, void *destination);
 SHL_FUNC Evaluator_DotItemsMapped(void *thisptr, void *encrypted1, void *encrypted2, void *item_map, void *destination);
+/* Galois sets - many rotations of a batch in one key switch (GaloisSet_Create, Evaluator_ApplyGaloisSet) - are declared in
+ * sealhip_galois_set.h, which this header includes at its end. */
 /* A sparse matrix of SCALAR weights over an item map (library extension): Evaluator_DotPlainMapped whose plaintexts are constants,
  *   out_o = sum_{t in row o} const(w[second[t]]) (.) ct[first[t]],   row_offsets[o] <= t < row_offsets[o + 1],  o < rows
  * - with one ciphertext per feature and the samples in the slots: a pruned dense layer, grouped, depthwise and dilated convolutions,
@@ -1223,4 +1225,6 @@ SHL_FUNC shl_timer_stop(void *timer, void *stream, float *milliseconds); /* sync
 #ifdef __cplusplus
 }
 #endif
+/* library extensions declared in headers of their own */
+#include "sealhip_galois_set.h"
 #endif /* SEALHIP_H */

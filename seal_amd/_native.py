@@ -125,6 +125,9 @@ SEALContext_LastContextData SEALContext_ParameterErrorMessage SEALContext_Parame
 SecretKey_ParmsId SecretKey_Save SecretKey_SaveSize
 """.split()
 
+# the extension headers' exports (include/sealhip_galois_set.h): bound like SYMBOLS, listed apart because SYMBOLS is sealhip.h's own list
+EXT_SYMBOLS = "GaloisSet_Create GaloisSet_CreateFromSteps GaloisSet_Destroy GaloisSet_Info Evaluator_ApplyGaloisSet SealHip_GaloisSetStats".split()
+
 _lib = None
 _lib_path = None
 
@@ -140,7 +143,7 @@ def load(path=None):
             "seal_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % want)
     lib = C.CDLL(want)
-    for name in SYMBOLS:
+    for name in SYMBOLS + EXT_SYMBOLS:
         getattr(lib, name).restype = C.c_long
     _lib, _lib_path = lib, want
     return lib

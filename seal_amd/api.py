@@ -1223,6 +1223,45 @@ class ItemMap:
     __del__ = destroy
 
 
+class GaloisSet:
+    """R Galois elements whose automorphisms Evaluator.apply_galois_set applies to every item of a batch in one key switch
+    (sealhip_galois_set.h: GaloisSet_Create).  Give galois_elts= (odd, below 2 N, each key present) or steps= (a step of 0 is an identity
+    entry: a copy; a step whose exact key is absent is refused - there is no NAF chain in a set).  Validated and uploaded once; the
+    keys object must outlive the set, and a key replaced afterwards makes the calls fail."""
+
+    def __init__(self, context, galois_keys, galois_elts=None, steps=None):
+        if (galois_elts is None) == (steps is None):
+            raise ValueError("give galois_elts or steps")
+        self.context, self.galois_keys = context, galois_keys
+        self._h = C.c_void_p()
+        if steps is not None:
+            steps = list(steps)
+            arr = (C.c_int * max(len(steps), 1))(*steps)
+            N.check(N.lib().GaloisSet_CreateFromSteps(context._h, galois_keys._h, C.c_uint64(len(steps)), arr, C.byref(self._h)))
+        else:
+            elts = list(galois_elts)
+            arr = (C.c_uint32 * max(len(elts), 1))(*elts)
+            N.check(N.lib().GaloisSet_Create(context._h, galois_keys._h, C.c_uint64(len(elts)), arr, C.byref(self._h)))
+
+    def info(self):
+        """-> (count, identity entries, distinct elements that are key-switched, every key in register order)"""
+        v = [C.c_uint64() for _ in range(3)]
+        ro = C.c_bool()
+        N.check(N.lib().GaloisSet_Info(self._h, *[C.byref(x) for x in v], C.byref(ro)))
+        return tuple(x.value for x in v) + (bool(ro.value),)
+
+    def count(self):
+        return self.info()[0]
+
+    def destroy(self):
+        """give the table back now (sealhip_galois_set.h: GaloisSet_Destroy is safe while work that reads it is queued)"""
+        if getattr(self, "_h", None):
+            N.lib().GaloisSet_Destroy(self._h)
+            self._h = None
+
+    __del__ = destroy
+
+
 class Conv2dShape(C.Structure):
     """sealhip.h: SHL_CONV2D, the shape of Evaluator.conv2d_scalars_items"""
     _fields_ = [(name, C.c_uint64) for name in ("in_channels", "height", "width", "out_channels", "kernel_h", "kernel_w",
@@ -1407,6 +1446,15 @@ class Evaluator:
     def rotate_columns(self, a, galois_keys, destination):
         N.check(N.lib().Evaluator_RotateColumns(self._h, a._h, galois_keys._h, destination._h, None))
         return destination
+
+    def apply_galois_set(self, a, galois_set, destination=None):
+        """item b * count + r of the result = apply_galois(item b of `a`, entry r of the set), word for word; the rotations of one
+        source are adjacent, so dot_plain_device(result, words, group=count) is the diagonal product (sealhip.h:
+        Evaluator_ApplyGaloisSet, sealhip_galois_set.h).  destination None: a new Ciphertext of a.batch() * count items; otherwise a handle of that batch,
+        distinct from `a`"""
+        d = Ciphertext(self.context, batch=a.batch() * galois_set.count()) if destination is None else destination
+        N.check(N.lib().Evaluator_ApplyGaloisSet(self._h, a._h, galois_set._h, d._h))
+        return d
 
     def rotate_vector(self, a, steps, galois_keys, destination):
         N.check(N.lib().Evaluator_RotateVector(self._h, a._h, C.c_int(steps), galois_keys._h, destination._h, None))
@@ -1951,6 +1999,14 @@ def galois_stats():
     a, b = C.c_uint64(), C.c_uint64()
     N.check(N.lib().SealHip_GaloisStats(C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def galois_set_stats():
+    """Galois sets (sealhip_galois_set.h: SealHip_GaloisSetStats): (calls on the one-batch route, calls served by the loop over the entries, fused
+    key-switch launches issued by set calls)"""
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    N.check(N.lib().SealHip_GaloisSetStats(C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
 
 
 def xof_stats():

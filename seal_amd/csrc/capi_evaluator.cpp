@@ -326,6 +326,59 @@ extern "C"
             *second_batch = m->second_batch();
         return SHL_S_OK;
     }
+    // Galois sets (library extension): R Galois elements, validated and uploaded once; one call rotates every item of a batch by all of them
+    SHL_FUNC GaloisSet_Create(void *context, void *galois_keys, uint64_t count, const uint32_t *galois_elts, void **galois_set)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        IfNullRet(galois_keys, SHL_E_POINTER);
+        IfNullRet(galois_set, SHL_E_POINTER);
+        SHL_TRY
+        *galois_set = new GaloisSet(*as<Context>(context), keys(galois_keys), count, galois_elts, false);
+        SHL_CATCH
+    }
+    SHL_FUNC GaloisSet_CreateFromSteps(void *context, void *galois_keys, uint64_t count, const int *steps, void **galois_set)
+    {
+        IfNullRet(context, SHL_E_POINTER);
+        IfNullRet(galois_keys, SHL_E_POINTER);
+        IfNullRet(galois_set, SHL_E_POINTER);
+        SHL_TRY
+        if (!steps)
+            throw std::invalid_argument("steps is null");
+        if (!count || count >= (uint64_t(1) << 32))
+            throw std::invalid_argument("1 <= count < 2^32");
+        Evaluator ev(*as<Context>(context));
+        std::vector<uint32_t> elts;
+        for (uint64_t r = 0; r < count; r++)
+            elts.push_back(steps[r] ? ev.galois_elt_from_step(steps[r]) : 0); // a step of 0: the identity entry (a copy)
+        *galois_set = new GaloisSet(*as<Context>(context), keys(galois_keys), count, elts.data(), true);
+        SHL_CATCH
+    }
+    SHL_FUNC GaloisSet_Destroy(void *thisptr)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        SHL_TRY
+        delete as<GaloisSet>(thisptr);
+        SHL_CATCH
+    }
+    SHL_FUNC GaloisSet_Info(void *thisptr, uint64_t *count, uint64_t *identities, uint64_t *distinct, bool *register_order)
+    {
+        IfNullRet(thisptr, SHL_E_POINTER);
+        const GaloisSet *s = as<GaloisSet>(thisptr);
+        if (count)
+            *count = s->count();
+        if (identities)
+            *identities = s->count() - s->switched();
+        if (distinct)
+            *distinct = s->distinct();
+        if (register_order)
+            *register_order = s->register_order();
+        return SHL_S_OK;
+    }
+    SHL_FUNC Evaluator_ApplyGaloisSet(void *thisptr, void *encrypted, void *galois_set, void *destination)
+    {
+        return ev_call(thisptr, { encrypted, galois_set, destination },
+                       [&](Evaluator &ev) { ev.apply_galois_set(ct(encrypted), *as<GaloisSet>(galois_set), ct(destination)); });
+    }
     SHL_FUNC Evaluator_SumItemsMapped(void *thisptr, void *encrypted, void *item_map, void *destination)
     {
         return ev_call(thisptr, { encrypted, item_map, destination },

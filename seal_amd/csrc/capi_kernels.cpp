@@ -585,6 +585,19 @@ extern "C"
             *permuted = p;
         SHL_CATCH
     }
+    SHL_FUNC SealHip_GaloisSetStats(uint64_t *batched, uint64_t *looped, uint64_t *fused_launches)
+    {
+        SHL_TRY
+        uint64_t b, l, f;
+        galois_set_stats(b, l, f);
+        if (batched)
+            *batched = b;
+        if (looped)
+            *looped = l;
+        if (fused_launches)
+            *fused_launches = f;
+        SHL_CATCH
+    }
     SHL_FUNC SealHip_TailStats(uint64_t *folded, uint64_t *plain, uint64_t *dropped)
     {
         SHL_TRY

@@ -90,10 +90,25 @@ namespace sealhip
         uint32_t galois_elt = 0;           // != 0: c0 and the target are the UNPERMUTED polynomials of a rotation's operand, read
         const uint64_t *c0 = nullptr;      //       through the automorphism's index map; else the ciphertext's own planes
         const LazyProduct *prod = nullptr; // the operands of a tensor product that was never stored, instead of planes
+        // a Galois set (ntt_kernels.h: KsSetView; v0 is filled per launch): key - and with set.map element and source item - per virtual
+        // item.  With set.map, c0 and the target are the BASE of the unpermuted operand's planes (as galois_elt, per item)
+        KsSetView set{};
         static KsAddend nothing() { return {}; }
         static KsAddend planes(bool c1_zero_unwritten = false) { return { true, c1_zero_unwritten, 0, nullptr, nullptr }; }
         static KsAddend galois(uint32_t elt, const uint64_t *operand_c0) { return { true, true, elt, operand_c0, nullptr }; }
         static KsAddend product(const LazyProduct &p) { return { true, false, 0, nullptr, &p }; }
+        static KsAddend galois_set(const KsSetView &view, const uint64_t *operand_c0) // the map-reading form
+        {
+            KsAddend a{ true, true, 0, operand_c0, nullptr };
+            a.set = view;
+            return a;
+        }
+        KsAddend with_keys_of(const KsSetView &view) const // permuted operands: only the key is per item
+        {
+            KsAddend a = *this;
+            a.set = view;
+            return a;
+        }
     };
 
     class Ciphertext
@@ -247,6 +262,9 @@ namespace sealhip
             // true: every component is stored in the register order of the fused key-switch
             // kernel, as doubles for primes of the double-precision back end (ntt2_kernels.h)
             bool register_order = false;
+            // which installation of a key this is (process-wide count, never 0 for a resident key): a slab address can come back
+            // from the allocator for the next key, a serial cannot (GaloisSet::keys_current)
+            uint64_t serial = 0;
         };
         ~KSwitchKeys();
         // words: `digits` digits starting at digit `digit0` of key `index`, each 2 x L x N words
@@ -316,6 +334,47 @@ namespace sealhip
         uint64_t *block_ = nullptr;
         const uint32_t *offsets_ = nullptr, *first_ = nullptr, *second_ = nullptr;
     };
+
+    // A Galois set (include/sealhip.h: GaloisSet_Create): R Galois elements whose automorphisms one call applies to every item of a
+    // batch (Evaluator::apply_galois_set).  The counterpart of ItemMap: validated once (std::invalid_argument), uploaded once - one
+    // KsSetEntry (ntt_kernels.h) per entry that is not the identity, with a synchronous copy after a device drain - and read from HBM
+    // by the key switch's per-item kernels, so one set serves many calls and recordings.  An element of 0 is an identity entry (a
+    // step of 0): a copy, never key-switched.  The keys object must outlive the set; a call checks on the host that every recorded
+    // key slab is still the key's current one.  The destructor follows ItemMap's pool rule.
+    class GaloisSet
+    {
+    public:
+        GaloisSet(const Context &context, const KSwitchKeys &galois_keys, uint64_t count, const uint32_t *galois_elts, bool zero_is_identity);
+        ~GaloisSet();
+        GaloisSet(const GaloisSet &) = delete;
+        GaloisSet &operator=(const GaloisSet &) = delete;
+        const Context *context() const { return ctx_; }
+        const KSwitchKeys &keys() const { return *keys_; }
+        size_t count() const { return elts_.size(); }
+        size_t switched() const { return entry_of_.size(); } // entries that are not the identity
+        uint32_t elt(size_t r) const { return elts_[r]; }
+        size_t entry_of(size_t i) const { return entry_of_[i]; } // the entry the i-th table row stands for
+        size_t distinct() const { return distinct_; }
+        bool register_order() const { return register_order_; }
+        const KsSetEntry *table() const { return table_; }
+        bool keys_current() const; // every recorded slab is still the key's
+        bool full_keys(size_t digits) const; // every key holds the digits [0, digits)
+
+    private:
+        const Context *ctx_;
+        const KSwitchKeys *keys_;
+        std::vector<uint32_t> elts_;
+        std::vector<size_t> entry_of_;
+        std::vector<const uint64_t *> slabs_; // per table row: the key's slab and the serial of its installation
+        std::vector<uint64_t> serials_;
+        size_t distinct_ = 0;
+        bool register_order_ = true;
+        uint64_t *block_ = nullptr;
+        const KsSetEntry *table_ = nullptr;
+    };
+    // set calls served by the one-batch route / by the loop over the entries; fused key-switch launches issued by set calls
+    void galois_set_stats(uint64_t &batched, uint64_t &looped, uint64_t &fused_launches);
+    void galois_set_count_fused_launch();
 
     class Evaluator
     {
@@ -442,6 +501,9 @@ namespace sealhip
         // out-of-place forms (evaluator.h:1072-1315 of the reference): with the exact Galois key present `encrypted` is read where
         // it lies - no copy into the destination first
         void apply_galois(const Ciphertext &encrypted, uint32_t galois_elt, const KSwitchKeys &galois_keys, Ciphertext &destination) const;
+        // include/sealhip.h: Evaluator_ApplyGaloisSet - item b R + r of `destination` (batch B R, another object) = apply_galois of item b
+        // with entry r; an identity entry is a copy
+        void apply_galois_set(const Ciphertext &encrypted, const GaloisSet &set, Ciphertext &destination) const;
         void rotate_rows(const Ciphertext &encrypted, int steps, const KSwitchKeys &galois_keys, Ciphertext &destination) const;
         void rotate_columns(const Ciphertext &encrypted, const KSwitchKeys &galois_keys, Ciphertext &destination) const;
         void rotate_vector(const Ciphertext &encrypted, int steps, const KSwitchKeys &galois_keys, Ciphertext &destination) const;

@@ -179,6 +179,8 @@ namespace sealhip
     // digit loop into `split` in-launch groups (their partial sums are added by a reduce pass): single-ciphertext
     // latency of multiply+relinearize+rescale at C5 0.63 -> 0.40 ms (profiles/HISTORY.md section 5, "Small batches / latency").
     // This is the shape's half of the rule - also asked at multiply time, before any key is known (may_defer_product).
+    // (Galois sets ask it with their virtual batch B x R; their own threshold - a set of one entry takes the single-key call - sits in
+    // Evaluator::apply_galois_set, evaluator_levels.cpp, with the profile line it comes from)
     unsigned Evaluator::ks_shape_split(const Level &lvl, size_t batch) const
     {
         const size_t wgs = batch * (size_t)(lvl.K + 1) * (context_.n() >> 12);
@@ -403,6 +405,9 @@ namespace sealhip
         if (j1 > K || j0 > j1)
             throw std::invalid_argument("digit range");
         const bool folds = addend.folds;
+        const KsSetView &set = addend.set;
+        if (set.table && (!route.fused || !set.count || e.batch() % set.count || j0 != 0 || j1 != K || (set.map && (!folds || !addend.c0 || addend.galois_elt))))
+            throw std::invalid_argument("galois set"); // the per-item forms are pass 2's and the two-pass inverse transform's
         if (folds && !(route.takes_product() && j0 == 0 && j1 == K))
             throw std::invalid_argument("fold_addend"); // an addend may only join the complete sum of the un-split folded launch
         if (j0 < j1 && (key.digit0 > j0 || key.digit0 + key.digits < j1))
@@ -440,6 +445,13 @@ namespace sealhip
             bt.src = target + b0 * poly_words;
             bt.src_outer_stride = poly_words;
             bt.src_galois_elt = addend.galois_elt;
+            if (set.map)
+            {
+                // the items [b0, b0 + nb) are VIRTUAL items: each reads its source item of the whole operand through its entry's map
+                bt.src = target;
+                bt.src_set = set;
+                bt.src_set.v0 = b0;
+            }
             if (product)
             {
                 // the target x1 y1 is formed while it is loaded; it is not stored (ks2 forms its diagonal terms from the operands too)
@@ -475,7 +487,9 @@ namespace sealhip
                 KsFusedArgs ka{};
                 ka.t = digits + b0 * poly_words;
                 // the I == J shortcut of evaluator.cpp:2682-2685 (a deferred product: x1 y1 is formed where it is needed, ks2 takes it from fold_x / fold_y)
-                ka.target_ntt = ntt_target && !product ? target + b0 * poly_words : nullptr;
+                ka.target_ntt = ntt_target && !product ? target + (set.map ? 0 : b0 * poly_words) : nullptr;
+                ka.set = set;
+                ka.set.v0 = b0;
                 ka.key = key.dev;
                 ka.mid = mid.p + (size_t)lane * plan.chunk * ks_item_words;
                 ka.acc = acc_out + (size_t)b0 * 2 * (K + 1) * N;
@@ -500,12 +514,15 @@ namespace sealhip
                 }
                 else if (folds)
                 {
-                    ka.fold_c0 = (addend.galois_elt ? addend.c0 : e.plane(0)) + b0 * poly_words;
+                    ka.fold_c0 = set.map ? addend.c0 : (addend.galois_elt ? addend.c0 : e.plane(0)) + b0 * poly_words;
                     ka.fold_c1 = addend.c1_zero ? nullptr : e.plane(1) + b0 * poly_words;
                     ka.galois_elt = addend.galois_elt;
                 }
                 return ka;
             };
+            if (set.table)
+                for (unsigned b0 = 0; b0 < B; b0 += plan.chunk)
+                    galois_set_count_fused_launch();
             if (!chunked)
                 ck(ks_fused(tb, fused_args(0, B, 0), stream_), "ks fused");
             else
@@ -686,8 +703,9 @@ namespace sealhip
         Scratch acc(switch_key_acc_words(e) * split);
         // (the planes are folded by ks2's epilogue when the digits run as one group, by the pass that adds the groups otherwise; a
         // rotation's unpermuted operand can only be folded by the former, which switch_key_partial checks)
-        const bool own_planes = !addend.galois_elt && !addend.prod;
-        switch_key_partial(e, target, keys, key_index, acc.p, route, own_planes && !route.takes_product() ? KsAddend::nothing() : addend);
+        const bool own_planes = !addend.galois_elt && !addend.prod && !addend.set.map;
+        switch_key_partial(e, target, keys, key_index, acc.p, route,
+                           own_planes && !route.takes_product() ? KsAddend::nothing().with_keys_of(addend.set) : addend);
         if (split > 1) // several digit groups (small batches): the pass that adds them adds the ciphertext's words too
             ck(k_keyswitch_reduce(context_.dev_mods(), acc.p, (unsigned)context_.log_n(), K, context_.key_level().K, (unsigned)e.batch(),
                                   stream_, split, fold ? e.plane(0) : nullptr, fold && !addend.c1_zero ? e.plane(1) : nullptr,

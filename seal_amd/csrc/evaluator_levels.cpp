@@ -406,6 +406,248 @@ namespace sealhip
     {
         complex_conjugate(e, gk, e);
     }
+    // ---- Galois sets (include/sealhip.h: GaloisSet_Create, Evaluator_ApplyGaloisSet): R rotations of every item of a batch
+    namespace
+    {
+        std::atomic<uint64_t> g_set_batched{ 0 }, g_set_looped{ 0 }, g_set_fused_launches{ 0 };
+    }
+    void galois_set_stats(uint64_t &batched, uint64_t &looped, uint64_t &fused_launches)
+    {
+        batched = g_set_batched.load();
+        looped = g_set_looped.load();
+        fused_launches = g_set_fused_launches.load();
+    }
+    void galois_set_count_fused_launch()
+    {
+        g_set_fused_launches++;
+    }
+    GaloisSet::GaloisSet(const Context &context, const KSwitchKeys &galois_keys, uint64_t count, const uint32_t *galois_elts, bool zero_is_identity)
+        : ctx_(&context), keys_(&galois_keys)
+    {
+        if (!galois_elts)
+            throw std::invalid_argument("galois_elts is null");
+        if (!count || count >= (uint64_t(1) << 32))
+            throw std::invalid_argument("1 <= count < 2^32");
+        if (galois_keys.context() != &context)
+            throw std::invalid_argument("galois_keys is not valid for encryption parameters");
+        const uint64_t m = 2 * (uint64_t)context.n();
+        std::vector<uint64_t> host; // KsSetEntry rows: (key, element)
+        std::vector<uint32_t> seen;
+        for (uint64_t r = 0; r < count; r++)
+        {
+            const uint32_t elt = galois_elts[r];
+            elts_.push_back(elt);
+            if (!elt && zero_is_identity)
+                continue;
+            if (!(elt & 1) || elt >= m)
+                throw std::invalid_argument("Galois element is not valid");
+            const size_t index = Evaluator::galois_index(elt);
+            if (!galois_keys.has_key(index))
+                throw std::invalid_argument("Galois key not present");
+            const KSwitchKeys::Key &key = galois_keys.key(index);
+            register_order_ = register_order_ && key.register_order;
+            entry_of_.push_back((size_t)r);
+            slabs_.push_back(key.dev);
+            serials_.push_back(key.serial);
+            host.push_back((uint64_t)(uintptr_t)key.dev);
+            host.push_back(elt);
+            if (std::find(seen.begin(), seen.end(), elt) == seen.end())
+                seen.push_back(elt);
+        }
+        distinct_ = seen.size();
+        if (host.empty())
+            return; // identity entries only: nothing is ever key-switched
+        static_assert(sizeof(KsSetEntry) == 16, "a table row is two words");
+        block_ = DevicePool::global().alloc_words(host.size());
+        try
+        {
+            ck(hipDeviceSynchronize(), "GaloisSet upload"); // not a hot-path call: whatever used the block before is done
+            copy_h2d(block_, host.data(), host.size() * 8);
+        }
+        catch (...)
+        {
+            DevicePool::global().free_words(block_);
+            throw;
+        }
+        table_ = reinterpret_cast<const KsSetEntry *>(block_);
+    }
+    GaloisSet::~GaloisSet()
+    {
+        DevicePool::global().free_words(block_); // (ItemMap's rule: tagged by the pool, work that still reads the table is waited for by the next user)
+    }
+    bool GaloisSet::keys_current() const
+    {
+        for (size_t i = 0; i < entry_of_.size(); i++)
+        {
+            const size_t index = Evaluator::galois_index(elts_[entry_of_[i]]);
+            if (!keys_->has_key(index) || keys_->key(index).dev != slabs_[i] || keys_->key(index).serial != serials_[i])
+                return false;
+        }
+        return true;
+    }
+    bool GaloisSet::full_keys(size_t digits) const
+    {
+        for (size_t i = 0; i < entry_of_.size(); i++)
+        {
+            const KSwitchKeys::Key &key = keys_->key(Evaluator::galois_index(elts_[entry_of_[i]]));
+            if (key.digit0 != 0 || key.digits < digits)
+                return false;
+        }
+        return true;
+    }
+
+    // Item b R + r of the result = apply_galois(item b, entry r), word for word.  Where every key is in register order (N >= 2^13) the
+    // B x (entries that are not the identity) rotations run as ONE key switch over that many virtual items: the route is asked with the
+    // virtual batch, so the digit groups and the chunks see the real amount of work.  On its un-split folded sub-route neither pi(c0)
+    // nor pi(c1) is stored - the opening inverse transform and pass 2 read the SOURCE item through the entry's index map; on the
+    // others the permuted operands go to scratch by virtual item and only the key is per item.  Everything else - smaller rings, keys in
+    // natural order, a digit-parallel slice of a key - is a host loop over the entries through apply_galois.
+    // Identity entries are device copies on the same stream.  With none the key switch writes the destination's slab itself and may
+    // leave its tail pending exactly as apply_galois does; with some it runs on the virtual batch and the items are copied into place.
+    void Evaluator::apply_galois_set(const Ciphertext &e, const GaloisSet &set, Ciphertext &dest) const
+    {
+        StreamScope pool_scope(stream_);
+        check_valid(e, "encrypted");
+        if (set.context() != &context_ || set.keys().context() != &context_)
+            throw std::invalid_argument("galois_set is not valid for encryption parameters");
+        if (&dest == &e)
+            throw std::invalid_argument("destination must be another object than encrypted");
+        const size_t B = e.batch(), R = set.count(), Rn = set.switched();
+        if (&dest.context() != &context_ || (uint64_t)B * R >= (uint64_t(1) << 32) || dest.batch() != B * R)
+            throw std::invalid_argument("destination must be a batch of encrypted's batch times the set's count");
+        if (!set.keys_current())
+            throw std::invalid_argument("a Galois key was replaced after the set was made");
+        if (e.size() != 2)
+            throw std::invalid_argument("encrypted size must be 2");
+        check_native_form(e);
+        const Level &lvl = *e.level();
+        const unsigned K = lvl.K;
+        const size_t KN = (size_t)K * context_.n();
+        const int ntt_form = context_.scheme() == Scheme::bfv ? 0 : 1;
+        const KSwitchKeys &keys = set.keys();
+        const uint64_t *c0 = e.plane(0), *c1 = e.plane(1); // (completes whatever is pending on the operand)
+        const auto like_operand = [&](Ciphertext &c) {
+            c.is_ntt_form() = e.is_ntt_form();
+            c.scale() = e.scale();
+            c.correction_factor() = e.correction_factor();
+        };
+        // item `from` of a batch of `from_batch` -> item `to` of the result's slab, both planes
+        const size_t out_plane = B * R * KN, out_words = 2 * out_plane;
+        const auto copy_item = [&](uint64_t *out, size_t to, const uint64_t *src, size_t from_batch, size_t from) {
+            for (size_t p = 0; p < 2; p++)
+                ck(hipMemcpyAsync(out + p * out_plane + to * KN, src + p * from_batch * KN + from * KN, KN * 8, hipMemcpyDeviceToDevice, stream_),
+                   "galois set copy item");
+        };
+        const auto copy_identities = [&](uint64_t *out) {
+            for (size_t b = 0; b < B; b++)
+                for (size_t r = 0; r < R; r++)
+                    if (!set.elt(r))
+                        copy_item(out, b * R + r, c0, B, b);
+        };
+        const size_t V = B * Rn;
+        KsRoute route;
+        if (Rn)
+            route = ks_route(lvl, V, keys, galois_index(set.elt(set.entry_of(0))), 0, K);
+        // The set's half of the route rule (the shape's half is ks_shape_split, evaluator_keyswitch.cpp).  A set of ONE entry is the
+        // single-key call on the batch: the per-item form has nothing to share there and measured behind it (C5, B = 1, R = 1: 0.343 ms
+        // against 0.317 ms eager, profiles/galois_set.txt section 2, first line of the table); from two entries on the one-batch form wins
+        // (R = 2: 0.478 against 0.623 / 0.570 ms) and the gap widens with R
+        const bool batched = R > 1 && Rn && route.fused && set.register_order() && set.full_keys(K);
+        if (R == 1 && Rn == 1)
+        {
+            g_set_looped++;
+            return apply_galois(e, set.elt(0), keys, dest); // (same batch: the operand is read where it lies, the tail may stay pending)
+        }
+        if (!batched)
+        {
+            // the loop: one single-key call per entry over the B sources, its items copied into their places
+            g_set_looped++;
+            uint64_t *out = DevicePool::global().alloc_words(out_words, stream_);
+            try
+            {
+                copy_identities(out);
+                for (size_t i = 0; i < Rn; i++)
+                {
+                    Ciphertext one(context_, B);
+                    apply_galois(e, set.elt(set.entry_of(i)), keys, one);
+                    const uint64_t *words = one.plane(0); // (completes a pending tail)
+                    for (size_t b = 0; b < B; b++)
+                        copy_item(out, b * R + set.entry_of(i), words, B, b);
+                }
+            }
+            catch (...)
+            {
+                DevicePool::global().free_words(out, stream_);
+                throw;
+            }
+            like_operand(dest);
+            dest.adopt(&lvl, 2, out, out_words);
+            return;
+        }
+        g_set_batched++;
+        const bool direct = Rn == R; // no identity entries: the virtual batch IS the result
+        Ciphertext staged(context_, direct ? 1 : V);
+        Ciphertext &t = direct ? dest : staged;
+        const size_t t_words = 2 * V * KN;
+        uint64_t *slab = DevicePool::global().alloc_words(t_words, stream_);
+        like_operand(t);
+        t.adopt(&lvl, 2, slab, t_words);
+        try
+        {
+            KsSetView view;
+            view.table = set.table();
+            view.count = (unsigned)Rn;
+            const size_t key_index = galois_index(set.elt(set.entry_of(0))); // (names a key of the set's shape; the kernels take each item's own)
+            if (route.reads_through_map())
+            {
+                g_galois_gathered++;
+                view.map = true;
+                switch_key_inplace(t, c1, keys, key_index, route, KsAddend::galois_set(view, c0));
+            }
+            else
+            {
+                g_galois_permuted++;
+                // pi(c0) straight into the slab, pi(c1) into scratch as the key-switch target, both by virtual item
+                Scratch perm(V * KN);
+                PlaneGeom g1{ (unsigned)context_.log_n(), K, 1 };
+                for (size_t b = 0; b < B; b++)
+                    for (size_t i = 0; i < Rn; i++)
+                    {
+                        const uint32_t elt = set.elt(set.entry_of(i));
+                        ck(k_apply_galois(context_.dev_mods(), c0 + b * KN, slab + (b * Rn + i) * KN, elt, ntt_form, g1, 1, stream_), "galois set c0");
+                        ck(k_apply_galois(context_.dev_mods(), c1 + b * KN, perm.p + (b * Rn + i) * KN, elt, ntt_form, g1, 1, stream_), "galois set c1");
+                    }
+                switch_key_inplace(t, perm.p, keys, key_index, route, KsAddend::planes(true).with_keys_of(view));
+            }
+            throw_if_transparent(t);
+            if (!direct)
+            {
+                uint64_t *out = DevicePool::global().alloc_words(out_words, stream_);
+                try
+                {
+                    copy_identities(out);
+                    const uint64_t *words = staged.plane(0); // (completes the pending tail)
+                    for (size_t b = 0; b < B; b++)
+                        for (size_t i = 0; i < Rn; i++)
+                            copy_item(out, b * R + set.entry_of(i), words, V, b * Rn + i);
+                }
+                catch (...)
+                {
+                    DevicePool::global().free_words(out, stream_);
+                    throw;
+                }
+                like_operand(dest);
+                dest.adopt(&lvl, 2, out, out_words);
+            }
+        }
+        catch (...)
+        {
+            if (direct)
+                dest.release(); // (as apply_galois: no half-built destination with valid-looking metadata)
+            throw;
+        }
+    }
+
     void Evaluator::rotate_internal(Ciphertext &e, int steps, const KSwitchKeys &galois_keys) const
     {
         expect_scope();

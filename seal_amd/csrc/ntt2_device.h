@@ -750,6 +750,14 @@ namespace sealhip
             const unsigned idx = (unsigned)(((uint64_t)elt * rev) >> 1) & (N - 1);
             return __brev(idx) >> (32 - n_log);
         }
+        // Galois sets (ntt_kernels.h: KsSetEntry): row `r` of the set's table - r is the same in every lane, the two words come
+        // through the constant address space (scalar loads), so the key's base and the element are wave-uniform like a launch argument
+        __device__ __forceinline__ void ld_uniform_set_entry(const KsSetEntry *table, unsigned r, const uint64_t *&key, uint32_t &galois_elt)
+        {
+            shl_uconst_ptr u = SHL_UCONST(reinterpret_cast<const uint64_t *>(table));
+            key = reinterpret_cast<const uint64_t *>((uintptr_t)u[2 * (size_t)r]);
+            galois_elt = (uint32_t)u[2 * (size_t)r + 1];
+        }
         // load_rows through the automorphism: `poly` = the polynomial's first word, j0 = natural index of this wave's first row
         __device__ __forceinline__ void load_rows_galois(uint64_t (&val)[16], uint64_t *lds_wave, const uint64_t *poly, unsigned j0, uint32_t elt,
                                                          unsigned n_log, unsigned tid)

@@ -78,6 +78,11 @@ namespace sealhip
         // Round 6, rotations without the permutation kernels: target_ntt and fold_c0 are the UNPERMUTED polynomials c1 and c0, read
         // through the NTT-domain automorphism of this Galois element (ntt2_device.h: galois_src_index); fold_c1 must be null (zero)
         uint32_t galois_elt = 0;
+        // Galois sets (ntt_kernels.h: KsSetView), instead of `key` and galois_elt: pass 2 runs its per-item form - item b of the launch is
+        // virtual item set.v0 + b, whose table row names the key and the element.  t, mid and acc are by virtual item as ever; with
+        // set.map, target_ntt and fold_c0 are the BASE of the unpermuted operand and are read by source item through the row's map
+        // (same restrictions as galois_elt); without it they are by virtual item and `key` alone comes from the table.
+        KsSetView set{};
         // Callers that cut a batch into chunks (Evaluator::switch_key_partial, round 5) decide these for the WHOLE batch:
         // order1 = which pass-1 kernel runs (-1: decided from this call's grid, 0: target-resident ks1_kernel, 1: digit-resident
         // ks1t_kernel); no_class_fork = the two arithmetic classes run one after the other on `stream` (the caller's chunk

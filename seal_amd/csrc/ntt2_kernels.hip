@@ -619,8 +619,10 @@ namespace sealhip
         constexpr int kInvE3 = inv_phase_exp<ICLS>(kInvE2<ICLS>, 4, 0);
 
         template <bool FP, int D1, int ICLS = 2>
-        __device__ __forceinline__ void inv_pa_body(const InvArgs &a, unsigned prime, unsigned comp, unsigned outer, uint64_t *lds, unsigned tile)
+        __device__ __forceinline__ void inv_pa_body(const InvArgs &a, unsigned prime, unsigned comp, unsigned outer, unsigned src_outer, uint64_t *lds,
+                                                    unsigned tile)
         {
+            // (src_outer: the item of `src` that is read - the outer item itself, except in the per-item form of a Galois set)
             typedef Field<FP> F;
             typedef Geo<D1> G;
             const unsigned tid = threadIdx.x, hg = tile;
@@ -691,9 +693,9 @@ namespace sealhip
                 }
             }
             else if (a.src_gal)
-                load_rows_galois(raw, lds_wave, a.src + (size_t)outer * a.src_outer_stride + ((size_t)comp << G::n), (hg * 16 + (tid >> 6) * 4) << 8, a.src_gal, G::n, tid);
+                load_rows_galois(raw, lds_wave, a.src + (size_t)src_outer * a.src_outer_stride + ((size_t)comp << G::n), (hg * 16 + (tid >> 6) * 4) << 8, a.src_gal, G::n, tid);
             else
-                load_rows(raw, lds_wave, a.src + (size_t)outer * a.src_outer_stride + rows, tid);
+                load_rows(raw, lds_wave, a.src + (size_t)src_outer * a.src_outer_stride + rows, tid);
             if (!have_x)
             {
 #pragma unroll
@@ -739,7 +741,28 @@ namespace sealhip
             HIP_DYNAMIC_SHARED(uint64_t, lds)
             const unsigned comp = blockIdx.y + a.comp0, outer = blockIdx.z, tile = blockIdx.x;
             const unsigned prime = SHL_UNIFORM(a.comp_prime ? a.comp_prime[comp] : a.prime_first + comp);
-            with_class<CLS>(a.t, prime, [&](auto fp, auto ic) { inv_pa_body<decltype(fp)::value, D1, decltype(ic)::value>(a, prime, comp, outer, lds, tile); });
+            with_class<CLS>(a.t, prime, [&](auto fp, auto ic) { inv_pa_body<decltype(fp)::value, D1, decltype(ic)::value>(a, prime, comp, outer, outer, lds, tile); });
+        }
+        // The per-item form (Galois sets, ntt_kernels.h: KsSetView): outer item o is virtual item v0 + o = entry (v0 + o) % count applied
+        // to source item (v0 + o) / count.  A workgroup works on one outer item, so its table row - the element - is one uniform load;
+        // everything else is the single-element form.  A kernel of its own: ntt2_inv_pa keeps its registers and instructions.
+        struct InvSetArgs
+        {
+            InvArgs a; // src = the base of the whole operand; src_gal is not used
+            const KsSetEntry *table;
+            unsigned count, v0;
+        };
+        template <int D1, int CLS>
+        __global__ void __launch_bounds__(kThreads) ntt2_inv_pa_set(InvSetArgs s)
+        {
+            HIP_DYNAMIC_SHARED(uint64_t, lds)
+            const unsigned comp = blockIdx.y + s.a.comp0, outer = blockIdx.z, tile = blockIdx.x;
+            const unsigned v = SHL_UNIFORM(s.v0 + outer), src_item = v / s.count;
+            InvArgs a = s.a;
+            const uint64_t *key;
+            ld_uniform_set_entry(s.table, v - src_item * s.count, key, a.src_gal);
+            const unsigned prime = SHL_UNIFORM(a.comp_prime ? a.comp_prime[comp] : a.prime_first + comp);
+            with_class<CLS>(a.t, prime, [&](auto fp, auto ic) { inv_pa_body<decltype(fp)::value, D1, decltype(ic)::value>(a, prime, comp, outer, src_item, lds, tile); });
         }
 
         template <bool FP, int D1, int ICLS = 2>
@@ -1400,9 +1423,11 @@ namespace sealhip
         };
 
         template <bool FP, int D1, int ICLS = 0>
-        __device__ __forceinline__ void ks2_body(const Ks2Args &a, uint64_t *lds, unsigned I, unsigned prime, unsigned koff, unsigned b, unsigned hg,
-                                                 unsigned j0, unsigned j1, uint64_t *acc_part)
+        __device__ __forceinline__ void ks2_body(const Ks2Args &a, uint64_t *lds, unsigned I, unsigned prime, unsigned koff, unsigned b, unsigned bs,
+                                                 unsigned hg, unsigned j0, unsigned j1, uint64_t *acc_part)
         {
+            // (bs: the item of `target` and of the folded planes that is read - b itself, except in the per-item form of a Galois set,
+            // where b is the virtual item and bs its source)
             typedef Field<FP> F;
             typedef Geo<D1> G;
             const unsigned tid = threadIdx.x;
@@ -1483,7 +1508,7 @@ namespace sealhip
             // (round 6) a deferred product's diagonal terms are x1 y1, formed here from the operands: diag_prod = the product is not stored
             const bool diag_prod = a.fold_x && !a.target && I < a.K;
             const bool has_diag = (a.target || diag_prod) && I < a.K;
-            const size_t diag_off = (((size_t)b * a.K + I) << G::n) + ((size_t)hg << 12);
+            const size_t diag_off = (((size_t)bs * a.K + I) << G::n) + ((size_t)hg << 12);
             const UniformView diag_view = uniform_view(diag_prod ? a.fold_x + a.fold_plane + diag_off : has_diag ? a.target + diag_off : a.mid);
             uint64_t nxt[16]; // digit J+1 is in flight while digit J is transformed
             auto fetch = [&](unsigned J) {
@@ -1492,7 +1517,7 @@ namespace sealhip
                     if (a.gal)
                     {
                         // a rotation's target is pi(c1), never stored: the thread's sixteen words come through the index map
-                        const uint64_t *poly = a.target + (((size_t)b * a.K + I) << G::n);
+                        const uint64_t *poly = a.target + (((size_t)bs * a.K + I) << G::n);
 #pragma unroll
                         for (int e = 0; e < 16; e++)
                             nxt[e] = poly[galois_src_index((hg << 12) + tid * 16 + e, a.gal, G::n)];
@@ -1737,7 +1762,7 @@ namespace sealhip
             {
                 // the key-switch tail's "c + S P^-1" happens here, where S is in registers: the tail then reads one operand, not two
                 // (evaluator.cpp:2845-2863 computes ct += (S - NTT(v)) P^-1 = (c + S P^-1) - NTT(v) P^-1; exact residue arithmetic)
-                const size_t crow = ((((size_t)b * a.K + I) << G::n)) + ((size_t)(hg * 16 + (tid >> 6) * 4) << 8);
+                const size_t crow = ((((size_t)bs * a.K + I) << G::n)) + ((size_t)(hg * 16 + (tid >> 6) * 4) << 8);
                 const uint64_t *C0 = a.fold_c0 + crow, *C1 = a.fold_c1 ? a.fold_c1 + crow : nullptr; // null: that addend is zero (rotations)
                 const ShoupOp pm = a.fold_pm[I];
                 const uint64_t q = a.tb.mods[prime].q;
@@ -1747,7 +1772,7 @@ namespace sealhip
                 {
                     const unsigned off = (k >> 2) * 256 + (k & 3) * 64 + (tid & 63);
                     if (a.gal) // the first addend is pi(c0) of a rotation, read through the index map
-                        cv0[k] = mid_ld(a.fold_c0 + (((size_t)b * a.K + I) << G::n) + galois_src_index(((hg * 16 + (tid >> 6) * 4) << 8) + off, a.gal, G::n));
+                        cv0[k] = mid_ld(a.fold_c0 + (((size_t)bs * a.K + I) << G::n) + galois_src_index(((hg * 16 + (tid >> 6) * 4) << 8) + off, a.gal, G::n));
                     else
                         cv0[k] = mid_ld(C0 + off);
                     cv1[k] = C1 ? mid_ld(C1 + off) : 0;
@@ -1818,9 +1843,57 @@ namespace sealhip
             const unsigned it = tile / G::TILES, hg = tile % G::TILES;
             const unsigned I = SHL_UNIFORM(a.targets[4 * it]), prime = SHL_UNIFORM(a.targets[4 * it + 1]), koff = SHL_UNIFORM(a.targets[4 * it + 3]);
             if constexpr (CLS == 1)
-                ks2_body<true, D1>(a, lds, I, prime, koff, b, hg, j0, j1, acc_part);
+                ks2_body<true, D1>(a, lds, I, prime, koff, b, b, hg, j0, j1, acc_part);
             else
-                with_int_class(a.tb, prime, [&](auto ic) { ks2_body<false, D1, decltype(ic)::value>(a, lds, I, prime, koff, b, hg, j0, j1, acc_part); });
+                with_int_class(a.tb, prime, [&](auto ic) { ks2_body<false, D1, decltype(ic)::value>(a, lds, I, prime, koff, b, b, hg, j0, j1, acc_part); });
+        }
+
+        // The per-item form of pass 2 (Galois sets, ntt_kernels.h: KsSetView): R rotations of B ciphertexts as one key switch over
+        // B * count virtual items.  A workgroup works on one batch item already, so the two things that differ per item - the
+        // switching key and the element - are one table row, fetched with uniform loads; t, mid and acc are by virtual item, the
+        // diagonal terms and the folded c0 by SOURCE item through the row's index map (map), or by virtual item from permuted
+        // scratch (!map: only the key is per item).  The body is ks2_body; the kernel is a separate instantiation so that
+        // ks2_kernel keeps its registers and instructions.
+        // Order: XCD-aware as above.  A launch that covers whole sources (src_batch != 0: v0 = 0, batch = src_batch * count)
+        // walks an (I, hg) tile entry by entry, the sources of one entry adjacent in time: items that share a key share its tile in
+        // that XCD's L2; distinct keys cannot.  (A design intention: not measured.)
+        struct Ks2SetArgs
+        {
+            Ks2Args a; // key and gal are not used
+            const KsSetEntry *table;
+            unsigned count, v0, src_batch;
+            int map;
+        };
+        template <int D1, int CLS>
+        __global__ void __launch_bounds__(kThreads, 2) ks2_set_kernel(Ks2SetArgs s)
+        {
+            typedef Geo<D1> G;
+            HIP_DYNAMIC_SHARED(uint64_t, lds)
+            const unsigned ntile = s.a.ntargets * G::TILES;
+            const unsigned bid = blockIdx.x;
+            const unsigned xcd = bid & 7, rest = bid >> 3;
+            const unsigned vbatch = s.a.batch * s.a.parts;
+            const unsigned vb = rest % vbatch, tile_hi = rest / vbatch;
+            const unsigned l = vb % s.a.batch, dg = vb / s.a.batch; // l: position of the item in time
+            const unsigned b = s.src_batch ? (l % s.src_batch) * s.count + l / s.src_batch : l;
+            const unsigned jlen = (s.a.j1 - s.a.j0 + s.a.parts - 1) / s.a.parts;
+            const unsigned j0 = s.a.j0 + dg * jlen, j1 = j0 + jlen < s.a.j1 ? j0 + jlen : s.a.j1;
+            uint64_t *acc_part = s.a.acc + (((size_t)dg * s.a.batch * 2 * (s.a.K + 1)) << G::n);
+            const unsigned tile = tile_hi * 8 + xcd;
+            if (tile >= ntile)
+                return;
+            const unsigned v = SHL_UNIFORM(s.v0 + b), src_item = v / s.count;
+            Ks2Args a = s.a;
+            uint32_t elt;
+            ld_uniform_set_entry(s.table, v - src_item * s.count, a.key, elt);
+            a.gal = s.map ? elt : 0;
+            const unsigned bs = s.map ? src_item : b;
+            const unsigned it = tile / G::TILES, hg = tile % G::TILES;
+            const unsigned I = SHL_UNIFORM(a.targets[4 * it]), prime = SHL_UNIFORM(a.targets[4 * it + 1]), koff = SHL_UNIFORM(a.targets[4 * it + 3]);
+            if constexpr (CLS == 1)
+                ks2_body<true, D1>(a, lds, I, prime, koff, b, bs, hg, j0, j1, acc_part);
+            else
+                with_int_class(a.tb, prime, [&](auto ic) { ks2_body<false, D1, decltype(ic)::value>(a, lds, I, prime, koff, b, bs, hg, j0, j1, acc_part); });
         }
 
         // per-component offsets of a digit in units of N words (ntt2_kernels.h: key_comp_offset_units), one table per workgroup
@@ -2246,14 +2319,14 @@ namespace sealhip
         }
 
         template <int D1>
-        hipError_t launch_inv(const InvArgs &a, unsigned nouter, hipStream_t s)
+        hipError_t launch_inv(const InvArgs &a, unsigned nouter, hipStream_t s, const KsSetView &set = KsSetView{})
         {
             typedef Geo<D1> G;
             bool fused = false;
             unsigned fchunks = 1;
             if constexpr (D1 == 5 || D1 == 6)
             {
-                if (!a.prod_x && !a.src_gal) // (the product and automorphism sources are features of the two-pass kernels)
+                if (!a.prod_x && !a.src_gal && !set.table) // (the product and automorphism sources are features of the two-pass kernels)
                 {
                     if (raise_lds<&ntt2_inv_fused2<D1, 1>>(FusedGeo<D1>::lds_bytes) != hipSuccess || raise_lds<&ntt2_inv_fused2<D1, 0>>(FusedGeo<D1, 2>::lds_bytes) != hipSuccess)
                         return hipErrorInvalidValue;
@@ -2281,7 +2354,9 @@ namespace sealhip
                     }
                 }
                 dim3 grid(G::TILES, r.nc, nouter);
-                const hipError_t e = launch_cls(r.cls, [](auto c) { return ntt2_inv_pa<D1, decltype(c)::value>; }, grid, kLds2Words * 8, st, g);
+                const hipError_t e = set.table ? launch_cls(r.cls, [](auto c) { return ntt2_inv_pa_set<D1, decltype(c)::value>; }, grid, kLds2Words * 8, st,
+                                                            InvSetArgs{ g, set.table, set.count, set.v0 })
+                                               : launch_cls(r.cls, [](auto c) { return ntt2_inv_pa<D1, decltype(c)::value>; }, grid, kLds2Words * 8, st, g);
                 if (e != hipSuccess)
                     return e;
                 return launch_cls(r.cls, [](auto c) { return ntt2_inv_pb<D1, decltype(c)::value>; }, grid, G::lds1_words * 8, st, g);
@@ -2289,7 +2364,8 @@ namespace sealhip
         }
 
         template <int D1>
-        hipError_t launch_ks(const Ks1Args &a1, const Ks2Args &a2, unsigned batch, unsigned n_int, hipStream_t s, int order1, bool no_class_fork)
+        hipError_t launch_ks(const Ks1Args &a1, const Ks2Args &a2, unsigned batch, unsigned n_int, hipStream_t s, int order1, bool no_class_fork,
+                             const KsSetView &set = KsSetView{})
         {
             typedef Geo<D1> G;
             if (a1.ntargets == 0)
@@ -2301,8 +2377,12 @@ namespace sealhip
             // the tile's twiddles staged in LDS (ks2_body): both phases' / phase A's and the last stage's.  68 and 72 KiB
             constexpr size_t l2_fp = kLds2Words * 8 + (240 + 3840) * sizeof(double), l2_int = kLds2Words * 8 + (240 + 2048) * sizeof(ShoupOp);
             static_assert(l2_fp > 65536 && l2_int > 65536, "above the default: raised below");
-            if ((n_int && raise_lds<&ks2_kernel<D1, 0>>(l2_int) != hipSuccess) || (n_fp && raise_lds<&ks2_kernel<D1, 1>>(l2_fp) != hipSuccess))
+            if (!set.table && ((n_int && raise_lds<&ks2_kernel<D1, 0>>(l2_int) != hipSuccess) || (n_fp && raise_lds<&ks2_kernel<D1, 1>>(l2_fp) != hipSuccess)))
                 return hipErrorInvalidValue;
+            if (set.table && ((n_int && raise_lds<&ks2_set_kernel<D1, 0>>(l2_int) != hipSuccess) || (n_fp && raise_lds<&ks2_set_kernel<D1, 1>>(l2_fp) != hipSuccess)))
+                return hipErrorInvalidValue;
+            // a set launch that covers whole sources walks entry by entry (ks2_set_kernel)
+            const unsigned set_src_batch = set.table && set.v0 == 0 && batch % set.count == 0 ? batch / set.count : 0;
             // both passes for the targets of one arithmetic class (targets = [integer moduli..., double-precision moduli...])
             auto run_class = [&](bool fp, hipStream_t st) -> hipError_t {
                 const unsigned t0 = fp ? n_int : 0, nt = fp ? n_fp : n_int;
@@ -2351,6 +2431,15 @@ namespace sealhip
                 c2.targets = a2.targets + 4 * t0;
                 c2.ntargets = nt;
                 const unsigned ntile = nt * G::TILES;
+                if (set.table)
+                {
+                    const Ks2SetArgs cs{ c2, set.table, set.count, set.v0, set_src_batch, set.map ? 1 : 0 };
+                    if (fp)
+                        hipLaunchKernelGGL((ks2_set_kernel<D1, 1>), dim3(((ntile + 7) / 8) * vbatch * 8), dim3(kThreads), l2_fp, st, cs);
+                    else
+                        hipLaunchKernelGGL((ks2_set_kernel<D1, 0>), dim3(((ntile + 7) / 8) * vbatch * 8), dim3(kThreads), l2_int, st, cs);
+                    return hipGetLastError();
+                }
                 if (fp)
                     hipLaunchKernelGGL((ks2_kernel<D1, 1>), dim3(((ntile + 7) / 8) * vbatch * 8), dim3(kThreads), l2_fp, st, c2);
                 else
@@ -2463,6 +2552,8 @@ namespace sealhip
         a.src_gal = b.src_galois_elt;
         if (b.src_galois_elt && (!b.src || b.prod_x || !(b.src_galois_elt & 1)))
             return hipErrorInvalidValue;
+        if (b.src_set.table && (!b.src || b.prod_x || b.src_galois_elt || !b.src_set.count || !b.src_set.map))
+            return hipErrorInvalidValue;
         if (b.prod_x && (!b.prod_y || !b.prod_batch || (size_t)b.nouter + b.prod_outer0 > (size_t)3 * b.prod_batch || !b.src_outer_stride))
             return hipErrorInvalidValue;
         if (b.prod_x && !b.prod_outer0 && b.nouter != 3 * b.prod_batch) // the whole product, as before round 6
@@ -2481,9 +2572,11 @@ namespace sealhip
             if (az.prod_out)
                 az.prod_out = a.prod_out + (size_t)z0 * a.prod_out_stride;
             az.data = a.data + (size_t)z0 * a.outer_stride;
-            az.src = a.src + (size_t)z0 * a.src_outer_stride;
+            KsSetView set = b.src_set;
+            set.v0 += z0;
+            az.src = set.table ? a.src : a.src + (size_t)z0 * a.src_outer_stride; // (a set's source is found from the virtual item)
             az.mid = a.mid + (((size_t)z0 * a.ncomp) << t.log_n);
-            const hipError_t e = with_d1(t.log_n, [&](auto d) { return launch_inv<decltype(d)::value>(az, nz, stream); });
+            const hipError_t e = with_d1(t.log_n, [&](auto d) { return launch_inv<decltype(d)::value>(az, nz, stream, set); });
             if (e != hipSuccess)
                 return e;
         }
@@ -2532,8 +2625,10 @@ namespace sealhip
         a2.gal = k.galois_elt;
         if (k.galois_elt && (!(k.galois_elt & 1) || !k.target_ntt || !k.fold_c0 || k.fold_c1 || k.fold_x))
             return hipErrorInvalidValue; // a rotation: target and first addend through the index map, the second addend zero
+        if (k.set.table && (!k.set.count || k.galois_elt || k.fold_x || (k.set.map && (!k.target_ntt || !k.fold_c0 || k.fold_c1))))
+            return hipErrorInvalidValue; // a set: key and element from the table; the map-reading form under the same restrictions
         a2.tb = t;
-        return with_d1(t.log_n, [&](auto d) { return launch_ks<decltype(d)::value>(a1, a2, k.batch, k.n_int, stream, k.order1, k.no_class_fork); });
+        return with_d1(t.log_n, [&](auto d) { return launch_ks<decltype(d)::value>(a1, a2, k.batch, k.n_int, stream, k.order1, k.no_class_fork, k.set); });
     }
 
     hipError_t key_to_register_order(const NttTables &t, const uint64_t *in, uint64_t *out, unsigned L, size_t digits, hipStream_t stream)

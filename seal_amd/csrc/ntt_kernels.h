@@ -58,6 +58,26 @@ namespace sealhip
         int a_has_c = 0;                 // epi_a holds c + S P^-1 (KsFusedArgs::fold_c0): c0 / c1 are not read
     };
 
+    // Galois sets (evaluator.h: GaloisSet; include/sealhip.h: Evaluator_ApplyGaloisSet): R rotations of each of B ciphertexts run as
+    // ONE key switch over B * count virtual items, count = the set's entries that are not the identity.  Virtual item v is entry
+    // v % count applied to source item v / count.  The device table has one row per such entry; a workgroup of the per-item
+    // kernels (ntt2_kernels.hip: ks2_set_kernel, ntt2_inv_pa_set) works on one virtual item and fetches its row with uniform loads.
+    struct __attribute__((aligned(16))) KsSetEntry
+    {
+        const uint64_t *key; // the entry's switching key, register order (KSwitchKeys::Key::dev)
+        uint32_t galois_elt;
+        uint32_t reserved;
+    };
+    struct KsSetView
+    {
+        const KsSetEntry *table = nullptr; // device; null: no set (the single-key forms)
+        unsigned count = 0;                // rows of the table
+        unsigned v0 = 0;                   // virtual item of the launch's first item (a chunk of a larger batch)
+        // true: the operand is read by SOURCE item through the entry's index map (the un-split folded route); false: the operand was
+        // permuted into scratch by virtual item and only the key is per item
+        bool map = false;
+    };
+
     // One batched launch: transforms live at data + outer*outer_stride + comp*N, comp in
     // [0, ncomp), outer in [0, nouter); prime of a component = comp_prime[comp] (device array) or
     // prime_first + comp when comp_prime == nullptr.
@@ -128,6 +148,9 @@ namespace sealhip
         // the NTT-domain automorphism of `src` with this Galois element - word j of a polynomial is read from position T(j) of the
         // same polynomial (galois.cpp:18-51; T keeps aligned blocks together, so the gather stays inside the lines a plain read touches)
         uint32_t src_galois_elt = 0;
+        // Galois sets, instead of src_galois_elt: outer item o is virtual item src_set.v0 + o - the automorphism of its entry's element,
+        // read from SOURCE item (v0 + o) / count of `src` (src is the base of the whole operand, not of the launch's first item)
+        KsSetView src_set{};
         // Two-pass engine: what the HOST knows about the arithmetic class of the components when they are named through comp_prime
         // (the launcher reads the class of prime_first + comp itself, a device table it cannot): -1 unknown - the launch carries both
         // back ends and guards every integer butterfly -, 0 every prime on the integer back end (single-class kernels, the

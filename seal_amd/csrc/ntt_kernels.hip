@@ -746,7 +746,7 @@ namespace sealhip
             Scratch mid(((size_t)b.nouter * b.ncomp) << t.log_n);
             return ntt2_inverse(t, b, out_lazy, mid.p, stream);
         }
-        if (b.out_add || b.prod_x || b.src_galois_elt)
+        if (b.out_add || b.prod_x || b.src_galois_elt || b.src_set.table)
             return hipErrorInvalidValue; // out_add, the product source and the Galois gather are features of the two-pass engine only
         if (b.ncomp == 0 || b.nouter == 0)
             return hipSuccess;

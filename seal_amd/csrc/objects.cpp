@@ -379,6 +379,11 @@ namespace sealhip
             if (k.dev)
                 (void)hipFree(k.dev);
     }
+    static uint64_t next_key_serial()
+    {
+        static std::atomic<uint64_t> serial{ 0 };
+        return ++serial;
+    }
     void KSwitchKeys::clear()
     {
         for (auto &k : keys_)
@@ -415,6 +420,7 @@ namespace sealhip
                 const size_t bytes = o.key_bytes(o.keys_[i]);
                 ck(hipMalloc(&p, bytes), "hipMalloc key");
                 fresh[i].dev = (uint64_t *)p;
+                fresh[i].serial = next_key_serial();
                 ck(hipMemcpy(p, o.keys_[i].dev, bytes, hipMemcpyDeviceToDevice), "copy key");
             }
         }
@@ -528,6 +534,7 @@ namespace sealhip
         keys_[index].digits = digits;
         keys_[index].digit0 = digit0;
         keys_[index].register_order = reorder;
+        keys_[index].serial = next_key_serial();
     }
 
 } // namespace sealhip
